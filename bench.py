@@ -9,7 +9,7 @@ all 263,173 blocks, the size prefix scan and the gather of the members into one
 contiguous BGZF stream.  value = input bytes of ALL ranks / time.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--mode encode|decode]
-                  [--level L] [--gib G] [--no-cpu] [--no-extra]
+                  [--level L] [--gib G] [--no-cpu] [--no-extra] [--dump-outputs DIR]
 
 N > 1: one rank per GPU.  The driver launches the ranks itself (torch.distributed.run, WORLD_SIZE
 in the environment); called plainly as `python bench.py --gpus N`, bench.py starts that launcher
@@ -72,7 +72,12 @@ def parse():
     ap.add_argument("--block-kib", type=int, default=0, help="0 = BGZF 0xff00-byte blocks; else MiGz blocks of N KiB")
     ap.add_argument("--stream", default="own", choices=["own", "libdeflate6", "zlib6", "libdeflate1"],
                     help="decode mode: who compressed the stream (reference encoders need oracle/_ref/libref.so)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (e.g. bench_outputs/; rank 0; at most "
+                         "64 MB: the per-member arrays whole, the stream's first MiB and a seeded sample of whole members)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     args.gib_default = args.gib is None
     if args.gib is None:
         args.gib = 16.0 if args.gpus <= 1 else 32.0
@@ -480,7 +485,7 @@ class Bench:
         head = bytes(packed[:4].cpu().numpy())
         assert head == b"\x1f\x8b\x08\x04", head
         res = dict(elapsed=elapsed, k_avg_s=k_avg_s, total=total, comp_total=comp_total, nb=nb, frame=frame,
-                   off=off, ln=ln, enc=enc, packed=packed, hdr=20 if migz else 18, dist=dict(state))
+                   off=off, ln=ln, enc=enc, packed=packed, hdr=20 if migz else 18, dist=dict(state), slot=slot)
         return res
 
     def verify_encode(self, res, data, block):
@@ -540,7 +545,53 @@ class Bench:
         assert int(st.abs().sum()) == 0 and torch.equal(out_len, ln)
         assert torch.equal(out[: 4 * block], data[: 4 * block]) and torch.equal(out[-block:], data[-block:])
         assert torch.equal(crc, want_crc)
-        return dict(elapsed=elapsed, k_avg_s=k_avg_s, total=total, comp_total=int(packed.numel()), nb=nb)
+        return dict(elapsed=elapsed, k_avg_s=k_avg_s, total=total, comp_total=int(packed.numel()), nb=nb,
+                    out=out, off=off, out_len=out_len, crc=crc, block=block)
+
+    def dump_outputs(self, res, mode, out_dir, budget=64_000_000):
+        """--dump-outputs: what a caller of the timed path received from its LAST step, as float64 / float32 .npy files.
+        encode: per member its offset in the whole stream, its length and CRC-32, and the bytes of the packed stream;
+        decode: per block its length and CRC-32, and the inflated bytes.  The per-member arrays are written whole up to
+        2^20 entries (else a seeded sample, its indices in member_index.npy); of the bytes the first MiB and every byte
+        of a seeded sample of whole members (their indices in sample_members.npy).  The samples depend on the arguments
+        alone, so two builds run with the same arguments can be compared output for output."""
+        torch = self.torch
+        if mode == "encode":
+            enc = res["enc"]
+            buf, nbytes, room = res["packed"], res["comp_total"], res["slot"]
+            start = (enc.dst_off - res["dist"]["base"]).cpu().numpy()
+            length = enc.out_len.cpu().numpy().astype(np.int64)
+            per = {"member_offset": enc.dst_off.cpu().numpy(), "member_len": length,
+                   "member_crc32": enc.crc.cpu().numpy().view(np.uint32)}
+        else:
+            buf, nbytes, room = res["out"], res["total"], res["block"]
+            start = res["off"].cpu().numpy()
+            length = res["out_len"].cpu().numpy().astype(np.int64)
+            per = {"block_len": length, "block_crc32": res["crc"].cpu().numpy().view(np.uint32)}
+        nb = len(length)
+        rng = np.random.default_rng(20251015)
+        arrays = {}
+        if nb > 1 << 20:
+            keep = np.sort(rng.choice(nb, 1 << 20, replace=False))
+            arrays["member_index"] = keep.astype(np.float64)
+            per = {k: v[keep] for k, v in per.items()}
+        arrays.update({k: v.astype(np.float64) for k, v in per.items()})
+        head = min(1 << 20, nbytes)
+        arrays["stream_head" if mode == "encode" else "output_head"] = buf[:head].cpu().numpy().astype(np.float32)
+        # whole members / blocks at seeded indices, as many as 20 MiB of float32 holds at the largest member size
+        nsel = min(nb, max(1, (20 << 20) // (4 * room)))
+        sel = np.sort(rng.choice(nb, nsel, replace=False))
+        assert int((start[sel] + length[sel]).max()) <= nbytes and int(start[sel].min()) >= 0
+        idx = np.concatenate([np.arange(start[i], start[i] + length[i], dtype=np.int64) for i in sel])
+        arrays["sample_members"] = sel.astype(np.float64)
+        arrays["stream_sample" if mode == "encode" else "output_sample"] = (
+            buf[torch.from_numpy(idx).to(buf.device)].cpu().numpy().astype(np.float32))
+        size = sum(a.nbytes for a in arrays.values())
+        assert size <= budget, "dump of %d bytes over the %d-byte budget" % (size, budget)
+        os.makedirs(out_dir, exist_ok=True)
+        for name, a in arrays.items():
+            np.save(os.path.join(out_dir, name + ".npy"), a)
+        return {"dir": out_dir, "bytes": int(size), "files": {k: list(a.shape) for k, a in arrays.items()}}
 
     def reference_stream(self, tile_np, reps, block, which):
         """BASELINE config 3: the REFERENCE's encoder (libdeflate 1.23 / zlib 1.3.1 built from the reference
@@ -645,6 +696,7 @@ def main():
     s = summary(res, args.steps, world, args.mode)
     verified = B.verify_encode(res, data, block) if args.mode == "encode" else {
         "how": "every pass: status, lengths, per-block CRC-32 against the reference stream's; first and last blocks byte for byte"}
+    dumped = B.dump_outputs(res, args.mode, args.dump_outputs) if args.dump_outputs and rank == 0 else None
 
     # HBM bytes per launch from the PMC counters: NOT measured in this run (counters need rocprofv3 around the
     # process); the tracked file holds the figure of the same command under `rocprofv3 --pmc` (tools/prof_round.sh)
@@ -701,6 +753,8 @@ def main():
                          "kernel_ms_avg": s["kernel_ms_avg"]},
         }
         line["verified"] = verified
+        if dumped is not None:
+            line["outputs"] = dumped
         line["ranks_seen"] = len(B.rank_elapsed)
         line["value_per_rank"] = [round(total * args.steps / e / 1e9, 3) for e in B.rank_elapsed]
         if B.use_dist and args.mode == "encode":

@@ -85,3 +85,33 @@ def test_bench_two_ranks_share_the_card_and_exchange_totals():
     assert so["totals"][0] != so["totals"][1]                # every rank has its own seed: its own shard of the stream
     assert "gloo" in j["config"]["collective"] and "all_gather" in j["config"]["step"]
     assert abs(j["value"] - 2 * (1 << 30) * j["steps"] / (j["ms_per_step"] * j["steps"] / 1e3) / 1e9) < 0.02 * j["value"]
+
+
+@pytest.mark.gpu
+def test_bench_dumps_what_the_last_step_computed(tmp_path):
+    """--dump-outputs DIR: float arrays of the last timed step, under the 64 MB budget, the same for any --steps.  The
+    member table describes the stream (contiguous, the head starts with a BGZF header, every sampled member ends with
+    its ISIZE), and a second run with other --steps / --warmup writes the same arrays."""
+    import numpy as np
+    a, b = tmp_path / "a", tmp_path / "b"
+    j = run_bench({}, "--dump-outputs", str(a))
+    run_bench({}, "--steps", "2", "--warmup", "0", "--dump-outputs", str(b))
+    assert j["outputs"]["bytes"] <= 64_000_000
+    names = sorted(p.name for p in a.iterdir())
+    assert names == sorted(p.name for p in b.iterdir()) == sorted(n + ".npy" for n in j["outputs"]["files"])
+    arr = {n[:-4]: np.load(str(a / n)) for n in names}
+    for n in names:
+        assert arr[n[:-4]].dtype in (np.float32, np.float64), n
+        assert np.array_equal(arr[n[:-4]], np.load(str(b / n))), n
+    off, ln = arr["member_offset"].astype(np.int64), arr["member_len"].astype(np.int64)
+    assert len(off) == j["config"]["blocks_per_gpu"] and off[0] == 0 and np.array_equal(off[1:], off[:-1] + ln[:-1])
+    assert list(arr["stream_head"][:4]) == [0x1f, 0x8b, 8, 4]
+    smp = arr["stream_sample"].astype(np.int64)
+    pos = 0
+    for i in arr["sample_members"].astype(np.int64):
+        m = smp[pos:pos + ln[i]]
+        assert list(m[:4]) == [0x1f, 0x8b, 8, 4]
+        isize = int(m[-4]) | int(m[-3]) << 8 | int(m[-2]) << 16 | int(m[-1]) << 24
+        assert isize == min(0xff00, j["config"]["input_bytes_per_gpu"] - i * 0xff00)
+        pos += ln[i]
+    assert pos == len(smp)
