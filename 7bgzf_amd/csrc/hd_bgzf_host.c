@@ -38,15 +38,13 @@
 #include <sys/time.h>
 #include <unistd.h>
 #include "hipdeflate.h"
+#include "hd_host_util.h"
 
 #define HD_BATCH 4096          /* decode: members per launch */
 #define HD_PIPE_BATCH 512      /* encode: blocks per pipe batch (32 MiB of pinned input each; pinning memory costs ~0.3 ms per MiB) */
 
 static const unsigned char eof_member[28] = { 0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0x00, 0xff, 0x06, 0x00, 'B',
 					      'C',  0x02, 0x00, 0x1b, 0x00, 0x03, 0x00, 0, 0, 0, 0, 0, 0, 0, 0 };
-
-static uint32_t rd16(const unsigned char *p) { return p[0] | (p[1] << 8); }
-static uint32_t rd32(const unsigned char *p) { return rd16(p) | (rd16(p + 2) << 16); }
 
 static size_t g_block = 0xff00;
 static int g_frame = HD_FRAME_BGZF;
@@ -318,13 +316,6 @@ static off_t g_in_size;
 static double g_t_ctor, g_t_main;       /* HD7BGZF_TIMING: when the process' constructors ran, when main() began */
 static int g_timing;                 /* HD7BGZF_TIMING=1: where the wall time of the file-to-file path goes (stderr) */
 static double g_t_read, g_t_write, g_t_result, g_t_open, g_t_input;
-
-static double now_s(void)
-{
-	struct timeval tv;
-	gettimeofday(&tv, NULL);
-	return tv.tv_sec + tv.tv_usec * 1e-6;
-}
 
 static void *file_reader_main(void *arg)
 {

@@ -13,29 +13,15 @@
  * device).  The reader inflates the members' payloads in batches; non-compressed
  * areas (which neither writer makes) are honoured.
  */
-#include <errno.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <unistd.h>
-#include "hipdeflate.h"
-#include "hd_host_util.h"
+#include "hd_host_batch.h"
 
 #define DX_BLOCK 8192u
 #define DX_BATCH 32768u
-
-static size_t read_full(FILE *f, unsigned char *buf, size_t want)
-{
-	size_t got = 0;
-	while (got < want) {
-		size_t r = fread(buf + got, 1, want - got, f);
-		if (!r)
-			break;
-		got += r;
-	}
-	return got;
-}
 
 static int dx_compress(FILE *in, FILE *out, int level)
 {
@@ -45,74 +31,55 @@ static int dx_compress(FILE *in, FILE *out, int level)
 		return 2;
 	}
 	const uint32_t nblk = (uint32_t)((total + DX_BLOCK - 1) / DX_BLOCK);
-	const size_t stride = (size_t)hipdeflate_bound(DX_BLOCK, level);
 	unsigned char hdr[32] = { 'D', 'A', 'X', 0 };
 	wr32(hdr + 4, (uint32_t)total);
 	wr32(hdr + 8, 1);
+	struct hd_batch b;
+	int ret = hd_batch_open(&b, DX_BATCH, (size_t)DX_BATCH * DX_BLOCK, hipdeflate_bound(DX_BLOCK, level), 0);
 	unsigned char *index = calloc(6, (size_t)nblk + 1);
-	unsigned char *ibuf = malloc((size_t)DX_BATCH * DX_BLOCK + 16);
-	unsigned char *obuf = malloc((size_t)DX_BATCH * stride + 16);
-	uint64_t *off = malloc(sizeof(uint64_t) * DX_BATCH);
-	uint32_t *len = malloc(sizeof(uint32_t) * DX_BATCH);
-	uint32_t *olen = malloc(sizeof(uint32_t) * DX_BATCH);
-	int32_t *st = malloc(sizeof(int32_t) * DX_BATCH);
-	if (!index || !ibuf || !obuf || !off || !len || !olen || !st) {
+	if (!ret && !index) {
 		fprintf(stderr, "out of memory\n");
-		return 2;
+		ret = 2;
 	}
+	if (ret)
+		goto out;
 	unsigned char *sizes = index + 4 * (size_t)nblk;
 	fwrite(hdr, 1, 32, out);
 	fwrite(index, 1, 6 * (size_t)nblk, out);
 	uint64_t pos = 32 + 6 * (uint64_t)nblk;
 	long long left = total;
-	int ret = 0;
-	for (uint32_t c = 0; c < nblk && !ret; c += DX_BATCH) {
+	for (uint32_t c = 0; c < nblk; c += DX_BATCH) {
 		const uint32_t n = nblk - c < DX_BATCH ? nblk - c : DX_BATCH;
-		const size_t want = left < (long long)n * DX_BLOCK ? (size_t)left : (size_t)n * DX_BLOCK;
-		if (fread(ibuf, 1, want, in) != want) {
-			fprintf(stderr, "short read\n");
-			ret = 2;
-			break;
-		}
+		if ((ret = hd_batch_read(&b, in, n, DX_BLOCK, &left)) || (ret = hd_batch_deflate(&b, n, level, HD_FRAME_ZLIB, HD_FRAME_ZLIB)))
+			goto out;
 		for (uint32_t i = 0; i < n; i++) {
-			off[i] = (uint64_t)i * DX_BLOCK;
-			len[i] = want - (size_t)off[i] < DX_BLOCK ? (uint32_t)(want - (size_t)off[i]) : DX_BLOCK;
-		}
-		int r = hipdeflate_batch_deflate(ibuf, off, len, n, level, HD_FRAME_ZLIB, obuf, stride, (uint32_t)stride, olen, NULL, st);
-		if (r) {
-			fprintf(stderr, "hip_deflate %d\n", r);
-			ret = 1;
-			break;
-		}
-		for (uint32_t i = 0; i < n; i++) {
-			if (st[i] || olen[i] > 0xffff) {
-				fprintf(stderr, "hip_deflate %d\n", st[i] ? st[i] : 1);
+			if (b.olen[i] > 0xffff) {
+				fprintf(stderr, "hip_deflate 1\n");
 				ret = 1;
-				break;
+				goto out;
 			}
 			if (pos >= (1ull << 32)) {
 				fprintf(stderr, "output too large for 32-bit DAX offsets\n");
 				ret = 2;
-				break;
+				goto out;
 			}
 			wr32(index + 4 * (size_t)(c + i), (uint32_t)pos);
-			wr16(sizes + 2 * (size_t)(c + i), olen[i]);
-			fwrite(obuf + (size_t)i * stride, 1, olen[i], out);
-			pos += olen[i];
+			wr16(sizes + 2 * (size_t)(c + i), b.olen[i]);
+			fwrite(b.out + (size_t)i * b.stride, 1, b.olen[i], out);
+			pos += b.olen[i];
 		}
-		left -= (long long)want;
 		fprintf(stderr, "%u / %u\r", c + n, nblk);
 	}
-	if (!ret) {
-		fseeko(out, 32, SEEK_SET);
-		fwrite(index, 1, 6 * (size_t)nblk, out);
-		fprintf(stderr, "%u / %u done.\n", nblk, nblk);
-		if (fflush(out) || ferror(out)) {
-			fprintf(stderr, "write error\n");
-			ret = 2;
-		}
+	fseeko(out, 32, SEEK_SET);
+	fwrite(index, 1, 6 * (size_t)nblk, out);
+	fprintf(stderr, "%u / %u done.\n", nblk, nblk);
+	if (fflush(out) || ferror(out)) {
+		fprintf(stderr, "write error\n");
+		ret = 2;
 	}
-	free(index), free(ibuf), free(obuf), free(off), free(len), free(olen), free(st);
+out:
+	hd_batch_close(&b);
+	free(index);
 	return ret;
 }
 
@@ -129,31 +96,31 @@ static int dx_decompress(FILE *in, FILE *out)
 		fprintf(stderr, "not DAX\n");
 		return 1;
 	}
+	struct hd_batch b;
+	int ret = hd_batch_open(&b, DX_BATCH, (size_t)DX_BATCH * (DX_BLOCK + 64), DX_BLOCK, 0);
 	unsigned char *index = malloc(6 * (size_t)nblk + 8 * (size_t)nnc + 16);
-	if (!index || read_full(in, index, 6 * (size_t)nblk + 8 * (size_t)nnc) != 6 * (size_t)nblk + 8 * (size_t)nnc) {
-		fprintf(stderr, "unexpected end of file\n");
-		return 1;
-	}
-	const unsigned char *sizes = index + 4 * (size_t)nblk, *nc = sizes + 2 * (size_t)nblk;
 	/* frames of the non-compressed areas: plain 8192-byte frames in the file (:194-203) */
 	unsigned char *plain = calloc(1, (size_t)nblk + 1);
-	unsigned char *ibuf = malloc((size_t)DX_BATCH * (DX_BLOCK + 64) + 16), *obuf = malloc((size_t)DX_BATCH * DX_BLOCK + 16);
-	uint64_t *ioff = malloc(sizeof(uint64_t) * DX_BATCH), *ooff = malloc(sizeof(uint64_t) * DX_BATCH);
-	uint32_t *ilen = malloc(sizeof(uint32_t) * DX_BATCH), *cap = malloc(sizeof(uint32_t) * DX_BATCH);
-	uint32_t *olen = malloc(sizeof(uint32_t) * DX_BATCH), *map = malloc(sizeof(uint32_t) * DX_BATCH);
-	int32_t *st = malloc(sizeof(int32_t) * DX_BATCH);
-	if (!plain || !ibuf || !obuf || !ioff || !ooff || !ilen || !cap || !olen || !map || !st) {
-		fprintf(stderr, "out of memory\n");
-		return 2;
+	if (ret)
+		goto out;
+	if (!index || read_full(in, index, 6 * (size_t)nblk + 8 * (size_t)nnc) != 6 * (size_t)nblk + 8 * (size_t)nnc) {
+		fprintf(stderr, "unexpected end of file\n");
+		ret = 1;
+		goto out;
 	}
+	if (!plain) {
+		fprintf(stderr, "out of memory\n");
+		ret = 2;
+		goto out;
+	}
+	const unsigned char *sizes = index + 4 * (size_t)nblk, *nc = sizes + 2 * (size_t)nblk;
 	for (uint32_t k = 0; k < nnc; k++) {
 		const uint32_t first = rd32(nc + 8 * (size_t)k), cnt = rd32(nc + 8 * (size_t)k + 4);
 		for (uint32_t j = 0; j < cnt && (uint64_t)first + j < nblk; j++)
 			plain[first + j] = 1;
 	}
 	uint64_t produced = 0;
-	int ret = 0;
-	for (uint32_t c = 0; c < nblk && !ret; c += DX_BATCH) {
+	for (uint32_t c = 0; c < nblk; c += DX_BATCH) {
 		const uint32_t m = nblk - c < DX_BATCH ? nblk - c : DX_BATCH;
 		size_t itotal = 0;
 		uint32_t nz = 0;
@@ -161,137 +128,95 @@ static int dx_decompress(FILE *in, FILE *out)
 			const uint32_t want = (uint64_t)(c + i + 1) * DX_BLOCK <= total ? DX_BLOCK : (uint32_t)(total - (uint64_t)(c + i) * DX_BLOCK);
 			const uint32_t sz = plain[c + i] ? DX_BLOCK : rd16(sizes + 2 * (size_t)(c + i));
 			if (sz > DX_BLOCK + 64 || (!plain[c + i] && sz < 6)) {
+				fprintf(stderr, "corrupted size table\n");
 				ret = 1;
-				break;
+				goto out;
 			}
 			if (!plain[c + i]) {
-				ioff[nz] = itotal + 2;                 /* behind the two zlib header bytes */
-				ilen[nz] = sz - 2;                     /* the Adler-32 rides along as trailing bytes */
-				ooff[nz] = (uint64_t)i * DX_BLOCK;
-				cap[nz] = want;
-				map[nz++] = i;
+				b.off[nz] = itotal + 2;                /* behind the two zlib header bytes */
+				b.len[nz] = sz - 2;                    /* the Adler-32 rides along as trailing bytes */
+				b.ooff[nz] = (uint64_t)i * DX_BLOCK;
+				b.cap[nz++] = want;
 			}
 			itotal += sz;
 		}
-		if (ret) {
-			fprintf(stderr, "corrupted size table\n");
-			break;
-		}
-		if (read_full(in, ibuf, itotal) != itotal) {
+		if (read_full(in, b.in, itotal) != itotal) {
 			fprintf(stderr, "unexpected end of file\n");
 			ret = 1;
-			break;
+			goto out;
 		}
 		size_t at = 0;
 		for (uint32_t i = 0; i < m; i++) {
 			if (plain[c + i]) {
-				memcpy(obuf + (size_t)i * DX_BLOCK, ibuf + at, DX_BLOCK);
+				memcpy(b.out + (size_t)i * DX_BLOCK, b.in + at, DX_BLOCK);
 				at += DX_BLOCK;
 			} else {
-				if ((ibuf[at] & 0x0f) != 8 || ((ibuf[at] << 8) | ibuf[at + 1]) % 31) {
+				if ((b.in[at] & 0x0f) != 8 || ((b.in[at] << 8) | b.in[at + 1]) % 31) {
 					fprintf(stderr, "frame %u is not a zlib stream\n", c + i);
 					ret = 1;
-					break;
+					goto out;
 				}
 				at += rd16(sizes + 2 * (size_t)(c + i));
 			}
 		}
-		if (ret)
-			break;
-		if (nz) {
-			int r = hipdeflate_batch_inflate(ibuf, ioff, ilen, nz, obuf, ooff, cap, olen, NULL, st);
-			if (r) {
-				fprintf(stderr, "inflate %d\n", r);
-				ret = 1;
-				break;
-			}
-		}
+		if ((ret = hd_batch_inflate(&b, nz, 0)))
+			goto out;
 		for (uint32_t k = 0; k < nz; k++) {
-			if (st[k] || olen[k] != cap[k]) {
-				fprintf(stderr, "inflate %d\n", st[k] ? st[k] : 1);
+			if (b.olen[k] != b.cap[k]) {
+				fprintf(stderr, "inflate 1\n");
 				ret = 1;
-				break;
+				goto out;
 			}
 		}
-		if (ret)
-			break;
 		const uint64_t bytes = produced + (uint64_t)m * DX_BLOCK <= total ? (uint64_t)m * DX_BLOCK : total - produced;
-		fwrite(obuf, 1, (size_t)bytes, out);
+		fwrite(b.out, 1, (size_t)bytes, out);
 		produced += bytes;
 		fprintf(stderr, "%u / %u\r", c + m, nblk);
 	}
-	if (!ret) {
-		fprintf(stderr, "%u / %u done.\n", nblk, nblk);
-		if (fflush(out) || ferror(out)) {
-			fprintf(stderr, "write error\n");
-			ret = 2;
-		}
+	fprintf(stderr, "%u / %u done.\n", nblk, nblk);
+	if (fflush(out) || ferror(out)) {
+		fprintf(stderr, "write error\n");
+		ret = 2;
 	}
-	free(index), free(plain), free(ibuf), free(obuf), free(ioff), free(ooff), free(ilen), free(cap), free(olen), free(map), free(st);
+out:
+	hd_batch_close(&b);
+	free(index);
+	free(plain);
 	return ret;
 }
 
 int main(int argc, char **argv)
 {
-	int level = -1, decode = 0, bad = 0, nn = 0;
-	const char *names[2] = { NULL, NULL };
-	for (int i = 1; i < argc; i++) {
-		const char *a = argv[i];
-		if (a[0] == '-' && a[1]) {
-			for (const char *p = a + 1; *p; p++) {
-				if (*p == 'd')
-					decode = 1;
-				else if (*p == 'c')
-					;
-				else if (*p == '@')
-					break;                          /* -@<threads>: accepted and ignored */
-				else if (*p == 'G' || *p == 'l') {
-					level = p[1] ? atoi(p + 1) : 1;
-					break;
-				} else {
-					bad = 1;
-					break;
-				}
-			}
-		} else if (nn < 2) {
-			names[nn++] = a;
-		} else {
-			bad = 1;
-		}
-	}
-	if (bad || (decode && (nn || level >= 0)) || (!decode && (nn != 2 || level < 0 || level > 9)) ||
-	    (decode && (isatty(0) || isatty(1)))) {
+	struct hd_host_args a;
+	hd_host_parse(&a, argc, argv, NULL);
+	if (a.bad || (a.decode && (a.n || a.level >= 0)) || (!a.decode && (a.n != 2 || a.level < 0 || a.level > 9)) ||
+	    (a.decode && (isatty(0) || isatty(1)))) {
 		fprintf(stderr, "usage: %s -G<level> dec.iso enc.dax   or   -d < enc.dax > dec.iso\n", argv[0]);
 		return 1;
 	}
-	int r = hipdeflate_init(-1);
-	if (r) {
-		fprintf(stderr, "hipdeflate: no usable device (%d): %s\n", r, hipdeflate_version());
-		return 4;
-	}
-	const double t0 = now_s();
-	int ret;
-	if (decode) {
+	double t0;
+	int ret = hd_host_begin(&t0);
+	if (ret)
+		return ret;
+	if (a.decode) {
 		ret = dx_decompress(stdin, stdout);
 	} else {
-		FILE *in = fopen(names[0], "rb");
+		FILE *in = fopen(a.name[0], "rb");
 		if (!in) {
-			fprintf(stderr, "failed to open %s\n", names[0]);
+			fprintf(stderr, "failed to open %s\n", a.name[0]);
 			return 2;
 		}
-		FILE *out = fopen(names[1], "wb");
+		FILE *out = fopen(a.name[1], "wb");
 		if (!out) {
-			fprintf(stderr, "failed to open %s\n", names[1]);
+			fprintf(stderr, "failed to open %s\n", a.name[1]);
 			fclose(in);
 			return 3;
 		}
-		fprintf(stderr, "compression level = %d (hip)\n", level);
-		ret = dx_compress(in, out, level);
+		fprintf(stderr, "compression level = %d (hip)\n", a.level);
+		ret = dx_compress(in, out, a.level);
 		fclose(in);
 		if (fclose(out) && !ret)
 			ret = 2;
 	}
-	fprintf(stderr, "ellapsed time: %.3f sec\n", now_s() - t0);
-	hipdeflate_shutdown();
-	return ret;
+	return hd_host_end(t0, ret);
 }

@@ -16,13 +16,11 @@
  * per-chunk CRCs the kernel returns (the reference runs fcrc32 over the input on
  * the host, :203), and the reader checks it, which the reference's does not.
  */
-#include <errno.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include "hipdeflate.h"
-#include "hd_host_util.h"
+#include "hd_host_batch.h"
 
 #define DZ_BATCH 2048                 /* chunks per device call */
 #define DZ_MAX_CHUNKS 32762           /* (0xffff - 10) / 2, applet/7dictzip.c:180 */
@@ -37,21 +35,17 @@ static int dz_compress(FILE *in, FILE *out, int level, uint32_t block_size)
 		fprintf(stderr, "cannot stat the input\n");
 		return 2;
 	}
-	const size_t stride = up16((size_t)block_size + 5 * (block_size / 65535 + 1) + 32);
-	unsigned char *ibuf = malloc((size_t)DZ_BATCH * block_size + 16);
-	unsigned char *obuf = malloc((size_t)DZ_BATCH * stride + 16);
-	uint64_t *off = malloc(sizeof(uint64_t) * DZ_BATCH);
-	uint32_t *len = malloc(sizeof(uint32_t) * DZ_BATCH);
-	uint32_t *olen = malloc(sizeof(uint32_t) * DZ_BATCH);
-	uint32_t *crc = malloc(sizeof(uint32_t) * DZ_BATCH);
-	int32_t *st = malloc(sizeof(int32_t) * DZ_BATCH);
+	/* a slot under 65535 bytes: every chunk's size fits the 16-bit table */
+	struct hd_batch b;
+	int ret = hd_batch_open(&b, DZ_BATCH, (size_t)DZ_BATCH * block_size, up16((size_t)block_size + 5 * (block_size / 65535 + 1) + 32), 1);
 	unsigned char *sizes = malloc(2 * DZ_MAX_CHUNKS + 16);
-	if (!ibuf || !obuf || !off || !len || !olen || !crc || !st || !sizes) {
+	if (!ret && !sizes) {
 		fprintf(stderr, "out of memory\n");
-		return 2;
+		ret = 2;
 	}
+	if (ret)
+		goto out;
 	long long done = 0;
-	int ret = 0;
 	do {
 		const long long cur = total - done < max_member ? total - done : max_member;
 		const uint32_t nchunks = (uint32_t)((cur + block_size - 1) / block_size);
@@ -69,41 +63,18 @@ static int dz_compress(FILE *in, FILE *out, int level, uint32_t block_size)
 
 		struct crc_fold fold = { 0, 0, 0 };
 		long long left = cur;
-		for (uint32_t c = 0; c < nchunks && !ret; c += DZ_BATCH) {
+		for (uint32_t c = 0; c < nchunks; c += DZ_BATCH) {
 			const uint32_t n = nchunks - c < DZ_BATCH ? nchunks - c : DZ_BATCH;
-			const size_t want = left < (long long)n * block_size ? (size_t)left : (size_t)n * block_size;
-			if (fread(ibuf, 1, want, in) != want) {
-				fprintf(stderr, "short read\n");
-				ret = 2;
-				break;
-			}
+			if ((ret = hd_batch_read(&b, in, n, block_size, &left)) ||
+			    (ret = hd_batch_deflate(&b, n, level, HD_FRAME_RAW_FLUSH, HD_FRAME_RAW_FLUSH)))
+				goto out;
 			for (uint32_t i = 0; i < n; i++) {
-				off[i] = (uint64_t)i * block_size;
-				const size_t rest = want - (size_t)off[i];
-				len[i] = rest < block_size ? (uint32_t)rest : block_size;
+				wr16(sizes + 2 * (size_t)(c + i), b.olen[i]);
+				fwrite(b.out + (size_t)i * b.stride, 1, b.olen[i], out);
+				crc_append(&fold, b.crc[i], b.len[i]);
 			}
-			int r = hipdeflate_batch_deflate(ibuf, off, len, n, level, HD_FRAME_RAW_FLUSH, obuf, stride, 65535, olen, crc,
-							 st);
-			if (r) {
-				fprintf(stderr, "hip_deflate %d\n", r);
-				ret = 1;
-				break;
-			}
-			for (uint32_t i = 0; i < n; i++) {
-				if (st[i]) {
-					fprintf(stderr, "hip_deflate %d\n", st[i]);
-					ret = 1;
-					break;
-				}
-				wr16(sizes + 2 * (size_t)(c + i), olen[i]);
-				fwrite(obuf + (size_t)i * stride, 1, olen[i], out);
-				crc_append(&fold, crc[i], len[i]);
-			}
-			left -= (long long)want;
 			fprintf(stderr, "%u / %u\r", c + n, nchunks);
 		}
-		if (ret)
-			break;
 		const long long pos = ftello(out);
 		fseeko(out, pos_sizes, SEEK_SET);
 		fwrite(sizes, 1, 2 * (size_t)nchunks, out);
@@ -115,11 +86,13 @@ static int dz_compress(FILE *in, FILE *out, int level, uint32_t block_size)
 		fprintf(stderr, "%u / %u done.\n", nchunks, nchunks);
 		done += cur;
 	} while (done < total);
-	if (!ret && (fflush(out) || ferror(out))) {
+	if (fflush(out) || ferror(out)) {
 		fprintf(stderr, "write error\n");
 		ret = 2;
 	}
-	free(ibuf), free(obuf), free(off), free(len), free(olen), free(crc), free(st), free(sizes);
+out:
+	hd_batch_close(&b);
+	free(sizes);
 	return ret;
 }
 
@@ -157,20 +130,17 @@ static size_t dz_header(const unsigned char *d, size_t size, size_t *sizes_off, 
 
 static int dz_decompress(FILE *in, FILE *out)
 {
-	unsigned char *head = malloc(65536 + 280);
-	unsigned char *ibuf = NULL, *obuf = NULL;
-	size_t icap = 0, ocap = 0;
-	uint64_t *ioff = malloc(sizeof(uint64_t) * DZ_BATCH), *ooff = malloc(sizeof(uint64_t) * DZ_BATCH);
-	uint32_t *ilen = malloc(sizeof(uint32_t) * DZ_BATCH), *cap = malloc(sizeof(uint32_t) * DZ_BATCH);
-	uint32_t *olen = malloc(sizeof(uint32_t) * DZ_BATCH), *crc = malloc(sizeof(uint32_t) * DZ_BATCH);
-	int32_t *st = malloc(sizeof(int32_t) * DZ_BATCH);
 	const long long fsize = file_size(in);
-	int ret = 0;
-	if (!head || !ioff || !ooff || !ilen || !cap || !olen || !crc || !st) {
+	struct hd_batch b;
+	int ret = hd_batch_open(&b, DZ_BATCH, 0, 0, 1);
+	unsigned char *head = malloc(65536 + 280);
+	if (!ret && !head) {
 		fprintf(stderr, "out of memory\n");
-		return 2;
+		ret = 2;
 	}
-	while (!ret) {
+	if (ret)
+		goto out;
+	for (;;) {
 		const long long pos = ftello(in);
 		if (pos >= fsize)
 			break;
@@ -181,60 +151,38 @@ static int dz_decompress(FILE *in, FILE *out)
 		if (!n || !block_size) {
 			fprintf(stderr, "header is not gzip (possibly corrupted)\n");
 			ret = 1;
-			break;
+			goto out;
 		}
 		const unsigned char *sizes = head + sizes_off;
 		fseeko(in, pos + (long long)n, SEEK_SET);
 		struct crc_fold fold = { 0, 0, 0 };
 		uint64_t produced = 0;
-		for (uint32_t c = 0; c < nchunks && !ret; c += DZ_BATCH) {
+		for (uint32_t c = 0; c < nchunks; c += DZ_BATCH) {
 			const uint32_t m = nchunks - c < DZ_BATCH ? nchunks - c : DZ_BATCH;
 			size_t itotal = 0;
 			for (uint32_t i = 0; i < m; i++) {
-				ioff[i] = itotal;
-				ilen[i] = rd16(sizes + 2 * (size_t)(c + i));
-				itotal += ilen[i];
-				ooff[i] = (uint64_t)i * up16(block_size);
-				cap[i] = block_size;
+				b.off[i] = itotal;
+				b.len[i] = rd16(sizes + 2 * (size_t)(c + i));
+				itotal += b.len[i];
+				b.ooff[i] = (uint64_t)i * up16(block_size);
+				b.cap[i] = block_size;
 			}
-			if (itotal + 16 > icap) {
-				free(ibuf);
-				ibuf = malloc(icap = itotal + 16);
-			}
-			if ((size_t)m * up16(block_size) + 16 > ocap) {
-				free(obuf);
-				obuf = malloc(ocap = (size_t)m * up16(block_size) + 16);
-			}
-			if (!ibuf || !obuf) {
-				fprintf(stderr, "out of memory\n");
-				ret = 2;
-				break;
-			}
-			if (fread(ibuf, 1, itotal, in) != itotal) {
+			if ((ret = hd_grow(&b.in, &b.icap, itotal)) || (ret = hd_grow(&b.out, &b.ocap, (size_t)m * up16(block_size))))
+				goto out;
+			if (fread(b.in, 1, itotal, in) != itotal) {
 				fprintf(stderr, "unexpected end of file\n");
 				ret = 1;
-				break;
+				goto out;
 			}
-			int r = hipdeflate_batch_inflate_flush(ibuf, ioff, ilen, m, obuf, ooff, cap, olen, crc, st);
-			if (r) {
-				fprintf(stderr, "inflate %d\n", r);
-				ret = 1;
-				break;
-			}
+			if ((ret = hd_batch_inflate(&b, m, 1)))
+				goto out;
 			for (uint32_t i = 0; i < m; i++) {
-				if (st[i]) {
-					fprintf(stderr, "inflate %d\n", st[i]);
-					ret = 1;
-					break;
-				}
-				fwrite(obuf + ooff[i], 1, olen[i], out);
-				crc_append(&fold, crc[i], olen[i]);
-				produced += olen[i];
+				fwrite(b.out + b.ooff[i], 1, b.olen[i], out);
+				crc_append(&fold, b.crc[i], b.olen[i]);
+				produced += b.olen[i];
 			}
 			fprintf(stderr, "%u / %u\r", c + m, nchunks);
 		}
-		if (ret)
-			break;
 		fprintf(stderr, "%u / %u done.\n", nchunks, nchunks);
 		/* trailer: `03 00` (ours and the reference's writer) or nothing (classic dictzip, whose last
 		 * chunk carries the final block), then CRC-32 and ISIZE; applet/7dictzip.c:393-399 */
@@ -246,86 +194,56 @@ static int dz_decompress(FILE *in, FILE *out)
 		if (tn < at + 8) {
 			fprintf(stderr, "unexpected end of file\n");
 			ret = 1;
-			break;
+			goto out;
 		}
 		if (rd32(t + at) != fold.crc || rd32(t + at + 4) != (uint32_t)produced) {
 			fprintf(stderr, "crc32 / size mismatch\n");
 			ret = 1;
-			break;
+			goto out;
 		}
 		fseeko(in, -(long long)(tn - at - 8), SEEK_CUR);
 	}
-	if (!ret && (fflush(out) || ferror(out))) {
+	if (fflush(out) || ferror(out)) {
 		fprintf(stderr, "write error\n");
 		ret = 2;
 	}
-	free(head), free(ibuf), free(obuf), free(ioff), free(ooff), free(ilen), free(cap), free(olen), free(crc), free(st);
+out:
+	hd_batch_close(&b);
+	free(head);
 	return ret;
 }
 
 int main(int argc, char **argv)
 {
-	int level = -1, decode = 0, extreme = 0;
-	const char *names[2] = { NULL, NULL };
-	int nn = 0;
-	for (int i = 1; i < argc; i++) {
-		const char *a = argv[i];
-		if (a[0] == '-' && a[1]) {
-			for (const char *p = a + 1; *p; p++) {
-				if (*p == 'd')
-					decode = 1;
-				else if (*p == 'c')
-					;
-				else if (*p == '@')
-					break;                          /* -@<threads>: accepted and ignored */
-				else if (*p == 'X')
-					extreme = 1;
-				else if (*p == 'G' || *p == 'l') {
-					level = p[1] ? atoi(p + 1) : 1;
-					break;
-				} else {
-					nn = 3;
-					break;
-				}
-			}
-		} else if (nn < 2) {
-			names[nn++] = a;
-		} else {
-			nn = 3;
-		}
-	}
-	if (nn == 3 || (decode && (nn != 1 || level >= 0)) || (!decode && (nn != 2 || level < 0 || level > 9))) {
+	struct hd_host_args a;
+	hd_host_parse(&a, argc, argv, "X");
+	if (a.bad || (a.decode && (a.n != 1 || a.level >= 0)) || (!a.decode && (a.n != 2 || a.level < 0 || a.level > 9))) {
 		fprintf(stderr, "usage: %s -G<level> [-X] dec.bin enc.dz   or   -d enc.dz > dec.bin\n", argv[0]);
 		return 1;
 	}
-	int r = hipdeflate_init(-1);
-	if (r) {
-		fprintf(stderr, "hipdeflate: no usable device (%d): %s\n", r, hipdeflate_version());
-		return 4;
-	}
-	const double t0 = now_s();
-	int ret;
-	FILE *in = fopen(names[0], "rb");
+	double t0;
+	int ret = hd_host_begin(&t0);
+	if (ret)
+		return ret;
+	FILE *in = fopen(a.name[0], "rb");
 	if (!in) {
-		fprintf(stderr, "failed to open %s\n", names[0]);
+		fprintf(stderr, "failed to open %s\n", a.name[0]);
 		return 2;
 	}
-	if (decode) {
+	if (a.decode) {
 		ret = dz_decompress(in, stdout);
 	} else {
-		FILE *out = fopen(names[1], "wb");
+		FILE *out = fopen(a.name[1], "wb");
 		if (!out) {
-			fprintf(stderr, "failed to open %s\n", names[1]);
+			fprintf(stderr, "failed to open %s\n", a.name[1]);
 			fclose(in);
 			return 3;
 		}
-		fprintf(stderr, "compression level = %d (hip)\n", level);
-		ret = dz_compress(in, out, level, extreme ? 0xff00 : 58315);
+		fprintf(stderr, "compression level = %d (hip)\n", a.level);
+		ret = dz_compress(in, out, a.level, a.opt ? 0xff00 : 58315);
 		if (fclose(out) && !ret)
 			ret = 2;
 	}
 	fclose(in);
-	fprintf(stderr, "ellapsed time: %.3f sec\n", now_s() - t0);
-	hipdeflate_shutdown();
-	return ret;
+	return hd_host_end(t0, ret);
 }

@@ -1,6 +1,7 @@
 /*
- * hd_host_util.h -- what the container hosts (hd7dictzip, hd7razf) share: little/big
- * endian fields, the CRC-32 of a concatenation from the CRCs of its parts, a clock.
+ * hd_host_util.h -- what the container hosts (hd7bgzf, hd7dictzip, hd7razf, hd7gzinga, hd7ciso,
+ * hd7daxcr, hd7png) share: little/big endian fields, the CRC-32 of a concatenation from the
+ * CRCs of its parts, a clock, file helpers.
  */
 #ifndef HD_HOST_UTIL_H
 #define HD_HOST_UTIL_H
@@ -69,6 +70,19 @@ static inline long long file_size(FILE *f)
 	if (fstat(fileno(f), &st))
 		return -1;
 	return st.st_size;
+}
+
+/* fread until want bytes or the end of the input (a pipe returns short counts) */
+static inline size_t read_full(FILE *f, unsigned char *buf, size_t want)
+{
+	size_t got = 0;
+	while (got < want) {
+		size_t r = fread(buf + got, 1, want - got, f);
+		if (!r)
+			break;
+		got += r;
+	}
+	return got;
 }
 
 static inline void wr32be(unsigned char *p, uint32_t v) { p[0] = v >> 24, p[1] = (v >> 16) & 0xff, p[2] = (v >> 8) & 0xff, p[3] = v & 0xff; }

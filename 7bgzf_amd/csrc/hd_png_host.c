@@ -20,9 +20,7 @@
 #include <string.h>
 #include "hipdeflate.h"
 #include "zlibutil_hip.h"
-
-static uint32_t be32(const unsigned char *p) { return (uint32_t)p[0] << 24 | p[1] << 16 | p[2] << 8 | p[3]; }
-static void put_be32(unsigned char *p, uint32_t v) { p[0] = v >> 24; p[1] = v >> 16; p[2] = v >> 8; p[3] = v; }
+#include "hd_host_util.h"
 
 struct image {
 	const char *in_path, *out_path;
@@ -73,7 +71,7 @@ static int load(struct image *im, FILE *f)
 	size_t pos = 8;
 	int seen_ihdr = 0;
 	while (pos + 12 <= im->file_len) {
-		const uint32_t len = be32(im->file + pos);
+		const uint32_t len = rd32be(im->file + pos);
 		const unsigned char *type = im->file + pos + 4;
 		if ((size_t)len + 12 > im->file_len - pos)
 			break;
@@ -83,7 +81,7 @@ static int load(struct image *im, FILE *f)
 		}
 		if (!memcmp(type, "IHDR", 4) && len >= 13) {
 			const unsigned char *d = im->file + pos + 8;
-			im->raw_len = png_raw_size(be32(d), be32(d + 4), d[8], d[9], d[12]);
+			im->raw_len = png_raw_size(rd32be(d), rd32be(d + 4), d[8], d[9], d[12]);
 			seen_ihdr = 1;
 		}
 		if (!memcmp(type, "IDAT", 4)) {
@@ -119,7 +117,7 @@ static int load(struct image *im, FILE *f)
 static void put_chunk(FILE *f, const char *type, const unsigned char *data, uint32_t len)
 {
 	unsigned char b[4];
-	put_be32(b, len);
+	wr32be(b, len);
 	fwrite(b, 1, 4, f);
 	fwrite(type, 1, 4, f);
 	if (len)
@@ -127,7 +125,7 @@ static void put_chunk(FILE *f, const char *type, const unsigned char *data, uint
 	unsigned int crc = hd_crc32(0, (const unsigned char *)type, 4);     /* applet/7png.c:58-61 */
 	if (len)
 		crc = hd_crc32(crc, data, len);
-	put_be32(b, crc);
+	wr32be(b, crc);
 	fwrite(b, 1, 4, f);
 }
 
@@ -142,7 +140,7 @@ static void write_png(const struct image *im, FILE *f, const unsigned char *z, u
 	size_t pos = 8;
 	int idat_done = 0;
 	while (pos + 12 <= im->file_len) {
-		const uint32_t len = be32(im->file + pos);
+		const uint32_t len = rd32be(im->file + pos);
 		const unsigned char *type = im->file + pos + 4;
 		if ((size_t)len + 12 > im->file_len - pos)
 			break;
@@ -222,7 +220,7 @@ int main(int argc, char **argv)
 	}
 	for (uint32_t k = 0; k < n; k++) {
 		const unsigned char *t = im[k].idat + im[k].idat_len - 4;
-		if (st[k] || rlen[k] != rcap[k] || hd_adler32(1, raw + roff[k], rlen[k]) != be32(t)) {
+		if (st[k] || rlen[k] != rcap[k] || hd_adler32(1, raw + roff[k], rlen[k]) != rd32be(t)) {
 			fprintf(stderr, "%s: inflate %d (pixels %u of %u bytes, Adler-32 %s)\n", im[k].in_path, st[k], rlen[k], rcap[k],
 				st[k] || rlen[k] != rcap[k] ? "not checked" : "differs");
 			return 1;
