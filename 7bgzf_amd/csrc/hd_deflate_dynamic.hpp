@@ -10,9 +10,9 @@
 //
 // One wavefront per block, persistent over a grid-stride loop so that every
 // workgroup owns one token slab in HBM:
-//   pass 1  parse (same 64-position step, prefix-scan greedy, optional one-lane
-//           lazy deferral), tokens -> LDS queue -> slab (64 at a time, coalesced
-//           4 B/lane), symbol histograms -> LDS (ds_add_u32)
+//   pass 1  parse (same 64-position step, prefix-scan greedy), tokens -> LDS
+//           queue -> slab (64 at a time, coalesced 4 B/lane), symbol histograms
+//           -> LDS (ds_add_u32)
 //   build   litlen/offset/precode code lengths: rank sort by all lanes, then the
 //           two-queue merge, depth, overflow and RLE steps on lane 0
 //   pass 2  tokens read back 64 at a time, codes looked up in LDS, <= 48 bits
@@ -85,13 +85,11 @@ inline uint64_t wg_scratch_bytes(uint32_t nblocks, uint32_t split_max, bool lat 
 	       (lat && split_max <= 65536 ? (uint64_t)(sub < 128 ? sub : 128) * 65536 + 256 : wg_beside_bytes(nblocks, split_max));
 }
 
-inline uint32_t dynamic_grid(uint32_t nblocks, int level)
+// the fused kernel (level 2): one persistent wave per slot it has on the chip, 10 per CU (11 did not fit, measured); a grid
+// larger than what is resident would run its tail serially
+inline uint32_t dynamic_grid(uint32_t nblocks)
 {
-	// one persistent wave per LDS slot of the level (levels 2-4: 14.5 KiB -> 10 resident per CU
-	// -- 11 do not fit, measured --; 5: 16 KiB -> 9; with the two-way tables 6: 21 KiB -> 7; 7: 29 KiB -> 5;
-	// 8: 35 KiB -> 4; 9: 60 KiB -> 2); a grid larger than what is resident would run its tail serially
-	const uint32_t per_cu = level >= 9 ? 2u : level >= 8 ? 4u : level >= 7 ? 5u : level >= 6 ? 7u : level >= 5 ? 9u : 10u;
-	const uint32_t slots = 256u * per_cu;
+	const uint32_t slots = 256u * 10u;
 	return nblocks < slots ? nblocks : slots;
 }
 
@@ -102,13 +100,13 @@ inline uint32_t dynamic_grid(uint32_t nblocks, int level)
 constexpr uint64_t SPLIT_SCRATCH_BUDGET = (uint64_t)12672 << 20;
 constexpr uint32_t SPLIT_SUB_BATCH_MAX = 65536;
 
-// resident waves of the parse kernel of a level (tests/test_abi.py::test_kernel_resource_budgets)
-inline uint32_t parse_slots(int level)
+// resident waves of level 2's parse kernel: 18 per CU (7 LDS units, <= 96 VGPRs: tests/test_abi.py::test_kernel_resource_budgets_by_template_args)
+inline uint32_t parse_slots()
 {
-	return 256u * (level == 2 ? 18u : level <= 4 ? 12u : level <= 5 ? 10u : level <= 6 ? 8u : level <= 7 ? 5u : level <= 8 ? 4u : 2u);
+	return 256u * 18u;
 }
 
-inline uint32_t split_sub_batch(uint32_t nblocks, uint32_t split_max, int level)
+inline uint32_t split_sub_batch(uint32_t nblocks, uint32_t split_max)
 {
 	const uint64_t per = split_layout(split_max).bytes;
 	uint64_t sub = SPLIT_SCRATCH_BUDGET / per;
@@ -124,7 +122,7 @@ inline uint32_t split_sub_batch(uint32_t nblocks, uint32_t split_max, int level)
 		return nblocks;
 	// launches are whole rounds of the resident parse waves where the budget allows one; when it allows
 	// less than half a round the fused kernel is the faster way again
-	const uint32_t slots = parse_slots(level);
+	const uint32_t slots = parse_slots();
 	if (sub >= slots)
 		sub -= sub % slots;
 	else if (sub < slots / 2)
@@ -139,9 +137,9 @@ inline uint32_t split_max_block(uint64_t out_stride, uint32_t out_cap)
 	return cap > 0x7fffffffu ? 0x7fffffffu : (uint32_t)cap;
 }
 
-inline uint64_t fused_scratch_bytes(uint32_t nblocks, int level)
+inline uint64_t fused_scratch_bytes(uint32_t nblocks)
 {
-	return (uint64_t)dynamic_grid(nblocks, level) * DYN_SLAB_TOKENS * 4;
+	return (uint64_t)dynamic_grid(nblocks) * DYN_SLAB_TOKENS * 4;
 }
 
 // segments parsed in parts (HD_LAT_PARTS; latency mode): segments per parse + emit launch pair -- all of them unless the
@@ -162,10 +160,10 @@ inline uint64_t dynamic_scratch_bytes(uint32_t nblocks, uint32_t split_max, int 
 	if (level >= HD_WG_LEVEL && !parts)
 		return wg_scratch_bytes(nblocks, split_max, lat);
 	if (parts)
-		return fused_scratch_bytes(nblocks, level) + (uint64_t)nblocks * 4 +
+		return fused_scratch_bytes(nblocks) + (uint64_t)nblocks * 4 +
 		       (uint64_t)part_sub_batch(nblocks, parts) * parts * part_layout().bytes + 16;
-	return fused_scratch_bytes(nblocks, level) + (uint64_t)nblocks * 4 +                 // + the overflow flags
-	       (uint64_t)split_sub_batch(nblocks, split_max, level) * split_layout(split_max).bytes + 16;
+	return fused_scratch_bytes(nblocks) + (uint64_t)nblocks * 4 +                        // + the overflow flags
+	       (uint64_t)split_sub_batch(nblocks, split_max) * split_layout(split_max).bytes + 16;
 }
 
 #ifdef HD_EMIT_STATS
@@ -520,16 +518,16 @@ typedef const __attribute__((address_space(1))) uint32_t *hd_global_u32p;
 #ifndef HD_BESIDE_EMIT_PRIO
 #define HD_BESIDE_EMIT_PRIO 0
 #endif
-template <int WIN_BITS, int HASH_BITS, int MINLEN, int LAZY, int EMIT, int INTRA = 0, int DEEP = 0, int PARTS = 0, int BESIDE = 0>
+template <int WIN_BITS, int HASH_BITS, int EMIT, int INTRA = 0, int PARTS = 0, int BESIDE = 0>
 __global__ __launch_bounds__(PARTS ? 128 : 64) void k_deflate_dynamic(DeflateArgs a)
 {
 	static_assert(!BESIDE || (EMIT && !PARTS), "beside the parse runs the emit-only kernel of the workgroup levels");
 	static_assert(!PARTS || EMIT, "parts are a matter of the emit-only kernel");
+	static_assert(EMIT || (WIN_BITS == HD_L2_WIN_BITS && HASH_BITS == HD_L2_HASH_BITS && HD_L2_MIN_LEN == HD_MIN_MATCH),
+		      "the fused kernel is level 2's: its ring, its table, its minimum length");
 	constexpr uint32_t W = 1u << WIN_BITS;
 	constexpr uint32_t W4M = W / 4 - 1;
-	// DEEP (the lazy levels, hipdeflate_params.h "LAZY LEVELS"): dword buckets of two positions; HS counts 16-bit units
-	constexpr uint32_t NB = HD_BUCKETS(WIN_BITS, HASH_BITS);
-	constexpr uint32_t HS = DEEP ? 2 * NB : HD_TABLE_ENTRIES(WIN_BITS, HASH_BITS);
+	constexpr uint32_t HS = HD_TABLE_ENTRIES(WIN_BITS, HASH_BITS);
 	// staging ring (dwords) and flush granule: the token loop adds up to 64 x 48 bits = 96 dwords to
 	// fewer than FLUSH_DW pending ones before it flushes one granule, so 128 + 96 <= 256 is what it takes
 	// (a 128-dword ring would do for typical data and overflow on 48-bit tokens)
@@ -547,7 +545,7 @@ __global__ __launch_bounds__(PARTS ? 128 : 64) void k_deflate_dynamic(DeflateArg
 	__shared__ __attribute__((aligned(16))) uint32_t stage[STG];
 	__shared__ DynLds L;
 	// token queue: < 64 waiting + <= 64 of one step.  (No dump slots for the lanes without a token as in
-	// the level-1 kernel: LDS is granted in 1280-byte units and levels 2-4 must stay within 12 of them
+	// the level-1 kernel: LDS is granted in 1280-byte units and the fused kernel must stay within 12 of them
 	// for 10 waves per CU.)
 	constexpr uint32_t TOKQ = 128;
 	__shared__ uint32_t tokq[EMIT ? 1 : TOKQ];
@@ -755,7 +753,7 @@ __global__ __launch_bounds__(PARTS ? 128 : 64) void k_deflate_dynamic(DeflateArg
 			crc.template fold<true>(ct, piece, piece * HD_PIECE + lane * 16 + 16 <= n, v);
 		};
 		struct Fetched {
-			uint32_t v, vh, c, c2;
+			uint32_t v, vh, c;
 		};
 		auto fetch = [&](uint32_t S_) -> Fetched {
 			Fetched f;
@@ -764,26 +762,14 @@ __global__ __launch_bounds__(PARTS ? 128 : 64) void k_deflate_dynamic(DeflateArg
 			const uint32_t w0 = w[0], w1 = w[1], w2 = w[2];
 			f.v = __builtin_amdgcn_alignbyte(w1, w0, p & 3);
 			f.vh = __builtin_amdgcn_alignbyte(w2, w1, p & 3);
-			const bool can = p + (DEEP ? HD_LAZY_KEY_BYTES : HD_MIN_MATCH) <= n;
-			uint32_t e, e2 = 0;
-			if (DEEP) {
-				// (a lane past the end reads and writes the spare bucket behind the table)
-				uint32_t *const bk = (uint32_t *)table;
-				const uint32_t h = can ? HD_HASH_SLOT6(f.v, f.vh, NB) : NB;
-				const uint32_t eb = bk[h];
-				bk[h] = (eb << 16) | ((p + 1) & 0xffffu);
-				e = eb & 0xffffu;
-				e2 = eb >> 16;
-			} else {
-				const uint32_t h = can ? HD_HASH_SLOT(f.v, HS) : HS;
-				const uint16_t mine = (uint16_t)(p + 1);
-				e = table[h];
-				table[h] = mine;
-			}
+			const bool can = p + HD_MIN_MATCH <= n;
+			// (a lane past the end reads and writes the spare entry behind the table)
+			const uint32_t h = can ? HD_HASH_SLOT(f.v, HS) : HS;
+			const uint16_t mine = (uint16_t)(p + 1);
+			const uint32_t e = table[h];
+			table[h] = mine;
 			const uint32_t back = (p + 1 - e) & 0xffffu;
 			f.c = (can && e && back) ? p + 1 - back : 0u;
-			const uint32_t back2 = (p + 1 - e2) & 0xffffu;
-			f.c2 = (DEEP && can && e2 && back2) ? p + 1 - back2 : 0u;
 			if (INTRA) {
 				// a nearer occurrence inside the step replaces the table's candidate
 				const uint32_t d = intra_step_distance<INTRA>(f.v, lane);
@@ -1167,7 +1153,7 @@ __global__ __launch_bounds__(PARTS ? 128 : 64) void k_deflate_dynamic(DeflateArg
 		uint32_t crcv;
 		if constexpr (!EMIT) {
 		// ---- pass 1: the parse ------------------------------------------------
-		Fetched f0 = { 0, 0, 0, 0 }, f1 = { 0, 0, 0, 0 };
+		Fetched f0 = { 0, 0, 0 }, f1 = { 0, 0, 0 };
 		Probed q0 = { 0, 0, 0 };
 		if (alive && n) {
 			fill_piece();
@@ -1188,47 +1174,17 @@ __global__ __launch_bounds__(PARTS ? 128 : 64) void k_deflate_dynamic(DeflateArg
 			f1 = fetch(S + 128);
 
 			const uint32_t p = S + lane;
-			const bool can = p + (DEEP ? HD_LAZY_KEY_BYTES : HD_MIN_MATCH) <= n;
+			const bool can = p + HD_MIN_MATCH <= n;
 			const uint32_t cv0 = fc.v, cvh0 = fc.vh;
 			const uint32_t room = n - p;
-			uint32_t cp = fc.c - 1;
-			bool had = can && fc.c != 0 && cp >= lo;
-			uint32_t cv = __builtin_amdgcn_alignbyte(qc.c1, qc.c0, cp & 3);
-			uint32_t cvh = __builtin_amdgcn_alignbyte(qc.c2, qc.c1, cp & 3);
-			if (DEEP) {
-				// both positions of the bucket, verified over 16 bytes (read here, byte by byte: this kernel only takes
-				// the blocks the split path leaves -- its speed does not matter, its bytes must be the twin's);
-				// the older one is taken only when it is strictly longer
-				auto prefix16 = [&](uint32_t cpos) -> uint32_t {
-					const uint32_t lim = room < 16 ? room : 16;
-					uint32_t k = 0;
-					while (k < lim && ring8[(p + k) & (W - 1)] == ring8[(cpos + k) & (W - 1)])
-						k++;
-					return k;
-				};
-				const uint32_t cpB = fc.c2 - 1;
-				const bool hadB = can && fc.c2 != 0 && cpB >= lo;
-				const uint32_t LA = had ? prefix16(cp) : 0u, LB = hadB ? prefix16(cpB) : 0u;
-				const uint32_t LAv = LA >= 4 ? LA : 0u, LBv = LB >= 4 ? LB : 0u;
-				if (LBv > LAv) {
-					cp = cpB;
-					had = hadB;
-					const uint32_t *wb = &ring32[(cpB >> 2) & W4M];
-					cv = __builtin_amdgcn_alignbyte(wb[1], wb[0], cpB & 3);
-					cvh = __builtin_amdgcn_alignbyte(wb[2], wb[1], cpB & 3);
-				}
-			}
+			const uint32_t cp = fc.c - 1;
+			const bool had = can && fc.c != 0 && cp >= lo;
+			const uint32_t cv = __builtin_amdgcn_alignbyte(qc.c1, qc.c0, cp & 3);
+			const uint32_t cvh = __builtin_amdgcn_alignbyte(qc.c2, qc.c1, cp & 3);
 			const uint32_t x = cvh ^ cvh0;
 			const uint32_t eqb = x ? (uint32_t)(__ffs((int)x) - 1) >> 3 : 4u;
 			uint32_t mylen = 4 + eqb < room ? 4 + eqb : room;
-			bool ok = had && cv == cv0 && mylen >= (uint32_t)MINLEN;
-			if (LAZY) {
-				// a candidate steps aside when its right neighbour's 8-byte length is longer
-				const uint32_t l8 = ok ? (mylen < 8 ? mylen : 8u) : 0u;
-				const uint32_t nx = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)l8, 0x130 /* wave_shl:1 */, 0xf, 0xf, false);
-				const bool defer = ok && lane + 1 < lanes && nx > l8;
-				ok = ok && !defer;
-			}
+			const bool ok = had && cv == cv0 && mylen >= HD_MIN_MATCH;
 			const uint32_t dist = ok ? p - cp : 1u;
 
 			if (carry >= lanes) {
@@ -1562,17 +1518,17 @@ __global__ __launch_bounds__(PARTS ? 128 : 64) void k_deflate_dynamic(DeflateArg
 	}
 }
 
-// Blocks up to a.split_max: parse kernel (the level-1 kernel with this level's parse parameters, at the
-// occupancy its ring + table allow and without a persistent loop), tokens + histograms through HBM,
-// then the one emit-only kernel (16 waves per CU).  Larger blocks (none, unless a block is larger
-// than its slot and will fail anyway, or the scratch budget cannot hold even one): the fused kernel.
-template <int W, int H, int MINLEN, int LAZY, int INTRA, int DEEP = 0>
-inline void launch_level(const DeflateArgs &a, int level, hipStream_t st)
+// Level 2.  Blocks up to a.split_max: parse kernel (the level-1 kernel with level 2's parse, at the occupancy
+// its ring + table allow and without a persistent loop), tokens + histograms through HBM, then the one
+// emit-only kernel (16 waves per CU).  Larger blocks (none, unless a block is larger than its slot and will
+// fail anyway, or the scratch budget cannot hold even one): the fused kernel.
+inline void launch_level2(const DeflateArgs &a, hipStream_t st)
 {
-	const uint32_t sub = a.parts ? part_sub_batch(a.nblocks, a.parts) : split_sub_batch(a.nblocks, a.split_max, level);
+	constexpr int W = HD_L2_WIN_BITS, H = HD_L2_HASH_BITS;
+	const uint32_t sub = a.parts ? part_sub_batch(a.nblocks, a.parts) : split_sub_batch(a.nblocks, a.split_max);
 	DeflateArgs s = a;
 	// scratch: [ fused slabs | overflow flags, one u32 per block | split records of one sub-batch ]
-	s.split_ovf = (uint32_t *)(a.scratch + fused_scratch_bytes(a.nblocks, level));
+	s.split_ovf = (uint32_t *)(a.scratch + fused_scratch_bytes(a.nblocks));
 	s.scratch = (uint8_t *)s.split_ovf + (((uint64_t)a.nblocks * 4 + 15) & ~(uint64_t)15);
 	if (a.parts) {
 		// latency segments (hd_segment.hpp sets a.parts = HD_LAT_PARTS): a parse wavefront per part, an emit wavefront per
@@ -1580,25 +1536,23 @@ inline void launch_level(const DeflateArgs &a, int level, hipStream_t st)
 		for (uint32_t first = 0; first < a.nblocks; first += sub) {
 			s.first = first;
 			s.count = a.nblocks - first < sub ? a.nblocks - first : sub;
-			hipLaunchKernelGGL((k_deflate_static<W, H, true, MINLEN, LAZY, INTRA, DEEP>), dim3(s.count * HD_LAT_PARTS_MAX), dim3(64), 0, st, s);
+			hipLaunchKernelGGL((k_deflate_static<W, H, true, HD_INTRA_DIST>), dim3(s.count * HD_LAT_PARTS_MAX), dim3(64), 0, st, s);
 			const uint32_t eg = s.count < 256u * 16u ? s.count : 256u * 16u;
-			hipLaunchKernelGGL((k_deflate_dynamic<HD_L2_WIN_BITS, HD_L2_HASH_BITS, HD_L2_MIN_LEN, 0, 1, 0, 0, HD_LAT_PARTS_MAX>), dim3(eg),
-					   dim3(128), 0, st, s);                 // (two wavefronts per workgroup: see the kernel)
+			hipLaunchKernelGGL((k_deflate_dynamic<W, H, 1, 0, HD_LAT_PARTS_MAX>), dim3(eg), dim3(128), 0, st, s);   // (two wavefronts per workgroup: see the kernel)
 		}
 		return;
 	}
 	for (uint32_t first = 0; sub && first < a.nblocks; first += sub) {
 		s.first = first;
 		s.count = a.nblocks - first < sub ? a.nblocks - first : sub;
-		hipLaunchKernelGGL((k_deflate_static<W, H, true, MINLEN, LAZY, INTRA, DEEP>), dim3(s.count), dim3(64), 0, st, s);
+		hipLaunchKernelGGL((k_deflate_static<W, H, true, HD_INTRA_DIST>), dim3(s.count), dim3(64), 0, st, s);
 		const uint32_t eg = s.count < 256u * 16u ? s.count : 256u * 16u;
-		hipLaunchKernelGGL((k_deflate_dynamic<HD_L2_WIN_BITS, HD_L2_HASH_BITS, HD_L2_MIN_LEN, 0, 1>), dim3(eg), dim3(64), 0,
-				   st, s);
+		hipLaunchKernelGGL((k_deflate_dynamic<W, H, 1>), dim3(eg), dim3(64), 0, st, s);
 	}
 	DeflateArgs f = a;
 	f.split_ovf = s.split_ovf;
 	f.skip_small = sub ? 1 : 0;                          // nothing went the split way: the fused kernel takes all
-	hipLaunchKernelGGL((k_deflate_dynamic<W, H, MINLEN, LAZY, 0, INTRA, DEEP>), dim3(dynamic_grid(a.nblocks, level)), dim3(64), 0, st, f);
+	hipLaunchKernelGGL((k_deflate_dynamic<W, H, 0, HD_INTRA_DIST>), dim3(dynamic_grid(a.nblocks)), dim3(64), 0, st, f);
 }
 
 void launch_wg(const DeflateArgs &a, int level, hipStream_t st);       // hd_deflate_wg.hpp
@@ -1612,7 +1566,7 @@ inline int launch_deflate_dynamic(const DeflateArgs &a, int level, hipStream_t s
 		launch_wg(a, level, st);
 		return 0;
 	}
-	launch_level<HD_L2_WIN_BITS, HD_L2_HASH_BITS, HD_L2_MIN_LEN, 0, HD_INTRA_DIST>(a, level, st);
+	launch_level2(a, st);
 	return 0;
 }
 

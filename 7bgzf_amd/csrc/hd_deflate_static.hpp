@@ -277,56 +277,36 @@ __device__ __forceinline__ uint8_t *part_block(uint8_t *scratch, uint32_t i)
 	return scratch + (uint64_t)i * part_layout().bytes;
 }
 
-// MINLEN / LAZY / INTRA: the parse variants of the dynamic levels (hd_deflate_dynamic.hpp), used with TOK
-// DEEP: the lazy levels' matchfinder (hipdeflate_params.h "LAZY LEVELS"): six-byte key, two positions per bucket, both verified
-// PRIMED: the instantiation latency-mode launches use -- parts and priming (HD_LAT_PRIME) are compiled in.  The parse kernels
-// always have them; the level-1 kernel of the 16 GiB runs does not (with them in, 0.5 % slower for nothing)
-template <int WIN_BITS, int HASH_BITS, bool TOK, int MINLEN = HD_MIN_MATCH, int LAZY = 0, int INTRA = 0, int DEEP = 0, bool PRIMED = TOK>
+// TOK: the parse kernel of level 2 (hd_deflate_dynamic.hpp), in level 2's geometry; INTRA: its in-step candidates (HD_INTRA_DIST)
+// PRIMED: the instantiation latency-mode launches use -- parts and priming (HD_LAT_PRIME) are compiled in.  The parse kernel
+// always has them; the level-1 kernel of the 16 GiB runs does not (with them in, 0.5 % slower for nothing)
+template <int WIN_BITS, int HASH_BITS, bool TOK, int INTRA = 0, bool PRIMED = TOK>
 __global__ __launch_bounds__(64) void k_deflate_static(DeflateArgs a)
 {
 	static_assert(PRIMED || !TOK, "the parse kernels are always built with the latency-mode paths");
+	static_assert(!TOK || (WIN_BITS == HD_L2_WIN_BITS && HASH_BITS == HD_L2_HASH_BITS && HD_L2_MIN_LEN == HD_MIN_MATCH),
+		      "the parse kernel is level 2's: its ring, its table, its minimum length");
 	constexpr uint32_t W = 1u << WIN_BITS;
 	constexpr uint32_t W4M = W / 4 - 1;
-	// table entries: 16-bit positions, or (DEEP) dword buckets of two -- HS counts 16-bit units either way
-	constexpr uint32_t NB = HD_BUCKETS(WIN_BITS, HASH_BITS);
-	constexpr uint32_t HS = DEEP ? 2 * NB : HD_TABLE_ENTRIES(WIN_BITS, HASH_BITS);
-	static_assert(!DEEP || (TOK && WIN_BITS > 12), "the two-way table belongs to the parse kernels of the lazy levels");
+	constexpr uint32_t HS = HD_TABLE_ENTRIES(WIN_BITS, HASH_BITS);
 	constexpr uint32_t STG = 256;            // staging ring, dwords
 	constexpr uint32_t FLUSH_DW = 128;       // flushed 512 B at a time, 8 B per lane
 	constexpr uint32_t TOKQ = 128;           // token queue: < 64 waiting + <= 64 of one step
 	// K16: every lane whose first eight bytes agree learns bytes 8..15 in the vector domain too (four more ring
-	// dwords per lane, issued ahead of the scan and used behind it), so the scalar extension loop below runs only
-	// for matches of 16 bytes and more.  On text 98 % of the "long" matches are 9..15 bytes long, and the parse
-	// kernels of the dynamic levels wait on that loop's LDS round trip; the level-1 kernel is bound by its vector
-	// instruction count instead and keeps the loop (HD_K16_LEVEL1 to try)
-#if defined(HD_K16_ALL)
-	constexpr bool K16 = true;
-#elif defined(HD_K16_OFF)
-	constexpr bool K16 = false;
-#elif defined(HD_K16_NOT_L2)
-	constexpr bool K16 = TOK && WIN_BITS > 12;
-#else
+	// dwords per lane), so the scalar extension loop below runs only for matches of 16 bytes and more.  On text
+	// 98 % of the "long" matches are 9..15 bytes long, and the parse kernel waits on that loop's LDS round trip;
+	// the level-1 kernel is bound by its vector instruction count instead and keeps the loop
 	constexpr bool K16 = TOK;
-#endif
-	// the ring dwords for it are read a step ahead, in probe(), where five more registers do not cost a wave
-	// (every geometry but the level-2 one, which LDS lets run 18 waves per CU: <= 96 VGPRs)
-	constexpr bool K16_EARLY = K16 && WIN_BITS > 12;
 
 	// + 16 bytes that mirror the start of the ring, so that the 3 dwords under an
 	// unaligned 8-byte read never wrap
 	__shared__ __attribute__((aligned(W))) uint32_t ring32[W / 4 + 4];       // W-aligned: ring address = (x & (W - 1)) | base
 	// (position + 1) mod 2^16, 0 = empty
-	__shared__ __attribute__((aligned(16))) uint16_t table[HS + (DEEP ? 2 : 0)];      // DEEP: + a spare dword for the deferred stores of lanes without a position
+	__shared__ __attribute__((aligned(16))) uint16_t table[HS];
 	// TOK: no bits are made here, the staging ring's place is taken by the symbol histograms
-	// (316 counters: litlen [0,286), offset [286,316).  LDS is granted in 1280-byte units, every byte counts:
-	// where it buys another wave per CU -- the level 5-6 geometry -- the counters are 16 bits wide, two to a
-	// dword; a DEFLATE block holds fewer than 2^16 tokens, so none can carry into its neighbour.  Elsewhere
-	// they stay 32 bits wide: packed ones measured 4 % slower), and the queue has no dump slots
-	constexpr uint32_t LDS_REST = (W + 16) + 2 * HS + 4 * TOKQ;      // ring + table + token queue
-	constexpr uint32_t WAVES32 = 163840 / (((LDS_REST + 1264 + 1279) / 1280) * 1280);
-	constexpr uint32_t WAVES16 = 163840 / (((LDS_REST + 632 + 1279) / 1280) * 1280);
-	constexpr bool PACK16 = TOK && WAVES16 > WAVES32;
-	__shared__ __attribute__((aligned(16))) uint32_t stage[TOK ? (PACK16 ? 158 : 316) : STG];
+	// (316 counters: litlen [0,286), offset [286,316), 32 bits wide: packed 16-bit ones measured 4 % slower
+	// where they bought no wave), and the queue has no dump slots
+	__shared__ __attribute__((aligned(16))) uint32_t stage[TOK ? 316 : STG];
 	// tokens waiting for the emit pass; [TOKQ, TOKQ + 32) = dump slots of lanes without one (two lanes share
 	// a slot: what lands there is never read)
 	__shared__ uint32_t tokbuf[TOK ? TOKQ : TOKQ + 32];
@@ -387,7 +367,7 @@ __global__ __launch_bounds__(64) void k_deflate_static(DeflateArgs a)
 	// ---- init LDS -------------------------------------------------------
 	for (uint32_t i = lane; i < HS / 8; i += 64)
 		((uint4 *)table)[i] = make_uint4(0, 0, 0, 0);
-	for (uint32_t i = lane; i < (TOK ? (PACK16 ? 158u : 316u) : STG); i += 64)
+	for (uint32_t i = lane; i < (TOK ? 316u : STG); i += 64)
 		stage[i] = 0;
 	if (!TOK && lane < 4 && hdr)
 		stage[lane] = frame_hdr_word(a.frame, lane);
@@ -402,9 +382,6 @@ __global__ __launch_bounds__(64) void k_deflate_static(DeflateArgs a)
 	fid.init(lane);
 	HashConsts hk;
 	hk.init(HS);
-	HashConsts6 hk6;
-	hk6.init(NB);
-	uint32_t pub_addr = 2u * HS, pub_val = 0;    // DEEP: the last fetch's bucket stores, issued by the next one
 	CrcLanes crc;
 	// (a primed part's CRC covers [prime, n): the lanes of the priming bytes -- all in the first piece -- fold zeros from
 	// state 0, which leaves them at 0, and the register's all-ones start sits on the part's first slot)
@@ -461,7 +438,6 @@ __global__ __launch_bounds__(64) void k_deflate_static(DeflateArgs a)
 	// largest position) stays, which is the result the CPU twin computes.
 	struct Fetched {
 		uint32_t v, vh, c;           // own bytes [p,p+4), [p+4,p+8); candidate position + 1 (0 = none)
-		uint32_t c2;                 // DEEP: the bucket's older position + 1
 	};
 	// INNER: every lane of the step has >= 9 bytes left and the block is shorter than
 	// 2^16 (all BGZF blocks; all but their last steps), so the end-of-block and the
@@ -499,44 +475,20 @@ __global__ __launch_bounds__(64) void k_deflate_static(DeflateArgs a)
 		}
 		f.v = __builtin_amdgcn_alignbyte(w1, w0, p & 3);
 		f.vh = __builtin_amdgcn_alignbyte(w2, w1, p & 3);
-		const bool can = INNER || p + (DEEP ? HD_LAZY_KEY_BYTES : HD_MIN_MATCH) <= n;
+		const bool can = INNER || p + HD_MIN_MATCH <= n;
 		// (a lane past the end of the block publishes nothing; it reads slot 0, harmlessly)
-		uint32_t e, e2 = 0;
-		if (DEEP) {
-			// one dword bucket: low half the newest position, high half the one before; every lane stores
-			// (what it read << 16) | itself -- { newest before the step, highest lane of the step } stays
-			// The store waits for the bucket it is made of: issued here it parked every wave on its own LDS read once
-			// per step (SQ_WAIT_ANY 33 % of the deep parse).  It goes out at the head of the NEXT fetch instead --
-			// still in front of that step's reads, which is all the order the twin knows: a step's positions are in
-			// the table before the next step looks.  (Lanes without a position store to a spare dword behind the table.)
-			*(uint32_t *)((uint8_t *)table + pub_addr) = pub_val;
-			const uint32_t ha = hash_slot_addr6(f.v, f.vh, hk6);
-			const uint32_t eb = *(const uint32_t *)((const uint8_t *)table + (can ? ha : 0u));
-			pub_addr = can ? ha : 2u * HS;
-			pub_val = (eb << 16) | ((p + 1) & 0xffffu);
-			e = eb & 0xffffu;
-			e2 = eb >> 16;
-		} else {
-			const uint32_t ha = hash_slot_addr(f.v, hk);             // byte offset of the entry
-			uint16_t *const slot = (uint16_t *)((uint8_t *)table + (can ? ha : 0u));
-			const uint16_t mine = (uint16_t)(p + 1);
-			e = *slot;
-			if (can)
-				*slot = mine;
-		}
-		f.c2 = 0;
+		const uint32_t ha = hash_slot_addr(f.v, hk);             // byte offset of the entry
+		uint16_t *const slot = (uint16_t *)((uint8_t *)table + (can ? ha : 0u));
+		const uint16_t mine = (uint16_t)(p + 1);
+		const uint32_t e = *slot;
+		if (can)
+			*slot = mine;
 		if (INNER) {
 			f.c = e;                                         // position + 1 itself: nothing has wrapped
-			if (DEEP)
-				f.c2 = e2;
 		} else {
 			// entry -> absolute position + 1 of the latest p' < p with p' + 1 == e (mod 2^16)
 			const uint32_t back = (p + 1 - e) & 0xffffu;         // 0: an entry exactly 2^16 back, i.e. stale
 			f.c = (can && e && back) ? p + 1 - back : 0u;
-			if (DEEP) {
-				const uint32_t back2 = (p + 1 - e2) & 0xffffu;
-				f.c2 = (can && e2 && back2) ? p + 1 - back2 : 0u;
-			}
 		}
 		if (INTRA) {
 			// a nearer occurrence inside the step replaces the table's candidate
@@ -551,38 +503,20 @@ __global__ __launch_bounds__(64) void k_deflate_static(DeflateArgs a)
 		// store to its re-read, so it never ran -- and never had to.)
 		return f;
 	};
+	// the three ring dwords under the candidate c (position + 1) of the lane at p.  Neither `spare` nor p is read: they are
+	// the shape of the probe of the removed wider geometries, which read ten more dwords here, and the compiler schedules
+	// these kernels by it -- without them a few moves trade places in all three.  Kept so that the machine code stays
+	// the measured one
 	struct Probed {
 		uint32_t c0, c1, c2;
-		uint32_t c3, c4, p2, p3, p4;     // K16: the candidate's and the lane's own bytes up to 16 (+ alignment)
-		uint32_t d0, d1, d2, d3, d4;     // DEEP: the five dwords under the bucket's older position
+		uint32_t spare[10];
 	};
-	auto probe = [&](uint32_t c, uint32_t p, uint32_t cB = 0) -> Probed {
-		Probed q;
-		if (DEEP) {
-			const uint32_t *wb = &ring32[((cB - 1) >> 2) & W4M];
-			q.d0 = wb[0];
-			q.d1 = wb[1];
-			q.d2 = wb[2];
-			q.d3 = wb[3];
-			q.d4 = wb[4];
-		} else {
-			q.d0 = q.d1 = q.d2 = q.d3 = q.d4 = 0;
-		}
+	auto probe = [&](uint32_t c, uint32_t p) -> Probed {
+		Probed q = {};
 		const uint32_t *w = &ring32[((c - 1) >> 2) & W4M];
 		q.c0 = w[0];
 		q.c1 = w[1];
 		q.c2 = w[2];
-		if (K16_EARLY) {
-			// (+ 16 mirrored bytes behind the ring: dwords [0,5) of an index never wrap)
-			const uint32_t *wp = &ring32[(p >> 2) & W4M];
-			q.c3 = w[3];
-			q.c4 = w[4];
-			q.p2 = wp[2];
-			q.p3 = wp[3];
-			q.p4 = wp[4];
-		} else {
-			q.c3 = q.c4 = q.p2 = q.p3 = q.p4 = 0;
-		}
 		return q;
 	};
 
@@ -591,10 +525,7 @@ __global__ __launch_bounds__(64) void k_deflate_static(DeflateArgs a)
 	// stream no longer fits under `limit`
 	uint32_t qhead = 0, qtail = 0;
 	auto count_symbol = [&](uint32_t c) {                             // TOK only
-		if (PACK16)
-			atomicAdd(&stage[c >> 1], 1u << (16 * (c & 1)));
-		else
-			atomicAdd(&stage[c], 1u);
+		atomicAdd(&stage[c], 1u);
 	};
 	auto emit_tokens = [&](uint32_t count) -> bool {
 		const uint32_t t = tokbuf[(qhead + lane) & (TOKQ - 1)];
@@ -645,12 +576,12 @@ __global__ __launch_bounds__(64) void k_deflate_static(DeflateArgs a)
 	if (!TOK)
 		put(lane == 0 ? (flush ? 2u : 3u) : 0u, lane == 0 ? 3u : 0u, 3u, 3u);
 
-	Fetched f0 = { 0, 0, 0, 0 }, f1 = { 0, 0, 0, 0 };
-	Probed q0 = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
+	Fetched f0 = { 0, 0, 0 }, f1 = { 0, 0, 0 };
+	Probed q0 = {};
 	if (use_static && n) {
 		fill_piece();
 		f0 = fetch(std::false_type{}, 0);
-		q0 = probe(f0.c, lane, f0.c2);
+		q0 = probe(f0.c, lane);
 		f1 = fetch(std::false_type{}, 64);
 		if (OWN_AHEAD)
 			o1 = own(128);
@@ -670,7 +601,7 @@ __global__ __launch_bounds__(64) void k_deflate_static(DeflateArgs a)
 		const Fetched fc = f0;
 		const Probed qc = q0;
 		f0 = f1;
-		q0 = probe(f1.c, S + 64 + lane, f1.c2);   // harmless beyond n: every index is masked into the ring
+		q0 = probe(f1.c, S + 64 + lane);   // harmless beyond n: every index is masked into the ring
 		f1 = fetch(inner_tag, S + 128);
 		if (OWN_AHEAD)
 			o1 = own(S + 192);                 // (every index is masked into the ring; bytes beyond the block never count)
@@ -682,66 +613,18 @@ __global__ __launch_bounds__(64) void k_deflate_static(DeflateArgs a)
 		const uint32_t p = S + lane;
 		const uint32_t cv0 = fc.v, cvh0 = fc.vh;
 		const uint32_t room = n - p;                  // >= 4 where a match can start
-		uint32_t c = fc.c, cp = c - 1;
-		uint32_t cv = __builtin_amdgcn_alignbyte(qc.c1, qc.c0, cp & 3);
-		uint32_t cvh = __builtin_amdgcn_alignbyte(qc.c2, qc.c1, cp & 3);
-		uint32_t x = cvh ^ cvh0;
-		uint64_t xm = __ballot(cvh == cvh0);                            // all eight bytes agree
-		uint32_t len8 = sel(xm, 8u, 4u + ((uint32_t)__builtin_ctz(x) >> 3));     // (x == 0: not selected)
+		const uint32_t c = fc.c, cp = c - 1;
+		const uint32_t cv = __builtin_amdgcn_alignbyte(qc.c1, qc.c0, cp & 3);
+		const uint32_t cvh = __builtin_amdgcn_alignbyte(qc.c2, qc.c1, cp & 3);
+		const uint32_t x = cvh ^ cvh0;
+		const uint64_t xm = __ballot(cvh == cvh0);                      // all eight bytes agree
+		const uint32_t len8 = sel(xm, 8u, 4u + ((uint32_t)__builtin_ctz(x) >> 3));     // (x == 0: not selected)
 		// candidate inside the window (c == 0, no candidate, makes cp = -1: one signed compare covers both;
 		// this kernel never sees a block of 2 GiB), its four bytes equal
 		uint64_t okm = __ballot((int32_t)cp >= (int32_t)lo) & __ballot(cv == cv0);
-		// bytes 8..15 of the candidate against the lane's own (valid where the first eight agree): K16, and DEEP's choice
-		uint32_t qc3 = qc.c3, qc4 = qc.c4, qc2 = qc.c2;
-		auto tail16 = [&](uint32_t w2, uint32_t w3, uint32_t w4, uint32_t cpos) -> uint32_t {
-			const uint32_t xa = __builtin_amdgcn_alignbyte(qc.p3, qc.p2, p & 3) ^ __builtin_amdgcn_alignbyte(w3, w2, cpos & 3);   // bytes 8..11
-			const uint32_t xb = __builtin_amdgcn_alignbyte(qc.p4, qc.p3, p & 3) ^ __builtin_amdgcn_alignbyte(w4, w3, cpos & 3);   // bytes 12..15
-			// (v_ffbl_b32 of 0 is -1: >> 3 and min 4 turn it into "all four agree"; ka >> 2 is 1 exactly then)
-			uint32_t fa, fb;
-			asm("v_ffbl_b32 %0, %1" : "=v"(fa) : "v"(xa));
-			asm("v_ffbl_b32 %0, %1" : "=v"(fb) : "v"(xb));
-			const uint32_t ka = (fa >> 3) < 4 ? (fa >> 3) : 4u, kb = (fb >> 3) < 4 ? (fb >> 3) : 4u;
-			return 8 + ka + (ka >> 2) * kb;
-		};
-		uint32_t len16_deep = 8;
-		if (DEEP) {
-			// the bucket's older position, verified the same way; it is taken only when it is strictly longer over
-			// 16 bytes (cut to the room that is left, as the twin's prefix lengths are)
-			const uint32_t cB = fc.c2, cpB = cB - 1;
-			const uint32_t cvB = __builtin_amdgcn_alignbyte(qc.d1, qc.d0, cpB & 3);
-			const uint32_t cvhB = __builtin_amdgcn_alignbyte(qc.d2, qc.d1, cpB & 3);
-			const uint32_t xB = cvhB ^ cvh0;
-			const uint64_t xmB = __ballot(cvhB == cvh0);
-			const uint32_t len8B = sel(xmB, 8u, 4u + ((uint32_t)__builtin_ctz(xB) >> 3));
-			const uint64_t okB = __ballot((int32_t)cpB >= (int32_t)lo) & __ballot(cvB == cv0);
-			const uint32_t l16A = tail16(qc.c2, qc.c3, qc.c4, cp), l16B = tail16(qc.d2, qc.d3, qc.d4, cpB);
-			uint32_t LA = sel(okm, sel(xm, l16A, len8), 0u), LB = sel(okB, sel(xmB, l16B, len8B), 0u);
-			if (!INNER) {
-				LA = LA < room ? LA : room;
-				LB = LB < room ? LB : room;
-			}
-			const uint64_t chB = __ballot(LB > LA);
-			c = sel(chB, cB, c);
-			cp = c - 1;
-			len8 = sel(chB, len8B, len8);
-			len16_deep = sel(chB, l16B, l16A);
-			qc2 = sel(chB, qc.d2, qc.c2);
-			qc3 = sel(chB, qc.d3, qc.c3);
-			qc4 = sel(chB, qc.d4, qc.c4);
-			xm = (xm & ~chB) | (xmB & chB);
-			okm = (okm & ~chB) | (okB & chB);
-		}
 		const uint32_t mylen = INNER ? len8 : (len8 < room ? len8 : room);     // <= 8 until a capped match is extended
 		if (!INNER)
-			okm &= __ballot(p + (DEEP ? HD_LAZY_KEY_BYTES : HD_MIN_MATCH) <= n);
-		if (MINLEN > HD_MIN_MATCH)
-			okm &= __ballot(mylen >= (uint32_t)MINLEN);
-		if (LAZY) {
-			// a candidate steps aside when its right neighbour's 8-byte length is longer
-			const uint32_t l8 = sel(okm, mylen, 0u);
-			const uint32_t nx = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)l8, 0x130 /* wave_shl:1 */, 0xf, 0xf, false);
-			okm &= ~(__ballot(nx > l8) & (lanem >> 1));                      // (lane + 1 < lanes)
-		}
+			okm &= __ballot(p + HD_MIN_MATCH <= n);
 
 		if (carry >= lanes) {                // the whole step lies inside the last match
 			carry -= lanes;
@@ -767,18 +650,16 @@ __global__ __launch_bounds__(64) void k_deflate_static(DeflateArgs a)
 		// DPP stages)  match: HD_TOKEN_MATCH_TAG | (len - 3) << 16 | (dist - 1), dist - 1 = p - c
 		const uint32_t mw_base = (p + (HD_TOKEN_MATCH_TAG - (3u << 16))) - c;
 		const uint32_t lit = cv0 & 0xff;
-		// K16: length over 16 bytes (valid on the capped lanes).  (The level-2 geometry reads the dwords here and is
-		// bound by its instruction count: it skips all of this in a step without a capped lane -- a quarter of the
-		// steps on FASTQ-like data)
+		// K16: length over 16 bytes (valid on the capped lanes).  (The dwords are read here, and the kernel is bound
+		// by its instruction count: it skips all of this in a step without a capped lane -- a quarter of the steps on
+		// FASTQ-like data.  + 16 mirrored bytes behind the ring: dwords [0,5) of an index never wrap)
 		uint32_t len16 = 8;
-		const bool k16_step = K16 && (K16_EARLY || capmask != 0);
-		if (DEEP) {
-			len16 = INNER ? len16_deep : (len16_deep < room ? len16_deep : room);
-		} else if (k16_step) {
+		const bool k16_step = K16 && capmask != 0;
+		if (k16_step) {
 			const uint32_t *wp = &ring32[(p >> 2) & W4M], *wc = &ring32[(cp >> 2) & W4M];
-			const uint32_t c2 = qc2;
-			const uint32_t p2 = K16_EARLY ? qc.p2 : wp[2], p3 = K16_EARLY ? qc.p3 : wp[3], p4 = K16_EARLY ? qc.p4 : wp[4];
-			const uint32_t c3 = K16_EARLY ? qc3 : wc[3], c4 = K16_EARLY ? qc4 : wc[4];
+			const uint32_t c2 = qc.c2;
+			const uint32_t p2 = wp[2], p3 = wp[3], p4 = wp[4];
+			const uint32_t c3 = wc[3], c4 = wc[4];
 			const uint32_t xa = __builtin_amdgcn_alignbyte(p3, p2, p & 3) ^ __builtin_amdgcn_alignbyte(c3, c2, cp & 3);   // bytes 8..11
 			const uint32_t xb = __builtin_amdgcn_alignbyte(p4, p3, p & 3) ^ __builtin_amdgcn_alignbyte(c4, c3, cp & 3);   // bytes 12..15
 			// (v_ffbl_b32 of 0 is -1: >> 3 and min 4 turn it into "all four agree"; ka >> 2 is 1 exactly then)
@@ -1015,7 +896,7 @@ __global__ __launch_bounds__(64) void k_deflate_static(DeflateArgs a)
 		return use_static;
 	};
 	// fetch runs two steps ahead: a step is INNER when the lanes of step S + 128 still have 9 bytes
-	// (<= 2^16: the last position that enters the table is n - 4 (n - 6 at the lazy levels), so position + 1 still fits the
+	// (<= 2^16: the last position that enters the table is n - 4, so position + 1 still fits the
 	// 16-bit entries of a block of exactly 0x10000 bytes -- the reference's single-thread block size, applet/7bgzf.c:146-147.
 	// Such blocks had been running through the general steps: 244 GB/s against 323 for 0xff00-byte blocks, which rounds 1-2
 	// took for HBM channel aliasing; a start stagger of the waves, tried on that theory, only cost time.)
@@ -1027,9 +908,9 @@ __global__ __launch_bounds__(64) void k_deflate_static(DeflateArgs a)
 		for (uint32_t i = lane; i < 320; i += 64) {
 			const uint32_t j = i < 286 ? i : i - 2;          // counter of litlen i / offset i - 288
 			const bool used = i < 286 || (i >= 288 && i < 318);
-			h[i] = !used ? 0u : PACK16 ? (stage[j >> 1] >> (16 * (j & 1))) & 0xffffu : stage[j];
+			h[i] = used ? stage[j] : 0u;
 		}
-		for (uint32_t i = lane; i < (PACK16 ? 158u : 316u); i += 64)
+		for (uint32_t i = lane; i < 316u; i += 64)
 			stage[i] = 0;
 		if (lane == 0)
 			((uint32_t *)(rec + lay.off_ntok))[ndb] = ntok_slab - db_start;
@@ -1062,7 +943,7 @@ __global__ __launch_bounds__(64) void k_deflate_static(DeflateArgs a)
 		if (filled < n && filled < S + HD_LOOKAHEAD)
 			fill_piece();
 		f0 = f1;
-		q0 = probe(f1.c, S + 64 + lane, f1.c2);
+		q0 = probe(f1.c, S + 64 + lane);
 		f1 = fetch(std::false_type{}, S + 128);
 		if (OWN_AHEAD)
 			o1 = own(S + 192);

@@ -810,7 +810,7 @@ inline void launch_wg(const DeflateArgs &a, int level, hipStream_t st)
 					s.span_sub = 0;
 					s.scratch = records;
 				} else {
-					hipLaunchKernelGGL((k_deflate_dynamic<HD_L2_WIN_BITS, HD_L2_HASH_BITS, HD_L2_MIN_LEN, 0, 1, 0, 0, 0, 1>), dim3(eg), dim3(64), 0, bs->side, e);
+					hipLaunchKernelGGL((k_deflate_dynamic<HD_L2_WIN_BITS, HD_L2_HASH_BITS, 1, 0, 0, 1>), dim3(eg), dim3(64), 0, bs->side, e);
 					(void)hipEventRecord(bs->done, bs->side);
 					hipLaunchKernelGGL(k_gate, dim3(1), dim3(64), 0, st, s.arrived, eg, 1u << 14, (uint32_t *)nullptr);
 				}
@@ -827,7 +827,7 @@ inline void launch_wg(const DeflateArgs &a, int level, hipStream_t st)
 				h.count = a.nblocks;
 				h.scratch = rec_a;
 				h.take_sub = k - 1;                          // (sub-batch k - 2, plus one)
-				hipLaunchKernelGGL((k_deflate_dynamic<HD_L2_WIN_BITS, HD_L2_HASH_BITS, HD_L2_MIN_LEN, 0, 1, 0, 0, 0, 1>), dim3(cnt < 256u * 16u ? cnt : 256u * 16u), dim3(64), 0,
+				hipLaunchKernelGGL((k_deflate_dynamic<HD_L2_WIN_BITS, HD_L2_HASH_BITS, 1, 0, 0, 1>), dim3(cnt < 256u * 16u ? cnt : 256u * 16u), dim3(64), 0,
 						   st, h);
 				hipLaunchKernelGGL(k_gate, dim3(1), dim3(64), 0, st, emitted + (k - 2), cnt, 1u << 22, s.poison);
 			}
@@ -881,12 +881,12 @@ inline void launch_wg(const DeflateArgs &a, int level, hipStream_t st)
 			}
 			const uint32_t hn = s.span_sub ? a.nblocks : s.count;
 			const uint32_t hg = hn < 256u * 16u ? hn : 256u * 16u;
-			hipLaunchKernelGGL((k_deflate_dynamic<HD_L2_WIN_BITS, HD_L2_HASH_BITS, HD_L2_MIN_LEN, 0, 1, 0, 0, 0, 1>), dim3(hg), dim3(64), 0, st, h);
+			hipLaunchKernelGGL((k_deflate_dynamic<HD_L2_WIN_BITS, HD_L2_HASH_BITS, 1, 0, 0, 1>), dim3(hg), dim3(64), 0, st, h);
 			(void)hipStreamWaitEvent(st, bs->done, 0);           // the caller's stream carries on behind the members
 			continue;
 		}
 		const uint32_t eg = s.count < 256u * 16u ? s.count : 256u * 16u;
-		hipLaunchKernelGGL((k_deflate_dynamic<HD_L2_WIN_BITS, HD_L2_HASH_BITS, HD_L2_MIN_LEN, 0, 1>), dim3(eg), dim3(64), 0, st, s);
+		hipLaunchKernelGGL((k_deflate_dynamic<HD_L2_WIN_BITS, HD_L2_HASH_BITS, 1>), dim3(eg), dim3(64), 0, st, s);
 	}
 }
 

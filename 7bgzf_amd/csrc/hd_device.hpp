@@ -247,7 +247,7 @@ __device__ __forceinline__ uint32_t hash_slot_addr(uint32_t v, const HashConsts 
 	return a;
 }
 
-// the lazy levels' key of six bytes (HD_HASH_SLOT6): vh = bytes [p+4, p+8), of which the low two count; returns the
+// the workgroup parse's key of six bytes (HD_HASH_SLOT6): vh = bytes [p+4, p+8), of which the low two count; returns the
 // BYTE offset of the dword bucket, 4 * slot
 struct HashConsts6 {
 	uint32_t k1, k2, k3, e4, m;

@@ -58,37 +58,23 @@
 #define HD_HASH_K2         0xC2B2AEu
 #define HD_HASH_SLOT(v, entries) \
 	((((((uint32_t)(v) & 0xffffffu) * HD_HASH_K1 + ((uint32_t)(v) >> 16) * HD_HASH_K2) >> 16) * (uint32_t)(entries)) >> 16)
-/* LAZY LEVELS (6..9; level 5 keeps the one-way table: the faster step of the ladder): the hash covers SIX bytes and a
- * bucket holds TWO positions.
+/* The workgroup parse's key (hd_deflate_wg.hpp, "WORKGROUP LEVELS" below): the hash covers SIX bytes.
  *   key      v = bytes [p, p+4), vh = bytes [p+4, p+6):  t += vh * K3 in the sum above (one more 24-bit multiply).  A
  *            position enters the table (and looks into it) only with six bytes left.  DNA-like data has 256 distinct
  *            4-byte keys in its reads; six bytes find the far repeats libdeflate's chains find (level 6, FASTQ-like
- *            set: 0.285 -> 0.278 of the input with this alone).
- *   bucket   one dword: low half the newest position of the key, high half the one before it.  A step reads the
- *            bucket and stores (bucket << 16) | own position -- the same one LDS read and one LDS write per lane as
- *            the one-way table; of the lanes of a step that share a bucket the highest keeps its store (as before),
- *            so the bucket becomes { newest before the step, highest lane of the step }.
- *   choice   both candidates are verified over 16 bytes; the older one is taken only when it is strictly longer.
- * The role of hc_matchfinder's chain walk (lib/libdeflate/hc_matchfinder.h:183-338: depth 35 at level 6) with the
- * depth LDS affords: 2.  tests/golden/ratio_ref.json + hdtest.RATIO_BOUNDS hold the resulting sizes against libdeflate's. */
+ *            set: 0.285 -> 0.278 of the input with this alone, measured on the one-wavefront parse of rounds 2-4).
+ * tests/golden/ratio_ref.json + hdtest.RATIO_BOUNDS hold the resulting sizes against libdeflate's. */
 #define HD_HASH_K3         0x85EBCAu
 #define HD_HASH_SLOT6(v, vh, entries) \
 	((((((uint32_t)(v) & 0xffffffu) * HD_HASH_K1 + ((uint32_t)(v) >> 16) * HD_HASH_K2 + ((uint32_t)(vh) & 0xffffu) * HD_HASH_K3) >> 16) * (uint32_t)(entries)) >> 16)
-#define HD_DEEP_LEVEL      6           /* first level with the two-way buckets */
-#define HD_LAZY_KEY_BYTES  6
-#define HD_LAZY_WAYS       2
-/* buckets of the two-way tables: 2560 x 4 B with the 8 KiB ring of levels 5..6 (8 parse waves per CU), 2560 / 4096 with the
- * 16 KiB ring of levels 7 / 8 (5 / 4 waves), 6144 with the 32 KiB ring of level 9 (2 waves) */
-#ifndef HD_L6_BUCKETS
-#define HD_L6_BUCKETS 2560u            /* (1536: ten parse waves per CU instead of eight -- measured below) */
-#endif
-#define HD_BUCKETS(win_bits, hash_bits) ((win_bits) == 15 ? 6144u : (win_bits) == 14 && (hash_bits) == 13 ? 4096u : (win_bits) == 13 ? HD_L6_BUCKETS : 2560u)
+#define HD_LAZY_KEY_BYTES  6           /* the key's bytes: a position with fewer left stays out of the table */
 
-/* Entries of the hash table.  LDS is granted in 1280-byte units, so the table sizes are what fills the units the ring
- * leaves: 1536 entries with the 4 KiB ring of levels 1..2 (7 units, 18 waves per CU instead of 16 with 2048) and the
- * 8 KiB ring of levels 3..4 (12 parse waves instead of 11), 2560 with the 8 KiB ring of levels 5..6 (10 parse waves
- * instead of 9 with 4096: level 6 106 -> 116 GB/s on the FASTQ-like set at the same ratio), 6144 at level 9 (5 waves
- * instead of 4 with 8192).  hash_bits only names the geometry (11: 1536, 12: 2560 / 4096, 13: 6144). */
+/* Entries of the one-wavefront hash table (levels 1..2).  LDS is granted in 1280-byte units, so the table sizes are what
+ * fills the units the ring leaves: 1536 entries with the 4 KiB ring (7 units, 18 waves per CU instead of 16 with 2048).
+ * The wider cases are the geometries rounds 1-4 ran levels 3..9 in, kept for level-1 builds with a wider window
+ * (HD_L1_WIN_BITS): 1536 with an 8 KiB ring, 2560 with an 8 KiB ring and hash_bits 12 (10 waves per CU instead of 9
+ * with 4096), 6144 with a 16 KiB ring and hash_bits 13.  hash_bits only names the geometry (11: 1536, 12: 2560 / 4096,
+ * 13: 6144). */
 #define HD_TABLE_34(win_bits, hash_bits)      (((win_bits) <= 13 && (hash_bits) == 11) || ((win_bits) == 14 && (hash_bits) == 13))
 #define HD_TABLE_58(win_bits, hash_bits)      ((win_bits) == 13 && (hash_bits) == 12)
 #define HD_TABLE_ENTRIES(win_bits, hash_bits) (HD_TABLE_34(win_bits, hash_bits) ? (3u << ((hash_bits) - 2)) : HD_TABLE_58(win_bits, hash_bits) ? 2560u : (1u << (hash_bits)))

@@ -132,8 +132,8 @@ def ring_lo(q, pn, win):
     """Levels 1..2: the oldest byte a candidate may name, in parse coordinates (0 = where the parse starts, priming
     included).  The header says "4 KiB window" (HD_L1_WIN_BITS, HD_L2_WIN_BITS); the exact bound is the ring's:
     the step at S refills the ring a HD_PIECE at a time until it holds HD_LOOKAHEAD bytes past S or the whole parse
-    (hd_deflate_static.hpp:664, hd_deflate_dynamic.hpp:1180), and a candidate must lie at or after
-    filled - 2^WIN_BITS (hd_deflate_static.hpp:666 + the okm test, hd_deflate_dynamic.hpp:1182).  So the farthest
+    (hd_deflate_static.hpp:595, hd_deflate_dynamic.hpp:1166), and a candidate must lie at or after
+    filled - 2^WIN_BITS (hd_deflate_static.hpp:597 + the okm test, hd_deflate_dynamic.hpp:1168).  So the farthest
     reach is 4096 - HD_LOOKAHEAD + 63 = 3775 inside a block and 4096 - HD_MIN_MATCH = 4092 at its end: a distance
     of 4096 is never written."""
     S = q - q % WAVE

@@ -140,11 +140,12 @@ def test_zlibutil_mirror_wrappers(pkg):
     assert lib.hd_adler32(1, v, len(v)) == hdtest.oracle().hdo_adler32(1, a.ctypes.data, len(a))
 
 
-def test_kernel_resource_budgets():
+def test_kernel_resource_budgets_by_template_args():
     """The compiler's resource report of the build (7bgzf_amd/csrc/hd_api.resources.log, written by the
     Makefile): no kernel may spill, and the dynamic-level kernels must stay at <= 168 VGPRs -- their
     persistent grids (dynamic_grid(), hd_deflate_dynamic.hpp) assume three waves per SIMD; one
-    register more and a third of the grid runs as a serial tail (measured: 96 -> 55 GB/s)."""
+    register more and a third of the grid runs as a serial tail (measured: 96 -> 55 GB/s).  The one-wavefront
+    encode kernels are told apart by their template arguments, read back from the mangled names."""
     import re
     log = os.path.join(os.path.dirname(hdtest.pkg().LIB_PATH), "csrc", "hd_api.resources.log")
     assert os.path.exists(log), "build with make -C 7bgzf_amd/csrc"
@@ -157,53 +158,45 @@ def test_kernel_resource_budgets():
         m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[bytes/\w+\])?: (\d+)", line)
         if m and cur is not None:
             cur[m.group(1).strip()] = int(m.group(2))
-    # k_deflate_dynamic<W, H, MINLEN, LAZY, EMIT, INTRA, DEEP, PARTS>: the emit-only instantiations have EMIT = 1 (PARTS = 0, and
-    # HD_LAT_PARTS_MAX for the latency segments parsed in parts)
-    emit = {k: v for k, v in kernels.items() if re.search(r"k_deflate_dynamicILi\d+ELi\d+ELi\d+ELi\d+ELi1ELi\d+ELi\d+ELi\d+ELi\d+EEEv", k)}
+    # k_deflate_dynamic<WIN_BITS, HASH_BITS, EMIT, INTRA, PARTS, BESIDE> and k_deflate_static<WIN_BITS, HASH_BITS, TOK, INTRA, PRIMED>:
+    # their template arguments, read back from the mangled names
+    def targs(k):
+        m = re.search(r"k_deflate_(?:static|dynamic)I((?:L[ib]\d+E)+)EEvNS_11DeflateArgsE$", k)
+        assert m, k
+        return [int(x) for x in re.findall(r"L[ib](\d+)E", m.group(1))]
+    emit = {k: v for k, v in kernels.items() if "k_deflate_dynamic" in k and targs(k)[2] == 1}
     dyn = {k: v for k, v in kernels.items() if "k_deflate_dynamic" in k and k not in emit}
     sta = {k: v for k, v in kernels.items() if "k_deflate_static" in k}
     inf = {k: v for k, v in kernels.items() if "k_inflateE" in k}
     inf_lat = {k: v for k, v in kernels.items() if "k_inflate_lat" in k}
     wg = {k: v for k, v in kernels.items() if "k_parse_wg" in k}
-    # (round 4: levels 6..9 are the workgroup parse in the throughput form; their latency segments share level 6's two-way
-    # kernels, so the 16 / 32 KiB geometries of rounds 2-3 are gone)
-    # (round 4, later: levels 3..9 reach the one-wavefront kernels only for their latency segments, parsed in parts: their fused
-    # kernels are not instantiated any more -- the fused kernel is level 2's)
     # (round 5: levels 3..9 are the workgroup parse in EVERY form -- one codec per level --, their member written by the one-wavefront
     # emit kernel or, behind the per-block boundary, by a workgroup (k_emit_wg); the one-wavefront parse kernels left are level 1's
-    # (plain and primed) and level 2's)
+    # (plain and primed) and level 2's, all in the 4 KiB ring / 1536-entry geometry)
     emit_wg = {k: v for k, v in kernels.items() if "k_emit_wg" in k}
     assert len(dyn) == 1 and len(emit) == 3 and len(sta) == 3 and len(inf) == 1 and len(inf_lat) == 1 and len(wg) == 8 and len(emit_wg) == 1, list(kernels)
     (v,) = emit_wg.values()
     assert v["VGPRs"] <= 128 and v["LDS Size"] <= 163840, v      # sixteen wavefronts, one workgroup per CU
+    beside = [k for k in emit if targs(k)[5] == 1]
+    assert len(beside) == 1, list(emit)
     for k, v in kernels.items():
         # (the one exception: the emit-only kernel's BESIDE instantiation spills a few of its ~230 scalar values past the VGPR lanes --
         # 32 bytes per lane, touched at block boundaries; it must stay within 128 registers to fit beside the parse, see below)
-        assert v["ScratchSize"] == 0 or (k.endswith("ELi0ELi1EEEvNS_11DeflateArgsE") and "k_deflate_dynamic" in k and v["ScratchSize"] <= 64), (k, v)
-    for k, v in dyn.items():
+        assert v["ScratchSize"] == 0 or (k in beside and v["ScratchSize"] <= 64), (k, v)
+    for k, v in dyn.items():                                     # the fused kernel (level 2)
         assert v["VGPRs"] <= 168, (k, v)
         # LDS is granted in 1280-byte units (measured: 10 waves of 15584 B do not fit a CU, of 15328 B do)
         units = -(-v["LDS Size"] // 1280)
-        deep = k.endswith("ELi1ELi0EEEvNS_11DeflateArgsE")      # the two-way tables (levels 6..9)
-        want = 12 if ("Li13ELi11E" in k or "Li12ELi11E" in k) else (18 if deep else 14) if "Li13ELi12E" in k else \
-            25 if "Li14ELi12E" in k else 32 if "Li14ELi13E" in k else 48
-        assert units <= want, (k, v)                 # 10 / 9 / 7 / 5 / 4 / 2 waves per CU: dynamic_grid()
+        assert units <= 12, (k, v)                   # 10 waves per CU: dynamic_grid()
     for k, v in emit.items():
-        # 16 waves per CU: launch_level().  The PARTS instantiation (latency segments: a handful of workgroups on an empty
+        # 16 waves per CU: launch_level2().  The PARTS instantiation (latency segments: a handful of workgroups on an empty
         # chip) is two wavefronts and two construction scratches per workgroup
-        parts = re.search(r"ELi0ELi[01]EEEvNS_11DeflateArgsE$", k) is None      # (..., PARTS, BESIDE)
+        parts = targs(k)[4] != 0
         assert v["VGPRs"] <= 128 and v["LDS Size"] <= (13 if parts else 8) * 1280, (k, v)
-    for k, v in sta.items():                                     # level 1 and the parse kernels of levels 2-9
-        # the level-1 geometry runs 18 waves per CU = five per SIMD on two of them: <= 96 VGPRs; the two-way parse kernels
-        # (8 / 5 / 4 waves per CU) have 168; the others <= 128 (four per SIMD)
-        # k_deflate_static<W, H, TOK, MINLEN, LAZY, INTRA, DEEP, PRIMED>
-        deep = re.search(r"ELi1ELb[01]EEEvNS_11DeflateArgsE$", k) is not None
-        assert v["VGPRs"] <= (96 if "Li12ELi11E" in k else 168 if deep else 128), (k, v)
+    for k, v in sta.items():                                     # level 1 (plain and primed) and level 2's parse
+        # the 4 KiB ring / 1536-entry geometry runs 18 waves per CU = five per SIMD on two of them: <= 96 VGPRs, 7 LDS units
         units = -(-v["LDS Size"] // 1280)
-        tok = "ELb1E" in k                           # parse kernels; level 1 itself is ELb0E
-        want = 7 if "Li12ELi11E" in k else 10 if "Li13ELi11E" in k else (16 if deep else 12) if "Li13ELi12E" in k else \
-            25 if "Li14ELi12E" in k else 32 if "Li14ELi13E" in k else 48
-        assert units <= want, (k, v)                 # 18 / 12 / 10 / 8 / 5 / 4 / 2 waves per CU: parse_slots() (two-way tables from level 6 on)
+        assert v["VGPRs"] <= 96 and units <= 7, (k, v)          # parse_slots()
     (v,) = inf.values()
     assert v["VGPRs"] <= 80 and v["LDS Size"] <= 6400, v         # five LDS units (25 per CU), 6 waves per SIMD: 24 waves per CU
     (v,) = inf_lat.values()
@@ -219,9 +212,9 @@ def test_kernel_resource_budgets():
             assert v["VGPRs"] <= 96 and v["LDS Size"] == 0, (k, v)
         else:
             assert v["VGPRs"] <= 128 and v["LDS Size"] <= 163840, (k, v)
-    for k, v in emit.items():
-        if k.endswith("ELi0ELi1EEEvNS_11DeflateArgsE"):
-            assert v["VGPRs"] <= 128 and v["LDS Size"] <= 8 * 1280, (k, v)      # ... the emit-only kernel that runs beside it
+    for k in beside:
+        v = kernels[k]
+        assert v["VGPRs"] <= 128 and v["LDS Size"] <= 8 * 1280, (k, v)          # ... the emit-only kernel that runs beside it
 
 
 def test_container_hosts_crc_fold_matches_zlib(tmp_path):

@@ -94,7 +94,7 @@ def main():
         cnt[last][kind] += 1
     steps = 4
     freq = {P_CODES: 1 / 4.6, P_PUT: 1 / 4.6, P_PSUM: 1 / 4.6, P_FLUSH: 1 / 18.4, P_FILL: 0.0, P_LONG: None}
-    out = {"kernel": "k_deflate_static<12,11,false,4,0,0>",
+    out = {"kernel": "k_deflate_static<12,11,false>",
            "what": "static instruction counts of the 16-step group loop body (4 unrolled INNER steps), per step, by phase "
                    "(tools/valu_by_phase.py: hipcc -S -gline-tables-only line tables).  runs_per_step: how often the phase's code "
                    "runs on the FASTQ-like set (the refill sits outside this loop body: once per 16 steps, ~60 VALU).",
