@@ -9,7 +9,12 @@ all 263,173 blocks, the size prefix scan and the gather of the members into one
 contiguous BGZF stream.  value = input bytes of ALL ranks / time.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--mode encode|decode]
-                  [--level L] [--gib G] [--no-cpu] [--no-extra] [--dump-outputs DIR]
+                  [--level L] [--gib G] [--dump-outputs DIR] [--full [--no-cpu] [--no-extra]]
+
+A plain run does what the headline needs and nothing more: it sets up, warms up, times the K steps,
+writes the outputs if --dump-outputs is given and prints the line.  --full adds everything else the
+benchmark measures or checks (the CPU baseline, the untimed full-size verification of an encode run,
+the other configs of BASELINE.json); --no-cpu and --no-extra leave parts of that out again.
 
 N > 1: one rank per GPU.  The driver launches the ranks itself (torch.distributed.run, WORLD_SIZE
 in the environment); called plainly as `python bench.py --gpus N`, bench.py starts that launcher
@@ -25,11 +30,14 @@ HD_BENCH_FORCE_DIST=1 runs that path at world size 1.
 The JSON line also carries
   roofline      the dominant kernel against the HBM roofline, timed with events on
                 the launch stream inside the timed region (DESIGN.md "Measurement")
+and with --full
+  verified      (encode) the whole packed stream of the last pass inflated on the device
+                and compared with the input, untimed (a plain run names the step's own checks)
   cpu_baseline  the REAL reference per-block path (libdeflate 1.23 through
                 libdeflate_deflate, lib/zlibutil.c:179, from oracle/_ref/libref.so)
                 on this box's host cores, on a bounded sample of the same workload;
                 plus the reused-compressor figure, one core alone, and our CPU twin.
-  configs       (N = 1, default invocation only) the other GPU configs of BASELINE.json
+  configs       (N = 1, default config only) the other GPU configs of BASELINE.json
                 measured in the same run: level 2 on the same data, decode of the
                 reference's libdeflate-6 stream (config 3), MiGz 1 MiB level 6 on
                 enwik-like text (config 5).
@@ -64,8 +72,10 @@ def parse():
     ap.add_argument("--tile-mib", type=int, default=64, help="host-generated tile replicated on the device")
     ap.add_argument("--first-record", type=int, default=0,
                     help="FASTQ-like data: the first record id (default: nine-digit ids, offset per tile; 1 = rounds 1-4's data, identical tiles)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="only the headline config (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the CPU baseline, the full-size verification and the other configs (a plain run times the headline only)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: no CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: no other configs")
     ap.add_argument("--data", default="fastq", choices=["fastq", "text", "random"],
                     help="fastq = configs[1..3]; text = config 5 (enwik-like); random = config 1 stand-in")
     ap.add_argument("--slot", type=int, default=0, help="experiment: output slot bytes per block (multiple of 16; 0 = default)")
@@ -659,7 +669,7 @@ def main():
         sys.exit(launch_ranks(args))             # before torch / HIP are touched in this process
     block = args.block_kib * 1024 if args.block_kib else BGZF_BLOCK
     cpu = None
-    if not args.no_cpu and int(os.environ.get("WORLD_SIZE", "1")) == 1:
+    if args.full and not args.no_cpu and int(os.environ.get("WORLD_SIZE", "1")) == 1:
         # The CPU legs come FIRST (a synthetic tile of the same generator, host only): the GPU phase then runs
         # in one piece at the end of the process instead of being followed by ~10 s of host-only work
         synth = importlib.import_module("7bgzf_amd.synth")
@@ -694,8 +704,14 @@ def main():
         B.free()
         res = B.decode(data, packed, in_off, in_len, want_crc, block, args.steps, args.warmup)
     s = summary(res, args.steps, world, args.mode)
-    verified = B.verify_encode(res, data, block) if args.mode == "encode" else {
-        "how": "every pass: status, lengths, per-block CRC-32 against the reference stream's; first and last blocks byte for byte"}
+    if args.mode == "decode":
+        verified = {"how": "every pass: status, lengths, per-block CRC-32 against the reference stream's; first and last "
+                           "blocks byte for byte"}
+    elif args.full:
+        verified = B.verify_encode(res, data, block)
+    else:
+        verified = {"how": "the last two passes: every member's status 0; the last: the member table ends where the stream "
+                           "does, the span starts with a member header (the full-size inflate-back check runs with --full)"}
     dumped = B.dump_outputs(res, args.mode, args.dump_outputs) if args.dump_outputs and rank == 0 else None
 
     # HBM bytes per launch from the PMC counters: NOT measured in this run (counters need rocprofv3 around the
@@ -768,8 +784,8 @@ def main():
             except Exception:
                 line["config"]["rccl_version"] = None
 
-    # ---- the other GPU configs of BASELINE.json, same run (default invocation, one GPU) ----------
-    default_run = (args.mode == "encode" and level == 1 and args.data == "fastq" and not args.block_kib
+    # ---- the other GPU configs of BASELINE.json, same run (--full on the default config, one GPU) ----------
+    default_run = (args.full and args.mode == "encode" and level == 1 and args.data == "fastq" and not args.block_kib
                    and world == 1 and not B.use_dist and not args.no_extra and not args.slot and args.gib == 16.0)
     if default_run:
         xs, xw = min(args.steps, 5), 2
@@ -867,7 +883,7 @@ def main():
         line["configs"] = configs
 
     if rank == 0:
-        if not args.no_cpu:
+        if args.full and not args.no_cpu:
             line["cpu_baseline"] = cpu           # N = 1 only (None on a multi-rank run)
         print(json.dumps(line), flush=True)
     if B.use_dist:

@@ -11,13 +11,15 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def run_bench(extra_env, *args):
+def run_bench(extra_env, *args, lean=True):
+    """bench.py on 1 GiB (a later --gib wins); lean: --no-cpu --no-extra, which leave the CPU baseline and the other
+    configs out of a --full run"""
     env = dict(os.environ, **extra_env)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):           # a launcher around pytest must not leak into the child
         if k not in extra_env:
             env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gib", "1", "--tile-mib", "16", "--steps", "3",
-                          "--warmup", "1", "--no-cpu", "--no-extra", *args],
+                          "--warmup", "1", *(["--no-cpu", "--no-extra"] if lean else []), *args],
                          env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -35,6 +37,30 @@ def test_bench_line_contract_small():
     assert j["value"] > 10 and 0 < j["roofline"]["frac"] < 1 and j["roofline"]["bound"] == "hbm"
     assert abs(j["roofline"]["achieved"] / j["roofline"]["peak"] - j["roofline"]["frac"]) < 1e-3
     assert "workload" in j["config"] and 0.3 < j["config"]["ratio"] < 0.6
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_leaves_the_rest_to_full():
+    """On the default config (16 GiB, level 1, FASTQ-like; the tile kept small) and with neither --no-cpu nor --no-extra, a
+    plain run times the headline and nothing more: no CPU baseline, no other configs, no full-size verification.  --full
+    brings all three back: the untimed inflate-back of the whole packed stream with no stalls, the reference's CPU figure
+    and every other config of BASELINE.json measured without an error."""
+    plain = run_bench({}, "--gib", "16", lean=False)
+    assert plain["config"]["input_bytes_per_gpu"] == 16 << 30
+    assert "cpu_baseline" not in plain and "configs" not in plain and "bytes" not in plain["verified"]
+    full = run_bench({}, "--gib", "16", "--full", lean=False)
+    v = full["verified"]
+    assert v["bytes"] == full["config"]["input_bytes_per_gpu"] and v["members"] == full["config"]["blocks_per_gpu"]
+    assert v["stalls"] == 0
+    have_ref = os.path.exists(os.path.join(ROOT, "oracle", "_ref", "libref.so"))
+    assert full["cpu_baseline"]["value"] > 0 and full["cpu_baseline"]["kind"] == ("reference" if have_ref else "port")
+    assert sorted(full["configs"]) == sorted(["encode_l2", "encode_l6", "decode_own_l1", "decode_libdeflate6", "decode_zlib6",
+                                              "migz_l6_text", "migz_l5_text", "migz_l3_text"])
+    for name, c in full["configs"].items():
+        if not have_ref and name in ("decode_libdeflate6", "decode_zlib6"):     # (the reference's encoders make their input)
+            assert c == {"error": "oracle/_ref/libref.so not built"}, (name, c)
+        else:
+            assert "error" not in c and c["value"] > 0, (name, c)
 
 
 @pytest.mark.gpu

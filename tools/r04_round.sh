@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 O=gpurun_out/r04_round; mkdir -p $O
 timeout -k 10 1000 python -m pytest tests -m gpu -x -q --timeout 300 -p no:cacheprovider > $O/gpu_tests.log 2>&1 || { tail -40 $O/gpu_tests.log; exit 1; }
 tail -2 $O/gpu_tests.log
-python3 bench.py > $O/bench_default.log 2>&1 || { tail -20 $O/bench_default.log; exit 1; }
+python3 bench.py --full > $O/bench_default.log 2>&1 || { tail -20 $O/bench_default.log; exit 1; }
 grep '^{' $O/bench_default.log > $O/bench_line_default.json
 python3 - $O/bench_line_default.json <<'PY'
 import json,sys

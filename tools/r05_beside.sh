@@ -6,7 +6,7 @@ line() { python3 -c "import sys,json; j=json.loads(sys.stdin.read().strip().spli
 for v in 0 1 0 1; do
   if [ $v = 1 ]; then export HIPDEFLATE_BESIDE=1; else unset HIPDEFLATE_BESIDE; fi
   echo "== HIPDEFLATE_BESIDE=${HIPDEFLATE_BESIDE:-unset}" | tee -a $O/ab.txt
-  timeout -k 10 120 python3 bench.py --level 6 --no-cpu --steps 3 --warmup 1 --no-extra 2>$O/err.log | line bgzf_l6 | tee -a $O/ab.txt || { tail -3 $O/err.log; exit 1; }
-  timeout -k 10 120 python3 bench.py --level 6 --data text --block-kib 1024 --no-cpu --steps 3 --warmup 1 --no-extra 2>$O/err.log | line migz_l6_text | tee -a $O/ab.txt || { tail -3 $O/err.log; exit 1; }
-  timeout -k 10 120 python3 bench.py --level 3 --data text --block-kib 1024 --no-cpu --steps 3 --warmup 1 --no-extra 2>$O/err.log | line migz_l3_text | tee -a $O/ab.txt || { tail -3 $O/err.log; exit 1; }
+  timeout -k 10 120 python3 bench.py --full --level 6 --no-cpu --steps 3 --warmup 1 --no-extra 2>$O/err.log | line bgzf_l6 | tee -a $O/ab.txt || { tail -3 $O/err.log; exit 1; }
+  timeout -k 10 120 python3 bench.py --full --level 6 --data text --block-kib 1024 --no-cpu --steps 3 --warmup 1 --no-extra 2>$O/err.log | line migz_l6_text | tee -a $O/ab.txt || { tail -3 $O/err.log; exit 1; }
+  timeout -k 10 120 python3 bench.py --full --level 3 --data text --block-kib 1024 --no-cpu --steps 3 --warmup 1 --no-extra 2>$O/err.log | line migz_l3_text | tee -a $O/ab.txt || { tail -3 $O/err.log; exit 1; }
 done

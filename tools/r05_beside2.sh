@@ -12,7 +12,7 @@ for v in 1 0 1 0; do
   if [ $v = 1 ]; then export HIPDEFLATE_NO_BESIDE=1; else unset HIPDEFLATE_NO_BESIDE; fi
   echo "== HIPDEFLATE_NO_BESIDE=${HIPDEFLATE_NO_BESIDE:-unset}" | tee -a $O/ab.txt
   for L in 3 5 6; do
-    timeout -k 10 120 python3 bench.py --level $L --no-cpu --steps 3 --warmup 1 --no-extra 2>$O/err.log | line bgzf_l$L | tee -a $O/ab.txt || { tail -3 $O/err.log; exit 1; }
+    timeout -k 10 120 python3 bench.py --full --level $L --no-cpu --steps 3 --warmup 1 --no-extra 2>$O/err.log | line bgzf_l$L | tee -a $O/ab.txt || { tail -3 $O/err.log; exit 1; }
   done
-  timeout -k 10 120 python3 bench.py --level 6 --data text --no-cpu --steps 3 --warmup 1 --no-extra 2>$O/err.log | line bgzf_text_l6 | tee -a $O/ab.txt || { tail -3 $O/err.log; exit 1; }
+  timeout -k 10 120 python3 bench.py --full --level 6 --data text --no-cpu --steps 3 --warmup 1 --no-extra 2>$O/err.log | line bgzf_text_l6 | tee -a $O/ab.txt || { tail -3 $O/err.log; exit 1; }
 done

@@ -3,7 +3,7 @@ set -e
 cd ${GRAFT_REPO_ROOT:-.}
 export TMPDIR=/tmp
 O=gpurun_out/r05_round; mkdir -p $O
-timeout -k 10 400 python3 bench.py > $O/bench_default.log 2>&1 || { tail -20 $O/bench_default.log; exit 1; }
+timeout -k 10 400 python3 bench.py --full > $O/bench_default.log 2>&1 || { tail -20 $O/bench_default.log; exit 1; }
 grep '^{' $O/bench_default.log > $O/bench_line_default.json
 python3 - $O/bench_line_default.json <<'PY'
 import json,sys

@@ -10,8 +10,8 @@ cp gpurun_out/r05_keep_trace/summary.txt $O/keep_trace_l6.txt
 line() { python3 -c "import sys,json; j=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$1', j['value'], 'GB/s, ms/step', j['ms_per_step'], 'stalls', j['verified'].get('stalls'))"; }
 : > $O/ab.txt
 for L in 5 3; do
-  timeout -k 10 150 python3 bench.py --level $L --data text --block-kib 1024 --no-cpu --steps 5 --warmup 1 --no-extra 2>$O/err.log | line migz_l${L}_text | tee -a $O/ab.txt || { tail -3 $O/err.log; exit 1; }
+  timeout -k 10 150 python3 bench.py --full --level $L --data text --block-kib 1024 --no-cpu --steps 5 --warmup 1 --no-extra 2>$O/err.log | line migz_l${L}_text | tee -a $O/ab.txt || { tail -3 $O/err.log; exit 1; }
 done
 for L in 6 5 3; do
-  timeout -k 10 150 python3 bench.py --level $L --no-cpu --steps 5 --warmup 1 --no-extra 2>$O/err.log | line encode_l$L | tee -a $O/ab.txt || { tail -3 $O/err.log; exit 1; }
+  timeout -k 10 150 python3 bench.py --full --level $L --no-cpu --steps 5 --warmup 1 --no-extra 2>$O/err.log | line encode_l$L | tee -a $O/ab.txt || { tail -3 $O/err.log; exit 1; }
 done

@@ -8,6 +8,6 @@ for v in 0 1 0 1; do
   if [ $v = 1 ]; then export HIPDEFLATE_NO_BESIDE=1; else unset HIPDEFLATE_NO_BESIDE; fi
   echo "== HIPDEFLATE_NO_BESIDE=${HIPDEFLATE_NO_BESIDE:-unset}" | tee -a $O/ab2.txt
   for L in 6 5 3; do
-    timeout -k 10 150 python3 bench.py --level $L --data text --block-kib 1024 --no-cpu --steps 3 --warmup 1 --no-extra 2>$O/err.log | line migz_l${L}_text | tee -a $O/ab2.txt || { tail -3 $O/err.log; exit 1; }
+    timeout -k 10 150 python3 bench.py --full --level $L --data text --block-kib 1024 --no-cpu --steps 3 --warmup 1 --no-extra 2>$O/err.log | line migz_l${L}_text | tee -a $O/ab2.txt || { tail -3 $O/err.log; exit 1; }
   done
 done
