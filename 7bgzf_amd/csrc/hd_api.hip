@@ -576,7 +576,7 @@ uint64_t hipdeflate_bound(uint64_t block_bytes, int level)
 // hardware counters (rocprofv3 --pmc dispatches one kernel at a time and exports these variables to its child) -- the emit kernel
 // follows the parse as in round 4: the same bytes, and no resident wavefronts waiting (bounded, ~2 s a block) for a parse that
 // cannot start.  HIPDEFLATE_NO_BESIDE=1 says the same by hand.
-static uint32_t g_test_beside_keep = 3;     // hipdeflate_test_beside
+static uint32_t g_test_beside_keep = hd::BESIDE_KEEP_MAX;     // hipdeflate_test_beside
 static bool beside_allowed()
 {
 	auto on = [](const char *name) {
@@ -2104,7 +2104,7 @@ static int inflate_one(unsigned char *dest, size_t *destLen, const unsigned char
 
 void hipdeflate_test_beside(int keep, uint32_t sub_cap)
 {
-	g_test_beside_keep = keep < 0 ? 0u : keep > 3 ? 3u : (uint32_t)keep;
+	g_test_beside_keep = keep < 0 ? 0u : (uint32_t)keep > hd::BESIDE_KEEP_MAX ? hd::BESIDE_KEEP_MAX : (uint32_t)keep;
 	hd::wg_sub_test() = sub_cap;
 }
 

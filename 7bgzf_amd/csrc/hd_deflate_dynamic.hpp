@@ -506,18 +506,6 @@ __device__ __noinline__ uint32_t crc_of_block(const CrcTables *ct, const uint8_t
 // (a pointer known to be to device memory: the records' loads are global_load, not flat_load -- a flat load counts as an LDS access too,
 // and every wait for the LDS in the token loops would wait for the tokens requested ahead)
 typedef const __attribute__((address_space(1))) uint32_t *hd_global_u32p;
-#ifndef HD_BESIDE_SC1_LOADS
-#define HD_BESIDE_SC1_LOADS 1
-#endif
-#ifndef HD_EXP_NO_COUNT
-#define HD_EXP_NO_COUNT 0
-#endif
-#ifndef HD_BESIDE_KEEP
-#define HD_BESIDE_KEEP 3                         // emit wavefronts a CU keeps beside a parse workgroup (k_deflate_dynamic<..., BESIDE>)
-#endif
-#ifndef HD_BESIDE_EMIT_PRIO
-#define HD_BESIDE_EMIT_PRIO 0
-#endif
 template <int WIN_BITS, int HASH_BITS, int EMIT, int INTRA = 0, int PARTS = 0, int BESIDE = 0>
 __global__ __launch_bounds__(PARTS ? 128 : 64) void k_deflate_dynamic(DeflateArgs a)
 {
@@ -599,15 +587,12 @@ __global__ __launch_bounds__(PARTS ? 128 : 64) void k_deflate_dynamic(DeflateArg
 				// cu: xcc_id [3:0] | se_id [15:13] | sh_id [12] | cu_id [11:8] of HW_ID -- 12 bits; simd_id [5:4]
 				const uint32_t cu = ((xcc & 15u) << 8) | (((hw >> 13) & 7u) << 5) | (((hw >> 12) & 1u) << 4) | ((hw >> 8) & 15u);
 				uint32_t *const places = a.arrived + 64;
-				stay = (la & 0xfffu) < (a.beside_keep < (uint32_t)HD_BESIDE_KEEP ? a.beside_keep : (uint32_t)HD_BESIDE_KEEP) * ((la >> 12) & 0x1ffu) &&
+				stay = (la & 0xfffu) < (a.beside_keep < BESIDE_KEEP_MAX ? a.beside_keep : BESIDE_KEEP_MAX) * ((la >> 12) & 0x1ffu) &&
 				       __hip_atomic_fetch_add(&places[4096 + 4 * cu + ((hw >> 4) & 3u)], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0;
 				__hip_atomic_fetch_add(a.arrived, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 			}
 			if (!uniform((uint32_t)stay))
 				return;
-#if HD_BESIDE_EMIT_PRIO
-			__builtin_amdgcn_s_setprio(HD_BESIDE_EMIT_PRIO);
-#endif
 		}
 	}
 	uint32_t *tok = (uint32_t *)a.scratch + (uint64_t)blockIdx.x * DYN_SLAB_TOKENS;
@@ -799,7 +784,7 @@ __global__ __launch_bounds__(PARTS ? 128 : 64) void k_deflate_dynamic(DeflateArg
 		auto wg_piece_load = [&](uint32_t k) {
 			if (k - wg_base >= 64) {
 				wg_base = k & ~63u;
-				if (BESIDE && HD_BESIDE_SC1_LOADS) {
+				if (BESIDE) {
 					// (beside the parse: what its workgroups wrote is read by loads that are coherent at the device's level themselves -- sc1 --
 					// instead of behind an invalidate of this XCD's L2 per block; see the wait below)
 					wg_pv = make_uint4(0, 0, 0, 0);
@@ -810,8 +795,9 @@ __global__ __launch_bounds__(PARTS ? 128 : 64) void k_deflate_dynamic(DeflateArg
 						wg_pv.z = __hip_atomic_load(pp + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 						wg_pv.w = __hip_atomic_load(pp + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 					}
-				} else
-				wg_pv = wg_base + lane < wg_np ? wg_pieces[wg_base + lane] : make_uint4(0, 0, 0, 0);
+				} else {
+					wg_pv = wg_base + lane < wg_np ? wg_pieces[wg_base + lane] : make_uint4(0, 0, 0, 0);
+				}
 			}
 		};
 		auto wg_piece_tokens = [&](uint32_t k) -> uint32_t {
@@ -829,10 +815,10 @@ __global__ __launch_bounds__(PARTS ? 128 : 64) void k_deflate_dynamic(DeflateArg
 				v = 0;
 				if (k < wg_k1) {
 					nv = c - base < 64 ? c - base : 64;
-					if (BESIDE && HD_BESIDE_SC1_LOADS)
+					if (BESIDE)
 						v = lane < nv ? __hip_atomic_load((hd_global_u32p)tok + (k * HD_WG_CUT + base + lane), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
 					else
-					v = lane < nv ? tok[k * HD_WG_CUT + base + lane] : 0u;
+						v = lane < nv ? tok[k * HD_WG_CUT + base + lane] : 0u;
 					base += 64;
 					if (base >= c) {
 						k++;
@@ -1337,8 +1323,9 @@ __global__ __launch_bounds__(PARTS ? 128 : 64) void k_deflate_dynamic(DeflateArg
 				if constexpr (BESIDE != 0) {
 					// beside the parse (hd_deflate_wg.hpp launch_wg): the block's workgroup says when its records are complete.  The
 					// polls are RMWs (they execute at the device's coherence point: no XCD's L2 can answer them with an old copy), a
-					// flag per 128-byte line, ~60 us apart; behind the wait an acquire at agent scope makes this XCD's L2 forget its
-					// clean lines, and the records -- written through their XCD's L2 by the parse (sc1) -- are read from memory.
+					// flag per 128-byte line, ~60 us apart; behind the wait the records -- written through their XCD's L2 by the parse
+					// (sc1) -- are read by sc1 loads, which this XCD's L2 cannot answer with an old copy, instead of behind an acquire at
+					// agent scope that makes the L2 forget its clean lines once per block.
 					// Bounded (~2 s where a whole sub-batch's parse is tens of milliseconds): stored and counted, never a hang
 					uint32_t spins = 0;
 					while (__hip_atomic_fetch_add(&a.ready[32 * (size_t)(a.span_sub ? b : bi)], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) {
@@ -1350,11 +1337,7 @@ __global__ __launch_bounds__(PARTS ? 128 : 64) void k_deflate_dynamic(DeflateArg
 						for (int z = 0; z < 16; z++)
 							__builtin_amdgcn_s_sleep(127);
 					}
-#if HD_BESIDE_SC1_LOADS
 					__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");     // (order only: the records are read by sc1 loads)
-#else
-					__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-#endif
 					if (waited_out && a.stalls && lane == 0)
 						atomicAdd(a.stalls, 1u);
 				}
@@ -1362,7 +1345,7 @@ __global__ __launch_bounds__(PARTS ? 128 : 64) void k_deflate_dynamic(DeflateArg
 				wg_base = 0xffffff00u;
 				tok = (uint32_t *)rec;
 				uint32_t m0;
-				if (BESIDE && HD_BESIDE_SC1_LOADS) {
+				if (BESIDE) {
 					m0 = __hip_atomic_load((hd_global_u32p)m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 					crcv = __hip_atomic_load((hd_global_u32p)m + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 				} else {
@@ -1436,25 +1419,18 @@ __global__ __launch_bounds__(PARTS ? 128 : 64) void k_deflate_dynamic(DeflateArg
 						w |= ls << (8 * q);
 					}
 					((uint32_t *)lsym)[lane] = w;
-#if HD_EXP_NO_COUNT != 2                      /* experiment (tools/r05_nocount.sh, timing only: with no counts every block gets the static code -- valid, larger) */
 					wg_for_tokens([&](uint32_t tk, uint32_t nv) {
 						const bool is_match = (tk & HD_TOKEN_MATCH) != 0;
 						const uint32_t idx = (tk >> 16) & 0x1ffu;                // literal, or 256 + (length - 3)
 						const uint32_t sym = is_match ? 257u + lsym[idx & 0xffu] : idx;
 						uint32_t ds, eb, ev;
 						off_slot((tk & 0xffff) + 1, ds, eb, ev);
-#if HD_EXP_NO_COUNT == 1
-						if (lane < nv && sym + ds == 0xffffffffu)     // (never: the arithmetic stays, the atomics go)
-							atomicAdd(&L.lf[0], 1u);
-#else
 						if (lane < nv) {
 							atomicAdd(&L.lf[sym], 1u);
 							if (is_match)
 								atomicAdd(&L.df[ds], 1u);
 						}
-#endif
 					});
-#endif
 				}
 					EMIT_T(5);
 					ntok_slab = blk_tok;

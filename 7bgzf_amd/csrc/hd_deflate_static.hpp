@@ -33,6 +33,7 @@ namespace hd {
 
 constexpr uint32_t HD_HINT_NO_WHOLE = 1;   // no block is short enough to be coded whole
 constexpr uint32_t HD_HINT_NO_SEG = 2;     // no block is long enough to be coded in segments
+constexpr uint32_t BESIDE_KEEP_MAX = 3;    // emit wavefronts a CU keeps at most beside a parse workgroup (k_deflate_dynamic<..., BESIDE>)
 
 struct DeflateArgs {
 	const uint8_t *in;
@@ -107,7 +108,7 @@ struct DeflateArgs {
 	// streams, not the twin's bytes
 	uint32_t take_sub = 0;
 	uint32_t *poison = nullptr;
-	uint32_t beside_keep = 3;                    // emit wavefronts a CU keeps (tests: hipdeflate_test_beside(keep = 0): nobody stays)
+	uint32_t beside_keep = BESIDE_KEEP_MAX;      // emit wavefronts a CU keeps (tests: hipdeflate_test_beside(keep = 0): nobody stays)
 	// host side only: a WgBeside (hd_deflate_wg.hpp) -- the second stream and the events of that scheme; nullptr = emit behind parse
 	void *beside = nullptr;
 };

@@ -33,23 +33,6 @@
 
 namespace hd {
 
-#ifndef HD_WG_OR_OFFSETS
-#define HD_WG_OR_OFFSETS 0                     /* (measured: no gain on 1 MiB members, -0.8 % on BGZF blocks -- tools/r05_ab_files.sh; the saturating adds stay) */
-#endif
-#ifndef HD_WG_UNIFORM_EDGES
-#define HD_WG_UNIFORM_EDGES 1
-#endif
-#ifndef HD_WG_UNALIGNED_LDS
-#define HD_WG_UNALIGNED_LDS 0                    /* own and candidate bytes by ONE ds_read_b128 at a byte address (gfx950 reads LDS unaligned) instead of five dwords + four v_alignbyte */
-#endif
-struct __attribute__((packed, aligned(1))) wg_u4u { uint32_t x, y, z, w; };
-struct __attribute__((packed, aligned(1))) wg_u2u { uint32_t x, y; };
-#ifndef HD_WG_LDS_AT_ZERO
-#define HD_WG_LDS_AT_ZERO 1
-#endif
-#ifndef HD_WG_LDS_AT_ZERO_BASE
-#define HD_WG_LDS_AT_ZERO_BASE 16                /* (not 0: address 0 cast to a pointer is the null pointer to the compiler, and what is reached through it is dead code) */
-#endif
 constexpr uint32_t WG_NW = HD_WG_WAVES;
 constexpr uint32_t WG_NP = WG_NW - 1;            // parsers
 constexpr uint32_t WG_STEPS = HD_WG_CUT / 64;
@@ -66,6 +49,8 @@ constexpr uint32_t WG_SPIN_LIMIT = HD_WG_SPIN_LIMIT;   // a turn that does not c
 static_assert(HD_WG_CUT == HD_PIECE && WG_STEPS == 16, "a piece of the parse is a piece of the ring");
 static_assert(HD_WG_RING == 65536 && HD_WG_WINDOW == 32768 && HD_WG_VCAP == 16, "the kernel is written for this geometry");
 constexpr uint32_t WG_TABLE_BYTES = 65536;      // ways x buckets x 2 at every level
+constexpr uint32_t WG_LDS_BASE = 16;            // LDS byte address of a BESIDE parse's WgLds (k_parse_wg; not 0: address 0 cast to a
+                                                // pointer is the null pointer to the compiler, and what is reached through it is dead code)
 
 struct WgLds {
 	__attribute__((aligned(16))) uint32_t ring32[HD_WG_RING / 4 + 8];      // + 32 bytes that mirror the start: unaligned reads never wrap
@@ -104,7 +89,9 @@ __device__ __forceinline__ bool wg_wait(wg_word_p word, uint32_t want, wg_word_p
 
 // first BIT at which two 16-byte strings differ, given the XOR of their dwords, capped at `cap_bits` (<= 128): v_ffbl_b32 of
 // an equal dword is 0xffffffff and stays there through the saturating add, so the minimum is the first differing dword's.
-// Nine instructions, pinned (the three adds as ORs since round 5's end): the compiler's own form of "first set bit or the next dword's" is a compare and a select per dword.
+// Nine instructions, pinned: the compiler's own form of "first set bit or the next dword's" is a compare and a select per dword.
+// (The three adds as ORs -- VOP2 at the fast issue rate where the saturating add is VOP3 -- measured no gain on 1 MiB members and
+// -0.8 % on BGZF blocks.)
 __device__ __forceinline__ uint32_t wg_common_bits(uint32_t x0, uint32_t x1, uint32_t x2, uint32_t x3, uint32_t cap_bits, uint32_t k96)
 {
 	uint32_t g0, g1, g2, g3, t;
@@ -112,18 +99,9 @@ __device__ __forceinline__ uint32_t wg_common_bits(uint32_t x0, uint32_t x1, uin
 	asm("v_ffbl_b32 %0, %1" : "=v"(g1) : "v"(x1));
 	asm("v_ffbl_b32 %0, %1" : "=v"(g2) : "v"(x2));
 	asm("v_ffbl_b32 %0, %1" : "=v"(g3) : "v"(x3));
-#if HD_WG_OR_OFFSETS
-	// (v_ffbl_b32 gives 0..31 or 0xffffffff: OR-ing the dword's bit offset in is the add, leaves 0xffffffff alone, and is a VOP2
-	// instruction at the fast issue rate where the saturating add is VOP3)
-	(void)k96;
-	asm("v_or_b32_e32 %0, 32, %1" : "=v"(g1) : "v"(g1));
-	asm("v_or_b32_e32 %0, 64, %1" : "=v"(g2) : "v"(g2));
-	asm("v_or_b32_e32 %0, 0x60, %1" : "=v"(g3) : "v"(g3));
-#else
 	asm("v_add_u32_e64 %0, %1, 32 clamp" : "=v"(g1) : "v"(g1));
 	asm("v_add_u32_e64 %0, %1, 64 clamp" : "=v"(g2) : "v"(g2));
 	asm("v_add_u32_e64 %0, %1, %2 clamp" : "=v"(g3) : "v"(g3), "s"(k96));
-#endif
 	asm("v_min3_u32 %0, %1, %2, %3" : "=v"(t) : "v"(g0), "v"(g1), "v"(g2));
 	asm("v_min3_u32 %0, %1, %2, %3" : "=v"(t) : "v"(t), "v"(g3), "v"(cap_bits));
 	return t;
@@ -168,16 +146,10 @@ __global__ __launch_bounds__(64 * HD_WG_WAVES) __attribute__((amdgpu_waves_per_e
 	// profiles/r05_wg_beside.txt).  Passed at launch (launch_wg), the size is not the compiler's business and 95 stays 96.
 	WgLds *Lraw;
 	if constexpr (BESIDE) {
-		extern __shared__ __attribute__((aligned(16))) uint8_t wg_lds_raw[];
-#if HD_WG_LDS_AT_ZERO
 		// (the kernel has no static LDS, so what it is given at launch starts at offset 0 of the workgroup's allocation, and the launch asks for
-		// HD_WG_LDS_AT_ZERO_BASE bytes more than the structure: it lies at that CONSTANT offset.  Through the symbol every address is
+		// WG_LDS_BASE bytes more than the structure: it lies at that CONSTANT offset.  Through an extern __shared__ symbol every address is
 		// `v_add_u32 v, 0, v` first -- the 0 being the symbol's value, which arrives too late to be folded: five vector instructions per step)
-		(void)wg_lds_raw;
-		Lraw = (WgLds *)(WG_LDS WgLds *)(uintptr_t)HD_WG_LDS_AT_ZERO_BASE;
-#else
-		Lraw = (WgLds *)wg_lds_raw;
-#endif
+		Lraw = (WgLds *)(WG_LDS WgLds *)(uintptr_t)WG_LDS_BASE;
 	} else {
 		__shared__ WgLds Ls;
 		Lraw = &Ls;
@@ -206,10 +178,6 @@ __global__ __launch_bounds__(64 * HD_WG_WAVES) __attribute__((amdgpu_waves_per_e
 	// slot where only the device knows them (hipdeflate_batch_deflate_dev: there a block longer than its slot is refused)
 	const bool refused = n > a.split_max;
 	const bool beside = BESIDE != 0;                 // the emit kernel runs beside this one and reads the records as the flags go up (launch_wg)
-#if HD_BESIDE_PARSE_PRIO
-	if constexpr (BESIDE != 0)
-		__builtin_amdgcn_s_setprio(HD_BESIDE_PARSE_PRIO);
-#endif
 	const uint32_t npieces = refused ? 0u : (n + HD_WG_CUT - 1) / HD_WG_CUT;
 	const uint32_t pfirst = npieces * q / SP, plast = npieces * (q + 1) / SP;    // (SP == 1: all of them)
 
@@ -318,17 +286,11 @@ __global__ __launch_bounds__(64 * HD_WG_WAVES) __attribute__((amdgpu_waves_per_e
 		// Pieces are handed out by a counter, not dealt round robin: three SIMDs carry four parsers and one carries three and
 		// the filler, and a parser that gets a larger share of its SIMD takes more pieces.  Whoever holds the lowest piece in
 		// work never waits for a higher one, so the hand-out cannot lock up.
-		uint32_t deal_round = 0;
-		(void)deal_round;
 		for (;;) {
 			uint32_t j = 0;
-#ifdef HD_WG_EXP_STATIC_DEAL                        /* experiment (tools/exp_wg_variants.sh): pieces dealt round robin */
-			j = w + WG_NP * deal_round++;
-#else
 			if (lane == 0)
 				j = __hip_atomic_fetch_add((WG_LDS uint32_t *)&Lp->next, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 			j = uniform(j);
-#endif
 			if (lane == 0)
 				vcur[w] = j < plast ? j : 0xffffffffu;
 			WG_BARRIER();
@@ -346,21 +308,14 @@ __global__ __launch_bounds__(64 * HD_WG_WAVES) __attribute__((amdgpu_waves_per_e
 #pragma unroll
 			for (int t = 0; t < (int)WG_STEPS; t++) {
 				const uint32_t p = P0 + 64 * t + lane;
-#if HD_WG_UNALIGNED_LDS
-				const wg_u2u kv = *(const wg_u2u *)((const uint8_t *)L.ring32 + (p & (HD_WG_RING - 1)));
-				const uint32_t v = kv.x, vh = kv.y;
-#else
 				const uint32_t *q = L.ring32 + ((p & (HD_WG_RING - 1)) >> 2);
 				const uint32_t d0 = q[0], d1 = q[1], d2 = q[2];
 				const uint32_t v = __builtin_amdgcn_alignbyte(d1, d0, p), vh = __builtin_amdgcn_alignbyte(d2, d1, p);   // (v_alignbyte_b32 reads bits [1:0] of its shift: tools/isa_probe.hip)
-#endif
 				ha[t] = hash_slot_addr6(v, vh, hk);
 			}
 			// ---- the turn: 16 steps of buckets, in order --------------------------------------------------------------
-#ifndef HD_WG_EXP_NO_TURN                           /* experiment (timing only: the bytes then depend on the race): no table turn */
 			if (!wg_wait(vturn, j, vfail))
 				break;
-#endif
 			__builtin_amdgcn_s_setprio(3);
 			wg_u32x16 cx, cy;
 			// one step's buckets: read, { itself, the WAYS - 1 newest before } written back; of the lanes of a step that share
@@ -416,18 +371,13 @@ __global__ __launch_bounds__(64 * HD_WG_WAVES) __attribute__((amdgpu_waves_per_e
 				const uint32_t S = P0 + 64 * t, p = S + lane;
 				const uint32_t lanes = pend - S < 64 ? pend - S : 64;
 				const uint64_t lanem = lanes == 64 ? ~0ull : (1ull << lanes) - 1;
-				// own 16 bytes
-#if HD_WG_UNALIGNED_LDS
-				const wg_u4u ov = *(const wg_u4u *)((const uint8_t *)L.ring32 + (p & (HD_WG_RING - 1)));
-				const uint32_t o0 = ov.x, o1 = ov.y, o2 = ov.z, o3 = ov.w;
-#else
+				// own 16 bytes: five dwords and four v_alignbyte, here and for the candidates below (ONE ds_read_b128 at the
+				// byte address, which gfx950 allows, measured half the speed: profiles/r05_wg_unaligned_lds.txt)
 				const uint32_t *q = L.ring32 + ((p & (HD_WG_RING - 1)) >> 2);
 				const uint32_t d0 = q[0], d1 = q[1], d2 = q[2], d3 = q[3], d4 = q[4];
 				const uint32_t sh = p;                           // (v_alignbyte_b32 reads bits [1:0] only)
 				const uint32_t o0 = __builtin_amdgcn_alignbyte(d1, d0, sh), o1 = __builtin_amdgcn_alignbyte(d2, d1, sh),
 					       o2 = __builtin_amdgcn_alignbyte(d3, d2, sh), o3 = __builtin_amdgcn_alignbyte(d4, d3, sh);
-#endif
-#if HD_WG_UNIFORM_EDGES
 				// (two per-lane values that are the same in every lane but at a block's edges -- its last positions, a piece's last
 				// step: decided by the scalar unit, the vector instructions only where they differ)
 				// (the empty asm statements: left to itself the compiler computes both sides and selects)
@@ -442,11 +392,6 @@ __global__ __launch_bounds__(64 * HD_WG_WAVES) __attribute__((amdgpu_waves_per_e
 					asm volatile("" : "+v"(room8));
 				}
 				const uint32_t lim = min(p, (uint32_t)HD_WG_WINDOW);              // (one instruction either way: no branch for it)
-#else
-				const uint64_t keyed = __ballot(p + HD_LAZY_KEY_BYTES <= n);
-				const uint32_t room8 = min(pend - p, (uint32_t)HD_WG_VCAP) << 3;  // in bits (keyed lanes: p < pend)
-				const uint32_t lim = min(p, (uint32_t)HD_WG_WINDOW);
-#endif
 				// the byte before (runs; only inside the step): as long as the own bytes repeat it
 				uint32_t best, dm1 = 0;                         // the best candidate's length, its distance - 1
 				{
@@ -473,22 +418,11 @@ __global__ __launch_bounds__(64 * HD_WG_WAVES) __attribute__((amdgpu_waves_per_e
 						asm("v_and_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_0 src1_sel:DWORD" : "=v"(ea) : "v"(cw), "v"(kfffc));
 					}
 					const uint64_t ok = __ballot(bm1 < lim) & keyed;
-#if HD_WG_UNALIGNED_LDS
-					uint32_t eb;                                          // the entry as it is: a byte offset in the ring
-					if (k & 1)
-						asm("v_mov_b32_sdwa %0, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_1" : "=v"(eb) : "v"(cw));
-					else
-						asm("v_mov_b32_sdwa %0, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_0" : "=v"(eb) : "v"(cw));
-					(void)ea;
-					const wg_u4u cv = *(const wg_u4u *)((const uint8_t *)L.ring32 + eb);
-					const uint32_t x0 = cv.x ^ o0, x1 = cv.y ^ o1, x2 = cv.z ^ o2, x3 = cv.w ^ o3;
-#else
 					const uint32_t *c = (const uint32_t *)((const uint8_t *)L.ring32 + ea);
 					const uint32_t c0 = c[0], c1 = c[1], c2 = c[2], c3 = c[3], c4 = c[4];
 					const uint32_t cs = (k & 1) ? cw >> 16 : cw;          // (v_alignbyte_b32 reads bits [1:0] of its shift)
 					const uint32_t x0 = __builtin_amdgcn_alignbyte(c1, c0, cs) ^ o0, x1 = __builtin_amdgcn_alignbyte(c2, c1, cs) ^ o1,
 						       x2 = __builtin_amdgcn_alignbyte(c3, c2, cs) ^ o2, x3 = __builtin_amdgcn_alignbyte(c4, c3, cs) ^ o3;
-#endif
 					const uint32_t m = wg_common_bits(x0, x1, x2, x3, room8, k96) >> 3;
 					const uint64_t better = __ballot(m > best) & ok;
 					best = sel(better, m, best);
@@ -680,10 +614,10 @@ void launch_emit_wg(const DeflateArgs &s, hipStream_t st);      // hd_emit_wg.hp
 // sub-batch k and a gate on its members.  Behind the last parse the same kernel runs once more at full occupancy for whatever has not
 // been taken.  The bytes do not depend on any of this.  What it needed, found the hard way: the parse's LDS passed at LAUNCH --
 // declared statically, the compiler pads the kernel's registers so that nothing else fits the SIMD -- and then at a CONSTANT offset
-// of that allocation (HD_WG_LDS_AT_ZERO_BASE), or every LDS address costs an add.
+// of that allocation (WG_LDS_BASE), or every LDS address costs an add.
 // Gain: config 5 (1 MiB members, level 6) 117.6 -> 131.8 GB/s, BGZF-sized blocks at level 6 115.6 -> 125.1, level 3 155 -> 175; the parse
 // runs a fifth slower beside the emit wavefronts, the emit kernel's own time is gone.
-constexpr size_t WG_LDS_DYNAMIC = sizeof(WgLds) + (HD_WG_LDS_AT_ZERO ? HD_WG_LDS_AT_ZERO_BASE : 0);     // what a BESIDE parse is launched with
+constexpr size_t WG_LDS_DYNAMIC = sizeof(WgLds) + WG_LDS_BASE;     // what a BESIDE parse is launched with
 struct WgBeside {
 	hipStream_t side = nullptr;
 	hipEvent_t ready = nullptr, done = nullptr;
@@ -717,9 +651,6 @@ struct WgBeside {
 		side = nullptr;
 	}
 };
-#ifndef HD_BESIDE_PARSE_PRIO
-#define HD_BESIDE_PARSE_PRIO 0                   // experiment switches of tools/r05_prio.sh (issue priority of the two kernels' wavefronts, emit wavefronts kept per CU)
-#endif
 constexpr uint32_t WG_BESIDE_WAVES = 768;        // three per CU ...
 constexpr uint32_t WG_BESIDE_CANDIDATES = 1536;  // ... kept from this many that are launched (k_deflate_dynamic<..., BESIDE>: a CU keeps those in its three lowest LDS blocks)
 constexpr uint32_t WG_BESIDE_MIN = 512;          // blocks in a sub-batch below which the emit kernel simply follows the parse

@@ -72,34 +72,6 @@ __device__ unsigned long long g_inf_cycles[8];       // [0] block headers + tabl
 #define INF_CYC_FLUSH do { } while (0)
 #endif
 
-// experiment switches (tools/exp_inflate_ab.sh rebuilds with -D...): the shipped values are the defaults
-#ifndef HD_INF_POLICY
-#define HD_INF_POLICY 0      // 1: a 16-lane-group pass only when it pays; 0: always, for every 9..16-byte match
-#endif
-#ifndef HD_INF_OWNER
-#define HD_INF_OWNER 0       // 1: short matches copied by their own lanes (measured: 146 GB/s against 160 with the lane groups --
-                             // sixteen ds_write_b8 per window and half cost the LDS path more than the vector units gained); 0: lane groups
-#endif
-#ifndef HD_INF_SPLIT_SRC
-#define HD_INF_SPLIT_SRC 1      // the lane-group passes read "ring byte, or flushed byte" as two typed loads (ds_read_u8 + a rare global_load_ubyte), not one flat load: +1.3 %
-#endif
-#ifndef HD_INF_ONEPERM
-#define HD_INF_ONEPERM 0     // 1: a lane-group pass pushes its owners' words with ONE ds_permute when no lane owns a match in both halves
-                             // (round 5, measured: 159.8 / 164.7 / 115.9 GB/s against 161.6 / 166.7 / 117.3 -- the test and the second
-                             // code path cost more than the permute and its five vector instructions: profiles/r05_inflate_cuts.txt)
-#endif
-#ifndef HD_INF_WALK5
-#define HD_INF_WALK5 1       // 1: five instructions and one branch per token -- the stop flag is bit 6 of the word that is ADDED to the position, so a
-                             // token the walk must stop in front of throws it out of the half by itself and the last token is taken back behind
-                             // the loop; 0: rounds 1-4's seven and two.  Round 5, ABAB on one box: 162.4 / 167.5 / 118.4 -> 164.5 / 169.4 / 119.6 GB/s
-#endif
-#ifndef HD_INF_DEFER
-#define HD_INF_DEFER 1       // 1: the first lane-group pass of a window stays open across the scalar copies
-#endif
-#ifndef HD_INF_PREFETCH
-#define HD_INF_PREFETCH 1    // 1: the stream piece after next is requested a refill ahead
-#endif
-
 constexpr uint32_t INF_LT_BITS = 9;      // litlen direct table (8 VGPRs once loaded)
 constexpr uint32_t INF_DT_BITS = 8;      // offset direct table
 constexpr uint32_t INF_RING    = 2048;   // LDS output ring of the throughput kernel: small on purpose, occupancy beats window
@@ -155,10 +127,7 @@ struct InfLdsT {
 	uint16_t lit_sorted[288];
 	uint16_t off_sorted[32];
 	uint16_t lit_count[16], off_count[16];
-	union {
-		__attribute__((aligned(16))) uint8_t ring[RING];
-		uint32_t ring32[RING / 4];
-	};
+	__attribute__((aligned(16))) uint8_t ring[RING];
 	union {
 		struct {
 			uint8_t cl[288 + 32 + 138 + 6];   // + worst-case RLE overrun
@@ -319,8 +288,6 @@ __device__ __forceinline__ void inflate_stream(const InflateArgs &a, InfLdsT<RIN
 	const CrcTables *ct = a.ct;
 	const bool want_crc = a.crc != nullptr;
 	const bool dst_aligned = (((uintptr_t)dst) & 15) == 0;
-	[[maybe_unused]] const bool dst_al4 = (((uintptr_t)dst) & 3) == 0;
-	[[maybe_unused]] const uint32_t ring_lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const void *)L.ring;   // LDS byte address of the ring
 
 	// ---- compressed input: 256-byte pieces, one dword per lane -----------
 	const uint32_t mis = (uint32_t)((uintptr_t)src & 3);
@@ -444,13 +411,9 @@ __device__ __forceinline__ void inflate_stream(const InflateArgs &a, InfLdsT<RIN
 				else
 					L.comp[lane] = load_piece(p0);
 				// the piece behind was requested when the last one was put in: its load has had ~16 windows to arrive
-				if (HD_INF_PREFETCH) {
-					L.comp[64 + lane] = pre_idx == p0 + 1 ? pre_piece : load_piece(p0 + 1);
-					pre_piece = load_piece(p0 + 2);
-					pre_idx = p0 + 2;
-				} else {
-					L.comp[64 + lane] = load_piece(p0 + 1);
-				}
+				L.comp[64 + lane] = pre_idx == p0 + 1 ? pre_piece : load_piece(p0 + 1);
+				pre_piece = load_piece(p0 + 2);
+				pre_idx = p0 + 2;
 				lds_p0 = p0;
 			}
 			// A window is 128 bits: every lane decodes the token that would start at bit
@@ -496,15 +459,18 @@ __device__ __forceinline__ void inflate_stream(const InflateArgs &a, InfLdsT<RIN
 
 			// The real chain from bit 0 of the window.  This walk is the hottest scalar
 			// code of the kernel (the CU has one scalar ALU) and the compiler spends ~20
-			// instructions per token on it, so it is written out: 4 SALU + 2 branches
+			// instructions per token on it, so it is written out: 3 SALU + 1 branch
 			// + 1 v_readlane per token (the lane select of v_readlane and s_bitset1 take
 			// the low 6 bits, so the second half runs on b itself).  It stops in front of
 			// the first token the window cannot take; that one goes to the scalar loop.
+			// The stop flag is bit 6 of the word that is ADDED to the position, so such a
+			// token throws the walk out of its half by itself and is taken back behind the
+			// loop.  (Testing the flag before every add, seven instructions and two
+			// branches, measured 1.0-1.3 % less throughput: profiles/r05_inflate_cuts.txt.)
 			// (A lane select written by the SALU needs no wait states before v_readlane,
 			// only one written by the VALU does.)
 			uint32_t b, wm;
 			uint64_t real0, real1;
-#if HD_INF_WALK5
 			asm volatile("s_mov_b32 %0, 0\n\t"
 				     "s_mov_b64 %1, 0\n\t"
 				     "s_mov_b64 %2, 0\n"
@@ -533,31 +499,6 @@ __device__ __forceinline__ void inflate_stream(const InflateArgs &a, InfLdsT<RIN
 				     : "=&s"(b), "=&s"(real0), "=&s"(real1), "=&s"(wm)
 				     : "v"(s0.walk), "v"(s1.walk)
 				     : "scc");
-#else
-			asm volatile("s_mov_b32 %0, 0\n\t"
-				     "s_mov_b64 %1, 0\n\t"
-				     "s_mov_b64 %2, 0\n"
-				     "Lhd_walk0_%=:\n\t"
-				     "v_readlane_b32 %3, %4, %0\n\t"
-				     "s_bitcmp1_b32 %3, 6\n\t"
-				     "s_cbranch_scc1 Lhd_walk_done_%=\n\t"
-				     "s_bitset1_b64 %1, %0\n\t"
-				     "s_add_u32 %0, %0, %3\n\t"
-				     "s_cmp_lt_u32 %0, 64\n\t"
-				     "s_cbranch_scc1 Lhd_walk0_%=\n"
-				     "Lhd_walk1_%=:\n\t"
-				     "v_readlane_b32 %3, %5, %0\n\t"
-				     "s_bitcmp1_b32 %3, 6\n\t"
-				     "s_cbranch_scc1 Lhd_walk_done_%=\n\t"
-				     "s_bitset1_b64 %2, %0\n\t"
-				     "s_add_u32 %0, %0, %3\n\t"
-				     "s_cmp_lt_u32 %0, 128\n\t"
-				     "s_cbranch_scc1 Lhd_walk1_%=\n"
-				     "Lhd_walk_done_%=:"
-				     : "=&s"(b), "=&s"(real0), "=&s"(real1), "=&s"(wm)
-				     : "v"(s0.walk), "v"(s1.walk)
-				     : "scc");
-#endif
 			// output positions; cut in front of the first token that would overrun the budget.  (Conditions are
 			// 64-bit lane masks: the ballot of ONE compare each, combined in scalar code, back to the lanes
 			// through sel() -- hd_device.hpp "lane masks".)
@@ -595,12 +536,8 @@ __device__ __forceinline__ void inflate_stream(const InflateArgs &a, InfLdsT<RIN
 			const uint32_t opos0 = pos + rel0, opos1 = pos + rel1;
 			// (lanes without a literal write to their dump slot: no exec juggling, no skip branches)
 			const uint64_t lit0 = real0 & s0.is_lit, lit1 = real1 & s1.is_lit;
-			auto store_literals = [&]() {
-				L.ring[sel(lit0, opos0 & (RING - 1), RING + lane)] = (uint8_t)(s0.e >> 16);
-				L.ring[sel(lit1, opos1 & (RING - 1), RING + lane)] = (uint8_t)(s1.e >> 16);
-			};
-			if (!HD_INF_OWNER)
-				store_literals();
+			L.ring[sel(lit0, opos0 & (RING - 1), RING + lane)] = (uint8_t)(s0.e >> 16);
+			L.ring[sel(lit1, opos1 & (RING - 1), RING + lane)] = (uint8_t)(s1.e >> 16);
 			const uint32_t wend = pos + cum;
 			// per-lane verdicts for the matches, so that the scalar loops below only dispatch
 			const uint64_t match0 = real0 & s0.is_len, match1 = real1 & s1.is_len;
@@ -635,28 +572,11 @@ __device__ __forceinline__ void inflate_stream(const InflateArgs &a, InfLdsT<RIN
 			// the group fetches it (ds_bpermute), each lane moves one byte -- from the ring, or, for a source that has
 			// left the ring, straight from the flushed output in HBM (one vector load for up to eight matches, where
 			// the scalar path below needs a load, three v_readlane and a dozen scalar instructions per match).
+			// (Copying each short match by its own lane instead -- aligned dwords, v_alignbyte, one ds_write_b8 per byte, no
+			// permutes -- measured 146 GB/s against 160: the LDS stores cost more than the vector units gained.)
 			const uint64_t l8_0 = __ballot(s0.length <= 8), l8_1 = __ballot(s1.length <= 8);
 			const uint64_t l16_0 = __ballot(s0.length <= 16), l16_1 = __ballot(s1.length <= 16);
-#if HD_INF_OWNER
-			// OWNER COPIES.  A short match (<= 16 bytes) of either kind is copied by ITS OWN LANE: three (five) aligned
-			// dwords from the source -- the ring, or the flushed output in HBM --, v_alignbyte, then the bytes one
-			// ds_write_b8 each with the byte number as the instruction's offset, for all such matches of the window
-			// at once.  All 8 (16) bytes are written whatever the length, highest byte first: what a match writes
-			// beyond its length lands on the bytes of the tokens behind it, and those are written LATER -- the lower
-			// bytes of the other owners by the instructions that follow, the literals and every other match after
-			// this block -- or, beyond the window's end, in the ring's 64 oldest bytes, which no source may touch.
-			// No compaction, no LDS permutes, no per-match scalar work: ~25 vector instructions for all of them where
-			// the lane groups took ~36 per pass (INSTS_VALU 209 -> 199 per 64 bytes with the groups; this kernel is
-			// bound by vector issue).  Not for: a destination run that wraps the ring (one scalar test per window),
-			// a ring source whose five dwords would, a far source when the output is not 4-byte aligned.
-			const bool ring_room = (pos & (RING - 1)) + cum + 16 <= RING;
-			const uint64_t sw0 = __ballot((srcl0 & (RING - 1)) <= RING - 20), sw1 = __ballot((srcl1 & (RING - 1)) <= RING - 20);
-			const uint64_t vfar0 = dst_al4 ? hbm0 : 0ull, vfar1 = dst_al4 ? hbm1 : 0ull;
-			const uint64_t vec0 = ring_room ? ((simple0 & sw0) | vfar0) & l16_0 : 0ull;
-			const uint64_t vec1 = ring_room ? ((simple1 & sw1) | vfar1) & l16_1 : 0ull;
-#else
 			const uint64_t vec0 = (simple0 | hbm0) & l16_0, vec1 = (simple1 | hbm1) & l16_1;
-#endif
 			uint64_t fa = hbm0 & ~vec0, fb = hbm1 & ~vec1;            // far and not taken above: the scalar path
 			// (FARK in flight; every one holds a register, and at 81 the kernel would lose a wave per SIMD -- the offset
 			// table's copy in registers made room: the scalar loop reads it from LDS now)
@@ -698,53 +618,6 @@ __device__ __forceinline__ void inflate_stream(const InflateArgs &a, InfLdsT<RIN
 			uint64_t done0 = 0, done1 = 0;                           // matches the lane groups took
 			bool pend = false;                                       // a lane-group pass is open: bytes pend_v for ring[pend_idx]
 			uint32_t pend_idx = 0, pend_v = 0;
-#if HD_INF_OWNER
-			{
-				auto owner_copy = [&](uint64_t vecm, uint64_t longm, uint64_t farm, uint32_t oposv, uint32_t srclv) {
-					if ((vecm >> lane) & 1) {
-						const uint32_t al = srclv & ~3u, sh = srclv & 3u;
-						uint32_t w0, w1, w2, w3, w4;
-						if ((farm >> lane) & 1) {
-							const uint32_t *g = (const uint32_t *)(dst + al);
-							w0 = g[0]; w1 = g[1]; w2 = g[2]; w3 = g[3]; w4 = g[4];
-						} else {
-							const uint32_t ri = (al & (RING - 1)) >> 2;
-							w0 = L.ring32[ri]; w1 = L.ring32[ri + 1]; w2 = L.ring32[ri + 2]; w3 = L.ring32[ri + 3]; w4 = L.ring32[ri + 4];
-						}
-						const uint32_t da = ring_lds + (oposv & (RING - 1));
-						if ((longm >> lane) & 1) {
-							const uint32_t b2 = __builtin_amdgcn_alignbyte(w3, w2, sh), b3 = __builtin_amdgcn_alignbyte(w4, w3, sh);
-							asm volatile("ds_write_b8_d16_hi %0, %4 offset:15\n\t"
-								     "ds_write_b8_d16_hi %0, %3 offset:14\n\t"
-								     "ds_write_b8 %0, %4 offset:13\n\t"
-								     "ds_write_b8 %0, %3 offset:12\n\t"
-								     "ds_write_b8_d16_hi %0, %2 offset:11\n\t"
-								     "ds_write_b8_d16_hi %0, %1 offset:10\n\t"
-								     "ds_write_b8 %0, %2 offset:9\n\t"
-								     "ds_write_b8 %0, %1 offset:8"
-								     :: "v"(da), "v"(b2), "v"(b2 >> 8), "v"(b3), "v"(b3 >> 8) : "memory");
-						}
-						const uint32_t b0 = __builtin_amdgcn_alignbyte(w1, w0, sh), b1 = __builtin_amdgcn_alignbyte(w2, w1, sh);
-						asm volatile("ds_write_b8_d16_hi %0, %4 offset:7\n\t"
-							     "ds_write_b8_d16_hi %0, %3 offset:6\n\t"
-							     "ds_write_b8 %0, %4 offset:5\n\t"
-							     "ds_write_b8 %0, %3 offset:4\n\t"
-							     "ds_write_b8_d16_hi %0, %2 offset:3\n\t"
-							     "ds_write_b8_d16_hi %0, %1 offset:2\n\t"
-							     "ds_write_b8 %0, %2 offset:1\n\t"
-							     "ds_write_b8 %0, %1"
-							     :: "v"(da), "v"(b0), "v"(b0 >> 8), "v"(b1), "v"(b1 >> 8) : "memory");
-					}
-				};
-				if (vec0)
-					owner_copy(vec0, vec0 & ~l8_0, hbm0, opos0, srcl0);
-				if (vec1)
-					owner_copy(vec1, vec1 & ~l8_1, hbm1, opos1, srcl1);
-				store_literals();
-				done0 = vec0;
-				done1 = vec1;
-			}
-#else
 			if (vec0 | vec1) {
 				// rel < 1024 (the window's budget), length <= 16, distance <= 32768: 10 + 5 + 16 bits
 				const uint32_t pk0 = rel0 | (s0.length << 10) | (s0.offset << 15);
@@ -759,42 +632,27 @@ __device__ __forceinline__ void inflate_stream(const InflateArgs &a, InfLdsT<RIN
 					const uint32_t slot0 = __builtin_amdgcn_mbcnt_hi((uint32_t)(own0 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)own0, 0));
 					const uint32_t slot1 = n0 + __builtin_amdgcn_mbcnt_hi((uint32_t)(own1 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)own1, 0));
 					const uint32_t sub = lane & (G - 1), lead = (lane & ~(G - 1)) << 2;
-					const bool both = (own0 & own1) != 0;
 					for (uint32_t base = 0; base < nt; base += NG) {
 						// an owner whose slot falls into this pass targets the first lane of group (slot - base); everybody
-						// else an odd lane (never a group's first): what arrives there is not looked at
-						uint32_t gg;
-						if (HD_INF_ONEPERM && !both) {
-							// (no lane owns a match in both halves -- nine windows in ten: one push instead of two)
-							const uint32_t d = sel(own0, slot0 - base, sel(own1, slot1 - base, NG));
-							const uint32_t ad = d < NG ? d * (4 * G) : ((lane | 1u) << 2);
-							gg = (uint32_t)__builtin_amdgcn_ds_permute((int)ad, (int)(d < NG ? sel(own0, pk0, pk1) : 0u));
-						} else {
-							const uint32_t d0 = sel(own0, slot0 - base, NG), d1 = sel(own1, slot1 - base, NG);
-							const uint32_t a0 = d0 < NG ? d0 * (4 * G) : ((lane | 1u) << 2), a1 = d1 < NG ? d1 * (4 * G) : ((lane | 1u) << 2);
-							const uint32_t g0 = (uint32_t)__builtin_amdgcn_ds_permute((int)a0, (int)(d0 < NG ? pk0 : 0u));
-							const uint32_t g1 = (uint32_t)__builtin_amdgcn_ds_permute((int)a1, (int)(d1 < NG ? pk1 : 0u));
-							gg = g0 | g1;
-						}
-						const uint32_t w = (uint32_t)__builtin_amdgcn_ds_bpermute((int)lead, (int)gg);
+						// else an odd lane (never a group's first): what arrives there is not looked at.  (One push instead of two
+						// where no lane owns a match in both halves measured 1.1 % slower: profiles/r05_inflate_cuts.txt.)
+						const uint32_t d0 = sel(own0, slot0 - base, NG), d1 = sel(own1, slot1 - base, NG);
+						const uint32_t a0 = d0 < NG ? d0 * (4 * G) : ((lane | 1u) << 2), a1 = d1 < NG ? d1 * (4 * G) : ((lane | 1u) << 2);
+						const uint32_t g0 = (uint32_t)__builtin_amdgcn_ds_permute((int)a0, (int)(d0 < NG ? pk0 : 0u));
+						const uint32_t g1 = (uint32_t)__builtin_amdgcn_ds_permute((int)a1, (int)(d1 < NG ? pk1 : 0u));
+						const uint32_t w = (uint32_t)__builtin_amdgcn_ds_bpermute((int)lead, (int)(g0 | g1));
 						const uint32_t ml = (w >> 10) & 31;                        // 0: no match in this group
 						const uint32_t dp = pos + (w & 1023) + sub, sp = dp - (w >> 15);
 						const bool act = sub < ml;
 						// (the whole source in the ring or the whole source flushed: the same test as inr above)
 						const bool ringsrc = wend - (sp - sub) <= RING - 64;
-#if HD_INF_SPLIT_SRC
 						// (said with the address spaces: left generic, the compiler turns "ring byte, or the flushed byte where the source is far"
 						// into ONE flat_load_ubyte from a selected address -- every pass then goes through the flat path, LDS and memory counters both)
 						uint32_t v = *((const __attribute__((address_space(3))) uint8_t *)&L.ring[0] + (sp & (RING - 1)));
 						if (act && !ringsrc)
 							v = *((const __attribute__((address_space(1))) uint8_t *)dst + sp);
-#else
-						uint32_t v = L.ring[sp & (RING - 1)];
-						if (act && !ringsrc)
-							v = dst[sp];
-#endif
 						const uint32_t di = act ? (dp & (RING - 1)) : RING + lane;
-						if (HD_INF_DEFER && !pend) {
+						if (!pend) {
 							pend = true;
 							pend_idx = di;
 							pend_v = v;
@@ -804,28 +662,11 @@ __device__ __forceinline__ void inflate_stream(const InflateArgs &a, InfLdsT<RIN
 					}
 				};
 				// A pass costs the same for one match as for a full set of groups (three LDS permutes, ~35 vector
-				// instructions): eight-lane groups take the <= 8-byte matches; the 9..16-byte ones get a pass of
-				// sixteen-lane groups when it pays -- a far one among them (the scalar far path is a load and ~45
-				// instructions per match), three or more, or when everything fits one such pass (<= 4 matches);
-				// otherwise they are "simple" and go one at a time below.
-				uint64_t a0 = vec0 & l8_0, a1 = vec1 & l8_1, b0 = vec0 & ~l8_0, b1 = vec1 & ~l8_1;
-				if (HD_INF_POLICY == 2) {
-					// a 16-lane-group pass only for a far match among the 9..16-byte ones, or two and more of them
-					const uint64_t bb = b0 | b1;
-					if (!((b0 & hbm0) | (b1 & hbm1)) && !(bb & (bb - 1)) && !(b0 && b1))
-						b0 = b1 = 0;
-				} else if (HD_INF_POLICY) {
-					const uint32_t n8 = (uint32_t)__popcll(a0) + (uint32_t)__popcll(a1);
-					const uint32_t n16 = (uint32_t)__popcll(b0) + (uint32_t)__popcll(b1);
-					const bool run16 = n16 && (((b0 & hbm0) | (b1 & hbm1)) != 0 || n16 >= 3 || n8 + n16 <= 4);
-					if (run16 && n8 + n16 <= 4) {
-						b0 |= a0;
-						b1 |= a1;
-						a0 = a1 = 0;
-					}
-					if (!run16)
-						b0 = b1 = 0;
-				}
+				// instructions): eight-lane groups take the <= 8-byte matches, sixteen-lane groups the 9..16-byte ones,
+				// however few there are.  (A sixteen-lane pass only when it paid -- a far match among them, three or more,
+				// or everything in one pass -- and the others one at a time below measured 4 % slower: one scalar copy
+				// loop per match costs more than a pass.)
+				const uint64_t a0 = vec0 & l8_0, a1 = vec1 & l8_1, b0 = vec0 & ~l8_0, b1 = vec1 & ~l8_1;
 				if (a0 | a1)
 					group_pass(std::integral_constant<uint32_t, 8>{}, a0, a1);
 				if (b0 | b1)
@@ -835,7 +676,6 @@ __device__ __forceinline__ void inflate_stream(const InflateArgs &a, InfLdsT<RIN
 				INF_STAT2(1, __popcll(INF_U64(a0)) + __popcll(INF_U64(a1)));
 				INF_STAT2(2, __popcll(INF_U64(b0)) + __popcll(INF_U64(b1)));
 			}
-#endif
 			INF_STAT2(0, __popcll(INF_U64(match0)) + __popcll(INF_U64(match1)));
 			INF_STAT2(3, __popcll(INF_U64(simple0 & ~done0)) + __popcll(INF_U64(simple1 & ~done1)));
 			INF_STAT2(4, __popcll(INF_U64(hbm0 & ~vec0)) + __popcll(INF_U64(hbm1 & ~vec1)));

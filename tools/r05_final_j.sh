@@ -1,4 +1,4 @@
-# round 5: the batch inflate kernel with the typed source loads (HD_INF_SPLIT_SRC) under the wide run of mutated streams
+# round 5: the batch inflate kernel with the typed source loads under the wide run of mutated streams
 set -o pipefail
 cd ${GRAFT_REPO_ROOT:?}
 O=gpurun_out/r05_final_j; mkdir -p $O
