@@ -1539,7 +1539,7 @@ static int lat_run_ex(hipdeflate_lat *c, const uint32_t *in_len, uint32_t n, int
 		if (in_len[i] > c->in_stride)
 			return HD_E_ARG;
 		h_len[i] = in_len[i];
-		const bool segd = seg_limit && in_len[i] > seg_limit;
+		const bool segd = hd::seg_coded(in_len[i], seg_limit, c->seg, frame, c->slot, out_cap < c->slot ? out_cap : c->slot);
 		hint &= segd ? ~hd::HD_HINT_NO_SEG : ~hd::HD_HINT_NO_WHOLE;
 		// the segment table k_seg_table would make (hd_segment.hpp), straight into device-visible memory
 		for (uint32_t k = 0; k < c->S; k++) {

@@ -642,8 +642,12 @@ __global__ __launch_bounds__(PARTS ? 128 : 64) void k_deflate_dynamic(DeflateArg
 		const uint32_t n = a.in_len[b];
 		if (PARTS ? false : EMIT ? (!a.wg && a.split_ovf[b] != 0) : (a.skip_small && a.split_ovf[b] == 0))
 			continue;                            // the other path's block
-		if (!EMIT && a.seg_limit && n > a.seg_limit)
+		if (!EMIT && seg_coded(n, a.seg_limit, a.seg_bytes, a.frame, a.out_stride, a.out_cap))
 			continue;                            // coded in segments (hd_segment.hpp)
+		if (!EMIT && whole_refused(a, n)) {
+			refuse_member(a, b, lane);
+			continue;
+		}
 		const bool aligned = (((uintptr_t)src) & 15) == 0;
 		uint32_t *dst32 = (uint32_t *)(a.out + (uint64_t)b * a.out_stride);
 

@@ -113,14 +113,14 @@ struct DeflateArgs {
 	void *beside = nullptr;
 };
 
-__device__ __forceinline__ uint32_t frame_hdr_bytes(int frame)
+__host__ __device__ __forceinline__ uint32_t frame_hdr_bytes(int frame)
 {
 	return frame == HD_FRAME_BGZF ? 18u : frame == HD_FRAME_MIGZ ? 20u : frame == HD_FRAME_ZLIB ? 2u
 	     : frame == HD_FRAME_GZIP ? 10u : 0u;
 }
 
 // CRC32 + ISIZE behind the gzip-family members, Adler-32 behind RFC 1950
-__device__ __forceinline__ uint32_t frame_trl_bytes(int frame)
+__host__ __device__ __forceinline__ uint32_t frame_trl_bytes(int frame)
 {
 	return frame == HD_FRAME_ZLIB ? 4u : (frame == HD_FRAME_BGZF || frame == HD_FRAME_MIGZ || frame == HD_FRAME_GZIP) ? 8u : 0u;
 }
@@ -137,6 +137,54 @@ __device__ __forceinline__ uint32_t frame_trl_field(int frame, uint32_t k, uint3
 __device__ __forceinline__ uint32_t frame_sfx_bytes(int frame)
 {
 	return frame == HD_FRAME_RAW_FLUSH ? 5u : 0u;
+}
+
+// segment slots per block (hd_segment.hpp): enough for the longest block whose worst case fits the slot
+__host__ __device__ inline uint32_t seg_slots_per_block(uint32_t cap, uint32_t seg)
+{
+	const uint32_t full = HD_STORED_SIZE(seg) + 5u;
+	// (a raw frame has no header, a flush frame no 03 00 tail -- its shortest last segment, one byte, takes
+	// 1 + 5 + 5 = 11 bytes: the count may be one high for the other frames, never low)
+	return cap / full + (cap % full >= 11u ? 1u : 0u);
+}
+
+// THE rule for which blocks of a launch are coded in segments (hd_segment.hpp) and which the ordinary coding takes -- the
+// segment table, the stitch and the finish, the level-1 kernel, level 2's parse, emit and fused kernel and the latency
+// contexts' host table all ask this one question.  (Here rather than in hd_segment.hpp: the ordinary kernels come first.)
+//   limit == 0 (every launch of blocks no longer than it; the headline): none.
+//   the throughput form (seg = HD_SEG_BYTES), and any block longer than HD_SEG_LIMIT: every block longer than `limit`,
+//     refused by the stitch when the room is below HD_SEG_WORST -- as the twin's twin_segmented().
+//   latency segments: a block longer than `limit` whose room covers the latency form's worst case; a longer block in a
+//     smaller room gets the ordinary form, as the twin and the per-block codecs give it (the twin's twin()).
+__host__ __device__ inline bool seg_coded(uint32_t len, uint32_t limit, uint32_t seg, int frame, uint64_t out_stride, uint32_t out_cap)
+{
+	if (!limit || len <= limit)
+		return false;
+	if (seg == HD_SEG_BYTES || len > HD_SEG_LIMIT)
+		return true;
+	uint64_t room = out_stride < out_cap ? out_stride : out_cap;
+	const uint32_t S = seg_slots_per_block(room > 0x7fffffffu ? 0x7fffffffu : (uint32_t)room, seg);
+	if (frame == HD_FRAME_BGZF && room > 65536)
+		room = 65536;
+	return HD_SEGN_COUNT(len, seg) <= S &&
+	       frame_hdr_bytes(frame) + HD_SEGN_WORST((uint64_t)len, seg, frame == HD_FRAME_RAW_FLUSH) + frame_trl_bytes(frame) <= room;
+}
+
+// Levels 1..2 in a launch that codes nothing in segments (its room is at most HD_SEG_LIMIT -- HD_LAT_SEG_BYTES in latency
+// mode): a block longer than HD_SEG_LIMIT has no form but the segmented one, whose worst case exceeds the block and so the
+// room -- refused, as the twin refuses it, instead of coded whole
+__device__ __forceinline__ bool whole_refused(const DeflateArgs &a, uint32_t n)
+{
+	return a.level >= 1 && !a.seg_limit && n > HD_SEG_LIMIT;
+}
+
+__device__ __forceinline__ void refuse_member(const DeflateArgs &a, uint32_t b, uint32_t lane)
+{
+	if (lane == 0) {
+		a.out_len[b] = 0;
+		if (a.status) a.status[b] = 1;
+		if (a.crc) a.crc[b] = 0;
+	}
 }
 
 // dword `j` (0..3) of the container header with its size field zero
@@ -338,13 +386,18 @@ __global__ __launch_bounds__(64) void k_deflate_static(DeflateArgs a)
 	const uint32_t n_own = n;
 	src -= prime;
 	n += prime;
-	if (TOK && !parted && n > a.split_max) {
+	// (a block coded in segments is flagged too: the emit kernel passes it over, and so does the fused kernel)
+	if (TOK && !parted && (n > a.split_max || seg_coded(n_own, a.seg_limit, a.seg_bytes, a.frame, a.out_stride, a.out_cap))) {
 		if (lane == 0)
 			a.split_ovf[b] = 1;
 		return;                              // the fused kernel takes the large blocks
 	}
-	if (!TOK && a.seg_limit && n > a.seg_limit)
+	if (!TOK && seg_coded(n_own, a.seg_limit, a.seg_bytes, a.frame, a.out_stride, a.out_cap))
 		return;                              // coded in segments (hd_segment.hpp)
+	if (!TOK && whole_refused(a, n_own)) {
+		refuse_member(a, b, lane);
+		return;
+	}
 	const bool aligned = (((uintptr_t)src) & 15) == 0;
 	uint32_t *dst32 = (uint32_t *)(a.out + (uint64_t)b * a.out_stride);
 	const CrcTables *ct = a.ct;

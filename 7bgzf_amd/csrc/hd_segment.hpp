@@ -30,15 +30,6 @@ struct SegArgs {
 	uint64_t *seg_dst;
 };
 
-// segment slots per block: enough for the longest block whose worst case fits the slot
-inline uint32_t seg_slots_per_block(uint32_t cap, uint32_t seg)
-{
-	const uint32_t full = HD_STORED_SIZE(seg) + 5u;
-	// (a raw frame has no header, a flush frame no 03 00 tail -- its shortest last segment, one byte, takes
-	// 1 + 5 + 5 = 11 bytes: the count may be one high for the other frames, never low)
-	return cap / full + (cap % full >= 11u ? 1u : 0u);
-}
-
 inline uint32_t seg_round_blocks(uint32_t nblocks, uint32_t S)
 {
 	uint32_t r = SEG_ROUND_MAX / S;
@@ -72,8 +63,9 @@ __global__ __launch_bounds__(256) void k_seg_table(SegArgs g)
 	const uint32_t i = g.first + t / g.S, k = t % g.S;
 	const uint32_t len = g.a.in_len[i];
 	const uint64_t o = (uint64_t)k * g.seg;
-	// blocks up to the limit are not segmented (the ordinary coding takes them): all their slots stay empty
-	const uint32_t sl = (len > g.limit && o < len) ? (len - o < g.seg ? (uint32_t)(len - o) : g.seg) : 0u;
+	// blocks the ordinary coding takes (seg_coded): all their slots stay empty
+	const bool segd = seg_coded(len, g.limit, g.seg, g.a.frame, g.a.out_stride, g.a.out_cap);
+	const uint32_t sl = (segd && o < len) ? (len - o < g.seg ? (uint32_t)(len - o) : g.seg) : 0u;
 	g.seg_off[t] = g.a.in_off[i] + (sl ? o : 0);
 	g.seg_len[t] = sl;
 }
@@ -90,9 +82,9 @@ __device__ __forceinline__ void seg_stitch_member(const SegArgs &g, uint32_t t, 
 	const CrcTables *ct = a.ct;
 	const uint32_t i = g.first + t, len = a.in_len[i];
 	const uint64_t base = (uint64_t)t * g.S;
-	if (len <= g.limit) {
+	if (!seg_coded(len, g.limit, g.seg, a.frame, a.out_stride, a.out_cap)) {
 		for (uint32_t k = lane; k < g.S; k += 64) {
-			g.seg_olen[base + k] = 0;               // nothing of this block's to gather
+			g.seg_olen[base + k] = 0;               // nothing of this block's to gather (its member, status and CRC: the ordinary coding's)
 			g.seg_dst[base + k] = 0;
 		}
 		return;
@@ -194,7 +186,7 @@ __device__ __forceinline__ void seg_finish_one(const SegArgs &g, const uint8_t *
 	const CrcTables *ct = a.ct;
 	const uint32_t i = g.first + t, len = a.in_len[i];
 	const uint64_t base = (uint64_t)t * g.S;
-	if (len <= g.limit)
+	if (!seg_coded(len, g.limit, g.seg, a.frame, a.out_stride, a.out_cap))
 		return;                                            // not a segmented block: the ordinary coding wrote its member
 	const uint32_t hdr = frame_hdr_bytes(a.frame), trl = frame_trl_bytes(a.frame);
 	const bool flush = a.frame == HD_FRAME_RAW_FLUSH;

@@ -155,7 +155,18 @@ uint64_t hipdeflate_bound(uint64_t block_bytes, int level);
  * min(out_stride, out_cap) bytes; out_len[i] = bytes written, crc32[i] = CRC-32
  * of the block's INPUT (fcrc32, applet/7bgzf.c:269), status[i] = 0 or 1 (does
  * not fit).  crc32/status may be NULL.  out_stride must be a multiple of 16.
- * Returns 0 if the batch ran (look at status[] per block), else HD_E_*. */
+ * Returns 0 if the batch ran (look at status[] per block), else HD_E_*.
+ * The room (tests/encode_room.py restates it): min(out_stride, out_cap), at most 65536 in HD_FRAME_BGZF, less the
+ * frame's header and trailer, must hold the member --
+ *   HD_FRAME_RAW_FLUSH keeps 5 bytes free behind the last data block for the flush suffix, which takes 4 or 5: a
+ *     member that would end exactly at the room may be refused;
+ *   levels 1..2, a block longer than HD_SEG_LIMIT: the room must cover HD_SEG_WORST whatever the data needs;
+ *   HD_FRAME_LATENCY, levels 1..2: a block longer than HD_LAT_SEG_BYTES(level) gets the latency form when the room
+ *     covers its worst case (HD_SEGN_WORST), else the ordinary form -- decided per block.  A block longer than
+ *     HD_SEG_LIMIT is the exception: it gets the latency form or none, where hip_deflate (and the twin) would fall
+ *     back to HD_SEG_BYTES segments in a room between the two worst cases.
+ * Stores are whole dwords: where min(out_stride, out_cap) is not a multiple of 4, the rest of its last dword (up to
+ * 3 bytes, never past out_stride) may be written too. */
 int hipdeflate_batch_deflate(const uint8_t *in, const uint64_t *in_off,
 			     const uint32_t *in_len, uint32_t nblocks,
 			     int level, int frame,
@@ -185,6 +196,9 @@ int hipdeflate_batch_inflate_flush(const uint8_t *in, const uint64_t *in_off,
 /* ---- batch API, device-resident buffers --------------------------------- */
 /* Same contracts, every pointer is a DEVICE address (hipMalloc'd, or a torch
  * CUDA tensor's data_ptr()); `stream` is a hipStream_t (NULL = default stream).
+ * One more rule for hipdeflate_batch_deflate_dev at levels >= 3: the host does not see the lengths, so the parse's
+ * records are sized by the slot, and a block longer than min(out_stride, out_cap) is refused (status 1) even where
+ * its member would fit.
  * Asynchronous: returns after enqueueing.  `in` and `out` bases must be
  * 16-byte aligned; fastest when every in_off[i] is too (0xff00 and 0x10000 are). */
 int hipdeflate_batch_deflate_dev(const void *in, const void *in_off,
