@@ -223,7 +223,10 @@ int hipdeflate_batch_inflate_flush_dev(const void *in, const void *in_off,
  * contiguous stream: member i (out_len[i] bytes at slots + i*stride) goes to
  * dst + dst_off[i], where dst_off is the exclusive prefix sum of out_len (plus
  * this rank's base when the stream is sharded across GPUs -- SURVEY.md 8(e)).
- * dst_off is computed on the device by hipdeflate_scan_sizes_dev. */
+ * dst_off is computed on the device by hipdeflate_scan_sizes_dev: dst_off[i] = base + out_len[0] + ... + out_len[i-1]
+ * in 64 bits.  *total (may be NULL) receives the sum of out_len[] alone: it excludes base; nblocks == 0 sets it to 0.
+ * hipdeflate_compact_dev wants stride a multiple of 4 and slots 4-byte aligned (else HD_E_ARG), writes member i's
+ * out_len[i] bytes and no byte beside them. */
 int hipdeflate_scan_sizes_dev(const void *out_len, uint32_t nblocks,
 			      uint64_t base, void *dst_off, void *total,
 			      void *stream);
@@ -254,7 +257,10 @@ int hipdeflate_compact_span_dev(const void *slots, uint64_t stride,
  *   hipdeflate_pipe_result(p, &data, &nbytes, &nblocks);  write(1, data, nbytes);
  */
 typedef struct hipdeflate_pipe hipdeflate_pipe;
-/* block_bytes must be a multiple of 16 (0xff00, 0x10000 and b * 1024 are); depth >= 2 */
+/* block_bytes must be a multiple of 16 (0xff00, 0x10000 and b * 1024 are); 2 <= depth <= 16; NULL otherwise.
+ * A slot is free again only when its result has been fetched AND a later call of hipdeflate_pipe_result has released
+ * it: a single thread may call hipdeflate_pipe_input only while (batches submitted and not yet fetched) + (1 if it
+ * holds a result) < depth, otherwise that call waits for ever.  hipdeflate_unpipe has the same limits and the same rule. */
 hipdeflate_pipe *hipdeflate_pipe_open(int level, int frame, uint32_t block_bytes,
 				      uint32_t blocks_per_batch, int depth);
 /* pinned buffer for the next batch, *cap = block_bytes * blocks_per_batch; waits for
@@ -263,14 +269,17 @@ uint8_t *hipdeflate_pipe_input(hipdeflate_pipe *p, size_t *cap);
 /* enqueue the batch just filled (nbytes <= cap, 0 allowed); returns at once */
 int hipdeflate_pipe_submit(hipdeflate_pipe *p, size_t nbytes);
 /* the oldest submitted batch: waits for it.  *data stays valid until the next call of
- * hipdeflate_pipe_result on this pipe.  Returns 0; 1 if a block did not fit its slot
- * (cannot happen for BGZF/MiGz block sizes); HD_E_*; HD_E_ARG when nothing is pending */
+ * hipdeflate_pipe_result on this pipe (also one that answers HD_E_ARG).  Returns 0; 1 if a block did not fit its slot
+ * (hipdeflate_bound(block_bytes, level), at most 65536 in HD_FRAME_BGZF: cannot happen for BGZF/MiGz block sizes,
+ * does for incompressible blocks of 65536 bytes in HD_FRAME_BGZF) -- such a block has out_len 0 in the member table
+ * and adds no bytes to the run, the other members are in place; HD_E_*; HD_E_ARG when nothing is pending */
 int hipdeflate_pipe_result(hipdeflate_pipe *p, const uint8_t **data, size_t *nbytes,
 			   uint32_t *nblocks);
 /* The members of the result last fetched (valid as long as its data): their sizes, their offsets inside the run --
  * the device's size prefix scan, i.e. the compressed offsets a block index needs (bgzip's .gzi, BAM virtual
  * offsets; the role of the index member of applet/7gzinga.c:173-193) -- and the CRC-32 of each block's input.
- * Any of the three may be NULL. */
+ * Any of the three may be NULL.  After a batch of 0 bytes there is no table: all three come back NULL.  HD_E_ARG when
+ * no result is held. */
 int hipdeflate_pipe_members(hipdeflate_pipe *p, const uint32_t **out_len, const uint64_t **dst_off,
 			    const uint32_t **crc32);
 /* BAM / tabix virtual file offset of byte `uoffset` of the block whose member starts at `coffset` */
@@ -291,7 +300,9 @@ typedef struct hipdeflate_unpipe hipdeflate_unpipe;
 hipdeflate_unpipe *hipdeflate_unpipe_open(uint32_t max_members, size_t in_cap, size_t out_cap, int depth);
 uint8_t *hipdeflate_unpipe_input(hipdeflate_unpipe *p, size_t *cap);
 /* member i: raw DEFLATE at in_off[i] .. +in_len[i] of the buffer (trailing bytes allowed),
- * inflating to exactly out_size[i] bytes (the ISIZE of its trailer); sum(out_size) <= out_cap */
+ * inflating to exactly out_size[i] bytes (the ISIZE of its trailer); sum(out_size) <= out_cap.
+ * HD_E_ARG, with the batch still the caller's to submit again, for nmembers > max_members, sum(out_size) > out_cap,
+ * a member reaching past in_cap, or a member of HD_INFLATE_MAX_IN bytes or more */
 int hipdeflate_unpipe_submit(hipdeflate_unpipe *p, const uint64_t *in_off, const uint32_t *in_len,
 			     const uint32_t *out_size, uint32_t nmembers);
 /* oldest submitted batch; returns 0, or the first member's non-zero inflate status
