@@ -16,15 +16,16 @@
 //   the greedy choice of token starts is a DPP prefix scan over 8-state
 //   transition functions (two v_perm_b32 per composition); the rare matches whose
 //   8 bytes all agree are extended cooperatively, 64 bytes per ballot; the step's
-//   tokens are compacted into an LDS queue, and once 64 wait there one pass turns
-//   them into static-Huffman codes, places them with a DPP prefix scan of their
-//   bit lengths and ORs them into an LDS staging ring that leaves as 512-byte
-//   stores.
+//   tokens are compacted into a queue -- a register, filled by a cross-lane push --
+//   and once 64 wait there one pass turns them into static-Huffman codes, places
+//   them with a DPP prefix scan of their bit lengths and ORs them into a small LDS
+//   staging ring, whose whole dwords leave in front of the next pass.
 //
 // HBM traffic per block: input read once (16 B/lane pieces), output written
-// once.  LDS per wave: ring 2^WIN_BITS + table (2 B x HD_TABLE_ENTRIES) + 1 KiB staging +
-// 640 B token queue = 8848 B at level 1: 7 of the 1280-byte units LDS is granted
-// in, 18 waves per CU.
+// once.  LDS per wave at level 1: ring 2^WIN_BITS + 16 + table (2 B x HD_TABLE_ENTRIES)
+// + 256 B staging = 7440 B: 6 of the 1280-byte units LDS is granted in, 21 waves
+// per CU (with the 1 KiB staging ring and the 640 B LDS queue it had been 8848 B, 7
+// units, 18 waves).  The level-2 parse (TOK) keeps its LDS queue and its 7 units.
 #pragma once
 #include <type_traits>
 #include "hd_device.hpp"
@@ -338,9 +339,10 @@ __global__ __launch_bounds__(64) void k_deflate_static(DeflateArgs a)
 	constexpr uint32_t W = 1u << WIN_BITS;
 	constexpr uint32_t W4M = W / 4 - 1;
 	constexpr uint32_t HS = HD_TABLE_ENTRIES(WIN_BITS, HASH_BITS);
-	constexpr uint32_t STG = 256;            // staging ring, dwords
-	constexpr uint32_t FLUSH_DW = 128;       // flushed 512 B at a time, 8 B per lane
-	constexpr uint32_t TOKQ = 128;           // token queue: < 64 waiting + <= 64 of one step
+	// staging ring, dwords: one emit pass adds at most 64 x 31 bits = 62 dwords, and every whole dword leaves in front
+	// of a pass, so at most one partial dword is live then: 1 + 62 + 1 (the spill-over slot put() always ORs into)
+	constexpr uint32_t STG = 64;
+	constexpr uint32_t TOKQ = 128;           // TOK: token queue in LDS, < 64 waiting + <= 64 of one step
 	// K16: every lane whose first eight bytes agree learns bytes 8..15 in the vector domain too (four more ring
 	// dwords per lane), so the scalar extension loop below runs only for matches of 16 bytes and more.  On text
 	// 98 % of the "long" matches are 9..15 bytes long, and the parse kernel waits on that loop's LDS round trip;
@@ -354,11 +356,11 @@ __global__ __launch_bounds__(64) void k_deflate_static(DeflateArgs a)
 	__shared__ __attribute__((aligned(16))) uint16_t table[HS];
 	// TOK: no bits are made here, the staging ring's place is taken by the symbol histograms
 	// (316 counters: litlen [0,286), offset [286,316), 32 bits wide: packed 16-bit ones measured 4 % slower
-	// where they bought no wave), and the queue has no dump slots
+	// where they bought no wave)
 	__shared__ __attribute__((aligned(16))) uint32_t stage[TOK ? 316 : STG];
-	// tokens waiting for the emit pass; [TOKQ, TOKQ + 32) = dump slots of lanes without one (two lanes share
-	// a slot: what lands there is never read)
-	__shared__ uint32_t tokbuf[TOK ? TOKQ : TOKQ + 32];
+	// TOK: tokens waiting for the emit pass.  Level 1 keeps them in a register (Q0 below) and has no such array:
+	// ring 4112 + table 3072 + staging 256 = 7440 B, six 1280-byte units where the LDS queue made it seven
+	__shared__ uint32_t tokbuf[TOKQ];
 	const uint32_t ring_lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const void *)ring32;   // LDS byte address of the ring
 
 	const uint32_t lane = threadIdx.x;
@@ -458,15 +460,18 @@ __global__ __launch_bounds__(64) void k_deflate_static(DeflateArgs a)
 		atomicOr(&stage[(i + 1) & (STG - 1)], (uint32_t)(wide >> 32));
 		bitpos += total;
 	};
-	// whenever 128 whole dwords are ready they leave as one 8-byte-per-lane store
-	auto flush_ready = [&]() {
-		if ((bitpos >> 5) - flushed >= FLUSH_DW) {
-			const uint32_t i = (flushed & (STG - 1)) + 2 * lane;   // flushed is a multiple of 128
-			const uint2 v = *(const uint2 *)&stage[i];
-			*(uint2 *)&stage[i] = make_uint2(0, 0);
-			*(uint2 *)&dst32[flushed + 2 * lane] = v;
-			flushed += FLUSH_DW;
+	// every whole dword staged so far leaves (at most 63: what one put() left), one contiguous 4-byte-per-lane store, and its
+	// place in the ring is zero again.  Called in front of every emit pass and of the member's tail, so that the ring only
+	// ever has to hold one partial dword and what comes then (a pass: 62 dwords; the tail: four)
+	auto drain = [&]() {
+		const uint32_t ready = (bitpos >> 5) - flushed;
+		if (lane < ready) {
+			const uint32_t i = (flushed + lane) & (STG - 1);
+			const uint32_t v = stage[i];
+			stage[i] = 0;
+			dst32[flushed + lane] = v;
 		}
+		flushed = bitpos >> 5;
 	};
 	auto fill_piece = [&]() {
 		const uint32_t piece = filled / HD_PIECE;
@@ -577,13 +582,22 @@ __global__ __launch_bounds__(64) void k_deflate_static(DeflateArgs a)
 	// ---- the back of the pipeline: codes + bit packing for up to 64 queued tokens
 	// (straight-line: both forms computed, one selected); false = the static
 	// stream no longer fits under `limit`
-	uint32_t qhead = 0, qtail = 0;
+	uint32_t qhead = 0, qtail = 0;                                    // TOK: the LDS queue
+	// Level 1: the queue is a register.  Lane j of Q0 holds waiting token j, qn of them wait (< 64 at every step's start);
+	// a step pushes its tokens across the lanes to [qn, qn + count) mod 64 (queue_push, hd_device.hpp), and when that
+	// passes 64 the pass takes Q0 and what wrapped round -- lanes [0, qn + count - 64) of the pushed register -- is the
+	// new Q0.  Lanes of Q0 from qn on hold anything
+	uint32_t Q0 = 0, qn = 0;
 	auto count_symbol = [&](uint32_t c) {                             // TOK only
 		atomicAdd(&stage[c], 1u);
 	};
-	auto emit_tokens = [&](uint32_t count) -> bool {
-		const uint32_t t = tokbuf[(qhead + lane) & (TOKQ - 1)];
-		qhead += count;
+	// tq: the tokens (level 1; TOK reads its queue)
+	auto emit_tokens = [&](uint32_t count, uint32_t tq) -> bool {
+		uint32_t t = tq;
+		if (TOK) {
+			t = tokbuf[(qhead + lane) & (TOKQ - 1)];
+			qhead += count;
+		}
 		if (!use_static)
 			return false;                            // given up earlier in this group of steps: nothing more is made
 		if (TOK) {
@@ -605,6 +619,7 @@ __global__ __launch_bounds__(64) void k_deflate_static(DeflateArgs a)
 			ntok_slab += count;
 			return true;
 		}
+		drain();
 		// literal / length: one table load (CrcTables::SL); offset: slot arithmetic, 5-bit code + extra bits
 		const uint64_t mmask = __ballot((int32_t)t < 0);
 		const uint64_t vmask = count >= 64 ? ~0ull : (1ull << (count & 63)) - 1;
@@ -622,7 +637,6 @@ __global__ __launch_bounds__(64) void k_deflate_static(DeflateArgs a)
 		if ((bitpos - paybase) + total + 7 > limit_bits)
 			return use_static = false;
 		put(code, nbits, incl, total);
-		flush_ready();
 		return true;
 	};
 
@@ -928,25 +942,31 @@ __global__ __launch_bounds__(64) void k_deflate_static(DeflateArgs a)
 		// token word: literal byte, or HD_TOKEN_MATCH_TAG | (len - 3) << 16 | (dist - 1), dist - 1 = p - c.
 		// The code generation and the bit packing below cost the same for 1 or 64
 		// tokens, and DNA-like input yields only ~14 tokens per step: they wait in
-		// a small LDS ring until 64 are there.
-		{
-			const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(tm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)tm, 0));
-			const uint32_t tw = sel(mm, (lenv << 16) + mw_base, lit);
-			const uint32_t qslot = (qtail + rank) & (TOKQ - 1);
-			if (TOK) {
-				if ((tm >> lane) & 1)
-					tokbuf[qslot] = tw;
-			} else {
-				tokbuf[sel(tm, qslot, TOKQ + (lane & 31))] = tw;
-			}
-			qtail += (uint32_t)__popcll(tm);
-			if (TOK)
-				db_room -= (int32_t)__popcll(tm);
-		}
+		// a queue (TOK: a small LDS ring; level 1: a register) until 64 are there.
 		// (a failed pass -- the stream would pass `limit`, or the slab is full -- clears use_static and the
 		// passes after it do nothing: the steps of a group need no exits between them)
-		if (qtail - qhead >= 64)
-			emit_tokens(64);
+		const uint32_t tw = sel(mm, (lenv << 16) + mw_base, lit);
+		if (TOK) {
+			const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(tm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)tm, 0));
+			const uint32_t qslot = (qtail + rank) & (TOKQ - 1);
+			if ((tm >> lane) & 1)
+				tokbuf[qslot] = tw;
+			qtail += (uint32_t)__popcll(tm);
+			db_room -= (int32_t)__popcll(tm);
+			if (qtail - qhead >= 64)
+				emit_tokens(64, 0);
+		} else {
+			const uint32_t R = queue_push(tm, qn, tw);
+			uint64_t newm;                                   // lanes qn..63 (lanes behind the step's last token take whatever came: not yet entries)
+			asm("s_lshl_b64 %0, -1, %1" : "=s"(newm) : "s"(qn) : "scc");
+			Q0 = sel(newm, R, Q0);
+			qn += (uint32_t)__popcll(tm);
+			if (qn >= 64) {
+				emit_tokens(64, Q0);
+				Q0 = R;
+				qn -= 64;
+			}
+		}
 		return use_static;
 	};
 	// fetch runs two steps ahead: a step is INNER when the lanes of step S + 128 still have 9 bytes
@@ -977,7 +997,7 @@ __global__ __launch_bounds__(64) void k_deflate_static(DeflateArgs a)
 	auto step_boundary = [&](auto inner_tag, uint32_t S) -> bool {
 		constexpr bool INNER = decltype(inner_tag)::value;
 		if (TOK && db_room <= 0 && use_static && (INNER || S + 64 < n)) {
-			if (qtail != qhead && !emit_tokens(qtail - qhead))
+			if (qtail != qhead && !emit_tokens(qtail - qhead, 0))
 				return false;
 			close_deflate_block();
 		}
@@ -1022,8 +1042,10 @@ __global__ __launch_bounds__(64) void k_deflate_static(DeflateArgs a)
 			break;
 		S += 64;
 	}
-	if (use_static && qtail != qhead)
-		emit_tokens(qtail - qhead);
+	if (TOK && use_static && qtail != qhead)
+		emit_tokens(qtail - qhead, 0);
+	if (!TOK && use_static && qn)
+		emit_tokens(uniform(qn), Q0);            // the short last pass (pinned: behind the loops the compiler takes the count for divergent)
 	clk.mark(1);                                 // steps done
 
 	// the CRC needs every piece, also when the static stream was abandoned
@@ -1059,6 +1081,7 @@ __global__ __launch_bounds__(64) void k_deflate_static(DeflateArgs a)
 
 	// end-of-block (7 zero bits), pad to a byte, then CRC32 + ISIZE as 4 x 16 bits
 	bitpos += 7;
+	drain();                                     // the tail adds at most four dwords to the one that stays
 	if (flush) {
 		// header of an empty stored block (BFINAL = 0, BTYPE = 00), alignment, LEN = 0, NLEN = ffff
 		bitpos = (bitpos + 3 + 7) & ~7u;
@@ -1081,7 +1104,7 @@ __global__ __launch_bounds__(64) void k_deflate_static(DeflateArgs a)
 		const uint32_t incl = wave_incl_scan<true>(nb);
 		put(tcode, nb, incl, 8 * trl);
 	}
-	// final flush: everything left, including the last partial dword (< 256 dwords)
+	// final flush: everything left, including the last partial dword (a handful)
 	for (uint32_t i = flushed + lane; i < ((bitpos + 31) >> 5); i += 64)
 		dst32[i] = stage[i & (STG - 1)];
 	if (lane == 0) {

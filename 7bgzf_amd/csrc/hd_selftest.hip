@@ -58,6 +58,18 @@ __global__ __launch_bounds__(64) void k_selftest_lds_order(const uint16_t *idx, 
 	}
 }
 
+// The level-1 encoder keeps its token queue in a register and pushes a step's tokens across the lanes (hd::queue_push): the
+// k-th token lane's word must arrive in lane (q + k) mod 64 -- the address wraps by itself -- and a lane that has no token
+// must not disturb one.  Case c: mask[c] = the token lanes, q[c] = tokens waiting; out = what every lane received
+__global__ __launch_bounds__(64) void k_selftest_queue_push(const uint64_t *mask, const uint32_t *q, uint32_t *out)
+{
+	const uint32_t c = blockIdx.x, lane = threadIdx.x;
+	// (in scalar registers, as the encoder has them)
+	const uint64_t tm = ((uint64_t)hd::uniform((uint32_t)(mask[c] >> 32)) << 32) | hd::uniform((uint32_t)mask[c]);
+	const uint32_t qn = hd::uniform(q[c]);
+	out[c * 64 + lane] = hd::queue_push(tm, qn, 0x5a000000u | (c << 8) | lane);
+}
+
 // one wavefront per frequency vector through the encoder's Huffman construction
 __global__ __launch_bounds__(64) void k_selftest_build(const uint32_t *freq, uint32_t nsyms, uint32_t maxbits, uint8_t *lens)
 {
@@ -113,6 +125,61 @@ int hd_probe_lds_order(void)
 	free(hx);
 	free(ho);
 	(void)hipFree(dx);
+	(void)hipFree(dout);
+	return bad;
+}
+
+// ---- the cross-lane push of the level-1 token queue: every q, masks from empty to full ----
+// Every token must arrive at lane (q + k) mod 64 (a lane without a token must not disturb one), and a lane nobody sends to
+// reads 0.  Returns the number of cases in which that does not hold; < 0 on an allocation or launch error.
+static int hd_probe_queue_push(void)
+{
+	const uint32_t per_q = 8, nc = 64 * per_q;
+	uint64_t *hm = (uint64_t *)malloc(nc * 8), *dm = nullptr;
+	uint32_t *hq = (uint32_t *)malloc(nc * 4), *ho = (uint32_t *)malloc(nc * 64 * 4), *dq = nullptr, *dout = nullptr;
+	int bad = -1;
+	if (hm && hq && ho && hipMalloc((void **)&dm, nc * 8) == hipSuccess && hipMalloc((void **)&dq, nc * 4) == hipSuccess &&
+	    hipMalloc((void **)&dout, nc * 64 * 4) == hipSuccess) {
+		uint64_t seed = 0x9e3779b97f4a7c15ull;
+		for (uint32_t c = 0; c < nc; c++) {
+			const uint32_t q = c / per_q, pat = c % per_q;
+			seed = seed * 6364136223846793005ull + 1442695040888963407ull;
+			const uint64_t r = seed ^ (seed >> 29);
+			// 0: every lane; 1: none; 2: one lane; 3: the low q + 1 lanes; 4: every other lane; 5: dense; 6: random; 7: sparse
+			hm[c] = pat == 0 ? ~0ull : pat == 1 ? 0ull : pat == 2 ? 1ull << (r >> 58) : pat == 3 ? (q == 63 ? ~0ull : (2ull << q) - 1)
+				: pat == 4 ? 0xaaaaaaaaaaaaaaaaull : pat == 5 ? r | (r << 17) | (r >> 23) : pat == 6 ? r : r & (r << 13) & (r >> 7);
+			hq[c] = q;
+		}
+		bool ok = hipMemcpy(dm, hm, nc * 8, hipMemcpyHostToDevice) == hipSuccess &&
+			  hipMemcpy(dq, hq, nc * 4, hipMemcpyHostToDevice) == hipSuccess;
+		if (ok) {
+			hipLaunchKernelGGL(k_selftest_queue_push, dim3(nc), dim3(64), 0, 0, dm, dq, dout);
+			ok = hipGetLastError() == hipSuccess && hipMemcpy(ho, dout, nc * 64 * 4, hipMemcpyDeviceToHost) == hipSuccess;
+		}
+		if (ok) {
+			bad = 0;
+			for (uint32_t c = 0; c < nc; c++) {
+				uint32_t k = 0, wrong = 0;
+				uint64_t fed = hm[c] == ~0ull ? 0ull : 1ull << ((hq[c] - 1) & 63);   // lanes somebody sends to
+				for (uint32_t l = 0; l < 64; l++)
+					if ((hm[c] >> l) & 1) {
+						wrong += ho[c * 64 + ((hq[c] + k) & 63)] != (0x5a000000u | (c << 8) | l);
+						fed |= 1ull << ((hq[c] + k) & 63);
+						k++;
+					}
+				for (uint32_t l = 0; l < 64; l++)
+					wrong += !((fed >> l) & 1) && ho[c * 64 + l] != 0;
+				if (wrong && bad++ < 5)
+					fprintf(stderr, "hipdeflate: queue push: q %u mask %016llx: %u lanes of %u tokens not what the queue reads\n",
+						hq[c], (unsigned long long)hm[c], wrong, k);
+			}
+		}
+	}
+	free(hm);
+	free(hq);
+	free(ho);
+	(void)hipFree(dm);
+	(void)hipFree(dq);
 	(void)hipFree(dout);
 	return bad;
 }
@@ -185,6 +252,13 @@ extern "C" int hipdeflate_selftest(void)
 	// ---- LDS write arbitration (also run by ctx_init) ----------------------------
 	{
 		const int bad = hd_probe_lds_order();
+		if (bad < 0)
+			return HD_E_NOMEM;
+		fails += bad;
+	}
+	// ---- the level-1 token queue's cross-lane push ----------------------------------
+	{
+		const int bad = hd_probe_queue_push();
 		if (bad < 0)
 			return HD_E_NOMEM;
 		fails += bad;

@@ -70,7 +70,9 @@
 #define HD_LAZY_KEY_BYTES  6           /* the key's bytes: a position with fewer left stays out of the table */
 
 /* Entries of the one-wavefront hash table (levels 1..2).  LDS is granted in 1280-byte units, so the table sizes are what
- * fills the units the ring leaves: 1536 entries with the 4 KiB ring (7 units, 18 waves per CU instead of 16 with 2048).
+ * fills the units the ring leaves: 1536 entries with the 4 KiB ring.  Level 1: ring 4112 + table 3072 + staging 256 = 7440 B,
+ * 6 units, 21 waves per CU; level 2's parse, which keeps a 1264 B histogram and a 512 B LDS token queue: 8960 B, 7 units,
+ * 18 per CU.  (2048 entries would cost either of them a unit: 18 and 16 per CU.)
  * The wider cases are the geometries rounds 1-4 ran levels 3..9 in, kept for level-1 builds with a wider window
  * (HD_L1_WIN_BITS): 1536 with an 8 KiB ring, 2560 with an 8 KiB ring and hash_bits 12 (10 waves per CU instead of 9
  * with 4096), 6144 with a 16 KiB ring and hash_bits 13.  hash_bits only names the geometry (11: 1536, 12: 2560 / 4096,
