@@ -16,7 +16,8 @@
 //   the greedy choice of token starts is a DPP prefix scan over 8-state
 //   transition functions (two v_perm_b32 per composition); the rare matches whose
 //   8 bytes all agree are extended cooperatively, 64 bytes per ballot; the step's
-//   tokens are compacted into a queue -- a register, filled by a cross-lane push --
+//   tokens are compacted into a queue -- a register, filled by a cross-lane push
+//   whose result joins it one step later, so that no step waits for it --
 //   and once 64 wait there one pass turns them into static-Huffman codes, places
 //   them with a DPP prefix scan of their bit lengths and ORs them into a small LDS
 //   staging ring, whose whole dwords leave in front of the next pass.
@@ -588,6 +589,17 @@ __global__ __launch_bounds__(64) void k_deflate_static(DeflateArgs a)
 	// passes 64 the pass takes Q0 and what wrapped round -- lanes [0, qn + count - 64) of the pushed register -- is the
 	// new Q0.  Lanes of Q0 from qn on hold anything
 	uint32_t Q0 = 0, qn = 0;
+	// What a step pushed joins Q0 one step LATER, behind the next step's probe and fetch have been issued: the push is an
+	// LDS-crossbar instruction, and merged where it is issued every step ended on its round trip (s_waitcnt lgkmcnt(0)
+	// straight behind the ds_permute_b32).  Now that wait is the one the next fetch makes for its own bytes anyway; only
+	// a step that runs the emit pass still waits at once.  Qp: the pushed register, qpm: its lanes that are entries of
+	// Q0 (the new ones; all 64 behind a pass, when what wrapped round is the whole queue)
+	uint32_t Qp = 0;
+	uint64_t qpm = 0;
+	auto queue_settle = [&]() {
+		Q0 = sel(qpm, Qp, Q0);
+		qpm = 0;
+	};
 	auto count_symbol = [&](uint32_t c) {                             // TOK only
 		atomicAdd(&stage[c], 1u);
 	};
@@ -673,6 +685,8 @@ __global__ __launch_bounds__(64) void k_deflate_static(DeflateArgs a)
 		f1 = fetch(inner_tag, S + 128);
 		if (OWN_AHEAD)
 			o1 = own(S + 192);                 // (every index is masked into the ring; bytes beyond the block never count)
+		if (!TOK)
+			queue_settle();                    // the last step's tokens (a covered step below pushes none and leaves qpm 0)
 
 		// ---- 3. verify the candidate + first 8 bytes of its length ---------
 		// Conditions live as 64-bit lane masks in scalar registers (hd_device.hpp "lane masks"): each is the
@@ -959,11 +973,12 @@ __global__ __launch_bounds__(64) void k_deflate_static(DeflateArgs a)
 			const uint32_t R = queue_push(tm, qn, tw);
 			uint64_t newm;                                   // lanes qn..63 (lanes behind the step's last token take whatever came: not yet entries)
 			asm("s_lshl_b64 %0, -1, %1" : "=s"(newm) : "s"(qn) : "scc");
-			Q0 = sel(newm, R, Q0);
+			Qp = R;
+			qpm = newm;
 			qn += (uint32_t)__popcll(tm);
 			if (qn >= 64) {
-				emit_tokens(64, Q0);
-				Q0 = R;
+				emit_tokens(64, sel(newm, R, Q0));
+				qpm = ~0ull;                             // Q0 = R, one step on
 				qn -= 64;
 			}
 		}
@@ -1044,6 +1059,8 @@ __global__ __launch_bounds__(64) void k_deflate_static(DeflateArgs a)
 	}
 	if (TOK && use_static && qtail != qhead)
 		emit_tokens(qtail - qhead, 0);
+	if (!TOK)
+		queue_settle();
 	if (!TOK && use_static && qn)
 		emit_tokens(uniform(qn), Q0);            // the short last pass (pinned: behind the loops the compiler takes the count for divergent)
 	clk.mark(1);                                 // steps done

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Static instruction counts of the level-1 kernel's 16-step group loop, per 64-byte step and by phase.
 
-  python3 tools/valu_by_phase.py > profiles/r02_l1_valu_by_phase.json
+  python3 tools/valu_by_phase.py > profiles/r07_l1_valu_by_phase.json
 
 hipcc -S -gline-tables-only gives every instruction its source line; the lines are mapped to the phases of
 7bgzf_amd/csrc/hd_deflate_static.hpp (fetch / probe / verify / scan / long matches / queue / emit / refill + CRC).
@@ -49,7 +49,7 @@ def main():
     P_POST, P_CODES, P_PUT = "post: carry, token words, queue", "emit: static codes of 64 queued tokens", "emit: bit packing into the staging ring"
     P_PSUM, P_FLUSH, P_FILL = "emit: bit-length prefix sum", "emit: flush of 512 staged bytes", "refill of the ring + CRC fold"
     P_HAND, P_LOOP = "step: pipeline hand-over", "loop control, step boundary"
-    marks = sorted([(find("auto put = [&]", src), P_PUT), (find("auto flush_ready = [&]", src), P_FLUSH), (find("auto fill_piece = [&]", src), P_FILL),
+    marks = sorted([(find("auto put = [&]", src), P_PUT), (find("auto drain = [&]", src), P_FLUSH), (find("auto fill_piece = [&]", src), P_FILL),
                     (find("auto fetch = [&]", src), P_FETCH), (find("auto probe = [&]", src), P_PROBE), (find("auto emit_tokens = [&]", src), P_CODES),
                     (find("BFINAL = 1 (0 in flush form)", src), P_LOOP), (find("auto step = [&]", src), P_HAND),
                     (find("---- 3. verify the candidate", src), P_VERIFY), (find("---- 4. greedy resolution", src), P_SCAN),
@@ -109,11 +109,11 @@ def main():
             tot[k] += v / steps
             if f:
                 wtot[k] += v / steps * f
-    out["long_match_path"] = ("its blocks (the extension loop and the re-threading walk, both inline asm since round 2) are laid out "
+    out["long_match_path"] = ("ROUND 2'S KERNEL, not re-measured since: its blocks (the extension loop and the re-threading walk, both inline asm since round 2) are laid out "
                               "behind the loop's back edge and are not in the counts above; measured instead: PMC per step minus the "
                               "weighted sum = ~41 SALU + ~12 branches + ~19 VALU per step at 1.27 long matches per step on the "
                               "FASTQ-like set (twin count), i.e. ~32 scalar + ~10 branch + ~15 vector instructions per long match")
-    out["measured_pmc_per_step"] = "profiles/r02_encode_l1_pmc_summary.json (tools/pmc_quick.sh): VALU 97.6, SALU 73.2, branch 16.0"
+    out["measured_pmc_per_step"] = "round 2's kernel, not re-measured since: profiles/r02_encode_l1_pmc_summary.json (tools/pmc_quick.sh): VALU 97.6, SALU 73.2, branch 16.0"
     out["sum_static_all_paths_per_step"] = {k: round(v, 1) for k, v in sorted(tot.items())}
     out["sum_weighted_by_frequency_per_step"] = {k: round(v, 1) for k, v in sorted(wtot.items())}
     json.dump(out, sys.stdout, indent=1)
