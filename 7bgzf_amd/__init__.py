@@ -38,6 +38,13 @@ class HipDeflateError(RuntimeError):
 _lib = None
 _vp = ctypes.c_void_p
 
+
+class MemberSummary(ctypes.Structure):
+    """hipdeflate_member_summary (include/hipdeflate.h)"""
+    _fields_ = [("nmembers", ctypes.c_uint64), ("out_bytes", ctypes.c_uint64), ("end_offset", ctypes.c_uint64),
+                ("status", ctypes.c_uint32)]
+
+
 # every symbol include/hipdeflate.h declares (checked by tests/test_abi.py)
 EXPORTS = [
     "hipdeflate_init", "hipdeflate_shutdown", "hipdeflate_available", "hipdeflate_version", "hipdeflate_stall_count",
@@ -48,7 +55,7 @@ EXPORTS = [
     "hipdeflate_pipe_close", "hipdeflate_unpipe_open", "hipdeflate_unpipe_input", "hipdeflate_unpipe_submit",
     "hipdeflate_unpipe_result", "hipdeflate_unpipe_close", "hipdeflate_test_build_lengths", "hipdeflate_test_beside",
     "hip_inflate_flush", "hipdeflate_batch_inflate_flush", "hipdeflate_batch_inflate_flush_dev", "hipdeflate_bound",
-    "hipdeflate_compact_span_dev",
+    "hipdeflate_compact_span_dev", "hipdeflate_index_members_dev", "hipdeflate_verify_members_dev",
     "hipdeflate_init_devices", "hipdeflate_device_count", "hipdeflate_use_device",
     "hipdeflate_pipe_open_on", "hipdeflate_unpipe_open_on", "hipdeflate_lat_open_on",
     "hipdeflate_pipe_members", "hipdeflate_lat_open", "hipdeflate_lat_input", "hipdeflate_lat_run", "hipdeflate_lat_output", "hipdeflate_lat_close",
@@ -124,6 +131,9 @@ def lib():
     L.hipdeflate_scan_sizes_dev.argtypes = [_vp, ctypes.c_uint32, ctypes.c_uint64, _vp, _vp, _vp]
     L.hipdeflate_compact_dev.argtypes = [_vp, ctypes.c_uint64, _vp, _vp, ctypes.c_uint32, _vp, _vp]
     L.hipdeflate_compact_span_dev.argtypes = [_vp, ctypes.c_uint64, _vp, _vp, ctypes.c_uint32, _vp, ctypes.c_uint64, _vp]
+    L.hipdeflate_index_members_dev.argtypes = [_vp, ctypes.c_uint64, ctypes.c_uint32, _vp, _vp, _vp, _vp, _vp,
+                                               ctypes.POINTER(MemberSummary), _vp]
+    L.hipdeflate_verify_members_dev.argtypes = [_vp, _vp, _vp, _vp, _vp, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint64), _vp]
     L.hipdeflate_pipe_open.restype = _vp
     L.hipdeflate_pipe_open.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int]
     L.hipdeflate_pipe_input.restype = _vp

@@ -24,6 +24,7 @@
 #include "hd_inflate.hpp"
 #include "hd_inflate_lat.hpp"
 #include "hd_compact.hpp"
+#include "hd_index.hpp"
 #include "hd_segment.hpp"
 
 namespace {
@@ -121,6 +122,10 @@ struct Ctx {
 	hipEvent_t ev_tiles = nullptr;   // the same for d_tiles
 	hipStream_t st_tiles = nullptr;
 	bool tiles_used = false;
+	// member index scratch (hd_index.hpp): the bitmap and tile counts of the blob, the candidate list and its successor
+	// tables.  An index call waits for its stream before it returns, so calls take turns by holding mu_index.
+	std::mutex mu_index;
+	Buf d_index, d_cand;
 };
 
 // One context per entry of the device list (hipdeflate_init(devices...)).  An entry is a HIP device ordinal;
@@ -524,7 +529,7 @@ void hipdeflate_shutdown(void)
 		(void)hipSetDevice(g.device);
 		(void)hipDeviceSynchronize();                        // launches on callers' streams may still use our scratch
 		for (Buf *b : { &g.d_in, &g.d_meta, &g.d_slots, &g.d_packed, &g.d_scratch, &g.d_scan, &g.h_in, &g.h_meta,
-				&g.h_out, &g.d_tok, &g.d_tiles })
+				&g.h_out, &g.d_tok, &g.d_tiles, &g.d_index, &g.d_cand })
 			b->release();
 		(void)hipFree(g.d_ct);
 		(void)hipFree(g.d_stalls);
@@ -782,6 +787,131 @@ int hipdeflate_compact_span_dev(const void *slots, uint64_t stride, const void *
 {
 	// k_compact only ever forms dst + dst_off[i] with dst_off[i] >= span_base: the address of "stream byte 0"
 	return hipdeflate_compact_dev(slots, stride, out_len, dst_off, nblocks, (uint8_t *)span - span_base, stream);
+}
+
+/* ---- device-resident container decode --------------------------------------- */
+
+// exclusive 64-bit prefix sum of len[0..n) into dst (n > 0), the sum into *total: the three scan kernels on scratch of the caller
+static void index_scan(const uint32_t *len, uint32_t n, uint64_t *tiles, uint64_t *dst, uint64_t *total, hipStream_t st)
+{
+	const uint32_t ntiles = (n + hd::SCAN_TILE - 1) / hd::SCAN_TILE;
+	hipLaunchKernelGGL(hd::k_scan_tile_sums, dim3(ntiles), dim3(256), 0, st, len, n, tiles);
+	hipLaunchKernelGGL(hd::k_scan_tiles, dim3(1), dim3(256), 0, st, tiles, ntiles, (uint64_t)0, total);
+	hipLaunchKernelGGL(hd::k_scan_finish, dim3(ntiles), dim3(256), 0, st, len, n, tiles, dst);
+}
+
+int hipdeflate_index_members_dev(const void *blob, uint64_t nbytes, uint32_t max_members, void *in_off, void *in_len,
+				 void *out_size, void *out_off, void *crc_want, hipdeflate_member_summary *summary, void *stream)
+{
+	Ctx &g = cur();
+	int r = ensure();
+	if (r)
+		return r;
+	if (!summary || ((uintptr_t)blob & 15) || (nbytes && !blob))
+		return HD_E_ARG;
+	memset(summary, 0, sizeof *summary);
+	if (nbytes == 0)
+		return 0;
+	hipStream_t st = (hipStream_t)stream;
+	const uint8_t *src = (const uint8_t *)blob;
+	std::lock_guard<std::mutex> lk(g.mu_index);
+	// pass 1 and 2: the sorted candidate list
+	const uint64_t nwords = (nbytes + hd::IDX_WORD - 1) / hd::IDX_WORD;
+	const uint64_t ntb64 = (nwords + hd::IDX_TILE_WORDS - 1) / hd::IDX_TILE_WORDS;
+	if (ntb64 > 0x7fffffffu)
+		return HD_E_ARG;
+	const uint32_t ntb = (uint32_t)ntb64;
+	const size_t scan_tiles_a = (ntb + hd::SCAN_TILE - 1) / hd::SCAN_TILE;
+	// sum[4] | scan tiles | tile_off | bitmap | tile_cnt
+	if (g.d_index.reserve(64 + (scan_tiles_a + ntb + nwords) * 8 + (size_t)ntb * 4))
+		return HD_E_NOMEM;
+	uint64_t *sum = (uint64_t *)g.d_index.p, *tiles_a = sum + 8, *tile_off = tiles_a + scan_tiles_a;
+	uint64_t *bitmap = tile_off + ntb;
+	uint32_t *tile_cnt = (uint32_t *)(bitmap + nwords);
+	HD_CHECK(hipMemsetAsync(sum, 0, 64, st));
+	hipLaunchKernelGGL(hd::k_index_flag, dim3(ntb), dim3(256), 0, st, src, nbytes, bitmap, tile_cnt);
+	index_scan(tile_cnt, ntb, tiles_a, tile_off, sum + 4, st);
+	HD_CHECK(hipGetLastError());
+	uint64_t h[4] = { 0, 0, 0, 0 };
+	HD_CHECK(hipMemcpyAsync(h, sum + 4, 8, hipMemcpyDeviceToHost, st));
+	HD_CHECK(hipStreamSynchronize(st));
+	if (h[0] > 0x7fffffffu)                                                  // candidate indices, and ncand + 255, stay well inside 32 bits
+		return HD_E_NOMEM;
+	const uint32_t ncand = (uint32_t)h[0];
+	uint64_t nrows = 0;
+	if (ncand) {
+		const size_t scan_tiles_b = ((size_t)ncand + hd::SCAN_TILE - 1) / hd::SCAN_TILE + ((size_t)max_members + hd::SCAN_TILE - 1) / hd::SCAN_TILE;
+		const size_t nc = ((size_t)ncand + 3) & ~(size_t)3;
+		// scan tiles | pos | succ[2] (later: rank) | mark | hdr | total
+		if (g.d_cand.reserve((scan_tiles_b + nc * 2) * 8 + nc * 12))
+			return HD_E_NOMEM;
+		uint64_t *tiles_b = (uint64_t *)g.d_cand.p, *pos = tiles_b + scan_tiles_b, *rank = pos + nc;
+		uint32_t *succ0 = (uint32_t *)rank, *succ1 = succ0 + nc, *mark = succ1 + nc, *hdr = mark + nc, *total = hdr + nc;
+		const uint32_t nwg = (ncand + 255) / 256;
+		hipLaunchKernelGGL(hd::k_index_write, dim3(ntb), dim3(256), 0, st, src, nbytes, (const uint64_t *)bitmap, nwords,
+				   (const uint64_t *)tile_off, pos);
+		hipLaunchKernelGGL(hd::k_index_links, dim3(nwg), dim3(256), 0, st, src, nbytes, (const uint64_t *)pos, ncand, succ0,
+				   hdr, total, mark);
+		// the true chain: rounds until 2^rounds >= ncand (a chain has at most ncand members)
+		for (uint64_t reach = 1; reach < ncand; reach *= 2) {
+			hipLaunchKernelGGL(hd::k_index_jump, dim3(nwg), dim3(256), 0, st, (const uint32_t *)succ0, succ1,
+					   (const uint32_t *)total, mark, ncand);
+			std::swap(succ0, succ1);
+		}
+		index_scan(mark, ncand, tiles_b, rank, sum + 0, st);                 // (the successor tables are dead: rank takes their place)
+		HD_CHECK(hipGetLastError());
+		HD_CHECK(hipMemcpyAsync(h, sum, 8, hipMemcpyDeviceToHost, st));
+		HD_CHECK(hipStreamSynchronize(st));
+		nrows = h[0];
+		if (nrows) {
+			const uint32_t ntab = (uint32_t)(nrows < max_members ? nrows : max_members);
+			hipLaunchKernelGGL(hd::k_members_tables, dim3(nwg), dim3(256), 0, st, src, (const uint64_t *)pos, (const uint32_t *)hdr,
+					   (const uint32_t *)total, (const uint32_t *)mark, (const uint64_t *)rank, ncand, nrows, max_members,
+					   (uint64_t *)in_off, (uint32_t *)in_len, (uint32_t *)out_size, (uint32_t *)crc_want, sum + 2);
+			if (ntab)
+				index_scan((const uint32_t *)out_size, ntab, tiles_b, (uint64_t *)out_off, sum + 1, st);
+		}
+	}
+	hipLaunchKernelGGL(hd::k_index_verdict, dim3(1), dim3(1), 0, st, src, nbytes, nrows, max_members, sum);
+	HD_CHECK(hipGetLastError());
+	HD_CHECK(hipMemcpyAsync(h, sum, 32, hipMemcpyDeviceToHost, st));
+	HD_CHECK(hipStreamSynchronize(st));
+	summary->nmembers = h[0];
+	summary->out_bytes = h[1];
+	summary->end_offset = h[2];
+	summary->status = (uint32_t)h[3];
+	return 0;
+}
+
+int hipdeflate_verify_members_dev(const void *status, const void *out_len, const void *crc32, const void *out_size,
+				  const void *crc_want, uint32_t nmembers, uint64_t *first_bad, void *stream)
+{
+	Ctx &g = cur();
+	int r = ensure();
+	if (r)
+		return r;
+	if (!first_bad)
+		return HD_E_ARG;
+	*first_bad = nmembers;
+	if (nmembers == 0)
+		return 0;
+	if (!status || !out_len || !crc32 || !out_size || !crc_want)
+		return HD_E_ARG;
+	hipStream_t st = (hipStream_t)stream;
+	std::lock_guard<std::mutex> lk(g.mu_index);
+	if (g.d_index.reserve(64))
+		return HD_E_NOMEM;
+	uint32_t *d_bad = (uint32_t *)g.d_index.p, bad = hd::IDX_NIL;
+	HD_CHECK(hipMemsetAsync(d_bad, 0xff, 4, st));
+	hipLaunchKernelGGL(hd::k_members_verify, dim3((nmembers + 255) / 256), dim3(256), 0, st, (const int32_t *)status,
+			   (const uint32_t *)out_len, (const uint32_t *)crc32, (const uint32_t *)out_size, (const uint32_t *)crc_want,
+			   nmembers, d_bad);
+	HD_CHECK(hipGetLastError());
+	HD_CHECK(hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, st));
+	HD_CHECK(hipStreamSynchronize(st));
+	if (bad != hd::IDX_NIL)
+		*first_bad = bad;
+	return 0;
 }
 
 /* ---- host-pointer API ------------------------------------------------------ */

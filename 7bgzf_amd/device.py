@@ -1,6 +1,7 @@
 """Device-resident view of the batch API for bench.py and the GPU tests: torch
 tensors own the HBM buffers (torch is plumbing here -- allocation, streams,
 torch.distributed), libhipdeflate.so does the work on the current stream."""
+import ctypes
 import importlib
 
 import numpy as np
@@ -47,6 +48,68 @@ class DeviceDeflate:
         rc = _pkg.lib().hipdeflate_compact_span_dev(_ptr(self.slots), self.slot, _ptr(self.out_len),
                                                     _ptr(self.dst_off), self.nblocks, _ptr(dst), span_base, _stream())
         _pkg._check(rc, "hipdeflate_compact_span_dev")
+
+
+class DeviceInflate:
+    """Decode a container file (BGZF, MiGz, any stream of the member kinds hd7bgzf -d reads) that lives in HBM: the
+    member table is made on the device (hipdeflate_index_members_dev), so no byte of the file visits the host.  Owns the
+    five table tensors of `max_members` entries plus out_len / crc / status of the inflate."""
+
+    def __init__(self, max_members, device="cuda"):
+        self.max_members = max_members
+
+        def table(dtype):
+            return torch.zeros(max_members, dtype=dtype, device=device)
+        self.in_off, self.out_off = table(torch.int64), table(torch.int64)
+        self.in_len, self.out_size, self.crc_want = table(torch.int32), table(torch.int32), table(torch.int32)
+        self.out_len, self.crc, self.status = table(torch.int32), table(torch.int32), table(torch.int32)
+
+    def index(self, blob):
+        """blob: uint8 tensor, 16-byte aligned -> MemberSummary; the tables hold min(nmembers, max_members) entries"""
+        summary = _pkg.MemberSummary()
+        rc = _pkg.lib().hipdeflate_index_members_dev(
+            _ptr(blob), blob.numel(), self.max_members, _ptr(self.in_off), _ptr(self.in_len), _ptr(self.out_size),
+            _ptr(self.out_off), _ptr(self.crc_want), ctypes.byref(summary), _stream())
+        _pkg._check(rc, "hipdeflate_index_members_dev")
+        return summary
+
+    def verify(self, nmembers):
+        """-> index of the first member whose inflate result disagrees with its trailer, nmembers if none"""
+        first_bad = ctypes.c_uint64()
+        rc = _pkg.lib().hipdeflate_verify_members_dev(_ptr(self.status), _ptr(self.out_len), _ptr(self.crc),
+                                                      _ptr(self.out_size), _ptr(self.crc_want), nmembers,
+                                                      ctypes.byref(first_bad), _stream())
+        _pkg._check(rc, "hipdeflate_verify_members_dev")
+        return first_bad.value
+
+    def run(self, blob, out, summary=None):
+        """index, inflate member i to out[out_off[i]:] with room for its ISIZE, verify -> the summary.
+        `summary`: what index(blob) has just answered for these tables, to spare the second pass over the blob"""
+        s = summary if summary is not None else self.index(blob)
+        if s.status:
+            why = {1: "not a member", 2: "member cut off", 3: "more members than max_members = %d" % self.max_members}
+            raise _pkg.HipDeflateError("member index: %s at offset %d (%d members)" % (why[s.status], s.end_offset, s.nmembers))
+        if out.numel() < s.out_bytes:
+            raise _pkg.HipDeflateError("output of %d bytes, the members hold %d" % (out.numel(), s.out_bytes))
+        n = s.nmembers
+        if n == 0:
+            return s
+        device_inflate(blob, self.in_off[:n], self.in_len, out, self.out_off, self.out_size, self.out_len, self.crc, self.status)
+        bad = self.verify(n)
+        if bad != n:
+            raise _pkg.HipDeflateError("member %d: inflate status %d, or CRC32/ISIZE mismatch" % (bad, int(self.status[bad])))
+        return s
+
+
+def inflate_container(blob):
+    """uint8 tensor holding a whole container file -> uint8 tensor of its contents; nothing visits the host.
+    Two passes over the blob: a table of no entries answers status 3 and the number of members the stream has, the
+    table of that size then gives out_bytes and is the one the inflate runs on."""
+    d = DeviceInflate(DeviceInflate(0, blob.device).index(blob).nmembers, blob.device)
+    s = d.index(blob)
+    out = torch.empty(s.out_bytes, dtype=torch.uint8, device=blob.device)
+    d.run(blob, out, s)
+    return out
 
 
 def device_inflate(comp, in_off, in_len, out, out_off, out_cap, out_len, crc, status):

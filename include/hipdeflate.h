@@ -243,6 +243,47 @@ int hipdeflate_compact_span_dev(const void *slots, uint64_t stride,
 				uint32_t nblocks, void *span, uint64_t span_base,
 				void *stream);
 
+/* ---- device-resident container decode --------------------------------------------
+ * The member table of a stream of gzip members that is already a device buffer (a tensor, the output of
+ * hipdeflate_compact_dev, a span handed over by another rank): the four tables hipdeflate_batch_inflate_dev wants plus
+ * the CRC-32 of every trailer, made on the device -- the host reads no byte of the blob.  Replaces the serial header walk
+ * of the reference's reader, _read_gz_header per member (applet/7bgzf.c:81-131) inside the loop of applet/7bgzf.c:306-328,
+ * and gives exactly what that walk gives: it starts at byte 0, takes a member's length from its extra field -- BC (BGZF),
+ * MZ (MiGz), IG v1, IG v2 and mgzip, with FNAME / FCOMMENT / FHCRC -- and goes on behind the member until the end.  Bytes
+ * inside a member that look like a header do not matter: the chain from byte 0 alone decides.  Member i of the table:
+ *   in_off[i]   (u64) offset of its raw DEFLATE payload       in_len[i]   (u32) payload + the 8-byte trailer, as :328 passes it
+ *   out_size[i] (u32) ISIZE of its trailer                    out_off[i]  (u64) exclusive prefix sum of out_size
+ *   crc_want[i] (u32) CRC-32 of its trailer
+ * all five device arrays of max_members entries.  *summary (host memory) says how the walk ended: */
+typedef struct hipdeflate_member_summary {
+	uint64_t nmembers;    /* members in the table (status 3: members the stream has) */
+	uint64_t out_bytes;   /* sum of ISIZE over the table */
+	uint64_t end_offset;  /* where the walk stopped; == nbytes when status is 0 */
+	uint32_t status;      /* 0 ok | 1 not a member at end_offset | 2 member at end_offset cut off | 3 table too small */
+} hipdeflate_member_summary;
+/* `blob` must be 16-byte aligned, nbytes is arbitrary (0: no members, status 0); no byte at or behind blob + nbytes is read,
+ * whatever the headers claim.  Status 1: the bytes at end_offset rule a member out (magic, FLG, an unknown extra field, a
+ * length below header + trailer); status 2: they run out first (inside the header, a name without its NUL, or the member
+ * reaches past nbytes).  With status 1 or 2 the table holds the members in front of end_offset, and they are usable.  With
+ * status 3 the first max_members members are in the table, nothing is written past them, and end_offset is the end of the
+ * last member the stream has.  Entries behind nmembers are never written.  Returns 0 whenever the index ran (the verdict
+ * on the data is summary->status), HD_E_* otherwise (HD_E_ARG: blob not aligned, summary NULL).  Scratch -- the candidate
+ * list, its successor tables -- is the library's, grow-only; calls on different streams take turns (one call at a time,
+ * on the host, for the length of the call).  Work: one streaming read of the blob, O(log candidates) passes over the
+ * candidate list, and FNAME / FCOMMENT scans that together read O(nbytes) however many headers the payloads imitate; a
+ * single name is scanned by one lane, byte by byte, so a name of megabytes costs what it costs the host walk.
+ * (Synchronises the stream.) */
+int hipdeflate_index_members_dev(const void *blob, uint64_t nbytes, uint32_t max_members,
+				 void *in_off, void *in_len, void *out_size, void *out_off, void *crc_want,
+				 hipdeflate_member_summary *summary /* HOST */, void *stream);
+/* The trailer check behind the inflate (applet/7bgzf.c:306-328 leaves it to the codec; bgzf_decompress_bytes does it per
+ * member on the host): compares what hipdeflate_batch_inflate_dev wrote -- status 0, out_len == out_size, crc32 ==
+ * crc_want -- for members 0..nmembers-1, all five device arrays.  *first_bad (host memory) = the index of the first member
+ * that disagrees, nmembers if none.  (Synchronises the stream.) */
+int hipdeflate_verify_members_dev(const void *status, const void *out_len, const void *crc32,
+				  const void *out_size, const void *crc_want, uint32_t nmembers,
+				  uint64_t *first_bad /* HOST: index, or nmembers if none */, void *stream);
+
 /* ---- streaming encoder: the host pipeline either side of the kernels ------------
  * Role of the read / compress / write loop of applet/7bgzf.c:159-293 (7migz.c:130-244)
  * for a stream of fixed-size blocks (the last may be short).  `depth` batches are in
