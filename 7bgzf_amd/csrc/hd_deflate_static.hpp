@@ -464,27 +464,55 @@ __global__ __launch_bounds__(64) void k_deflate_static(DeflateArgs a)
 	// every whole dword staged so far leaves (at most 63: what one put() left), one contiguous 4-byte-per-lane store, and its
 	// place in the ring is zero again.  Called in front of every emit pass and of the member's tail, so that the ring only
 	// ever has to hold one partial dword and what comes then (a pass: 62 dwords; the tail: four)
-	auto drain = [&]() {
+	// In two halves, for the emit pass, which waits for its table gather between them: the LDS half reads the lane's dword
+	// and zeroes its place (in front of the pass's put(), which ORs into it again), the store half sends it to HBM.
+	// (Two divergent regions on purpose.  In one, with the wait inside, the compiler waits again where the lanes join --
+	// vmcnt(0), the store included.  `fl` is pinned so that both halves share it; `v` starts undefined, not zero: the
+	// lanes that do not drain never store it, and a zero would be a v_mov per pass)
+	auto drain_read = [&](uint32_t &fl) -> uint32_t {
 		const uint32_t ready = (bitpos >> 5) - flushed;
+		fl = flushed + lane;
+		asm("" : "+v"(fl));
+		uint32_t v;
+		asm("" : "=v"(v));
 		if (lane < ready) {
-			const uint32_t i = (flushed + lane) & (STG - 1);
-			const uint32_t v = stage[i];
+			const uint32_t i = fl & (STG - 1);
+			v = stage[i];
 			stage[i] = 0;
-			dst32[flushed + lane] = v;
 		}
+		return v;
+	};
+	auto drain_store = [&](uint32_t fl, uint32_t v) {
+		const uint32_t ready = (bitpos >> 5) - flushed;
+		if (lane < ready)
+			dst32[fl] = v;
 		flushed = bitpos >> 5;
+	};
+	auto drain = [&]() {
+		uint32_t fl;
+		const uint32_t v = drain_read(fl);
+		drain_store(fl, v);
+	};
+	// vmcnt counts vector-memory operations in issue order: a wait for a younger one cannot pass before every older one
+	// is back.  The next piece is an HBM miss (the input is streamed once) that nothing needs for 16 steps, so it is
+	// requested BEHIND the CRC's twenty table gathers and their waits -- the youngest operation, which nothing waits for.
+	// (Requested first, as it was, the gathers' first wait -- vmcnt(18) of 21 outstanding -- stood for the whole HBM round
+	// trip at the head of every 16-step group.)  The fence keeps the compiler from moving the load back up.
+	auto crc_then_prefetch = [&](uint32_t piece, uint4 v) {
+		crc.fold(ct, piece, piece * HD_PIECE + lane * 16 + 16 <= n && piece * HD_PIECE + lane * 16 >= prime, v);
+		asm volatile("" : "+v"(crc.s) : : "memory");
+		if (filled < n)
+			pre = load_slot(src, n, piece + 1, lane, aligned);
 	};
 	auto fill_piece = [&]() {
 		const uint32_t piece = filled / HD_PIECE;
 		const uint4 v = pre;
 		filled += HD_PIECE;
-		if (filled < n)
-			pre = load_slot(src, n, piece + 1, lane, aligned);
 		const uint32_t ro = (piece * HD_PIECE) & (W - 1);
 		((uint4 *)ring32)[ro / 16 + lane] = v;
 		if (ro == 0 && lane == 0)
 			((uint4 *)ring32)[W / 16] = v;          // mirror of ring bytes [0,16)
-		crc.fold(ct, piece, piece * HD_PIECE + lane * 16 + 16 <= n && piece * HD_PIECE + lane * 16 >= prime, v);
+		crc_then_prefetch(piece, v);
 	};
 	// ---- the front of the pipeline -------------------------------------------
 	// A step is split in three stages that run one iteration apart, so that no
@@ -631,14 +659,23 @@ __global__ __launch_bounds__(64) void k_deflate_static(DeflateArgs a)
 			ntok_slab += count;
 			return true;
 		}
-		drain();
 		// literal / length: one table load (CrcTables::SL); offset: slot arithmetic, 5-bit code + extra bits
+		// The table gather goes out first, and the staged dwords leave in its shadow: their LDS round trip runs beside
+		// the gather's, and their store is issued behind the wait for the gather -- vmcnt counts in issue order, so a
+		// store in front of the gather (drain() first, as it was) made that wait stand for the store's round trip too.
+		// Behind it, nothing ever waits for the store: the next vector-memory wait is a pass or a refill away
 		const uint64_t mmask = __ballot((int32_t)t < 0);
 		const uint64_t vmask = count >= 64 ? ~0ull : (1ull << (count & 63)) - 1;
-		const uint32_t e0 = ct->SL[sel(mmask, (t >> 16) & 0x1ff, t & 0xff)];
+		uint32_t e0 = ct->SL[sel(mmask, (t >> 16) & 0x1ff, t & 0xff)];
 		uint32_t ds, deb, dev;
 		off_slot((t & 0xffff) + 1, ds, deb, dev);
-		const uint32_t dpart = (__brev(ds) >> 27) | (dev << 5);
+		uint32_t dpart = (__brev(ds) >> 27) | (dev << 5);
+		// (the gather and the offset arithmetic stay in front of the LDS half, the store behind the wait for the gather)
+		asm volatile("" : "+v"(dpart), "+v"(deb) : : "memory");
+		uint32_t fl;
+		const uint32_t dv = drain_read(fl);
+		asm volatile("" : "+v"(e0) : : "memory");
+		drain_store(fl, dv);
 		const uint32_t nb0 = e0 >> 16;
 		const uint32_t code = sel(vmask, sel(mmask, (e0 & 0xffff) | (dpart << nb0), e0 & 0xffff), 0u);
 		const uint32_t nbits = sel(vmask, sel(mmask, nb0 + 5 + deb, nb0), 0u);
@@ -669,9 +706,12 @@ __global__ __launch_bounds__(64) void k_deflate_static(DeflateArgs a)
 	uint32_t carry = 0;                  // leading positions covered by the last match
 	// one step; false = the static stream was abandoned
 	// NOFILL: the caller has refilled the ring for this step (the 16-step groups of the main loop)
-	auto step = [&](auto inner_tag, auto nofill_tag, uint32_t S) -> bool {
+	// ROOM258: every lane of the step has HD_MAX_MATCH bytes ahead (the groups again), so no long match is clipped by the
+	// block's end and the extension's bound is a constant
+	auto step = [&](auto inner_tag, auto nofill_tag, auto room258_tag, uint32_t S) -> bool {
 		constexpr bool INNER = decltype(inner_tag)::value;
 		constexpr bool NOFILL = decltype(nofill_tag)::value;
+		constexpr bool ROOM258 = decltype(room258_tag)::value;
 		if (!NOFILL && filled < n && filled < S + HD_LOOKAHEAD)
 			fill_piece();
 		const uint32_t lo = filled > W ? filled - W : 0;
@@ -730,7 +770,7 @@ __global__ __launch_bounds__(64) void k_deflate_static(DeflateArgs a)
 		const uint64_t livem = ~0ull << carry;                       // lanes the last match does not cover (carry < 64)
 		// (token words are prepared here, ahead of the scan: independent work for the wait states between its
 		// DPP stages)  match: HD_TOKEN_MATCH_TAG | (len - 3) << 16 | (dist - 1), dist - 1 = p - c
-		const uint32_t mw_base = (p + (HD_TOKEN_MATCH_TAG - (3u << 16))) - c;
+		const uint32_t mw_base = (p + (HD_TOKEN_MATCH_TAG - (3u << 16) - 1u)) - cp;
 		const uint32_t lit = cv0 & 0xff;
 		// K16: length over 16 bytes (valid on the capped lanes).  (The dwords are read here, and the kernel is bound
 		// by its instruction count: it skips all of this in a step without a capped lane -- a quarter of the steps on
@@ -869,12 +909,19 @@ __global__ __launch_bounds__(64) void k_deflate_static(DeflateArgs a)
 				pend = ~1ull << m;
 			}
 		} else {
-			uint64_t cm = starts & capmask;
+			// todo: the capped lanes no event has handled yet.  An event clears its own bit, and that is all the
+			// bookkeeping there is: the events run in rising lane order, fresh starts lie behind the match that made
+			// them, and a lane below the last event is a start now iff it was one then -- so starts & todo is "the capped
+			// starts above m" without the shift and the second AND that spelled it out
+			uint64_t todo = capmask;
+			uint64_t cm = starts & todo;
 			while (cm) {
 				const uint32_t m = (uint32_t)__ffsll((unsigned long long)cm) - 1;
 				const uint32_t pm = S + m;
-				const uint32_t dm = pm + 1 - readlane(c, m);
-				const uint32_t maxlen = n - pm < HD_MAX_MATCH ? n - pm : HD_MAX_MATCH;
+				asm("s_bitset0_b64 %0, %1" : "+s"(todo) : "s"(m));
+				// minus the distance: (c - 1) - pm, from the register the verify stage keeps anyway
+				const uint32_t ndm = readlane(cp, m) - pm;
+				const uint32_t maxlen = ROOM258 ? (uint32_t)HD_MAX_MATCH : (n - pm < HD_MAX_MATCH ? n - pm : HD_MAX_MATCH);
 				uint32_t len = 8;
 				{
 					// 64 bytes per pass, every index masked into the ring (lanes past maxlen may read too: the length
@@ -900,7 +947,7 @@ __global__ __launch_bounds__(64) void k_deflate_static(DeflateArgs a)
 						     "s_add_u32 %[len], %[len], %[k]\n"
 						     "Lhd_ext_done_%=:"
 						     : [len] "+s"(len), [t0] "=&v"(t0), [t1] "=&v"(t1), [k] "=&s"(k)
-						     : [vb] "v"(pm + lane), [ndm] "s"(0u - dm), [msk] "s"(W - 1), [rb] "v"(ring_lds), [maxlen] "s"(maxlen)
+						     : [vb] "v"(pm + lane), [ndm] "s"(ndm), [msk] "s"(W - 1), [rb] "v"(ring_lds), [maxlen] "s"(maxlen)
 						     : "vcc", "scc", "memory");
 				}
 				len = len < maxlen ? len : maxlen;
@@ -936,7 +983,7 @@ __global__ __launch_bounds__(64) void k_deflate_static(DeflateArgs a)
 					asm("s_bfm_b64 %0, %1, %2" : "=s"(gone) : "s"(xe - m - 1), "s"(m + 1));
 					starts = (starts & ~gone) | fresh;
 				}
-				cm = starts & capmask & (~1ull << m);             // lanes > m
+				cm = starts & todo;
 			}
 		}
 		// coverage behind the last token of the step
@@ -1038,21 +1085,23 @@ __global__ __launch_bounds__(64) void k_deflate_static(DeflateArgs a)
 			o1 = own(S + 192);
 	}
 	while (S < n && use_static) {
-		if (small && filled < n && filled < S + HD_LOOKAHEAD && S + 15 * 64 + 192 + 8 <= n) {
+		// (... and, for ROOM258, the last lane of its last step has a full match length ahead: 1281 bytes from S on, where
+		// INNER alone asks for 1160.  The last group of a 0xff00-byte block fails both)
+		if (small && filled < n && filled < S + HD_LOOKAHEAD && S + 15 * 64 + 63 + HD_MAX_MATCH <= n) {
 			fill_piece();
 #pragma unroll 1
 			for (uint32_t g = 0; g < 4 && use_static; g++) {
 #pragma unroll
 				for (uint32_t u = 0; u < 4; u++) {
-					step(std::true_type{}, std::true_type{}, S);
+					step(std::true_type{}, std::true_type{}, std::true_type{}, S);
 					step_boundary(std::true_type{}, S);
 					S += 64;
 				}
 			}
 			continue;
 		}
-		const bool ok_step = (small && S + 192 + 8 <= n) ? step(std::true_type{}, std::false_type{}, S)
-								  : step(std::false_type{}, std::false_type{}, S);
+		const bool ok_step = (small && S + 192 + 8 <= n) ? step(std::true_type{}, std::false_type{}, std::false_type{}, S)
+								  : step(std::false_type{}, std::false_type{}, std::false_type{}, S);
 		if (!ok_step || !step_boundary(std::false_type{}, S))
 			break;
 		S += 64;
@@ -1070,6 +1119,8 @@ __global__ __launch_bounds__(64) void k_deflate_static(DeflateArgs a)
 		const uint32_t piece = filled / HD_PIECE;
 		const uint4 pv = pre;
 		filled += HD_PIECE;
+		// (here the next piece IS needed at once, by the next pass of this loop: requested first, its round trip
+		// and the gathers' overlap; behind them, as in fill_piece, the two would add up)
 		if (filled < n)
 			pre = load_slot(src, n, piece + 1, lane, aligned);
 		crc.fold(ct, piece, piece * HD_PIECE + lane * 16 + 16 <= n && piece * HD_PIECE + lane * 16 >= prime, pv);
