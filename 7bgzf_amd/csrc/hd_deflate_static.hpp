@@ -909,86 +909,115 @@ __global__ __launch_bounds__(64) void k_deflate_static(DeflateArgs a)
 				pend = ~1ull << m;
 			}
 		} else {
-			// todo: the capped lanes no event has handled yet.  An event clears its own bit, and that is all the
-			// bookkeeping there is: the events run in rising lane order, fresh starts lie behind the match that made
-			// them, and a lane below the last event is a start now iff it was one then -- so starts & todo is "the capped
-			// starts above m" without the shift and the second AND that spelled it out
+			// The long-match events of the step: one block of assembly, run once per event.  (The loop around it is the
+			// compiler's, s_cmp_lg_u64 + branch on the block's last result: an asm goto with scalar outputs, which
+			// would let the block branch on the SCC of its own last AND, crashes this compiler's instruction selection.)
+			//   todo   the capped lanes no event has handled yet.  An event clears its own bit, and that is all the
+			//          bookkeeping there is: the events run in rising lane order, fresh starts lie behind the match
+			//          that made them, and a lane below the last event is a start now iff it was one then -- so
+			//          starts & todo is "the capped starts above m": the AND at the block's bottom is the loop test
+			//   m      lives in M0 from the s_ff1_i32_b64 on: s_bitset0_b64, s_add, s_sub, v_readlane_b32 and
+			//          v_writelane_b32 all take it there (v_writelane_b32 with the lane select in M0 is the one form
+			//          that may name two scalar operands on gfx9).  Nothing else in this kernel uses M0 -- LDS
+			//          instructions do not need it here
+			//   x      m + length so far: the scalar half of the step-relative address (p = S + lane is the vector
+			//          half, so no per-event vector add forms pm + lane), and the walk's first lane when the
+			//          extension ends.  The candidate's side is cq = (c - 1 of lane m) + length so far + lane
+			//   extension  64 bytes per pass, every index masked into the ring.  The passes compare bytes 2..65,
+			//          66..129, 130..193 and 194..257 of the match (the first eight are known to agree; the 2 is the
+			//          candidate read's offset and the first x, and the ring's 16 mirrored bytes cover it): the last
+			//          pass ends on byte 257, so a mismatch found in any pass is a length below 258 and the
+			//          no-hit exit is 258 itself -- ROOM258 needs no clamp at all.  A step that is not ROOM258 cuts
+			//          both exits to the bytes the block has left (lanes past them may read too)
+			//   len == 8   (one event in six) takes the same path: lane m + 8 is an old start or lies behind the step, so
+			//          the walk ends where it begins and `gone` holds no start.  An exit of its own -- a compare and a
+			//          branch in every event -- measured slower
+			//   the walk   re-threads the chain behind the match: lanes it lands on become starts (fresh) until it
+			//          lands on an old start -- two parses that start a token on one lane coincide from there on -- or
+			//          leaves the step.  It reads lenv: behind the match no event has touched it yet.  The lane
+			//          selects of v_readlane / s_bitcmp1 / s_bitset1 take the low 6 bits and x < 64 is tested first;
+			//          an SGPR written by the SALU needs no wait states before v_readlane uses it as lane select
+			//   gone   the old starts in (m, x): one s_bfm_b64 of min(x, 64) - m - 1 ones from bit m + 1 (m == 63
+			//          makes it empty)
 			uint64_t todo = capmask;
 			uint64_t cm = starts & todo;
-			while (cm) {
-				const uint32_t m = (uint32_t)__ffsll((unsigned long long)cm) - 1;
-				const uint32_t pm = S + m;
-				asm("s_bitset0_b64 %0, %1" : "+s"(todo) : "s"(m));
-				// minus the distance: (c - 1) - pm, from the register the verify stage keeps anyway
-				const uint32_t ndm = readlane(cp, m) - pm;
-				const uint32_t maxlen = ROOM258 ? (uint32_t)HD_MAX_MATCH : (n - pm < HD_MAX_MATCH ? n - pm : HD_MAX_MATCH);
-				uint32_t len = 8;
-				{
-					// 64 bytes per pass, every index masked into the ring (lanes past maxlen may read too: the length
-					// is cut to maxlen behind the loop).  Written out: left to the compiler the two exits become 11
-					// scalar instructions of cselect per pass; here 3 (mismatch found) or 4 (another pass).
-					uint32_t t0, t1, k;
-					asm volatile("Lhd_ext_%=:\n\t"
-						     "v_add_u32 %[t0], %[len], %[vb]\n\t"
-						     "v_add_u32 %[t1], %[ndm], %[t0]\n\t"
-						     "v_and_or_b32 %[t0], %[t0], %[msk], %[rb]\n\t"
-						     "v_and_or_b32 %[t1], %[t1], %[msk], %[rb]\n\t"
-						     "ds_read_u8 %[t0], %[t0]\n\t"
-						     "ds_read_u8 %[t1], %[t1]\n\t"
-						     "s_waitcnt lgkmcnt(0)\n\t"
-						     "v_cmp_ne_u16 vcc, %[t0], %[t1]\n\t"
-						     "s_cbranch_vccnz Lhd_ext_hit_%=\n\t"
-						     "s_add_u32 %[len], %[len], 64\n\t"
-						     "s_cmp_lt_u32 %[len], %[maxlen]\n\t"
-						     "s_cbranch_scc1 Lhd_ext_%=\n\t"
-						     "s_branch Lhd_ext_done_%=\n"
-						     "Lhd_ext_hit_%=:\n\t"
-						     "s_ff1_i32_b64 %[k], vcc\n\t"
-						     "s_add_u32 %[len], %[len], %[k]\n"
-						     "Lhd_ext_done_%=:"
-						     : [len] "+s"(len), [t0] "=&v"(t0), [t1] "=&v"(t1), [k] "=&s"(k)
-						     : [vb] "v"(pm + lane), [ndm] "s"(ndm), [msk] "s"(W - 1), [rb] "v"(ring_lds), [maxlen] "s"(maxlen)
-						     : "vcc", "scc", "memory");
-				}
-				len = len < maxlen ? len : maxlen;
-				if (len > 8) {
-					// (v_writelane_b32 with the lane select in M0: the one form that may name two scalar operands on
-					// gfx9.  Nothing else in this kernel uses M0 -- LDS instructions do not need it here)
-					asm("s_mov_b32 m0, %2\n\ts_nop 0\n\tv_writelane_b32 %0, %1, m0" : "+v"(lenv) : "s"(len), "s"(m));
-					const uint32_t q = m + len;                   // first lane behind the match
-					// the walk, written out (the compiler spends ~11 scalar instructions per hop on it; here 4 + 2
-					// branches + one v_readlane.  The lane selects of v_readlane / s_bitcmp1 / s_bitset1 take the low
-					// 6 bits and xq < 64 is tested first; an SGPR written by the SALU needs no wait states before
-					// v_readlane uses it as lane select)
-					uint64_t fresh = 0;
-					uint32_t xq = q, hop;
-					asm volatile("s_cmp_gt_u32 %0, 63\n\t"
-						     "s_cbranch_scc1 Lhd_rethread_done_%=\n"
-						     "Lhd_rethread_%=:\n\t"
-						     "s_bitcmp1_b64 %3, %0\n\t"
-						     "s_cbranch_scc1 Lhd_rethread_done_%=\n\t"
-						     "s_bitset1_b64 %1, %0\n\t"
-						     "v_readlane_b32 %2, %4, %0\n\t"
-						     "s_add_u32 %0, %0, %2\n\t"
-						     "s_cmp_lt_u32 %0, 64\n\t"
-						     "s_cbranch_scc1 Lhd_rethread_%=\n"
-						     "Lhd_rethread_done_%=:"
-						     : "+s"(xq), "+s"(fresh), "=&s"(hop)
-						     : "s"(starts), "v"(jump8)
-						     : "scc");
-					// the old parse holds from lane xq on: its starts in (m, xq) go (one s_bfm_b64: xq - m - 1 >= 8 ones
-					// from bit m + 1; xq >= 64 makes the run end at lane 63, m == 63 makes it empty)
-					const uint32_t xe = xq < 64 ? xq : 64;
-					uint64_t gone;
-					asm("s_bfm_b64 %0, %1, %2" : "=s"(gone) : "s"(xe - m - 1), "s"(m + 1));
-					starts = (starts & ~gone) | fresh;
-				}
-				cm = starts & todo;
+			if (cm) {
+				uint32_t t0, t1, x, cq, len, k;
+				uint64_t fresh;
+#define HD_L1_EVENTS(CLAMP)                                                                  \
+	"s_ff1_i32_b64 m0, %[cm]\n\t"                                                        \
+	"s_bitset0_b64 %[todo], m0\n\t"                                                      \
+	"v_readlane_b32 %[cq], %[cp], m0\n\t"                                                \
+	"s_add_u32 %[x], m0, 2\n"                                                            \
+	"Lhd_ext_%=:\n\t"                                                                    \
+	"v_add_u32 %[t0], %[x], %[p]\n\t"                                                    \
+	"v_add_u32 %[t1], %[cq], %[lane]\n\t"                                                \
+	"v_and_or_b32 %[t0], %[t0], %[msk], %[rb]\n\t"                                       \
+	"v_and_or_b32 %[t1], %[t1], %[msk], %[rb]\n\t"                                       \
+	"ds_read_u8 %[t0], %[t0]\n\t"                                                        \
+	"ds_read_u8 %[t1], %[t1] offset:2\n\t"                                               \
+	"s_waitcnt lgkmcnt(0)\n\t"                                                           \
+	"v_cmp_ne_u16 vcc, %[t0], %[t1]\n\t"                                                 \
+	"s_cbranch_vccnz Lhd_ext_hit_%=\n\t"                                                 \
+	"s_add_u32 %[x], %[x], 64\n\t"                                                       \
+	"s_add_u32 %[cq], %[cq], 64\n\t"                                                     \
+	"s_sub_u32 %[len], %[x], m0\n\t"                                                     \
+	"s_cmp_lt_u32 %[len], 258\n\t"                                                       \
+	"s_cbranch_scc1 Lhd_ext_%=\n\t"                                                      \
+	"s_branch Lhd_ext_len_%=\n"                                                          \
+	"Lhd_ext_hit_%=:\n\t"                                                                \
+	"s_ff1_i32_b64 %[k], vcc\n\t"                                                        \
+	"s_add_u32 %[x], %[x], %[k]\n\t"                                                     \
+	"s_sub_u32 %[len], %[x], m0\n"                                                       \
+	"Lhd_ext_len_%=:\n\t"                                                                \
+	CLAMP                                                                                \
+	"v_writelane_b32 %[lenv], %[len], m0\n\t"                                            \
+	"s_mov_b64 %[fresh], 0\n\t"                                                          \
+	"s_cmp_gt_u32 %[x], 63\n\t"                                                          \
+	"s_cbranch_scc1 Lhd_rethread_out_%=\n"                                               \
+	"Lhd_rethread_%=:\n\t"                                                               \
+	"s_bitcmp1_b64 %[starts], %[x]\n\t"                                                  \
+	"s_cbranch_scc1 Lhd_rethread_done_%=\n\t"                                            \
+	"s_bitset1_b64 %[fresh], %[x]\n\t"                                                   \
+	"v_readlane_b32 %[k], %[lenv], %[x]\n\t"                                             \
+	"s_add_u32 %[x], %[x], %[k]\n\t"                                                     \
+	"s_cmp_lt_u32 %[x], 64\n\t"                                                          \
+	"s_cbranch_scc1 Lhd_rethread_%=\n"                                                   \
+	"Lhd_rethread_out_%=:\n\t"                                                           \
+	"s_movk_i32 %[x], 64\n"                                                              \
+	"Lhd_rethread_done_%=:\n\t"                                                          \
+	"s_add_u32 %[k], m0, 1\n\t"                                                          \
+	"s_sub_u32 %[len], %[x], %[k]\n\t"                                                   \
+	"s_bfm_b64 %[cm], %[len], %[k]\n\t"                                                  \
+	"s_andn2_b64 %[starts], %[starts], %[cm]\n\t"                                        \
+	"s_or_b64 %[starts], %[starts], %[fresh]\n"                                          \
+	"s_and_b64 %[cm], %[starts], %[todo]"
+				do {
+					if (ROOM258)
+						asm volatile(HD_L1_EVENTS("")
+						  : [starts] "+s"(starts), [todo] "+s"(todo), [cm] "+s"(cm), [lenv] "+v"(lenv), [t0] "=&v"(t0), [t1] "=&v"(t1),
+						    [x] "=&s"(x), [cq] "=&s"(cq), [len] "=&s"(len), [k] "=&s"(k), [fresh] "=&s"(fresh)
+						  : [cp] "v"(cp), [p] "v"(p), [lane] "v"(lane), [msk] "s"(W - 1), [rb] "v"(ring_lds)
+						  : "vcc", "scc", "memory");
+					else
+						asm volatile(HD_L1_EVENTS("s_sub_u32 %[k], %[left], m0\n\t"
+								       "s_min_u32 %[k], %[k], 258\n\t"
+								       "s_min_u32 %[len], %[len], %[k]\n\t"
+								       "s_add_u32 %[x], %[len], m0\n\t")
+						  : [starts] "+s"(starts), [todo] "+s"(todo), [cm] "+s"(cm), [lenv] "+v"(lenv), [t0] "=&v"(t0), [t1] "=&v"(t1),
+						    [x] "=&s"(x), [cq] "=&s"(cq), [len] "=&s"(len), [k] "=&s"(k), [fresh] "=&s"(fresh)
+						  : [cp] "v"(cp), [p] "v"(p), [lane] "v"(lane), [msk] "s"(W - 1), [rb] "v"(ring_lds), [left] "s"(n - S)
+						  : "vcc", "scc", "memory");
+				} while (cm);
+#undef HD_L1_EVENTS
 			}
 		}
 		// coverage behind the last token of the step
 		// (the last REAL start: a continuation lane behind it belongs to its token)
-		const uint32_t last = 63 - (uint32_t)__clzll((long long)(starts & ~v));      // != 0: carry < lanes, and the first start is real
+		// != 0: carry < lanes, and the first start is real -- so level 1 takes the bare s_flbit_i32_b64 (__clzll also answers
+		// for 0: an s_min_u32 ..., 64 behind it in every step)
+		const uint64_t real = starts & ~v;
+		const uint32_t last = 63 - (uint32_t)(K16 ? __clzll((long long)real) : __builtin_clzll(real));
 		const uint32_t E = last + readlane(lenv, last);
 		const uint64_t tm = starts & lanem & ~v;           // tokens: matches + literals inside the block
 		const uint64_t mm = tm & okm;                      // matches

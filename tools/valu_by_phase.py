@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Static instruction counts of the level-1 kernel's 16-step group loop, per 64-byte step and by phase.
 
-  python3 tools/valu_by_phase.py > profiles/r07_l1_valu_by_phase.json
+  python3 tools/valu_by_phase.py > profiles/r09_l1_valu_by_phase.json
 
 hipcc -S -gline-tables-only gives every instruction its source line; the lines are mapped to the phases of
 7bgzf_amd/csrc/hd_deflate_static.hpp (fetch / probe / verify / scan / long matches / queue / emit / refill + CRC).
@@ -109,11 +109,14 @@ def main():
             tot[k] += v / steps
             if f:
                 wtot[k] += v / steps * f
-    out["long_match_path"] = ("ROUND 2'S KERNEL, not re-measured since: its blocks (the extension loop and the re-threading walk, both inline asm since round 2) are laid out "
-                              "behind the loop's back edge and are not in the counts above; measured instead: PMC per step minus the "
-                              "weighted sum = ~41 SALU + ~12 branches + ~19 VALU per step at 1.27 long matches per step on the "
-                              "FASTQ-like set (twin count), i.e. ~32 scalar + ~10 branch + ~15 vector instructions per long match")
-    out["measured_pmc_per_step"] = "round 2's kernel, not re-measured since: profiles/r02_encode_l1_pmc_summary.json (tools/pmc_quick.sh): VALU 97.6, SALU 73.2, branch 16.0"
+    out["long_match_path"] = ("one block of assembly per step (HD_L1_EVENTS) that runs all of the step's events; its instructions carry the line of the "
+                              "asm statement and are counted in the phase above, with the step's entry test and the loop the compiler keeps round the "
+                              "block (s_cmp_lg_u64 + branch).  Run: 1.42 events per step on the FASTQ-like set (twin count), 1.14 hops of the walk per event; "
+                              "measured as the PMC figures per step minus the weighted sum of the other phases")
+    out["measured_pmc_per_step"] = ("this kernel (profiles/r09_l1_ab_parent_vs_new.txt; tools/pmc_quick.sh, one counter pass per run, no tracing beside it): "
+                                    "VALU 93.91, SALU 60.32, branch 14.91, LDS 10.83; wave cycles 506.8 (x4 clocks), busy 13.3; an instruction issues in "
+                                    "37.0 % of the wave cycles, the wavefront waits on one in 32.6 %.  "
+                                    "The parent commit in the same way: VALU 95.10, SALU 66.50, branch 17.08, LDS 10.83, wave cycles 529.7, 37.5 % / 31.3 %")
     out["sum_static_all_paths_per_step"] = {k: round(v, 1) for k, v in sorted(tot.items())}
     out["sum_weighted_by_frequency_per_step"] = {k: round(v, 1) for k, v in sorted(wtot.items())}
     json.dump(out, sys.stdout, indent=1)
