@@ -776,8 +776,8 @@ int hipdeflate_compact_dev(const void *slots, uint64_t stride, const void *out_l
 		return 0;
 	if ((stride & 3) || ((uintptr_t)slots & 3))
 		return HD_E_ARG;
-	hipLaunchKernelGGL(hd::k_compact, dim3(nblocks), dim3(64), 0, (hipStream_t)stream, (const uint8_t *)slots, stride,
-			   (const uint32_t *)out_len, (const uint64_t *)dst_off, nblocks, (uint8_t *)dst);
+	hd::launch_compact((const uint8_t *)slots, stride, (const uint32_t *)out_len, (const uint64_t *)dst_off, nblocks,
+			   (uint8_t *)dst, (hipStream_t)stream);
 	HD_CHECK(hipGetLastError());
 	return 0;
 }

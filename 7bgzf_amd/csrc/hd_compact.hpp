@@ -7,6 +7,7 @@
 // SURVEY.md 8(e)) through the `base` argument.  HBM-bound byte copy.
 #pragma once
 #include "hd_device.hpp"
+#include <atomic>
 
 namespace hd {
 
@@ -130,14 +131,153 @@ __device__ __forceinline__ void compact_one(const uint8_t *s, uint32_t L, uint8_
 		d[done + lane] = s[done + lane];
 }
 
-// one wavefront per member: slots + i*stride (16-byte aligned) -> dst + dst_off[i]
-__global__ __launch_bounds__(64) void k_compact(const uint8_t *slots, uint64_t stride, const uint32_t *len,
-						const uint64_t *dst_off, uint32_t n, uint8_t *dst)
+// ---- the gather: 16 bytes per lane and access, several in flight, a persistent grid ---------------------------------
+//
+// A member's bytes go from its slot (4-byte aligned, any length) to dst + dst_off[i] (any alignment).  The body is whole
+// 16-byte lines of the DESTINATION, stored with global_store_dwordx4; their source bytes arrive by 16-byte loads from
+// whatever address that makes (gfx950 takes a byte-aligned global_load_dwordx4), so the copy runs no funnel shift and no
+// vector ALU beyond its addresses.  A wavefront moves COMPACT_GROUP bytes per trip of its loop: COMPACT_UNROLL loads per
+// lane, one wait, COMPACT_UNROLL stores, one back edge.  The ragged ends of a member -- up to 15 bytes in front of the
+// first whole line and up to 15 behind the last -- are byte stores of one lane each: two members' wavefronts may share a
+// 16-byte line, so no line is ever read, merged and written back.  Exactly the member's bytes are read, none beside them.
+// Loads and stores are nontemporal: they pass the CU's L1 by, which the encode kernel running beside the gather uses for
+// its own tables (worth 0.1 ms of the encoder's 45).
+// The three figures of the kernel, each overridable from the compiler's command line (make EXTRA=-DHD_COMPACT_...=...),
+// which is how the rows of DESIGN.md 6d were built from this one source.
+#ifndef HD_COMPACT_UNROLL
+#define HD_COMPACT_UNROLL 4
+#endif
+#ifndef HD_COMPACT_NT
+#define HD_COMPACT_NT 1
+#endif
+#ifndef HD_COMPACT_WAVES_PER_CU
+#define HD_COMPACT_WAVES_PER_CU 3
+#endif
+constexpr uint32_t COMPACT_UNROLL = HD_COMPACT_UNROLL;              // 16-byte accesses per lane between two waits
+constexpr uint32_t COMPACT_GROUP = 64 * 16 * COMPACT_UNROLL;        // bytes per wavefront and trip of the body loop
+constexpr bool COMPACT_NT = HD_COMPACT_NT != 0;                     // nontemporal loads and stores
+// The persistent grid, wavefronts per CU.  What the gather takes from an encode kernel beside it grows with the bytes it
+// keeps in flight, not with the instructions it issues: 3 x 4 KiB per CU is the least that still copies, alone, as fast
+// as one wavefront per member did (DESIGN.md 6d has the sweep).
+constexpr uint32_t COMPACT_WAVES_PER_CU = HD_COMPACT_WAVES_PER_CU;
+
+typedef uint32_t compact_u32x4 __attribute__((ext_vector_type(4)));
+typedef compact_u32x4 compact_u32x4_any __attribute__((aligned(1)));   // a source line: wherever the destination's alignment puts it
+
+template <bool NT>
+__device__ __forceinline__ compact_u32x4 compact_ld16(const uint8_t *p)
 {
-	const uint32_t i = blockIdx.x, lane = threadIdx.x;
+	const compact_u32x4_any *q = (const compact_u32x4_any *)p;
+	if (NT)
+		return __builtin_nontemporal_load(q);
+	return *q;
+}
+
+template <bool NT>
+__device__ __forceinline__ void compact_st16(uint8_t *p, compact_u32x4 v)
+{
+	compact_u32x4 *q = (compact_u32x4 *)p;
+	if (NT)
+		__builtin_nontemporal_store(v, q);
+	else
+		*q = v;
+}
+
+template <bool NT, uint32_t U>
+__device__ __forceinline__ void compact_wide(const uint8_t *__restrict__ s, uint32_t L, uint8_t *__restrict__ d, uint32_t lane)
+{
+	uint32_t head = (uint32_t)(0 - (uintptr_t)d) & 15;        // bytes in front of the first whole destination line
+	if (head > L)
+		head = L;
+	const uint32_t lines = (L - head) >> 4;                   // whole destination lines
+	const uint32_t done = head + 16 * lines;
+	// both ragged ends in one byte access: lanes 0..15 the head, lanes 16..31 the tail; requested ahead of the body
+	const uint32_t eo = lane < 16 ? lane : done + lane - 16;
+	const bool edge = lane < 16 ? lane < head : lane < 32 && lane - 16 < L - done;
+	uint8_t eb = 0;
+	if (edge)
+		eb = s[eo];
+	const uint8_t *sb = s + head + 16 * lane;
+	uint8_t *db = d + head + 16 * lane;
+	uint32_t k = 0;                                           // the trip's first line (uniform)
+	for (; k + 64 * U <= lines; k += 64 * U) {
+		compact_u32x4 v[U];
+#pragma unroll
+		for (uint32_t j = 0; j < U; j++)
+			v[j] = compact_ld16<NT>(sb + 16 * (k + 64 * j));
+#pragma unroll
+		for (uint32_t j = 0; j < U; j++)
+			compact_st16<NT>(db + 16 * (k + 64 * j), v[j]);
+	}
+	// the lines left, fewer than a trip's: the same group once more, a lane past the end loading the last line again
+	// (no branch round a load) and storing nothing
+	if (k < lines) {
+		compact_u32x4 v[U];
+		uint32_t q[U];
+#pragma unroll
+		for (uint32_t j = 0; j < U; j++) {
+			q[j] = k + 64 * j + lane;
+			v[j] = compact_ld16<NT>(s + head + 16 * (uint64_t)(q[j] < lines ? q[j] : lines - 1));
+		}
+#pragma unroll
+		for (uint32_t j = 0; j < U; j++)
+			if (q[j] < lines)
+				compact_st16<NT>(d + head + 16 * (uint64_t)q[j], v[j]);
+	}
+	if (edge)
+		d[eo] = eb;
+}
+
+// slots + i*stride (4-byte aligned) -> dst + dst_off[i].  A grid of at least n wavefronts is one wavefront per member;
+// a smaller one is persistent, wavefront w taking members w, w + grid, ...; the next member's length and offset are
+// requested before the current member is copied.
+__global__ __launch_bounds__(64) void k_compact(const uint8_t *__restrict__ slots, uint64_t stride, const uint32_t *__restrict__ len,
+						const uint64_t *__restrict__ dst_off, uint32_t n, uint8_t *__restrict__ dst)
+{
+	const uint32_t lane = threadIdx.x, step = gridDim.x;
+	uint32_t i = blockIdx.x;
 	if (i >= n)
 		return;
-	compact_one(slots + (uint64_t)i * stride, len[i], dst + dst_off[i], lane);
+	uint32_t L = len[i];
+	uint64_t o = dst_off[i];
+	for (;;) {
+		const uint32_t nx = i + step;
+		const bool more = nx < n && nx > i;
+		const uint32_t nc = more ? nx : i;                // (no branch round the two scalar loads)
+		const uint32_t Ln = len[nc];
+		const uint64_t on = dst_off[nc];
+		compact_wide<COMPACT_NT, COMPACT_UNROLL>(slots + (uint64_t)i * stride, L, dst + o, lane);
+		if (!more)
+			break;
+		i = nx;
+		L = Ln;
+		o = on;
+	}
+}
+
+// compute units of the calling thread's device (the persistent grid's measure), asked once per device
+inline uint32_t compact_device_cus()
+{
+	static std::atomic<uint32_t> cus[64];
+	int dev = 0;
+	if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64)
+		return 256;
+	uint32_t c = cus[dev].load(std::memory_order_relaxed);
+	if (!c) {
+		int v = 0;
+		if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0)
+			v = 256;
+		cus[dev].store(c = (uint32_t)v, std::memory_order_relaxed);
+	}
+	return c;
+}
+
+// a launch of fewer members than the persistent grid holds is one wavefront per member
+inline void launch_compact(const uint8_t *slots, uint64_t stride, const uint32_t *len, const uint64_t *dst_off, uint32_t n,
+			   uint8_t *dst, hipStream_t st)
+{
+	const uint64_t cap = (uint64_t)compact_device_cus() * COMPACT_WAVES_PER_CU;
+	hipLaunchKernelGGL(k_compact, dim3(n < cap ? n : (uint32_t)cap), dim3(64), 0, st, slots, stride, len, dst_off, n, dst);
 }
 
 // RFC 1950 members (HD_FRAME_ZLIB): the Adler-32 of every block's input, written big-endian

@@ -333,8 +333,8 @@ inline int launch_deflate_segmented(const DeflateArgs &a, int level, hipStream_t
 			hipLaunchKernelGGL(k_seg_finish, dim3(ns), dim3(64), 0, st, gr, (const uint8_t *)slots, stride);
 		} else {
 			hipLaunchKernelGGL(k_seg_stitch, dim3(g.count), dim3(64), 0, st, g);
-			hipLaunchKernelGGL(k_compact, dim3(ns), dim3(64), 0, st, (const uint8_t *)slots, (uint64_t)stride,
-					   (const uint32_t *)g.seg_olen, (const uint64_t *)g.seg_dst, ns, a.out);
+			launch_compact((const uint8_t *)slots, (uint64_t)stride, (const uint32_t *)g.seg_olen,
+				       (const uint64_t *)g.seg_dst, ns, a.out, st);
 		}
 	}
 	return 0;
