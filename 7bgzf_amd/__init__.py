@@ -45,6 +45,21 @@ class MemberSummary(ctypes.Structure):
                 ("status", ctypes.c_uint32)]
 
 
+class RangeSummary(ctypes.Structure):
+    """hipdeflate_range_summary (include/hipdeflate.h)"""
+    _fields_ = [("out_bytes", ctypes.c_uint64), ("nselected", ctypes.c_uint64), ("sel_bytes", ctypes.c_uint64),
+                ("nrefused", ctypes.c_uint64), ("bad_member", ctypes.c_uint64), ("status", ctypes.c_uint32)]
+
+
+RANGE_BYTES, RANGE_VOFFSET = 0, 1    # HD_RANGE_*: what the begin / end of a ranged read are
+RANGE_PIECE = 256 << 10              # include/hipdeflate_params.h HD_RANGE_PIECE: bytes a wavefront of the slice copy takes at a time
+
+
+def voffset(coffset, uoffset):
+    """HIPDEFLATE_VOFFSET: the BAM / tabix virtual offset of byte `uoffset` of the member that starts at file offset `coffset`"""
+    return (int(coffset) << 16) | (int(uoffset) & 0xffff)
+
+
 # every symbol include/hipdeflate.h declares (checked by tests/test_abi.py)
 EXPORTS = [
     "hipdeflate_init", "hipdeflate_shutdown", "hipdeflate_available", "hipdeflate_version", "hipdeflate_stall_count",
@@ -56,6 +71,7 @@ EXPORTS = [
     "hipdeflate_unpipe_result", "hipdeflate_unpipe_close", "hipdeflate_test_build_lengths", "hipdeflate_test_beside",
     "hip_inflate_flush", "hipdeflate_batch_inflate_flush", "hipdeflate_batch_inflate_flush_dev", "hipdeflate_bound",
     "hipdeflate_compact_span_dev", "hipdeflate_index_members_dev", "hipdeflate_verify_members_dev",
+    "hipdeflate_read_ranges_dev",
     "hipdeflate_init_devices", "hipdeflate_device_count", "hipdeflate_use_device",
     "hipdeflate_pipe_open_on", "hipdeflate_unpipe_open_on", "hipdeflate_lat_open_on",
     "hipdeflate_pipe_members", "hipdeflate_lat_open", "hipdeflate_lat_input", "hipdeflate_lat_run", "hipdeflate_lat_output", "hipdeflate_lat_close",
@@ -134,6 +150,8 @@ def lib():
     L.hipdeflate_index_members_dev.argtypes = [_vp, ctypes.c_uint64, ctypes.c_uint32, _vp, _vp, _vp, _vp, _vp,
                                                ctypes.POINTER(MemberSummary), _vp]
     L.hipdeflate_verify_members_dev.argtypes = [_vp, _vp, _vp, _vp, _vp, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint64), _vp]
+    L.hipdeflate_read_ranges_dev.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint32, ctypes.c_int, _vp, _vp, ctypes.c_uint32,
+                                             _vp, ctypes.c_uint64, _vp, _vp, _vp, ctypes.POINTER(RangeSummary), _vp]
     L.hipdeflate_pipe_open.restype = _vp
     L.hipdeflate_pipe_open.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int]
     L.hipdeflate_pipe_input.restype = _vp

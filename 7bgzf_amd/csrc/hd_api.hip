@@ -25,6 +25,7 @@
 #include "hd_inflate_lat.hpp"
 #include "hd_compact.hpp"
 #include "hd_index.hpp"
+#include "hd_range.hpp"
 #include "hd_segment.hpp"
 
 namespace {
@@ -126,6 +127,8 @@ struct Ctx {
 	// tables.  An index call waits for its stream before it returns, so calls take turns by holding mu_index.
 	std::mutex mu_index;
 	Buf d_index, d_cand;
+	// ranged reads (hd_range.hpp), behind mu_index too: the per-member and per-query tables of a call, and the members it decodes
+	Buf d_range, d_range_out;
 };
 
 // One context per entry of the device list (hipdeflate_init(devices...)).  An entry is a HIP device ordinal;
@@ -529,7 +532,7 @@ void hipdeflate_shutdown(void)
 		(void)hipSetDevice(g.device);
 		(void)hipDeviceSynchronize();                        // launches on callers' streams may still use our scratch
 		for (Buf *b : { &g.d_in, &g.d_meta, &g.d_slots, &g.d_packed, &g.d_scratch, &g.d_scan, &g.h_in, &g.h_meta,
-				&g.h_out, &g.d_tok, &g.d_tiles, &g.d_index, &g.d_cand })
+				&g.h_out, &g.d_tok, &g.d_tiles, &g.d_index, &g.d_cand, &g.d_range, &g.d_range_out })
 			b->release();
 		(void)hipFree(g.d_ct);
 		(void)hipFree(g.d_stalls);
@@ -911,6 +914,102 @@ int hipdeflate_verify_members_dev(const void *status, const void *out_len, const
 	HD_CHECK(hipStreamSynchronize(st));
 	if (bad != hd::IDX_NIL)
 		*first_bad = bad;
+	return 0;
+}
+
+int hipdeflate_read_ranges_dev(const void *blob, const void *in_off, const void *in_len, const void *out_size, const void *out_off,
+			       const void *crc_want, uint32_t nmembers, int kind, const void *q_begin, const void *q_end,
+			       uint32_t nqueries, void *dst, uint64_t dst_cap, void *dst_off, void *q_len, void *q_status,
+			       hipdeflate_range_summary *summary, void *stream)
+{
+	Ctx &g = cur();
+	int r = ensure();
+	if (r)
+		return r;
+	if (!summary)
+		return HD_E_ARG;
+	memset(summary, 0, sizeof *summary);
+	summary->bad_member = nmembers;
+	if (((uintptr_t)blob & 15) || (kind != HD_RANGE_BYTES && kind != HD_RANGE_VOFFSET) || (!dst && dst_cap) ||
+	    nmembers > 0x7fffffffu || nqueries > 0x7fffffffu ||                       // (n + 1 and n + 255 stay inside 32 bits)
+	    (nmembers && (!blob || !in_off || !in_len || !out_size || !out_off || !crc_want)) ||
+	    (nqueries && (!q_begin || !q_end || !dst_off || !q_len || !q_status)))
+		return HD_E_ARG;
+	if (nmembers == 0 || nqueries == 0)
+		return 0;
+	hipStream_t st = (hipStream_t)stream;
+	const size_t n = nmembers, nq = nqueries;
+	const uint32_t wg_n = (nmembers + 255) / 256, wg_q = (nqueries + 255) / 256;
+	std::lock_guard<std::mutex> lk(g.mu_index);
+	// sum[8] | scan tiles | cover_scan[n + 1] | rank, scratch_off, c_in_off, c_out_off [n] | q_from, piece_off [nq] |
+	// cover[n + 1] | sel, sel_size, c_in_len, c_out_cap, c_crc_want, c_member, c_out_len, c_crc, c_status [n] | q_pieces, q_first [nq]
+	const size_t ntiles = ((n + 1 > nq ? n + 1 : nq) + hd::SCAN_TILE - 1) / hd::SCAN_TILE;
+	if (g.d_range.reserve((8 + ntiles + (n + 1) + 4 * n + 2 * nq) * 8 + ((n + 1) + 9 * n + 2 * nq) * 4))
+		return HD_E_NOMEM;
+	uint64_t *sum = (uint64_t *)g.d_range.p, *tiles = sum + 8, *cover_scan = tiles + ntiles, *rank = cover_scan + n + 1;
+	uint64_t *scratch_off = rank + n, *c_in_off = scratch_off + n, *c_out_off = c_in_off + n, *q_from = c_out_off + n;
+	uint64_t *piece_off = q_from + nq;
+	uint32_t *cover = (uint32_t *)(piece_off + nq), *sel = cover + n + 1, *sel_size = sel + n, *c_in_len = sel_size + n;
+	uint32_t *c_out_cap = c_in_len + n, *c_crc_want = c_out_cap + n, *c_member = c_crc_want + n, *c_out_len = c_member + n;
+	uint32_t *c_crc = c_out_len + n, *c_status = c_crc + n, *q_pieces = c_status + n, *q_first = q_pieces + nq;
+	// sum[]: 0 out_bytes | 1 pieces | 2 (the cover scan's total) | 3 nselected | 4 sel_bytes | 5 bad_member | 6 nrefused (u32) | 7 first bad row (u32)
+	uint32_t *d_refused = (uint32_t *)(sum + 6), *d_bad_row = (uint32_t *)(sum + 7);
+	HD_CHECK(hipMemsetAsync(sum, 0, 56, st));
+	HD_CHECK(hipMemsetAsync(d_bad_row, 0xff, 4, st));
+	HD_CHECK(hipMemsetAsync(cover, 0, (n + 1) * 4, st));
+	// queries -> lengths, first members, coverage; coverage -> selection, ranks, scratch layout
+	hipLaunchKernelGGL(hd::k_range_resolve, dim3(wg_q), dim3(256), 0, st, (const uint64_t *)in_off, (const uint32_t *)in_len,
+			   (const uint32_t *)out_size, (const uint64_t *)out_off, nmembers, kind, (const uint64_t *)q_begin,
+			   (const uint64_t *)q_end, nqueries, (uint32_t *)q_len, (int32_t *)q_status, q_pieces, q_first, q_from, cover,
+			   d_refused);
+	index_scan((const uint32_t *)q_len, nqueries, tiles, (uint64_t *)dst_off, sum + 0, st);
+	index_scan(q_pieces, nqueries, tiles, piece_off, sum + 1, st);
+	index_scan(cover, nmembers + 1, tiles, cover_scan, sum + 2, st);
+	hipLaunchKernelGGL(hd::k_range_select, dim3(wg_n), dim3(256), 0, st, (const uint64_t *)cover_scan, (const uint32_t *)out_size,
+			   nmembers, sel, sel_size);
+	index_scan(sel, nmembers, tiles, rank, sum + 3, st);
+	index_scan(sel_size, nmembers, tiles, scratch_off, sum + 4, st);
+	HD_CHECK(hipGetLastError());
+	uint64_t h[8];
+	HD_CHECK(hipMemcpyAsync(h, sum, 64, hipMemcpyDeviceToHost, st));
+	HD_CHECK(hipStreamSynchronize(st));
+	summary->out_bytes = h[0];
+	summary->nselected = h[3];
+	summary->sel_bytes = h[4];
+	summary->nrefused = (uint32_t)h[6];
+	if (h[0] > dst_cap) {
+		summary->status = 3;
+		return 0;
+	}
+	if (h[3] == 0)                                                           // no query took a byte
+		return 0;
+	// the selected members, inflated back to back into the scratch and held to their trailers
+	const uint32_t nsel = (uint32_t)h[3];
+	if (g.d_range_out.reserve(h[4] + 16))
+		return HD_E_NOMEM;
+	uint8_t *scratch = (uint8_t *)g.d_range_out.p;
+	hipLaunchKernelGGL(hd::k_range_tables, dim3(wg_n), dim3(256), 0, st, (const uint64_t *)in_off, (const uint32_t *)in_len,
+			   (const uint32_t *)out_size, (const uint32_t *)crc_want, (const uint32_t *)sel, (const uint64_t *)rank,
+			   (const uint64_t *)scratch_off, nmembers, c_in_off, c_in_len, c_out_off, c_out_cap, c_crc_want, c_member);
+	if ((r = batch_inflate_dev(blob, c_in_off, c_in_len, nsel, scratch, c_out_off, c_out_cap, c_out_len, c_crc, c_status, stream, 0)))
+		return r;
+	hipLaunchKernelGGL(hd::k_members_verify, dim3((nsel + 255) / 256), dim3(256), 0, st, (const int32_t *)c_status,
+			   (const uint32_t *)c_out_len, (const uint32_t *)c_crc, (const uint32_t *)c_out_cap, (const uint32_t *)c_crc_want,
+			   nsel, d_bad_row);
+	hipLaunchKernelGGL(hd::k_range_verdict, dim3(1), dim3(1), 0, st, (const uint32_t *)d_bad_row, (const uint32_t *)c_member,
+			   nmembers, sum + 5);
+	// every query's run of the scratch -> dst + dst_off[q], in pieces over a persistent grid
+	const uint64_t grid_cap = (uint64_t)hd::compact_device_cus() * hd::COMPACT_WAVES_PER_CU;
+	hipLaunchKernelGGL(hd::k_range_gather, dim3((uint32_t)(h[1] < grid_cap ? h[1] : grid_cap)), dim3(64), 0, st,
+			   (const uint8_t *)scratch, (const uint64_t *)scratch_off, (const uint64_t *)out_off, (const uint32_t *)q_first,
+			   (const uint64_t *)q_from, (const uint32_t *)q_len, (const uint64_t *)dst_off, (const uint64_t *)piece_off,
+			   nqueries, h[1], (uint8_t *)dst);
+	HD_CHECK(hipGetLastError());
+	HD_CHECK(hipMemcpyAsync(h, sum + 5, 8, hipMemcpyDeviceToHost, st));
+	HD_CHECK(hipStreamSynchronize(st));
+	summary->bad_member = h[0];
+	if (h[0] != nmembers)
+		summary->status = 2;
 	return 0;
 }
 

@@ -63,6 +63,7 @@ class DeviceInflate:
         self.in_off, self.out_off = table(torch.int64), table(torch.int64)
         self.in_len, self.out_size, self.crc_want = table(torch.int32), table(torch.int32), table(torch.int32)
         self.out_len, self.crc, self.status = table(torch.int32), table(torch.int32), table(torch.int32)
+        self.nmembers = None             # entries the last index() filled
 
     def index(self, blob):
         """blob: uint8 tensor, 16-byte aligned -> MemberSummary; the tables hold min(nmembers, max_members) entries"""
@@ -71,6 +72,7 @@ class DeviceInflate:
             _ptr(blob), blob.numel(), self.max_members, _ptr(self.in_off), _ptr(self.in_len), _ptr(self.out_size),
             _ptr(self.out_off), _ptr(self.crc_want), ctypes.byref(summary), _stream())
         _pkg._check(rc, "hipdeflate_index_members_dev")
+        self.nmembers = min(summary.nmembers, self.max_members)
         return summary
 
     def verify(self, nmembers):
@@ -100,6 +102,47 @@ class DeviceInflate:
             raise _pkg.HipDeflateError("member %d: inflate status %d, or CRC32/ISIZE mismatch" % (bad, int(self.status[bad])))
         return s
 
+    def ranges_call(self, blob, begins, ends, kind, nmembers, dst, dst_cap):
+        """one hipdeflate_read_ranges_dev on these tables: begins / ends int64 device tensors (the bits of the u64 values),
+        dst a uint8 tensor of any alignment or None -> (dst_off, q_len, q_status, RangeSummary)"""
+        nq = begins.numel()
+        dst_off = torch.zeros(nq, dtype=torch.int64, device=blob.device)
+        q_len = torch.zeros(nq, dtype=torch.int32, device=blob.device)
+        q_status = torch.zeros(nq, dtype=torch.int32, device=blob.device)
+        summary = _pkg.RangeSummary()
+        rc = _pkg.lib().hipdeflate_read_ranges_dev(
+            _ptr(blob), _ptr(self.in_off), _ptr(self.in_len), _ptr(self.out_size), _ptr(self.out_off), _ptr(self.crc_want),
+            nmembers, kind, _ptr(begins), _ptr(ends), nq, _ptr(dst), dst_cap, _ptr(dst_off), _ptr(q_len), _ptr(q_status),
+            ctypes.byref(summary), _stream())
+        _pkg._check(rc, "hipdeflate_read_ranges_dev")
+        return dst_off, q_len, q_status, summary
+
+    def read_ranges(self, blob, begins, ends, kind=_pkg.RANGE_BYTES, nmembers=None):
+        """the bytes of the ranges [begins[q], ends[q]) of the decoded file -- offsets in it, or virtual offsets with
+        kind=RANGE_VOFFSET -- on the tables index(blob) filled; only the members the ranges touch are inflated.
+        -> (out, dst_off, q_len, q_status, RangeSummary): query q is out[dst_off[q]:dst_off[q] + q_len[q]], q_status[q] != 0
+        where it was refused (1: no such range, 2: 4 GiB or more)"""
+        n = (self.nmembers if self.nmembers is not None else self.max_members) if nmembers is None else nmembers
+        begins, ends = _u64_tensor(begins, blob.device), _u64_tensor(ends, blob.device)
+        if begins.numel() != ends.numel():
+            raise ValueError("%d begins, %d ends" % (begins.numel(), ends.numel()))
+        s = self.ranges_call(blob, begins, ends, kind, n, None, 0)[3]             # the sizing call
+        out = torch.empty(s.out_bytes, dtype=torch.uint8, device=blob.device)
+        dst_off, q_len, q_status, s = self.ranges_call(blob, begins, ends, kind, n, out, out.numel())
+        if s.status == 2:
+            raise _pkg.HipDeflateError("member %d: inflate status, or CRC32/ISIZE mismatch" % s.bad_member)
+        if s.status:
+            raise _pkg.HipDeflateError("ranged read: status %d" % s.status)
+        return out, dst_off, q_len, q_status, s
+
+
+def _u64_tensor(v, device):
+    """u64 values (a sequence of ints, a numpy array, or an int64 tensor holding their bits) -> int64 device tensor"""
+    if isinstance(v, torch.Tensor):
+        return v.to(device=device, dtype=torch.int64).contiguous()
+    a = np.array([int(x) for x in v], dtype=np.uint64) if not isinstance(v, np.ndarray) else v.astype(np.uint64)
+    return torch.from_numpy(a.view(np.int64).copy()).to(device)
+
 
 def inflate_container(blob):
     """uint8 tensor holding a whole container file -> uint8 tensor of its contents; nothing visits the host.
@@ -110,6 +153,17 @@ def inflate_container(blob):
     out = torch.empty(s.out_bytes, dtype=torch.uint8, device=blob.device)
     d.run(blob, out, s)
     return out
+
+
+def read_ranges(blob, begins, ends, kind=_pkg.RANGE_BYTES):
+    """uint8 tensor holding a whole container file + ranges of its contents -> what DeviceInflate.read_ranges answers;
+    the file is indexed first, as inflate_container does"""
+    d = DeviceInflate(DeviceInflate(0, blob.device).index(blob).nmembers, blob.device)
+    s = d.index(blob)
+    if s.status:
+        why = {1: "not a member", 2: "member cut off"}
+        raise _pkg.HipDeflateError("member index: %s at offset %d (%d members)" % (why[s.status], s.end_offset, s.nmembers))
+    return d.read_ranges(blob, begins, ends, kind)
 
 
 def device_inflate(comp, in_off, in_len, out, out_off, out_cap, out_len, crc, status):

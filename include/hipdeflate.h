@@ -284,6 +284,52 @@ int hipdeflate_verify_members_dev(const void *status, const void *out_len, const
 				  const void *out_size, const void *crc_want, uint32_t nmembers,
 				  uint64_t *first_bad /* HOST: index, or nmembers if none */, void *stream);
 
+/* Ranged reads on that table -- what a BGZF index is for (`bgzip -b OFFSET -s SIZE`, the chunks of a .bai / .tbi lookup):
+ * nqueries ranges [q_begin[q], q_end[q]) of the decoded file are delivered, and only the members they touch are inflated,
+ * each once however many queries touch it.  The five tables are those of hipdeflate_index_members_dev for `blob`
+ * (nmembers entries); q_begin / q_end are u64 device arrays read according to `kind`: */
+#define HD_RANGE_BYTES   0   /* q_begin/q_end: offsets in the decoded file, [begin, end) */
+#define HD_RANGE_VOFFSET 1   /* q_begin/q_end: virtual offsets, HIPDEFLATE_VOFFSET(coffset, uoffset), [begin, end) */
+/* With total = out_off[nmembers-1] + out_size[nmembers-1] (taken on the device):
+ *   HD_RANGE_BYTES    begin > end is refused (q_status 1); end is clipped to total; begin >= total gives length 0, status 0.
+ *   HD_RANGE_VOFFSET  v names the decoded position U(v) = out_off[m] + uoffset, where m is the member that STARTS at
+ *                     coffset = v >> 16 (member 0 starts at 0, member i at in_off[i-1] + in_len[i-1]: in_len counts the
+ *                     trailer, so this holds for all five member kinds) and uoffset = v & 0xffff <= out_size[m]; coffset ==
+ *                     the end of the last member with uoffset 0 names total.  Everything else is refused (q_status 1): a
+ *                     coffset inside a member, the offset of a payload, a uoffset past ISIZE, U(begin) > U(end).
+ * A query of 2^32 bytes or more after clipping is refused with q_status 2 (q_len is 32 bits wide: split the range).  A
+ * refused query has q_len 0, takes no room in dst and does not disturb the others; the call still returns 0.
+ * Output: q_len[q] (u32) bytes of query q at dst + dst_off[q], dst_off (u64) the exclusive prefix sum of q_len made on the
+ * device, q_status[q] (i32); all three device arrays of nqueries entries.  No byte of dst outside [0, out_bytes) is
+ * written; dst needs no alignment.  Overlapping, nested, duplicate and unsorted queries each get their own copy.
+ * A member is inflated if and only if an accepted query takes at least one byte of it: members of ISIZE 0 (the EOF
+ * block) and queries of length 0 select nothing.  *summary (host memory): */
+typedef struct hipdeflate_range_summary {
+	uint64_t out_bytes;   /* sum of q_len[] */
+	uint64_t nselected;   /* distinct members decoded */
+	uint64_t sel_bytes;   /* sum of their ISIZE */
+	uint64_t nrefused;    /* queries with q_status != 0 */
+	uint64_t bad_member;  /* status 2: lowest index, in the CALLER's table, of a decoded member whose inflate
+	                       * disagrees with its trailer; nmembers otherwise */
+	uint32_t status;      /* 0 ok | 2 a decoded member is bad | 3 dst too small */
+} hipdeflate_range_summary;
+/* Status 3 (out_bytes > dst_cap): nothing is inflated and dst is not touched; q_len, dst_off, q_status and the summary are
+ * complete, so a call with dst == NULL and dst_cap == 0 is the sizing call.  Status 2: a selected member disagrees with its
+ * trailer by the rules of hipdeflate_verify_members_dev; dst is written all the same, the bytes of the queries that touch
+ * a bad member are unspecified, and bad_member names the lowest one.  nmembers == 0 or nqueries == 0: returns 0 with a
+ * zero summary (bad_member == nmembers) and writes nothing.  Returns 0 whenever the read ran (the verdict is
+ * summary->status), HD_E_ARG for a NULL summary, a kind that is neither of the two, a blob that is not 16-byte aligned, a NULL table or query array where
+ * there are entries, or dst == NULL with dst_cap != 0, and HD_E_NOMEM if the scratch cannot grow.  The decoded members
+ * live in scratch of the library (sel_bytes of it, grow-only); calls take turns with one another and with the index.
+ * (Synchronises the stream: nselected, sel_bytes and out_bytes size the inflate launch and the scratch.) */
+int hipdeflate_read_ranges_dev(const void *blob,
+			       const void *in_off, const void *in_len, const void *out_size, const void *out_off,
+			       const void *crc_want, uint32_t nmembers,
+			       int kind, const void *q_begin, const void *q_end, uint32_t nqueries,
+			       void *dst, uint64_t dst_cap,
+			       void *dst_off /* u64[nqueries] */, void *q_len /* u32[nqueries] */, void *q_status /* i32[nqueries] */,
+			       hipdeflate_range_summary *summary /* HOST */, void *stream);
+
 /* ---- streaming encoder: the host pipeline either side of the kernels ------------
  * Role of the read / compress / write loop of applet/7bgzf.c:159-293 (7migz.c:130-244)
  * for a stream of fixed-size blocks (the last may be short).  `depth` batches are in

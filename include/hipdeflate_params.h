@@ -203,6 +203,10 @@
  * as 32-bit bit counts (8 n + 64 + 24 < 2^32) */
 #define HD_INFLATE_MAX_IN  (1u << 28)
 
+/* hipdeflate_read_ranges_dev: the slice copy deals a query's bytes in pieces of at most this many, one wavefront per
+ * piece at a time, so that one range of gigabytes spreads over the chip like thousands of small ones */
+#define HD_RANGE_PIECE     (256u << 10)
+
 /* result codes of the inflate path = enum libdeflate_result
  * (lib/libdeflate/libdeflate.h:193-208), which libdeflate_inflate
  * (lib/zlibutil.c:194-204) hands straight back to the applet */
