@@ -27,6 +27,7 @@
 #include "hd_index.hpp"
 #include "hd_range.hpp"
 #include "hd_segment.hpp"
+#include "hd_tables.hpp"
 
 namespace {
 
@@ -100,6 +101,44 @@ struct Buf {
 	}
 };
 
+// A grow-only device buffer that every launch of the library shares: launches on different streams take turns on it
+// (guarded by Ctx::mu_dev)
+struct SharedScratch {
+	Buf buf;
+	hipEvent_t ev = nullptr;         // the last launch that used buf: a launch on ANOTHER stream waits for it
+	hipStream_t last = nullptr;
+	bool used = false;
+	int enter(hipStream_t st)
+	{
+		if (!ev)
+			HD_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+		if (used && last != st)                                     // same stream: already in order
+			HD_CHECK(hipStreamWaitEvent(st, ev, 0));
+		return 0;
+	}
+	int leave(hipStream_t st)
+	{
+		HD_CHECK(hipEventRecord(ev, st));
+		last = st;
+		used = true;
+		return 0;
+	}
+	void drained(hipStream_t st)             // everything on st has finished: nobody need wait for its event any more
+	{
+		if (last == st)
+			used = false;
+	}
+	void reset()
+	{
+		buf.release();
+		if (ev)
+			(void)hipEventDestroy(ev);
+		ev = nullptr;
+		last = nullptr;
+		used = false;
+	}
+};
+
 struct Ctx {
 	bool ready = false;
 	int failed = 0;
@@ -110,19 +149,18 @@ struct Ctx {
 	uint32_t *d_stalls = nullptr;    // blocks the workgroup parse gave up on (hipdeflate_stall_count)
 	// host-pointer API pools (guarded by mu)
 	std::mutex mu;
-	Buf d_in, d_meta, d_slots, d_packed, d_scratch, d_scan;
+	Buf d_in, d_meta, d_slots, d_packed, d_scratch;
 	Buf h_in{ nullptr, 0, true }, h_meta{ nullptr, 0, true }, h_out{ nullptr, 0, true };
 	// device-pointer API scratch (token slabs for the dynamic levels), guarded by mu_dev
 	std::mutex mu_dev;
-	Buf d_tok;
-	Buf d_tiles;
-	hipEvent_t ev_tok = nullptr;     // last launch that used d_tok: a launch on ANOTHER stream waits for it
-	hipStream_t st_tok = nullptr;
-	bool tok_used = false;
-	hd::WgBeside beside;             // the workgroup levels' emit kernel beside their parse (hd_deflate_wg.hpp), with d_tok
-	hipEvent_t ev_tiles = nullptr;   // the same for d_tiles
-	hipStream_t st_tiles = nullptr;
-	bool tiles_used = false;
+	SharedScratch tok, tiles;        // token slabs and segment slots of a launch / the tile sums of a scan
+	hd::WgBeside beside;             // the workgroup levels' emit kernel beside their parse (hd_deflate_wg.hpp), with tok
+	void stream_drained(hipStream_t st)
+	{
+		std::lock_guard<std::mutex> lk(mu_dev);
+		tok.drained(st);
+		tiles.drained(st);
+	}
 	// member index scratch (hd_index.hpp): the bitmap and tile counts of the blob, the candidate list and its successor
 	// tables.  An index call waits for its stream before it returns, so calls take turns by holding mu_index.
 	std::mutex mu_index;
@@ -438,6 +476,113 @@ int launch_deflate(const hd::DeflateArgs &a, int level, hipStream_t st)
 
 inline size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
 
+// one range of a table, between its pinned and its device copy
+template <class Table> hipError_t table_copy(const Table &dst, const Table &src, hd::Span s, hipMemcpyKind kind, hipStream_t st)
+{
+	return hipMemcpyAsync(dst.ptr(s), src.ptr(s), s.bytes, kind, st);
+}
+
+/* ---- the ring of slots both streaming pipes run on ----------------------------- */
+
+struct PipeSlot {
+	Buf h_in{ nullptr, 0, true }, h_out{ nullptr, 0, true }, h_meta{ nullptr, 0, true };
+	Buf d_in, d_meta, d_slots, d_packed;
+	hipStream_t st = nullptr;
+	size_t nbytes = 0;
+	uint32_t nb = 0;
+	int state = 0;               // 0 free, 1 being filled, 2 submitted, 3 result held by the caller
+};
+
+// `depth` slots handed round in order: one thread fills and submits, one fetches results (tests/pipe_model.py)
+struct SlotRing {
+	int ctx = 0;                                 // entry of the device list the pipe lives on
+	int depth = 0;
+	std::vector<PipeSlot> slots;
+	std::mutex mu;
+	std::condition_variable cv;
+	uint64_t n_in = 0, n_sub = 0, n_out = 0;     // slots handed out / submitted / fetched
+	int held = -1;
+
+	// A slot's memory is pinned / allocated when the slot is first handed out (fill): pinning costs ~0.3 ms per MiB, and a
+	// stream that ends after one batch -- or a caller that wants its first bytes soon -- should not wait for `depth` batches'
+	// worth of it.  Only the streams are made here.
+	bool open(int depth_)
+	{
+		ctx = t_cur;
+		depth = depth_;
+		slots.resize(depth);
+		for (PipeSlot &s : slots)
+			if (hipStreamCreateWithFlags(&s.st, hipStreamNonBlocking) != hipSuccess)
+				return false;
+		return true;
+	}
+	// the slot to fill, once it is free: nullptr for input() twice without submit(), or when alloc (the slot's memory, outside
+	// the lock; the caller is the one thread that does input() / submit() on this pipe) fails
+	template <class Alloc> PipeSlot *fill(Alloc alloc)
+	{
+		std::unique_lock<std::mutex> lk(mu);
+		PipeSlot &s = slots[n_in % depth];
+		if (s.state == 1)
+			return nullptr;
+		cv.wait(lk, [&] { return s.state == 0; });
+		lk.unlock();
+		{
+			const OnCtx on(ctx);
+			if (ensure() || bind_device() || (!s.h_in.p && alloc(s)))
+				return nullptr;
+		}
+		lk.lock();
+		s.state = 1;
+		return &s;
+	}
+	PipeSlot *filling()                          // the slot input() handed out (nullptr: none)
+	{
+		std::lock_guard<std::mutex> lk(mu);
+		PipeSlot &s = slots[n_in % depth];
+		return s.state == 1 ? &s : nullptr;
+	}
+	void submitted(PipeSlot &s)
+	{
+		std::lock_guard<std::mutex> lk(mu);
+		s.state = 2;
+		n_in++;
+		n_sub++;
+		cv.notify_all();
+	}
+	PipeSlot *next_result()                      // the previous result goes back to the pool; nullptr: nothing pending
+	{
+		std::lock_guard<std::mutex> lk(mu);
+		if (held >= 0) {
+			slots[held].state = 0;
+			held = -1;
+			cv.notify_all();
+		}
+		return n_out == n_sub ? nullptr : &slots[n_out % depth];
+	}
+	void hold(PipeSlot &s)
+	{
+		std::lock_guard<std::mutex> lk(mu);
+		s.state = 3;
+		held = (int)(n_out % depth);
+		n_out++;
+	}
+	void close()
+	{
+		const OnCtx on(ctx);
+		Ctx &g = cur();
+		(void)hipSetDevice(g.device);
+		(void)hipDeviceSynchronize();
+		for (PipeSlot &s : slots) {
+			for (Buf *b : { &s.h_in, &s.h_out, &s.h_meta, &s.d_in, &s.d_meta, &s.d_slots, &s.d_packed })
+				b->release();
+			if (s.st) {
+				g.stream_drained(s.st);
+				(void)hipStreamDestroy(s.st);
+			}
+		}
+	}
+};
+
 } // namespace
 
 extern "C" {
@@ -531,21 +676,16 @@ void hipdeflate_shutdown(void)
 			continue;
 		(void)hipSetDevice(g.device);
 		(void)hipDeviceSynchronize();                        // launches on callers' streams may still use our scratch
-		for (Buf *b : { &g.d_in, &g.d_meta, &g.d_slots, &g.d_packed, &g.d_scratch, &g.d_scan, &g.h_in, &g.h_meta,
-				&g.h_out, &g.d_tok, &g.d_tiles, &g.d_index, &g.d_cand, &g.d_range, &g.d_range_out })
+		for (Buf *b : { &g.d_in, &g.d_meta, &g.d_slots, &g.d_packed, &g.d_scratch, &g.h_in, &g.h_meta, &g.h_out, &g.d_index,
+				&g.d_cand, &g.d_range, &g.d_range_out })
 			b->release();
 		(void)hipFree(g.d_ct);
 		(void)hipFree(g.d_stalls);
 		g.d_stalls = nullptr;
 		(void)hipStreamDestroy(g.stream);
-		if (g.ev_tok)
-			(void)hipEventDestroy(g.ev_tok);
-		if (g.ev_tiles)
-			(void)hipEventDestroy(g.ev_tiles);
-		g.ev_tok = g.ev_tiles = nullptr;
+		g.tok.reset();
+		g.tiles.reset();
 		g.beside.release();
-		g.st_tok = g.st_tiles = nullptr;
-		g.tok_used = g.tiles_used = false;
 		g.d_ct = nullptr;
 		g.stream = nullptr;
 		g.ready = false;
@@ -578,7 +718,6 @@ uint64_t hipdeflate_bound(uint64_t block_bytes, int level)
 
 /* ---- device-pointer API ---------------------------------------------------- */
 
-// max_in: the longest block of the batch where the host knows the lengths (0: only the device does)
 // The emit kernel BESIDE the parse (hd_deflate_wg.hpp launch_wg) needs its two kernels on the device at the same time.  Where the
 // process says that kernels run one at a time -- the runtime's launch-blocking and serialising switches, a profiler collecting
 // hardware counters (rocprofv3 --pmc dispatches one kernel at a time and exports these variables to its child) -- the emit kernel
@@ -596,6 +735,50 @@ static bool beside_allowed()
 	       !getenv("ROCPROF_COUNTERS");
 }
 
+// The segments of a launch (hd_segment.hpp): a slot that could hold a block longer than the segment limit -- HD_SEG_LIMIT;
+// the segment size itself in latency mode -- has such blocks coded in segments, the ordinary coding leaves them alone.
+// limit 0: no segments (the workgroup levels take a block of any length whole).
+struct SegRule {
+	uint32_t bytes, limit;
+};
+static SegRule seg_rule(int level, bool latency, uint32_t room)
+{
+	const uint32_t seg = latency ? HD_LAT_SEG_BYTES(level) : HD_SEG_BYTES, lim = latency ? seg : HD_SEG_LIMIT;
+	return { seg, (level >= 1 && level < HD_WG_LEVEL && room > lim) ? lim : 0u };
+}
+
+// What every encode launch sets the same way (the rest of DeflateArgs: zero).  room: the longest block a slot can hold;
+// max_in: the longest block of the batch where the host knows the lengths (0: only the device does)
+static hd::DeflateArgs deflate_args(const Ctx &g, const void *in, const uint64_t *in_off, const uint32_t *in_len, uint32_t nblocks,
+				    int level, int frame, bool latency, void *out, uint64_t out_stride, uint32_t out_cap,
+				    uint32_t *out_len, uint32_t *crc, int32_t *status, uint32_t room, uint32_t max_in)
+{
+	hd::DeflateArgs a{};
+	a.in = (const uint8_t *)in;
+	a.in_off = in_off;
+	a.in_len = in_len;
+	a.nblocks = nblocks;
+	a.frame = frame;
+	a.level = level;
+	a.out = (uint8_t *)out;
+	a.out_stride = out_stride;
+	a.out_cap = out_cap;
+	a.out_len = out_len;
+	a.crc = crc;
+	a.status = status;
+	a.ct = g.d_ct;
+	a.stalls = g.d_stalls;
+	const SegRule seg = seg_rule(level, latency, room);
+	a.seg_bytes = seg.bytes;
+	a.seg_limit = seg.limit;
+	// the workgroup levels: the parse's records are sized by the longest block where the host knows it, else by the slot
+	// (k_parse_wg refuses a block longer than its record)
+	a.split_max = (level >= HD_WG_LEVEL && max_in) ? max_in : room;
+	// ... and in latency mode the member is written by a workgroup, the same bytes (blocks up to 64 KiB; hd_emit_wg.hpp)
+	a.lat = (latency && level >= HD_WG_LEVEL && a.split_max <= hd::EW_BLOCK_MAX) ? 1u : 0u;
+	return a;
+}
+
 static int batch_deflate_dev_impl(const void *in, const void *in_off, const void *in_len, uint32_t nblocks, int level,
 				  int frame, void *out, uint64_t out_stride, uint32_t out_cap, void *out_len,
 				  void *crc32, void *status, void *stream, uint32_t max_in)
@@ -608,78 +791,39 @@ static int batch_deflate_dev_impl(const void *in, const void *in_off, const void
 	frame &= ~HD_FRAME_LATENCY;
 	if (frame < HD_FRAME_RAW || frame > HD_FRAME_GZIP || (out_stride & 15) || ((uintptr_t)out & 15) || !out_len)
 		return HD_E_ARG;
-	hd::DeflateArgs a;
-	a.in = (const uint8_t *)in;
-	a.in_off = (const uint64_t *)in_off;
-	a.in_len = (const uint32_t *)in_len;
-	a.nblocks = nblocks;
-	a.frame = frame;
-	a.level = level;
-	a.out = (uint8_t *)out;
-	a.out_stride = out_stride;
-	a.out_cap = out_cap;
-	a.out_len = (uint32_t *)out_len;
-	a.crc = (uint32_t *)crc32;
-	a.status = (int32_t *)status;
-	a.ct = g.d_ct;
-	a.scratch = nullptr;
-	a.first = 0;
-	a.count = 0;
-	a.skip_small = 0;
-	a.split_max = hd::split_max_block(out_stride, out_cap);
-	a.split_ovf = nullptr;
-	// slots that could hold a block longer than the segment limit (HD_SEG_LIMIT; the segment size itself in latency
-	// mode): such blocks are coded in segments, the ordinary coding leaves them alone
-	const uint32_t seg_lim = latency ? HD_LAT_SEG_BYTES(level) : HD_SEG_LIMIT;
-	a.seg_bytes = latency ? HD_LAT_SEG_BYTES(level) : HD_SEG_BYTES;
-	a.seg_limit = (level >= 1 && level < HD_WG_LEVEL && a.split_max > seg_lim) ? seg_lim : 0;
-	// the workgroup levels: the parse's records are sized by the longest block where the host knows it, else by the slot
-	// (k_parse_wg refuses a block longer than its record)
-	if (level >= HD_WG_LEVEL && max_in)
-		a.split_max = max_in;
-	// ... and in latency mode the member is written by a workgroup, the same bytes (blocks up to 64 KiB)
-	a.lat = (latency && level >= HD_WG_LEVEL && a.split_max <= hd::EW_BLOCK_MAX) ? 1u : 0u;
-	a.stalls = g.d_stalls;
-	a.hint = 0;
-	a.host_seg_off = nullptr;
-	a.host_seg_len = nullptr;
+	hipStream_t st = (hipStream_t)stream;
+	hd::DeflateArgs a = deflate_args(g, in, (const uint64_t *)in_off, (const uint32_t *)in_len, nblocks, level, frame, latency, out,
+					 out_stride, out_cap, (uint32_t *)out_len, (uint32_t *)crc32, (int32_t *)status,
+					 hd::split_max_block(out_stride, out_cap), max_in);
 	const uint64_t need = scratch_need(nblocks, a.split_max, level, latency);
-	if (need) {
-		// token slabs of the dynamic levels, segment slots of large blocks: library-owned, grow-only
-		std::lock_guard<std::mutex> lk(g.mu_dev);
-		// (a re-allocation must not pull the rug from under launches in flight: the old scratch stays alive)
-		bool beside_fits = true;
-		if (g.d_tok.grow_keep_old(need)) {
-			// (what the emit kernel BESIDE the parse adds -- a second buffer of records, the flag lines -- is an option, not a need:
-			// without it the launch runs in the old order)
-			const uint64_t extra = (level >= HD_WG_LEVEL && !a.lat) ? hd::wg_beside_bytes(nblocks, a.split_max) : 0;
-			if (!extra || extra >= need || g.d_tok.grow_keep_old(need - extra))
-				return HD_E_NOMEM;
-			beside_fits = false;
-		}
-		a.scratch = (uint8_t *)g.d_tok.p;
-		// the slabs are shared by every launch: launches on different streams take turns
-		if (!g.ev_tok)
-			HD_CHECK(hipEventCreateWithFlags(&g.ev_tok, hipEventDisableTiming));
-		if (g.tok_used && g.st_tok != (hipStream_t)stream)          // same stream: already in order
-			HD_CHECK(hipStreamWaitEvent((hipStream_t)stream, g.ev_tok, 0));
-		if (level >= HD_WG_LEVEL && !a.lat && beside_fits && beside_allowed() && g.beside.init() == 0) {
-			a.beside = &g.beside;
-			// (emit wavefronts a CU keeps: three -- but two beside the four-way parse of BGZF-sized blocks, where the third costs the parse
-			// more than it takes off the launch's end: encode_l6 123.8 -> 125.8 GB/s, 1 MiB members the other way, 131.1 -> 128.5;
-			// tools/r05_keep_ab.sh)
-			const uint32_t keep = (HD_WG_WAYS(level) == 4 && a.split_max <= 65536) ? 2u : 3u;
-			a.beside_keep = g_test_beside_keep < keep ? g_test_beside_keep : keep;
-		}
-		r = launch_deflate(a, level, (hipStream_t)stream);
-		if (!r) {
-			HD_CHECK(hipEventRecord(g.ev_tok, (hipStream_t)stream));
-			g.st_tok = (hipStream_t)stream;
-			g.tok_used = true;
-		}
-		return r;
+	if (!need)
+		return launch_deflate(a, level, st);
+	// token slabs of the dynamic levels, segment slots of large blocks: library-owned, grow-only
+	std::lock_guard<std::mutex> lk(g.mu_dev);
+	// (a re-allocation must not pull the rug from under launches in flight: the old scratch stays alive)
+	bool beside_fits = true;
+	if (g.tok.buf.grow_keep_old(need)) {
+		// (what the emit kernel BESIDE the parse adds -- a second buffer of records, the flag lines -- is an option, not a need:
+		// without it the launch runs in the old order)
+		const uint64_t extra = (level >= HD_WG_LEVEL && !a.lat) ? hd::wg_beside_bytes(nblocks, a.split_max) : 0;
+		if (!extra || extra >= need || g.tok.buf.grow_keep_old(need - extra))
+			return HD_E_NOMEM;
+		beside_fits = false;
 	}
-	return launch_deflate(a, level, (hipStream_t)stream);
+	a.scratch = (uint8_t *)g.tok.buf.p;
+	if ((r = g.tok.enter(st)))
+		return r;
+	if (level >= HD_WG_LEVEL && !a.lat && beside_fits && beside_allowed() && g.beside.init() == 0) {
+		a.beside = &g.beside;
+		// (emit wavefronts a CU keeps: three -- but two beside the four-way parse of BGZF-sized blocks, where the third costs the parse
+		// more than it takes off the launch's end: encode_l6 123.8 -> 125.8 GB/s, 1 MiB members the other way, 131.1 -> 128.5;
+		// tools/r05_keep_ab.sh)
+		const uint32_t keep = (HD_WG_WAYS(level) == 4 && a.split_max <= 65536) ? 2u : 3u;
+		a.beside_keep = g_test_beside_keep < keep ? g_test_beside_keep : keep;
+	}
+	if ((r = launch_deflate(a, level, st)))
+		return r;
+	return g.tok.leave(st);
 }
 
 int hipdeflate_batch_deflate_dev(const void *in, const void *in_off, const void *in_len, uint32_t nblocks, int level,
@@ -690,6 +834,22 @@ int hipdeflate_batch_deflate_dev(const void *in, const void *in_off, const void 
 				      stream, 0);
 }
 
+// the decode launch over a table (one layout on every side: hd_tables.hpp)
+static hd::InflateArgs inflate_args(const Ctx &g, const void *in, const hd::DecTable &t, uint32_t nblocks, void *out, bool want_crc,
+				    uint32_t flags)
+{
+	return { (const uint8_t *)in, t.in_off(), t.in_len(), nblocks, (uint8_t *)out, t.out_off(), t.out_cap(), t.out_len(),
+		 want_crc ? t.crc() : nullptr, t.status(), g.d_ct, flags };
+}
+
+static int launch_inflate(const hd::InflateArgs &a, hipStream_t st)
+{
+	hipLaunchKernelGGL(hd::k_inflate, dim3(a.nblocks), dim3(64), 0, st, a);
+	HD_CHECK(hipGetLastError());
+	return 0;
+}
+
+// ... and over the caller's own columns
 static int batch_inflate_dev(const void *in, const void *in_off, const void *in_len, uint32_t nblocks, void *out,
 			     const void *out_off, const void *out_cap, void *out_len, void *crc32, void *status, void *stream,
 			     uint32_t flags)
@@ -702,22 +862,10 @@ static int batch_inflate_dev(const void *in, const void *in_off, const void *in_
 		return HD_E_ARG;
 	if (nblocks == 0)
 		return 0;
-	hd::InflateArgs a;
-	a.in = (const uint8_t *)in;
-	a.in_off = (const uint64_t *)in_off;
-	a.in_len = (const uint32_t *)in_len;
-	a.nblocks = nblocks;
-	a.out = (uint8_t *)out;
-	a.out_off = (const uint64_t *)out_off;
-	a.out_cap = (const uint32_t *)out_cap;
-	a.out_len = (uint32_t *)out_len;
-	a.crc = (uint32_t *)crc32;
-	a.status = (int32_t *)status;
-	a.ct = g.d_ct;
-	a.flags = flags;
-	hipLaunchKernelGGL(hd::k_inflate, dim3(nblocks), dim3(64), 0, (hipStream_t)stream, a);
-	HD_CHECK(hipGetLastError());
-	return 0;
+	return launch_inflate({ (const uint8_t *)in, (const uint64_t *)in_off, (const uint32_t *)in_len, nblocks, (uint8_t *)out,
+				(const uint64_t *)out_off, (const uint32_t *)out_cap, (uint32_t *)out_len, (uint32_t *)crc32,
+				(int32_t *)status, g.d_ct, flags },
+			      (hipStream_t)stream);
 }
 
 int hipdeflate_batch_inflate_dev(const void *in, const void *in_off, const void *in_len, uint32_t nblocks, void *out,
@@ -750,23 +898,18 @@ int hipdeflate_scan_sizes_dev(const void *out_len, uint32_t nblocks, uint64_t ba
 	const uint32_t ntiles = (nblocks + hd::SCAN_TILE - 1) / hd::SCAN_TILE;
 	// the tile buffer is one for the whole library: scans on different streams take turns
 	std::lock_guard<std::mutex> lk(g.mu_dev);
-	if (g.d_tiles.grow_keep_old((size_t)ntiles * 8))
+	if (g.tiles.buf.grow_keep_old((size_t)ntiles * 8))
 		return HD_E_NOMEM;
-	uint64_t *tiles = (uint64_t *)g.d_tiles.p;
+	uint64_t *tiles = (uint64_t *)g.tiles.buf.p;
 	hipStream_t st = (hipStream_t)stream;
-	if (!g.ev_tiles)
-		HD_CHECK(hipEventCreateWithFlags(&g.ev_tiles, hipEventDisableTiming));
-	if (g.tiles_used && g.st_tiles != st)                               // same stream: already in order
-		HD_CHECK(hipStreamWaitEvent(st, g.ev_tiles, 0));
+	if ((r = g.tiles.enter(st)))
+		return r;
 	hipLaunchKernelGGL(hd::k_scan_tile_sums, dim3(ntiles), dim3(256), 0, st, (const uint32_t *)out_len, nblocks, tiles);
 	hipLaunchKernelGGL(hd::k_scan_tiles, dim3(1), dim3(256), 0, st, tiles, ntiles, base, (uint64_t *)total);
 	hipLaunchKernelGGL(hd::k_scan_finish, dim3(ntiles), dim3(256), 0, st, (const uint32_t *)out_len, nblocks, tiles,
 			   (uint64_t *)dst_off);
 	HD_CHECK(hipGetLastError());
-	HD_CHECK(hipEventRecord(g.ev_tiles, st));
-	g.st_tiles = st;
-	g.tiles_used = true;
-	return 0;
+	return g.tiles.leave(st);
 }
 
 int hipdeflate_compact_dev(const void *slots, uint64_t stride, const void *out_len, const void *dst_off,
@@ -1043,72 +1186,53 @@ int hipdeflate_batch_deflate(const uint8_t *in, const uint64_t *in_off, const ui
 	// device slot: what the user allows, but never more than any encoding needs
 	const size_t need = (size_t)hipdeflate_bound(max_len, level);
 	const size_t slot = up16(cap_user < need ? cap_user : need);
-	const size_t meta_bytes = (size_t)nblocks * (8 + 4 + 4 + 4 + 4 + 8);
+	const size_t meta_bytes = hd::EncTable::bytes(nblocks);
 	if (g.h_in.reserve(in_total + 16) || g.h_meta.reserve(meta_bytes) || g.d_in.reserve(in_total + 16) ||
-	    g.d_meta.reserve(meta_bytes) || g.d_slots.reserve(slot * nblocks + 16) || g.d_scan.reserve(16))
+	    g.d_meta.reserve(meta_bytes) || g.d_slots.reserve(slot * nblocks + 16))
 		return HD_E_NOMEM;
+	const hd::EncTable h(g.h_meta.p, nblocks), d(g.d_meta.p, nblocks);
 	uint8_t *hin = (uint8_t *)g.h_in.p;
-	uint64_t *h_off = (uint64_t *)g.h_meta.p;
-	uint32_t *h_len = (uint32_t *)(h_off + nblocks);
 	size_t o = 0;
 	for (uint32_t i = 0; i < nblocks; i++) {
-		h_off[i] = o;
-		h_len[i] = in_len[i];
+		h.in_off()[i] = o;
+		h.in_len()[i] = in_len[i];
 		if (in_len[i])
 			memcpy(hin + o, in + in_off[i], in_len[i]);
 		o += up16(in_len[i]);
 	}
-	uint8_t *dm = (uint8_t *)g.d_meta.p;
-	uint64_t *d_off = (uint64_t *)dm;
-	uint32_t *d_len = (uint32_t *)(d_off + nblocks);
-	uint32_t *d_olen = d_len + nblocks;
-	uint32_t *d_crc = d_olen + nblocks;
-	int32_t *d_st = (int32_t *)(d_crc + nblocks);
-	uint64_t *d_doff = (uint64_t *)(d_st + nblocks);
 	HD_CHECK(hipMemcpyAsync(g.d_in.p, hin, in_total, hipMemcpyHostToDevice, g.stream));
-	HD_CHECK(hipMemcpyAsync(d_off, h_off, (size_t)nblocks * 12, hipMemcpyHostToDevice, g.stream));
-	r = batch_deflate_dev_impl(g.d_in.p, d_off, d_len, nblocks, level, frame, g.d_slots.p, slot,
-				   (uint32_t)(cap_user < slot ? cap_user : slot), d_olen, d_crc, d_st, g.stream,
+	HD_CHECK(table_copy(d, h, h.inputs(), hipMemcpyHostToDevice, g.stream));
+	r = batch_deflate_dev_impl(g.d_in.p, d.in_off(), d.in_len(), nblocks, level, frame, g.d_slots.p, slot,
+				   (uint32_t)(cap_user < slot ? cap_user : slot), d.out_len(), d.crc(), d.status(), g.stream,
 				   max_len ? (uint32_t)max_len : 1u);
 	if (r)
 		return r;
 	// gather on the device so that only the compressed bytes cross PCIe
-	uint64_t *d_total = (uint64_t *)g.d_scan.p;
-	if ((r = hipdeflate_scan_sizes_dev(d_olen, nblocks, 0, d_doff, d_total, g.stream)))
+	if ((r = hipdeflate_scan_sizes_dev(d.out_len(), nblocks, 0, d.dst_off(), d.total(), g.stream)))
 		return r;
 	if (g.d_packed.reserve(slot * nblocks + 16))
 		return HD_E_NOMEM;
-	if ((r = hipdeflate_compact_dev(g.d_slots.p, slot, d_olen, d_doff, nblocks, g.d_packed.p, g.stream)))
+	if ((r = hipdeflate_compact_dev(g.d_slots.p, slot, d.out_len(), d.dst_off(), nblocks, g.d_packed.p, g.stream)))
 		return r;
-	uint32_t *h_olen = (uint32_t *)g.h_meta.p;               // reuse: olen, crc, status
-	HD_CHECK(hipMemcpyAsync(h_olen, d_olen, (size_t)nblocks * 12, hipMemcpyDeviceToHost, g.stream));
+	HD_CHECK(table_copy(h, d, h.results(), hipMemcpyDeviceToHost, g.stream));
 	uint64_t total = 0;
-	HD_CHECK(hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, g.stream));
+	HD_CHECK(hipMemcpyAsync(&total, d.total(), 8, hipMemcpyDeviceToHost, g.stream));
 	HD_CHECK(hipStreamSynchronize(g.stream));
 	if (g.h_out.reserve(total + 16))
 		return HD_E_NOMEM;
 	HD_CHECK(hipMemcpyAsync(g.h_out.p, g.d_packed.p, total, hipMemcpyDeviceToHost, g.stream));
 	HD_CHECK(hipStreamSynchronize(g.stream));
-	{
-		// our stream is drained: launches on other streams need not wait for its events
-		std::lock_guard<std::mutex> lk2(g.mu_dev);
-		if (g.st_tiles == g.stream)
-			g.tiles_used = false;
-		if (g.st_tok == g.stream)
-			g.tok_used = false;
-	}
+	g.stream_drained(g.stream);
 	const uint8_t *hp = (const uint8_t *)g.h_out.p;
-	const uint32_t *h_crc = h_olen + nblocks;
-	const int32_t *h_st = (const int32_t *)(h_crc + nblocks);
 	size_t po = 0;
 	for (uint32_t i = 0; i < nblocks; i++) {
-		out_len[i] = h_olen[i];
+		out_len[i] = h.out_len()[i];
 		if (crc32)
-			crc32[i] = h_crc[i];
+			crc32[i] = h.crc()[i];
 		if (status)
-			status[i] = h_st[i];
-		memcpy(out + (uint64_t)i * out_stride, hp + po, h_olen[i]);
-		po += h_olen[i];
+			status[i] = h.status()[i];
+		memcpy(out + (uint64_t)i * out_stride, hp + po, out_len[i]);
+		po += out_len[i];
 	}
 	return 0;
 }
@@ -1135,54 +1259,38 @@ static int batch_inflate_host(const uint8_t *in, const uint64_t *in_off, const u
 		in_total += up16(in_len[i]);
 		out_total += up16(out_cap[i]);
 	}
-	const size_t meta_bytes = (size_t)nblocks * (8 + 4 + 8 + 4 + 4 + 4 + 4);
+	const size_t meta_bytes = hd::DecTable::bytes(nblocks);
 	if (g.h_in.reserve(in_total + 16) || g.h_meta.reserve(meta_bytes) || g.d_in.reserve(in_total + 16) ||
 	    g.d_meta.reserve(meta_bytes) || g.d_slots.reserve(out_total + 16) || g.h_out.reserve(out_total + 16))
 		return HD_E_NOMEM;
+	const hd::DecTable h(g.h_meta.p, nblocks), d(g.d_meta.p, nblocks);
 	uint8_t *hin = (uint8_t *)g.h_in.p;
-	uint64_t *h_ioff = (uint64_t *)g.h_meta.p;
-	uint64_t *h_ooff = h_ioff + nblocks;
-	uint32_t *h_ilen = (uint32_t *)(h_ooff + nblocks);
-	uint32_t *h_ocap = h_ilen + nblocks;
 	size_t io = 0, oo = 0;
 	for (uint32_t i = 0; i < nblocks; i++) {
-		h_ioff[i] = io;
-		h_ooff[i] = oo;
-		h_ilen[i] = in_len[i];
-		h_ocap[i] = out_cap[i];
+		h.in_off()[i] = io;
+		h.out_off()[i] = oo;
+		h.in_len()[i] = in_len[i];
+		h.out_cap()[i] = out_cap[i];
 		if (in_len[i])
 			memcpy(hin + io, in + in_off[i], in_len[i]);
 		io += up16(in_len[i]);
 		oo += up16(out_cap[i]);
 	}
-	uint8_t *dm = (uint8_t *)g.d_meta.p;
-	uint64_t *d_ioff = (uint64_t *)dm;
-	uint64_t *d_ooff = d_ioff + nblocks;
-	uint32_t *d_ilen = (uint32_t *)(d_ooff + nblocks);
-	uint32_t *d_ocap = d_ilen + nblocks;
-	uint32_t *d_olen = d_ocap + nblocks;
-	uint32_t *d_crc = d_olen + nblocks;
-	int32_t *d_st = (int32_t *)(d_crc + nblocks);
 	HD_CHECK(hipMemcpyAsync(g.d_in.p, hin, in_total, hipMemcpyHostToDevice, g.stream));
-	HD_CHECK(hipMemcpyAsync(dm, g.h_meta.p, (size_t)nblocks * 24, hipMemcpyHostToDevice, g.stream));
-	r = batch_inflate_dev(g.d_in.p, d_ioff, d_ilen, nblocks, g.d_slots.p, d_ooff, d_ocap, d_olen, crc32 ? d_crc : nullptr,
-			      d_st, g.stream, flags);
-	if (r)
+	HD_CHECK(table_copy(d, h, h.inputs(), hipMemcpyHostToDevice, g.stream));
+	if ((r = launch_inflate(inflate_args(g, g.d_in.p, d, nblocks, g.d_slots.p, crc32 != nullptr, flags), g.stream)))
 		return r;
-	uint32_t *h_olen = (uint32_t *)g.h_meta.p + 6 * (size_t)nblocks;     // past the 24 B/blk inputs
-	HD_CHECK(hipMemcpyAsync(h_olen, d_olen, (size_t)nblocks * 12, hipMemcpyDeviceToHost, g.stream));
+	HD_CHECK(table_copy(h, d, h.results_crc(), hipMemcpyDeviceToHost, g.stream));
 	HD_CHECK(hipMemcpyAsync(g.h_out.p, g.d_slots.p, out_total, hipMemcpyDeviceToHost, g.stream));
 	HD_CHECK(hipStreamSynchronize(g.stream));
-	const uint32_t *h_crc = h_olen + nblocks;
-	const int32_t *h_st = (const int32_t *)(h_crc + nblocks);
 	for (uint32_t i = 0; i < nblocks; i++) {
-		out_len[i] = h_olen[i];
+		out_len[i] = h.out_len()[i];
 		if (crc32)
-			crc32[i] = h_crc[i];
+			crc32[i] = h.crc()[i];
 		if (status)
-			status[i] = h_st[i];
-		if (h_st[i] == 0 && h_olen[i])
-			memcpy(out + out_off[i], (const uint8_t *)g.h_out.p + h_ooff[i], h_olen[i]);
+			status[i] = h.status()[i];
+		if (h.status()[i] == 0 && out_len[i])
+			memcpy(out + out_off[i], (const uint8_t *)g.h_out.p + h.out_off()[i], out_len[i]);
 	}
 	return 0;
 }
@@ -1201,28 +1309,12 @@ int hipdeflate_batch_inflate_flush(const uint8_t *in, const uint64_t *in_off, co
 	return batch_inflate_host(in, in_off, in_len, nblocks, out, out_off, out_cap, out_len, crc32, status, hd::INF_FLUSHED);
 }
 
-/* ---- streaming encoder ---------------------------------------------------------- */
+/* ---- streaming encoder and decoder (SlotRing above) -------------------------------- */
 
-struct PipeSlot {
-	Buf h_in{ nullptr, 0, true }, h_out{ nullptr, 0, true }, h_meta{ nullptr, 0, true };
-	std::vector<uint64_t> doff;      // member offsets of the held result, 8-byte aligned (pipe_members)
-	Buf d_in, d_meta, d_slots, d_packed;
-	hipStream_t st = nullptr;
-	size_t nbytes = 0;
-	uint32_t nb = 0;
-	int state = 0;               // 0 free, 1 being filled, 2 submitted, 3 result held by the caller
-};
-
-struct hipdeflate_pipe {
-	int ctx = 0;                                 // entry of the device list the pipe lives on
-	int level, frame, depth;
+struct hipdeflate_pipe : SlotRing {
+	int level, frame;
 	uint32_t block, per_batch;
 	size_t slot_stride;
-	std::vector<PipeSlot> slots;
-	std::mutex mu;
-	std::condition_variable cv;
-	uint64_t n_in = 0, n_sub = 0, n_out = 0;     // slots handed out / submitted / fetched
-	int held = -1;
 };
 
 hipdeflate_pipe *hipdeflate_pipe_open(int level, int frame, uint32_t block_bytes, uint32_t blocks_per_batch, int depth)
@@ -1233,40 +1325,19 @@ hipdeflate_pipe *hipdeflate_pipe_open(int level, int frame, uint32_t block_bytes
 	    depth < 2 || depth > 16 || (uint64_t)block_bytes * blocks_per_batch > 0xffff0000ull)
 		return nullptr;
 	hipdeflate_pipe *p = new hipdeflate_pipe;
-	p->ctx = t_cur;
 	p->level = level;
 	p->frame = frame;
-	p->depth = depth;
 	p->block = block_bytes;
 	p->per_batch = blocks_per_batch;
 	// a member never needs more than the stored form + the largest frame
 	p->slot_stride = (size_t)hipdeflate_bound(block_bytes, level);
 	if (frame == HD_FRAME_BGZF && p->slot_stride > 65536)
 		p->slot_stride = 65536;
-	p->slots.resize(depth);
-	// A slot's memory is pinned / allocated when the slot is first handed out (pipe_slot_alloc): pinning costs ~0.3 ms per
-	// MiB, and a stream that ends after one batch -- or a caller that wants its first bytes soon -- should not wait for
-	// `depth` batches' worth of it.  Only the streams are made here.
-	for (PipeSlot &s : p->slots) {
-		if (hipStreamCreateWithFlags(&s.st, hipStreamNonBlocking) != hipSuccess) {
-			hipdeflate_pipe_close(p);
-			return nullptr;
-		}
+	if (!p->open(depth)) {
+		hipdeflate_pipe_close(p);
+		return nullptr;
 	}
 	return p;
-}
-
-// (the caller is the one thread that does input() / submit() on this pipe)
-static int pipe_slot_alloc(hipdeflate_pipe *p, PipeSlot &s)
-{
-	if (s.h_in.p)
-		return 0;
-	const size_t in_cap = (size_t)p->block * p->per_batch;
-	const size_t meta = (size_t)p->per_batch * (8 + 4 + 4 + 4 + 4 + 8) + 16;
-	if (s.h_in.reserve(in_cap) || s.d_in.reserve(in_cap + 16) || s.h_meta.reserve(meta) || s.d_meta.reserve(meta) ||
-	    s.d_slots.reserve(p->slot_stride * p->per_batch + 16) || s.d_packed.reserve(p->slot_stride * p->per_batch + 16))
-		return HD_E_NOMEM;
-	return 0;
 }
 
 hipdeflate_pipe *hipdeflate_pipe_open_on(int index, int level, int frame, uint32_t block_bytes, uint32_t blocks_per_batch,
@@ -1282,35 +1353,24 @@ uint8_t *hipdeflate_pipe_input(hipdeflate_pipe *p, size_t *cap)
 {
 	if (!p)
 		return nullptr;
-	std::unique_lock<std::mutex> lk(p->mu);
-	PipeSlot &s = p->slots[p->n_in % p->depth];
-	if (s.state == 1)
-		return nullptr;                          // input() twice without submit()
-	p->cv.wait(lk, [&] { return s.state == 0; });
-	lk.unlock();
-	{
-		const OnCtx on(p->ctx);
-		if (ensure() || bind_device() || pipe_slot_alloc(p, s))
-			return nullptr;
-	}
-	lk.lock();
-	s.state = 1;
+	const size_t in_cap = (size_t)p->block * p->per_batch;
+	PipeSlot *s = p->fill([&](PipeSlot &s) {
+		const size_t meta = hd::EncTable::bytes(p->per_batch), packed = p->slot_stride * p->per_batch + 16;
+		return s.h_in.reserve(in_cap) || s.d_in.reserve(in_cap + 16) || s.h_meta.reserve(meta) || s.d_meta.reserve(meta) ||
+		       s.d_slots.reserve(packed) || s.d_packed.reserve(packed);
+	});
+	if (!s)
+		return nullptr;
 	if (cap)
-		*cap = (size_t)p->block * p->per_batch;
-	return (uint8_t *)s.h_in.p;
+		*cap = in_cap;
+	return (uint8_t *)s->h_in.p;
 }
 
 int hipdeflate_pipe_submit(hipdeflate_pipe *p, size_t nbytes)
 {
-	if (!p)
+	PipeSlot *sp = p ? p->filling() : nullptr;
+	if (!sp || nbytes > (size_t)p->block * p->per_batch)
 		return HD_E_ARG;
-	PipeSlot *sp;
-	{
-		std::lock_guard<std::mutex> lk(p->mu);
-		sp = &p->slots[p->n_in % p->depth];
-		if (sp->state != 1 || nbytes > (size_t)p->block * p->per_batch)
-			return HD_E_ARG;
-	}
 	PipeSlot &s = *sp;
 	const OnCtx on(p->ctx);
 	int r = ensure();
@@ -1320,38 +1380,24 @@ int hipdeflate_pipe_submit(hipdeflate_pipe *p, size_t nbytes)
 	s.nb = (uint32_t)((nbytes + p->block - 1) / p->block);
 	if (s.nb) {
 		// block table: offsets i * block (16-byte aligned), the last block may be short
-		uint64_t *h_off = (uint64_t *)s.h_meta.p;
-		uint32_t *h_len = (uint32_t *)(h_off + s.nb);
+		const hd::EncTable h(s.h_meta.p, s.nb), d(s.d_meta.p, s.nb);
 		for (uint32_t i = 0; i < s.nb; i++) {
-			h_off[i] = (uint64_t)i * p->block;
-			h_len[i] = i + 1 < s.nb ? p->block : (uint32_t)(nbytes - (size_t)i * p->block);
+			h.in_off()[i] = (uint64_t)i * p->block;
+			h.in_len()[i] = i + 1 < s.nb ? p->block : (uint32_t)(nbytes - (size_t)i * p->block);
 		}
-		uint8_t *dm = (uint8_t *)s.d_meta.p;
-		uint64_t *d_off = (uint64_t *)dm;
-		uint32_t *d_len = (uint32_t *)(d_off + s.nb);
-		uint32_t *d_olen = d_len + s.nb;
-		uint32_t *d_crc = d_olen + s.nb;
-		int32_t *d_st = (int32_t *)(d_crc + s.nb);
-		uint64_t *d_doff = (uint64_t *)(((uintptr_t)(d_st + s.nb) + 7) & ~(uintptr_t)7);
-		uint64_t *d_total = d_doff + s.nb;
 		HD_CHECK(hipMemcpyAsync(s.d_in.p, s.h_in.p, nbytes, hipMemcpyHostToDevice, s.st));
-		HD_CHECK(hipMemcpyAsync(d_off, h_off, (size_t)s.nb * 12, hipMemcpyHostToDevice, s.st));
-		if ((r = batch_deflate_dev_impl(s.d_in.p, d_off, d_len, s.nb, p->level, p->frame, s.d_slots.p,
-						p->slot_stride, (uint32_t)p->slot_stride, d_olen, d_crc, d_st, s.st, p->block)))
+		HD_CHECK(table_copy(d, h, h.inputs(), hipMemcpyHostToDevice, s.st));
+		if ((r = batch_deflate_dev_impl(s.d_in.p, d.in_off(), d.in_len(), s.nb, p->level, p->frame, s.d_slots.p, p->slot_stride,
+						(uint32_t)p->slot_stride, d.out_len(), d.crc(), d.status(), s.st, p->block)))
 			return r;
-		if ((r = hipdeflate_scan_sizes_dev(d_olen, s.nb, 0, d_doff, d_total, s.st)))
+		if ((r = hipdeflate_scan_sizes_dev(d.out_len(), s.nb, 0, d.dst_off(), d.total(), s.st)))
 			return r;
-		if ((r = hipdeflate_compact_dev(s.d_slots.p, p->slot_stride, d_olen, d_doff, s.nb, s.d_packed.p, s.st)))
+		if ((r = hipdeflate_compact_dev(s.d_slots.p, p->slot_stride, d.out_len(), d.dst_off(), s.nb, s.d_packed.p, s.st)))
 			return r;
 		// sizes, status and the total come back first; the payload follows in result()
-		HD_CHECK(hipMemcpyAsync(s.h_meta.p, d_olen, (size_t)((uint8_t *)(d_total + 1) - (uint8_t *)d_olen),
-					hipMemcpyDeviceToHost, s.st));
+		HD_CHECK(table_copy(h, d, h.results_placed(), hipMemcpyDeviceToHost, s.st));
 	}
-	std::lock_guard<std::mutex> lk(p->mu);
-	s.state = 2;
-	p->n_in++;
-	p->n_sub++;
-	p->cv.notify_all();
+	p->submitted(s);
 	return 0;
 }
 
@@ -1359,18 +1405,9 @@ int hipdeflate_pipe_result(hipdeflate_pipe *p, const uint8_t **data, size_t *nby
 {
 	if (!p || !data || !nbytes)
 		return HD_E_ARG;
-	PipeSlot *sp;
-	{
-		std::unique_lock<std::mutex> lk(p->mu);
-		if (p->held >= 0) {                      // the previous result goes back to the pool
-			p->slots[p->held].state = 0;
-			p->held = -1;
-			p->cv.notify_all();
-		}
-		if (p->n_out == p->n_sub)
-			return HD_E_ARG;                 // nothing pending
-		sp = &p->slots[p->n_out % p->depth];
-	}
+	PipeSlot *sp = p->next_result();
+	if (!sp)
+		return HD_E_ARG;
 	PipeSlot &s = *sp;
 	const OnCtx on(p->ctx);
 	int r = ensure();
@@ -1380,18 +1417,10 @@ int hipdeflate_pipe_result(hipdeflate_pipe *p, const uint8_t **data, size_t *nby
 	size_t total = 0;
 	if (s.nb) {
 		HD_CHECK(hipStreamSynchronize(s.st));
-		// the device layout from d_olen on: olen[nb], crc[nb], status[nb], doff[nb] (u64), total (u64);
-		// d_meta is 256-byte aligned and 24 nb bytes precede doff, so there is no padding
-		const uint32_t *h_olen = (const uint32_t *)s.h_meta.p;
-		const int32_t *h_st = (const int32_t *)(h_olen + 2 * s.nb);
-		uint64_t t64;
-		memcpy(&t64, (const uint8_t *)s.h_meta.p + (size_t)20 * s.nb, 8);
-		total = (size_t)t64;
-		// (doff[] sits 12 nb bytes into the pinned table: only 4-byte aligned for an odd nb)
-		s.doff.resize(s.nb);
-		memcpy(s.doff.data(), (const uint8_t *)s.h_meta.p + (size_t)12 * s.nb, (size_t)8 * s.nb);
+		const hd::EncTable h(s.h_meta.p, s.nb);
+		total = (size_t)*h.total();
 		for (uint32_t i = 0; i < s.nb; i++)
-			bad |= h_st[i] != 0;
+			bad |= h.status()[i] != 0;
 		// the pinned landing buffer follows what the data needs (+ 25 %), not the worst case of the slots
 		if (s.h_out.reserve(total + 16))
 			return HD_E_NOMEM;
@@ -1402,10 +1431,7 @@ int hipdeflate_pipe_result(hipdeflate_pipe *p, const uint8_t **data, size_t *nby
 	*nbytes = total;
 	if (nblocks)
 		*nblocks = s.nb;
-	std::lock_guard<std::mutex> lk(p->mu);
-	s.state = 3;
-	p->held = (int)(p->n_out % p->depth);
-	p->n_out++;
+	p->hold(s);
 	return bad ? 1 : 0;
 }
 
@@ -1417,15 +1443,14 @@ int hipdeflate_pipe_members(hipdeflate_pipe *p, const uint32_t **out_len, const 
 	if (p->held < 0)
 		return HD_E_ARG;                         // no result is held
 	const PipeSlot &s = p->slots[p->held];
-	// the layout pipe_submit() copied back: olen[nb], crc[nb], status[nb], doff[nb] (u64), total (u64)
-	const uint32_t *h_olen = (const uint32_t *)s.h_meta.p;
+	const hd::EncTable h(s.h_meta.p, s.nb);
 	const bool none = s.nb == 0;             // an empty batch: the pinned table holds an earlier batch's figures
 	if (out_len)
-		*out_len = none ? nullptr : h_olen;
+		*out_len = none ? nullptr : h.out_len();
 	if (crc32)
-		*crc32 = none ? nullptr : h_olen + s.nb;
+		*crc32 = none ? nullptr : h.crc();
 	if (dst_off)
-		*dst_off = none ? nullptr : s.doff.data();
+		*dst_off = none ? nullptr : h.dst_off();
 	return 0;
 }
 
@@ -1433,43 +1458,13 @@ void hipdeflate_pipe_close(hipdeflate_pipe *p)
 {
 	if (!p)
 		return;
-	const OnCtx on(p->ctx);
-	Ctx &g = cur();
-	(void)hipSetDevice(g.device);
-	(void)hipDeviceSynchronize();
-	for (PipeSlot &s : p->slots) {
-		s.h_in.release();
-		s.h_out.release();
-		s.h_meta.release();
-		s.d_in.release();
-		s.d_meta.release();
-		s.d_slots.release();
-		s.d_packed.release();
-		if (s.st) {
-			// everything on the stream has finished: nobody needs to wait for its events any more
-			std::lock_guard<std::mutex> lk(g.mu_dev);
-			if (g.st_tiles == s.st)
-				g.tiles_used = false;
-			if (g.st_tok == s.st)
-				g.tok_used = false;
-			(void)hipStreamDestroy(s.st);
-		}
-	}
+	p->close();
 	delete p;
 }
 
-/* ---- streaming decoder ---------------------------------------------------------- */
-
-struct hipdeflate_unpipe {
-	int ctx = 0;
-	int depth;
+struct hipdeflate_unpipe : SlotRing {
 	uint32_t max_members;
 	size_t in_cap, out_cap;
-	std::vector<PipeSlot> slots;
-	std::mutex mu;
-	std::condition_variable cv;
-	uint64_t n_in = 0, n_sub = 0, n_out = 0;
-	int held = -1;
 };
 
 hipdeflate_unpipe *hipdeflate_unpipe_open(uint32_t max_members, size_t in_cap, size_t out_cap, int depth)
@@ -1479,30 +1474,14 @@ hipdeflate_unpipe *hipdeflate_unpipe_open(uint32_t max_members, size_t in_cap, s
 	if (!max_members || !in_cap || !out_cap || depth < 2 || depth > 16 || in_cap > 0xffff0000ull)
 		return nullptr;
 	hipdeflate_unpipe *p = new hipdeflate_unpipe;
-	p->ctx = t_cur;
-	p->depth = depth;
 	p->max_members = max_members;
 	p->in_cap = in_cap;
 	p->out_cap = out_cap;
-	p->slots.resize(depth);
-	for (PipeSlot &s : p->slots) {                            // memory: when a slot is first handed out (unpipe_slot_alloc)
-		if (hipStreamCreateWithFlags(&s.st, hipStreamNonBlocking) != hipSuccess) {
-			hipdeflate_unpipe_close(p);
-			return nullptr;
-		}
+	if (!p->open(depth)) {
+		hipdeflate_unpipe_close(p);
+		return nullptr;
 	}
 	return p;
-}
-
-static int unpipe_slot_alloc(hipdeflate_unpipe *p, PipeSlot &s)
-{
-	if (s.h_in.p)
-		return 0;
-	const size_t meta = (size_t)p->max_members * (8 + 8 + 4 + 4 + 4 + 4 + 4) + 64;
-	if (s.h_in.reserve(p->in_cap) || s.d_in.reserve(p->in_cap + 16) || s.h_meta.reserve(meta) || s.d_meta.reserve(meta) ||
-	    s.d_slots.reserve(p->out_cap + 16) || s.h_out.reserve(p->out_cap + 16))
-		return HD_E_NOMEM;
-	return 0;
 }
 
 hipdeflate_unpipe *hipdeflate_unpipe_open_on(int index, uint32_t max_members, size_t in_cap, size_t out_cap, int depth)
@@ -1517,22 +1496,16 @@ uint8_t *hipdeflate_unpipe_input(hipdeflate_unpipe *p, size_t *cap)
 {
 	if (!p)
 		return nullptr;
-	std::unique_lock<std::mutex> lk(p->mu);
-	PipeSlot &s = p->slots[p->n_in % p->depth];
-	if (s.state == 1)
+	PipeSlot *s = p->fill([&](PipeSlot &s) {
+		const size_t meta = hd::DecTable::bytes(p->max_members);
+		return s.h_in.reserve(p->in_cap) || s.d_in.reserve(p->in_cap + 16) || s.h_meta.reserve(meta) || s.d_meta.reserve(meta) ||
+		       s.d_slots.reserve(p->out_cap + 16) || s.h_out.reserve(p->out_cap + 16);
+	});
+	if (!s)
 		return nullptr;
-	p->cv.wait(lk, [&] { return s.state == 0; });
-	lk.unlock();
-	{
-		const OnCtx on(p->ctx);
-		if (ensure() || bind_device() || unpipe_slot_alloc(p, s))
-			return nullptr;
-	}
-	lk.lock();
-	s.state = 1;
 	if (cap)
 		*cap = p->in_cap;
-	return (uint8_t *)s.h_in.p;
+	return (uint8_t *)s->h_in.p;
 }
 
 int hipdeflate_unpipe_submit(hipdeflate_unpipe *p, const uint64_t *in_off, const uint32_t *in_len,
@@ -1540,30 +1513,24 @@ int hipdeflate_unpipe_submit(hipdeflate_unpipe *p, const uint64_t *in_off, const
 {
 	if (!p || nmembers > p->max_members || (nmembers && (!in_off || !in_len || !out_size)))
 		return HD_E_ARG;
-	PipeSlot *sp;
-	{
-		std::lock_guard<std::mutex> lk(p->mu);
-		sp = &p->slots[p->n_in % p->depth];
-		if (sp->state != 1)
-			return HD_E_ARG;
-	}
+	PipeSlot *sp = p->filling();
+	if (!sp)
+		return HD_E_ARG;
 	PipeSlot &s = *sp;
 	const OnCtx on(p->ctx);
 	int r = ensure();
 	if (r || (r = bind_device()))
 		return r;
-	// pinned table: ioff[n] ooff[n] (u64) | ilen[n] ocap[n] (u32); results olen[n] crc[n] st[n] behind it
 	const uint32_t n = nmembers;
-	uint64_t *h_ioff = (uint64_t *)s.h_meta.p, *h_ooff = h_ioff + n;
-	uint32_t *h_ilen = (uint32_t *)(h_ooff + n), *h_ocap = h_ilen + n;
+	const hd::DecTable h(s.h_meta.p, n), d(s.d_meta.p, n);
 	size_t in_end = 0, osum = 0;
 	for (uint32_t i = 0; i < n; i++) {
 		if (in_len[i] >= HD_INFLATE_MAX_IN)
 			return HD_E_ARG;
-		h_ioff[i] = in_off[i];
-		h_ilen[i] = in_len[i];
-		h_ooff[i] = osum;
-		h_ocap[i] = out_size[i];
+		h.in_off()[i] = in_off[i];
+		h.in_len()[i] = in_len[i];
+		h.out_off()[i] = osum;
+		h.out_cap()[i] = out_size[i];
 		osum += out_size[i];
 		if (in_off[i] + in_len[i] > in_end)
 			in_end = (size_t)(in_off[i] + in_len[i]);
@@ -1573,25 +1540,15 @@ int hipdeflate_unpipe_submit(hipdeflate_unpipe *p, const uint64_t *in_off, const
 	s.nb = n;
 	s.nbytes = osum;
 	if (n) {
-		uint8_t *dm = (uint8_t *)s.d_meta.p;
-		uint64_t *d_ioff = (uint64_t *)dm, *d_ooff = d_ioff + n;
-		uint32_t *d_ilen = (uint32_t *)(d_ooff + n), *d_ocap = d_ilen + n, *d_olen = d_ocap + n;
-		int32_t *d_st = (int32_t *)(d_olen + n);
 		HD_CHECK(hipMemcpyAsync(s.d_in.p, s.h_in.p, in_end, hipMemcpyHostToDevice, s.st));
-		HD_CHECK(hipMemcpyAsync(dm, s.h_meta.p, (size_t)n * 24, hipMemcpyHostToDevice, s.st));
-		if ((r = hipdeflate_batch_inflate_dev(s.d_in.p, d_ioff, d_ilen, n, s.d_slots.p, d_ooff, d_ocap, d_olen, nullptr,
-						      d_st, s.st)))
+		HD_CHECK(table_copy(d, h, h.inputs(), hipMemcpyHostToDevice, s.st));
+		if ((r = launch_inflate(inflate_args(cur(), s.d_in.p, d, n, s.d_slots.p, false, 0), s.st)))
 			return r;
-		HD_CHECK(hipMemcpyAsync((uint8_t *)s.h_meta.p + (size_t)n * 24, d_olen, (size_t)n * 8, hipMemcpyDeviceToHost,
-					s.st));
+		HD_CHECK(table_copy(h, d, h.results(), hipMemcpyDeviceToHost, s.st));
 		if (osum)
 			HD_CHECK(hipMemcpyAsync(s.h_out.p, s.d_slots.p, osum, hipMemcpyDeviceToHost, s.st));
 	}
-	std::lock_guard<std::mutex> lk(p->mu);
-	s.state = 2;
-	p->n_in++;
-	p->n_sub++;
-	p->cv.notify_all();
+	p->submitted(s);
 	return 0;
 }
 
@@ -1599,18 +1556,9 @@ int hipdeflate_unpipe_result(hipdeflate_unpipe *p, const uint8_t **data, size_t 
 {
 	if (!p || !data || !nbytes)
 		return HD_E_ARG;
-	PipeSlot *sp;
-	{
-		std::unique_lock<std::mutex> lk(p->mu);
-		if (p->held >= 0) {
-			p->slots[p->held].state = 0;
-			p->held = -1;
-			p->cv.notify_all();
-		}
-		if (p->n_out == p->n_sub)
-			return HD_E_ARG;
-		sp = &p->slots[p->n_out % p->depth];
-	}
+	PipeSlot *sp = p->next_result();
+	if (!sp)
+		return HD_E_ARG;
 	PipeSlot &s = *sp;
 	const OnCtx on(p->ctx);
 	int r = ensure();
@@ -1619,19 +1567,13 @@ int hipdeflate_unpipe_result(hipdeflate_unpipe *p, const uint8_t **data, size_t 
 	int verdict = 0;
 	if (s.nb) {
 		HD_CHECK(hipStreamSynchronize(s.st));
-		const uint32_t n = s.nb;
-		const uint32_t *h_ocap = (const uint32_t *)((const uint8_t *)s.h_meta.p + (size_t)n * 20);
-		const uint32_t *h_olen = h_ocap + n;
-		const int32_t *h_st = (const int32_t *)(h_olen + n);
-		for (uint32_t i = 0; i < n && !verdict; i++)
-			verdict = h_st[i] ? h_st[i] : (h_olen[i] != h_ocap[i] ? HD_INSUFFICIENT_SPACE : 0);
+		const hd::DecTable h(s.h_meta.p, s.nb);
+		for (uint32_t i = 0; i < s.nb && !verdict; i++)
+			verdict = h.status()[i] ? h.status()[i] : (h.out_len()[i] != h.out_cap()[i] ? HD_INSUFFICIENT_SPACE : 0);
 	}
 	*data = (const uint8_t *)s.h_out.p;
 	*nbytes = s.nbytes;
-	std::lock_guard<std::mutex> lk(p->mu);
-	s.state = 3;
-	p->held = (int)(p->n_out % p->depth);
-	p->n_out++;
+	p->hold(s);
 	return verdict;
 }
 
@@ -1639,27 +1581,7 @@ void hipdeflate_unpipe_close(hipdeflate_unpipe *p)
 {
 	if (!p)
 		return;
-	const OnCtx on(p->ctx);
-	Ctx &g = cur();
-	(void)hipSetDevice(g.device);
-	(void)hipDeviceSynchronize();
-	for (PipeSlot &s : p->slots) {
-		s.h_in.release();
-		s.h_out.release();
-		s.h_meta.release();
-		s.d_in.release();
-		s.d_meta.release();
-		s.d_slots.release();
-		if (s.st) {
-			// everything on the stream has finished: nobody needs to wait for its events any more
-			std::lock_guard<std::mutex> lk(g.mu_dev);
-			if (g.st_tiles == s.st)
-				g.tiles_used = false;
-			if (g.st_tok == s.st)
-				g.tok_used = false;
-			(void)hipStreamDestroy(s.st);
-		}
-	}
+	p->close();
 	delete p;
 }
 
@@ -1677,8 +1599,11 @@ struct hipdeflate_lat {
 	Buf d_scratch;
 	uint8_t *din = nullptr, *dout = nullptr, *dmeta = nullptr;      // device views of the pinned buffers
 	bool latency = true;
-	uint32_t seg = 0, seg_limit = 0, S = 0;                         // segment bytes, limit, segment slots per block
-	size_t meta_seg = 0;                                            // offset of the segment table in the meta buffer
+	uint32_t seg = 0, S = 0;                                        // segment bytes, segment slots per block (0: no segments)
+	// the meta buffer: an EncTable of max_blocks | seg_off u64 [max_blocks * S] | seg_len u32 [max_blocks * S] | the poll word
+	size_t meta_seg = 0;                                            // offset of the segment table
+	hd::EncTable table() const { return { h_meta.p, max_blocks }; }
+	hd::EncTable dev_table() const { return { dmeta, max_blocks }; }
 	// completion without hipStreamSynchronize (HIPDEFLATE_LAT_POLL): the run's last kernel stores the run's number here
 	size_t flag_off = 0;                                            // ... in the meta buffer (pinned, device-visible)
 	Buf d_count;                                                    // the word its workgroups count themselves off on
@@ -1703,13 +1628,11 @@ hipdeflate_lat *hipdeflate_lat_open(int level, int frame, uint32_t max_blocks, u
 	c->slot = (uint32_t)hipdeflate_bound(max_block_bytes, level);
 	if (fr == HD_FRAME_BGZF && c->slot > 65536)
 		c->slot = 65536;
-	const uint32_t seg_lim = c->latency ? HD_LAT_SEG_BYTES(level) : HD_SEG_LIMIT;
-	c->seg = c->latency ? HD_LAT_SEG_BYTES(level) : HD_SEG_BYTES;
-	c->seg_limit = (level >= 1 && level < HD_WG_LEVEL && c->slot > seg_lim) ? seg_lim : 0;
-	c->S = c->seg_limit ? hd::seg_slots_per_block(c->slot, c->seg) : 0;
-	// [ in_off u64 | in_len, out_len, crc, status u32 | seg_off u64 [max_blocks * S] | seg_len u32 [max_blocks * S] ]
-	c->meta_seg = (((size_t)max_blocks * (8 + 4 + 4 + 4 + 4)) + 15) & ~(size_t)15;
-	const size_t meta = c->meta_seg + (size_t)max_blocks * c->S * 12 + 64;
+	const SegRule seg = seg_rule(level, c->latency, c->slot);
+	c->seg = seg.bytes;
+	c->S = seg.limit ? hd::seg_slots_per_block(c->slot, c->seg) : 0;
+	c->meta_seg = up16(hd::EncTable::bytes(max_blocks));
+	const size_t meta = c->meta_seg + (size_t)max_blocks * c->S * (sizeof(uint64_t) + sizeof(uint32_t)) + 64;
 	c->flag_off = meta - 16;
 	// (the workgroup levels' records are sized by the longest block, not by the slot)
 	const uint64_t scr = scratch_need(max_blocks, level >= HD_WG_LEVEL ? c->in_stride : c->slot, level, c->latency);
@@ -1724,9 +1647,8 @@ hipdeflate_lat *hipdeflate_lat_open(int level, int frame, uint32_t max_blocks, u
 		return nullptr;
 	}
 	memset(c->h_meta.p, 0, meta);
-	uint64_t *off = (uint64_t *)c->h_meta.p;
 	for (uint32_t i = 0; i < max_blocks; i++)
-		off[i] = (uint64_t)i * c->in_stride;
+		c->table().in_off()[i] = (uint64_t)i * c->in_stride;
 	return c;
 }
 
@@ -1758,12 +1680,17 @@ static int lat_run_ex(hipdeflate_lat *c, const uint32_t *in_len, uint32_t n, int
 	int r = ensure();
 	if (r || (r = bind_device()))
 		return r;
-	const uint32_t mb = c->max_blocks;
-	const uint32_t seg_limit = latency ? c->seg_limit : 0;           // (a context's slots are far below HD_SEG_LIMIT)
-	uint32_t *h_len = (uint32_t *)((uint64_t *)c->h_meta.p + mb);
+	const hd::EncTable d = c->dev_table();
+	hd::DeflateArgs a = deflate_args(g, c->din, d.in_off(), d.in_len(), n, c->level, frame, latency, c->dout, c->slot,
+					 out_cap < c->slot ? out_cap : c->slot, d.out_len(), d.crc(), d.status(),
+					 hd::split_max_block(c->slot, c->slot), c->in_stride);
+	if (!latency)
+		a.seg_limit = 0;                                         // a context codes in segments in latency mode only
+	const uint32_t seg_limit = a.seg_limit;
+	uint32_t *h_len = c->table().in_len();
 	uint32_t hint = hd::HD_HINT_NO_WHOLE | hd::HD_HINT_NO_SEG;
 	uint64_t *h_soff = (uint64_t *)((uint8_t *)c->h_meta.p + c->meta_seg);
-	uint32_t *h_slen = (uint32_t *)(h_soff + (size_t)mb * c->S);
+	uint32_t *h_slen = (uint32_t *)(h_soff + (size_t)c->max_blocks * c->S);
 	for (uint32_t i = 0; i < n; i++) {
 		if (in_len[i] > c->in_stride)
 			return HD_E_ARG;
@@ -1778,37 +1705,12 @@ static int lat_run_ex(hipdeflate_lat *c, const uint32_t *in_len, uint32_t n, int
 			h_slen[(size_t)i * c->S + k] = sl;
 		}
 	}
-	uint64_t *d_off = (uint64_t *)c->dmeta;
-	uint32_t *d_len = (uint32_t *)(d_off + mb), *d_olen = d_len + mb, *d_crc = d_olen + mb;
-	int32_t *d_st = (int32_t *)(d_crc + mb);
-	hd::DeflateArgs a;
-	a.in = c->din;
-	a.in_off = d_off;
-	a.in_len = d_len;
-	a.nblocks = n;
-	a.frame = frame;
-	a.level = c->level;
-	a.out = c->dout;
-	a.out_stride = c->slot;
-	a.out_cap = out_cap < c->slot ? out_cap : c->slot;
-	a.out_len = d_olen;
-	a.crc = d_crc;
-	a.status = d_st;
-	a.ct = g.d_ct;
 	a.scratch = (uint8_t *)c->d_scratch.p;
-	a.first = 0;
-	a.count = 0;
-	a.skip_small = 0;
-	a.split_max = c->level >= HD_WG_LEVEL ? c->in_stride : hd::split_max_block(c->slot, c->slot);
-	a.split_ovf = nullptr;
-	a.seg_bytes = c->seg;
-	a.seg_limit = seg_limit;
-	// the workgroup levels: the member written by a workgroup (hd_emit_wg.hpp) when no block can be longer than 64 KiB
-	a.lat = (latency && c->level >= HD_WG_LEVEL && a.split_max <= hd::EW_BLOCK_MAX) ? 1u : 0u;
-	a.stalls = g.d_stalls;
-	a.hint = seg_limit ? hint : 0;
-	a.host_seg_off = seg_limit ? (const uint64_t *)(c->dmeta + c->meta_seg) : nullptr;
-	a.host_seg_len = seg_limit ? (const uint32_t *)((const uint64_t *)(c->dmeta + c->meta_seg) + (size_t)mb * c->S) : nullptr;
+	if (seg_limit) {
+		a.hint = hint;
+		a.host_seg_off = (const uint64_t *)(c->dmeta + c->meta_seg);
+		a.host_seg_len = (const uint32_t *)(a.host_seg_off + (size_t)c->max_blocks * c->S);
+	}
 	// the segmented path's last kernel can report by itself (members of up to 64 segments, at least one segmented block)
 	static const bool poll_on = [] { const char *e = getenv("HIPDEFLATE_LAT_POLL"); return e && *e && *e != '0'; }();
 	const bool poll = poll_on && seg_limit && c->S <= 64 && !(a.hint & hd::HD_HINT_NO_SEG);
@@ -1845,14 +1747,13 @@ const uint8_t *hipdeflate_lat_output(hipdeflate_lat *c, uint32_t i, uint32_t *ou
 {
 	if (!c || i >= c->max_blocks)
 		return nullptr;
-	const uint32_t mb = c->max_blocks;
-	const uint32_t *h_olen = (const uint32_t *)((const uint64_t *)c->h_meta.p + mb) + mb;
+	const hd::EncTable h = c->table();
 	if (out_len)
-		*out_len = h_olen[i];
+		*out_len = h.out_len()[i];
 	if (crc32)
-		*crc32 = h_olen[mb + i];
+		*crc32 = h.crc()[i];
 	if (status)
-		*status = (int32_t)h_olen[2 * mb + i];
+		*status = h.status()[i];
 	return (const uint8_t *)c->h_out.p + (size_t)i * c->slot;
 }
 
@@ -2031,13 +1932,8 @@ struct InfBatch {
 	size_t in_used = 0, out_used = 0;
 	uint32_t flags = 0;
 	int ready = 0, taken = 0, sleepers = 0, rc = 0;
-	// the pinned table, device-visible: in_off u64[S] | out_off u64[S] | in_len, out_cap, out_len, status u32[S]
-	uint64_t *in_off() { return (uint64_t *)h_meta.p; }
-	uint64_t *out_off() { return in_off() + INFB_SLOTS; }
-	uint32_t *in_len() { return (uint32_t *)(out_off() + INFB_SLOTS); }
-	uint32_t *out_cap() { return in_len() + INFB_SLOTS; }
-	uint32_t *out_len() { return out_cap() + INFB_SLOTS; }
-	int32_t *status() { return (int32_t *)(out_len() + INFB_SLOTS); }
+	hd::DecTable table() const { return { h_meta.p, INFB_SLOTS }; }       // pinned, device-visible
+	hd::DecTable dev_table() const { return { dmeta, INFB_SLOTS }; }
 };
 InfBatch g_infb[INFB_CTX];
 std::mutex g_inf_mu;
@@ -2088,8 +1984,7 @@ static int infb_create(InfBatch &b, int k)
 	const OnCtx on(b.ctx);
 	if (ensure() || bind_device())
 		return HD_E_NODEVICE;
-	const size_t meta = (size_t)INFB_SLOTS * (8 + 8 + 4 + 4 + 4 + 4);
-	if (b.h_in.reserve(INFB_IN_ARENA + 64) || b.h_out.reserve(INFB_OUT_ARENA + 64) || b.h_meta.reserve(meta) ||
+	if (b.h_in.reserve(INFB_IN_ARENA + 64) || b.h_out.reserve(INFB_OUT_ARENA + 64) || b.h_meta.reserve(hd::DecTable::bytes(INFB_SLOTS)) ||
 	    hipStreamCreateWithFlags(&b.st, hipStreamNonBlocking) != hipSuccess ||
 	    hipHostGetDevicePointer((void **)&b.din, b.h_in.p, 0) != hipSuccess ||
 	    hipHostGetDevicePointer((void **)&b.dout, b.h_out.p, 0) != hipSuccess ||
@@ -2194,10 +2089,11 @@ static int inflate_one(unsigned char *dest, size_t *destLen, const unsigned char
 	const int idx = b->n;
 	const bool leader = idx == 0;
 	const size_t my_in = b->in_used, my_out = b->out_used;
-	b->in_off()[idx] = my_in;
-	b->out_off()[idx] = my_out;
-	b->in_len()[idx] = (uint32_t)sourceLen;
-	b->out_cap()[idx] = (uint32_t)ocap;
+	const hd::DecTable t = b->table();
+	t.in_off()[idx] = my_in;
+	t.out_off()[idx] = my_out;
+	t.in_len()[idx] = (uint32_t)sourceLen;
+	t.out_cap()[idx] = (uint32_t)ocap;
 	b->in_used += in_need;
 	b->out_used += out_need;
 	__atomic_store_n(&b->n, idx + 1, __ATOMIC_RELAXED);
@@ -2263,19 +2159,7 @@ static int inflate_one(unsigned char *dest, size_t *destLen, const unsigned char
 		{
 			const OnCtx on(b->ctx);
 			if (!(rc = ensure()) && !(rc = bind_device())) {
-				hd::InflateArgs a;
-				a.in = b->din;
-				a.in_off = (const uint64_t *)b->dmeta;
-				a.out_off = a.in_off + INFB_SLOTS;
-				a.in_len = (const uint32_t *)(a.out_off + INFB_SLOTS);
-				a.out_cap = a.in_len + INFB_SLOTS;
-				a.out_len = (uint32_t *)(a.out_cap + INFB_SLOTS);
-				a.status = (int32_t *)(a.out_len + INFB_SLOTS);
-				a.nblocks = (uint32_t)n;
-				a.out = b->dout;
-				a.crc = nullptr;
-				a.ct = cur().d_ct;
-				a.flags = b->flags;
+				const hd::InflateArgs a = inflate_args(cur(), b->din, b->dev_table(), (uint32_t)n, b->dout, false, b->flags);
 				hipLaunchKernelGGL(hd::k_inflate_lat, dim3((uint32_t)n), dim3(hd::INF_LAT_THREADS), 0, b->st, a);      // (four wavefronts per stream: hd_inflate_lat.hpp)
 				if (hipGetLastError() != hipSuccess || hipStreamSynchronize(b->st) != hipSuccess) {
 					fprintf(stderr, "hipdeflate: hip_inflate: the latency kernel did not run\n");
@@ -2310,8 +2194,8 @@ static int inflate_one(unsigned char *dest, size_t *destLen, const unsigned char
 	const int rc = b->rc, nb = b->n;
 	int ret = rc;
 	if (!rc) {
-		const int32_t st = b->status()[idx];
-		const uint32_t olen = b->out_len()[idx];
+		const int32_t st = t.status()[idx];
+		const uint32_t olen = t.out_len()[idx];
 		if (st) {
 			ret = st;
 		} else {

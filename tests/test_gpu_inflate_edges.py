@@ -83,6 +83,16 @@ def test_batch_inflate_one_launch_per_family(pkg, cases):
         cs = [c for c in cases if c.family == fam]
         outs, crc, st = pkg.batch_inflate([c.stream for c in cs], [c.cap for c in cs])
         bad += _mismatches(cs, outs, crc, st, False)
+    # 1, 3 and 5 small members, with and without the caller's crc array: the host table's columns at odd counts (the
+    # crc column is the last one back, hd_tables.hpp DecTable), and a caller that wants no crc gets none written
+    small = [c for c in cases if c.code == dg.OK and 0 < len(c.expected) and len(c.stream) <= 300 and c.cap <= 300]
+    assert len(small) >= 9
+    for k, count in enumerate((1, 3, 5)):
+        cs = small[k * 2:k * 2 + count]
+        for want_crc in (True, False):
+            outs, crc, st = pkg.batch_inflate([c.stream for c in cs], [c.cap for c in cs], want_crc=want_crc)
+            bad += _mismatches(cs, outs, crc if want_crc else None, st, False)
+            assert want_crc or not crc.any()
     assert not bad, _report(bad)
 
 
