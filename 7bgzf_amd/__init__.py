@@ -51,6 +51,14 @@ class RangeSummary(ctypes.Structure):
                 ("nrefused", ctypes.c_uint64), ("bad_member", ctypes.c_uint64), ("status", ctypes.c_uint32)]
 
 
+class StreamSummary(ctypes.Structure):
+    """hipdeflate_stream_summary (include/hipdeflate.h)"""
+    _fields_ = [("out_bytes", ctypes.c_uint64), ("in_bytes", ctypes.c_uint64), ("bad_chunk", ctypes.c_uint64),
+                ("nchunks", ctypes.c_uint32), ("check", ctypes.c_uint32), ("status", ctypes.c_uint32)]
+
+
+STREAM_WINDOW_BYTES = 1 << 30        # include/hipdeflate_params.h HD_STREAM_WINDOW_BYTES: slots of one window of the stream encoder
+CHECK_CRC32, CHECK_ADLER32 = 0, 1    # `kind` of hipdeflate_check_combine_dev
 RANGE_BYTES, RANGE_VOFFSET = 0, 1    # HD_RANGE_*: what the begin / end of a ranged read are
 RANGE_PIECE = 256 << 10              # include/hipdeflate_params.h HD_RANGE_PIECE: bytes a wavefront of the slice copy takes at a time
 
@@ -72,6 +80,8 @@ EXPORTS = [
     "hip_inflate_flush", "hipdeflate_batch_inflate_flush", "hipdeflate_batch_inflate_flush_dev", "hipdeflate_bound",
     "hipdeflate_compact_span_dev", "hipdeflate_index_members_dev", "hipdeflate_verify_members_dev",
     "hipdeflate_read_ranges_dev",
+    "hipdeflate_stream_bound", "hipdeflate_stream_deflate_dev", "hipdeflate_stream_inflate_dev",
+    "hipdeflate_check_combine_dev", "hip_deflate_stream", "hipdeflate_test_stream_window",
     "hipdeflate_init_devices", "hipdeflate_device_count", "hipdeflate_use_device",
     "hipdeflate_pipe_open_on", "hipdeflate_unpipe_open_on", "hipdeflate_lat_open_on",
     "hipdeflate_pipe_members", "hipdeflate_lat_open", "hipdeflate_lat_input", "hipdeflate_lat_run", "hipdeflate_lat_output", "hipdeflate_lat_close",
@@ -152,6 +162,16 @@ def lib():
     L.hipdeflate_verify_members_dev.argtypes = [_vp, _vp, _vp, _vp, _vp, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint64), _vp]
     L.hipdeflate_read_ranges_dev.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint32, ctypes.c_int, _vp, _vp, ctypes.c_uint32,
                                              _vp, ctypes.c_uint64, _vp, _vp, _vp, ctypes.POINTER(RangeSummary), _vp]
+    L.hipdeflate_stream_bound.restype = ctypes.c_uint64
+    L.hipdeflate_stream_bound.argtypes = [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int, ctypes.c_int]
+    L.hipdeflate_stream_deflate_dev.argtypes = [_vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int, ctypes.c_int, _vp,
+                                                ctypes.c_uint64, _vp, ctypes.POINTER(StreamSummary), _vp]
+    L.hipdeflate_stream_inflate_dev.argtypes = [_vp, ctypes.c_uint64, ctypes.c_int, _vp, ctypes.c_uint32, ctypes.c_uint32,
+                                                ctypes.c_uint64, _vp, ctypes.c_uint64, ctypes.POINTER(StreamSummary), _vp]
+    L.hipdeflate_check_combine_dev.argtypes = [_vp, _vp, ctypes.c_uint32, ctypes.c_int, ctypes.POINTER(ctypes.c_uint32), _vp]
+    L.hip_deflate_stream.argtypes = [_vp, sz_p, _vp, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_uint32]
+    L.hipdeflate_test_stream_window.argtypes = [ctypes.c_uint32]
+    L.hipdeflate_test_stream_window.restype = None
     L.hipdeflate_pipe_open.restype = _vp
     L.hipdeflate_pipe_open.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int]
     L.hipdeflate_pipe_input.restype = _vp
@@ -236,6 +256,17 @@ def hip_deflate_flush(data, level=1, cap=None):
     dst = np.zeros(max(cap, 1), dtype=np.uint8)
     n = ctypes.c_size_t(cap)
     r = lib().hip_deflate_flush(_p(dst), ctypes.byref(n), _p(src), len(src), level)
+    return r, bytes(dst[: n.value]) if r == 0 else b""
+
+
+def hip_deflate_stream(data, level=6, frame=FRAME_GZIP, chunk=1 << 16, cap=None):
+    """-> (ret, bytes): ONE raw / zlib / gzip stream of `data`, coded in independent chunks of `chunk` bytes on the
+    device (hipdeflate_stream_deflate_dev behind a host buffer); cap: the room, the bound by default"""
+    src = as_u8(data)
+    cap = int(lib().hipdeflate_stream_bound(len(src), chunk, level, frame)) if cap is None else cap
+    dst = np.zeros(max(cap, 1), dtype=np.uint8)
+    n = ctypes.c_size_t(cap)
+    r = lib().hip_deflate_stream(_p(dst), ctypes.byref(n), _p(src), len(src), level, frame, chunk)
     return r, bytes(dst[: n.value]) if r == 0 else b""
 
 

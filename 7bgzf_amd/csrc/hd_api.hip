@@ -26,6 +26,7 @@
 #include "hd_compact.hpp"
 #include "hd_index.hpp"
 #include "hd_range.hpp"
+#include "hd_stream.hpp"
 #include "hd_segment.hpp"
 #include "hd_tables.hpp"
 
@@ -167,6 +168,8 @@ struct Ctx {
 	Buf d_index, d_cand;
 	// ranged reads (hd_range.hpp), behind mu_index too: the per-member and per-query tables of a call, and the members it decodes
 	Buf d_range, d_range_out;
+	// one stream from a resident buffer (hd_stream.hpp), behind mu_index too: the tables of a window of chunks, and its slots
+	Buf d_stream, d_stream_slots;
 };
 
 // One context per entry of the device list (hipdeflate_init(devices...)).  An entry is a HIP device ordinal;
@@ -677,7 +680,7 @@ void hipdeflate_shutdown(void)
 		(void)hipSetDevice(g.device);
 		(void)hipDeviceSynchronize();                        // launches on callers' streams may still use our scratch
 		for (Buf *b : { &g.d_in, &g.d_meta, &g.d_slots, &g.d_packed, &g.d_scratch, &g.h_in, &g.h_meta, &g.h_out, &g.d_index,
-				&g.d_cand, &g.d_range, &g.d_range_out })
+				&g.d_cand, &g.d_range, &g.d_range_out, &g.d_stream, &g.d_stream_slots })
 			b->release();
 		(void)hipFree(g.d_ct);
 		(void)hipFree(g.d_stalls);
@@ -707,13 +710,18 @@ uint64_t hipdeflate_scratch_bytes(uint32_t nblocks, uint32_t max_block, int leve
 	return scratch_need(nblocks, max_block, level, false);
 }
 
-uint64_t hipdeflate_bound(uint64_t block_bytes, int level)
+// the longest payload a block of block_bytes can have at `level`, in any form
+static uint64_t bound_payload(uint64_t block_bytes, int level)
 {
 	// (latency mode included: its segments are the smallest, their worst case the largest)
 	const uint32_t lat = HD_LAT_SEG_BYTES(level);
-	const uint64_t payload = (level >= 1 && level < HD_WG_LEVEL && block_bytes > lat) ? HD_SEGN_WORST(block_bytes, lat, 0)
-								   : block_bytes + 5 * (block_bytes / 65535 + 1) + 5;
-	return (payload + 32 + 15) & ~(uint64_t)15;       // + the longest container (20 + 8 bytes)
+	return (level >= 1 && level < HD_WG_LEVEL && block_bytes > lat) ? HD_SEGN_WORST(block_bytes, lat, 0)
+								: block_bytes + 5 * (block_bytes / 65535 + 1) + 5;
+}
+
+uint64_t hipdeflate_bound(uint64_t block_bytes, int level)
+{
+	return (bound_payload(block_bytes, level) + 32 + 15) & ~(uint64_t)15;       // + the longest container (20 + 8 bytes)
 }
 
 /* ---- device-pointer API ---------------------------------------------------- */
@@ -937,12 +945,13 @@ int hipdeflate_compact_span_dev(const void *slots, uint64_t stride, const void *
 
 /* ---- device-resident container decode --------------------------------------- */
 
-// exclusive 64-bit prefix sum of len[0..n) into dst (n > 0), the sum into *total: the three scan kernels on scratch of the caller
-static void index_scan(const uint32_t *len, uint32_t n, uint64_t *tiles, uint64_t *dst, uint64_t *total, hipStream_t st)
+// exclusive 64-bit prefix sum of len[0..n) into dst (n > 0), plus base, the sum (without base) into *total: the three scan kernels on scratch of the caller
+static void index_scan(const uint32_t *len, uint32_t n, uint64_t *tiles, uint64_t *dst, uint64_t *total, hipStream_t st,
+		       uint64_t base = 0)
 {
 	const uint32_t ntiles = (n + hd::SCAN_TILE - 1) / hd::SCAN_TILE;
 	hipLaunchKernelGGL(hd::k_scan_tile_sums, dim3(ntiles), dim3(256), 0, st, len, n, tiles);
-	hipLaunchKernelGGL(hd::k_scan_tiles, dim3(1), dim3(256), 0, st, tiles, ntiles, (uint64_t)0, total);
+	hipLaunchKernelGGL(hd::k_scan_tiles, dim3(1), dim3(256), 0, st, tiles, ntiles, base, total);
 	hipLaunchKernelGGL(hd::k_scan_finish, dim3(ntiles), dim3(256), 0, st, len, n, tiles, dst);
 }
 
@@ -1153,6 +1162,238 @@ int hipdeflate_read_ranges_dev(const void *blob, const void *in_off, const void 
 	summary->bad_member = h[0];
 	if (h[0] != nmembers)
 		summary->status = 2;
+	return 0;
+}
+
+/* ---- one stream from a resident buffer (hd_stream.hpp) ------------------------ */
+
+static uint32_t g_test_stream_window = 0;                     // hipdeflate_test_stream_window
+static inline uint32_t stream_hdr(int frame) { return frame == HD_FRAME_GZIP ? 10u : frame == HD_FRAME_ZLIB ? 2u : 0u; }
+static inline uint32_t stream_trl(int frame) { return frame == HD_FRAME_GZIP ? 8u : frame == HD_FRAME_ZLIB ? 4u : 0u; }
+static inline bool stream_frame_ok(int frame) { return frame == HD_FRAME_RAW || frame == HD_FRAME_ZLIB || frame == HD_FRAME_GZIP; }
+static inline bool stream_chunk_ok(uint32_t c) { return c >= 16 && c <= (64u << 20) && !(c & 15); }
+constexpr uint32_t STREAM_MAX_PARTS = 0x7fffffffu;            // (n + 1, n + 255 and n + SCAN_TILE stay inside 32 bits)
+
+uint64_t hipdeflate_stream_bound(uint64_t nbytes, uint32_t chunk_bytes, int level, int frame)
+{
+	if (!stream_chunk_ok(chunk_bytes))
+		return 0;
+	const uint64_t full = nbytes / chunk_bytes, rest = nbytes % chunk_bytes;
+	return stream_hdr(frame) + full * bound_payload(chunk_bytes, level) + (rest ? bound_payload(rest, level) : 0) + 2 +
+	       stream_trl(frame);
+}
+
+void hipdeflate_test_stream_window(uint32_t chunks) { g_test_stream_window = chunks; }
+
+// check[] / len[] of n parts folded onto *carry.  sum: u64[3] { the parts' bytes, two accumulators }; tiles: the scan's;
+// prefix: u64[n]
+static int fold_launch(const uint32_t *check, const uint32_t *len, uint32_t n, uint32_t kind, uint64_t *tiles, uint64_t *prefix,
+		       uint64_t *sum, uint32_t *carry, hipStream_t st)
+{
+	HD_CHECK(hipMemsetAsync(sum, 0, 24, st));
+	if (n) {
+		index_scan(len, n, tiles, prefix, sum, st);
+		const uint32_t wgs = (n + 255) / 256;
+		hipLaunchKernelGGL(hd::k_check_combine, dim3(wgs < hd::FOLD_GRID ? wgs : hd::FOLD_GRID), dim3(256), 0, st, check, len,
+				   (const uint64_t *)prefix, (const uint64_t *)sum, n, kind, sum + 1);
+	}
+	hipLaunchKernelGGL(hd::k_check_combine_finish, dim3(1), dim3(64), 0, st, (const uint64_t *)(sum + 1),
+			   n ? (const uint64_t *)sum : (const uint64_t *)nullptr, kind, carry);
+	HD_CHECK(hipGetLastError());
+	return 0;
+}
+
+int hipdeflate_check_combine_dev(const void *check, const void *len, uint32_t n, int kind, uint32_t *result, void *stream)
+{
+	Ctx &g = cur();
+	int r = ensure();
+	if (r)
+		return r;
+	if (!result || (kind != (int)hd::CHECK_CRC32 && kind != (int)hd::CHECK_ADLER32) || n > STREAM_MAX_PARTS || (n && (!check || !len)))
+		return HD_E_ARG;
+	hipStream_t st = (hipStream_t)stream;
+	const size_t ntiles = ((size_t)n + hd::SCAN_TILE - 1) / hd::SCAN_TILE;
+	std::lock_guard<std::mutex> lk(g.mu_index);
+	if (g.d_stream.reserve((8 + ntiles + (size_t)n) * 8))
+		return HD_E_NOMEM;
+	uint64_t *sum = (uint64_t *)g.d_stream.p, *tiles = sum + 8, *prefix = tiles + ntiles;
+	uint32_t *carry = (uint32_t *)(sum + 4);
+	HD_CHECK(hipMemsetD32Async((hipDeviceptr_t)carry, kind == (int)hd::CHECK_ADLER32 ? 1 : 0, 1, st));
+	if ((r = fold_launch((const uint32_t *)check, (const uint32_t *)len, n, (uint32_t)kind, tiles, prefix, sum, carry, st)))
+		return r;
+	HD_CHECK(hipMemcpyAsync(result, carry, 4, hipMemcpyDeviceToHost, st));
+	HD_CHECK(hipStreamSynchronize(st));
+	return 0;
+}
+
+int hipdeflate_stream_deflate_dev(const void *in, uint64_t nbytes, uint32_t chunk_bytes, int level, int frame, void *dst,
+				  uint64_t dst_cap, void *chunk_off, hipdeflate_stream_summary *summary, void *stream)
+{
+	Ctx &g = cur();
+	int r = ensure();
+	if (r)
+		return r;
+	if (!summary)
+		return HD_E_ARG;
+	memset(summary, 0, sizeof *summary);
+	if (!stream_frame_ok(frame) || !stream_chunk_ok(chunk_bytes) || ((uintptr_t)in & 15) || ((uintptr_t)dst & 15) || (nbytes && !in) ||
+	    (dst_cap && !dst) || (nbytes + chunk_bytes - 1) / chunk_bytes > STREAM_MAX_PARTS)
+		return HD_E_ARG;
+	const uint32_t nchunks = (uint32_t)((nbytes + chunk_bytes - 1) / chunk_bytes);
+	const uint32_t hdr = stream_hdr(frame), trl = stream_trl(frame);
+	const uint32_t kind = frame == HD_FRAME_ZLIB ? hd::CHECK_ADLER32 : hd::CHECK_CRC32;
+	const uint64_t slot = hipdeflate_bound(chunk_bytes, level);
+	// a window of chunks: its slots total at most HD_STREAM_WINDOW_BYTES
+	uint64_t W = g_test_stream_window ? g_test_stream_window : HD_STREAM_WINDOW_BYTES / slot;
+	W = W < 1 ? 1 : W > nchunks ? (nchunks ? nchunks : 1) : W;
+	if (!g_test_stream_window && nchunks)                          // windows of one size: no short one left over at the end
+		W = (nchunks + (nchunks + W - 1) / W - 1) / ((nchunks + W - 1) / W);
+	hipStream_t st = (hipStream_t)stream;
+	const size_t ntiles = (W + hd::SCAN_TILE - 1) / hd::SCAN_TILE;
+	std::lock_guard<std::mutex> lk(g.mu_index);
+	// sum[8] | scan tiles | in_off, own_off, prefix [W] | in_len, out_len, crc, adler, status [W]
+	if (g.d_stream.reserve((8 + ntiles + 3 * W) * 8 + 5 * W * 4) || (nchunks && g.d_stream_slots.reserve(W * slot + 16)))
+		return HD_E_NOMEM;
+	uint64_t *sum = (uint64_t *)g.d_stream.p, *tiles = sum + 8, *in_off = tiles + ntiles, *own_off = in_off + W, *prefix = own_off + W;
+	uint32_t *in_len = (uint32_t *)(prefix + W), *out_len = in_len + W, *crc = out_len + W, *adler = crc + W;
+	int32_t *status = (int32_t *)(adler + W);
+	uint8_t *slots = (uint8_t *)g.d_stream_slots.p;
+	// sum[]: 0 the window's bytes out | 1 its bytes in, 2..3 the fold's accumulators | 4 the running check (u32), the window's first bad chunk (u32)
+	uint32_t *carry = (uint32_t *)(sum + 4), *d_bad = carry + 1;
+	HD_CHECK(hipMemsetD32Async((hipDeviceptr_t)carry, kind == hd::CHECK_ADLER32 ? 1 : 0, 1, st));
+	uint64_t pos = hdr, bad_chunk = nchunks;
+	bool fits = true;
+	for (uint32_t c0 = 0; c0 < nchunks; c0 += (uint32_t)W) {
+		const uint32_t w = nchunks - c0 < W ? nchunks - c0 : (uint32_t)W, wgs = (w + 255) / 256;
+		hipLaunchKernelGGL(hd::k_stream_table, dim3(wgs), dim3(256), 0, st, c0, w, chunk_bytes, nbytes, in_off, in_len);
+		if ((r = batch_deflate_dev_impl(in, in_off, in_len, w, level, HD_FRAME_RAW_FLUSH, slots, slot, (uint32_t)slot, out_len, crc,
+						status, stream, 0)))
+			return r;
+		// every chunk's place in the stream, straight into the caller's table where there is one: the running total goes
+		// from window to window as the scan's base
+		uint64_t *dst_off = chunk_off ? (uint64_t *)chunk_off + c0 : own_off;
+		index_scan(out_len, w, tiles, dst_off, sum + 0, st, pos);
+		HD_CHECK(hipMemsetAsync(d_bad, 0xff, 4, st));
+		hipLaunchKernelGGL(hd::k_members_verify, dim3(wgs), dim3(256), 0, st, (const int32_t *)status, (const uint32_t *)out_len,
+				   (const uint32_t *)crc, (const uint32_t *)out_len, (const uint32_t *)crc, w, d_bad);     // (the status alone)
+		if (kind == hd::CHECK_ADLER32)
+			hipLaunchKernelGGL(hd::k_chunk_adler, dim3(w), dim3(64), 0, st, (const uint8_t *)in, (const uint64_t *)in_off,
+					   (const uint32_t *)in_len, (const uint32_t *)nullptr, w, adler);
+		if ((r = fold_launch(kind == hd::CHECK_ADLER32 ? adler : crc, in_len, w, kind, tiles, prefix, sum + 1, carry, st)))
+			return r;
+		uint64_t h[5];
+		HD_CHECK(hipMemcpyAsync(h, sum, 40, hipMemcpyDeviceToHost, st));
+		HD_CHECK(hipStreamSynchronize(st));
+		const uint32_t bad = (uint32_t)(h[4] >> 32);
+		if (bad != hd::IDX_NIL && bad_chunk == nchunks)
+			bad_chunk = (uint64_t)c0 + bad;
+		// the gather, the scan's base as the header and the windows in front: only while every byte of it has room
+		if (fits && pos + h[0] <= dst_cap)
+			hd::launch_compact(slots, slot, out_len, dst_off, w, (uint8_t *)dst, st);
+		else
+			fits = false;
+		pos += h[0];
+	}
+	const uint64_t need = pos + 2 + trl;
+	fits = fits && need <= dst_cap;
+	if (fits)
+		hipLaunchKernelGGL(hd::k_stream_ends, dim3(1), dim3(64), 0, st, (uint8_t *)dst, frame, pos, (const uint32_t *)carry,
+				   (uint32_t)nbytes, chunk_off ? (uint64_t *)chunk_off + nchunks : (uint64_t *)nullptr);
+	else if (chunk_off)
+		HD_CHECK(hipMemcpyAsync((uint64_t *)chunk_off + nchunks, &pos, 8, hipMemcpyHostToDevice, st));
+	HD_CHECK(hipGetLastError());
+	uint32_t check = 0;
+	HD_CHECK(hipMemcpyAsync(&check, carry, 4, hipMemcpyDeviceToHost, st));
+	HD_CHECK(hipStreamSynchronize(st));
+	summary->out_bytes = need;
+	summary->in_bytes = nbytes;
+	summary->bad_chunk = bad_chunk;
+	summary->nchunks = nchunks;
+	summary->check = check;
+	summary->status = bad_chunk != nchunks ? 2u : fits ? 0u : 3u;
+	return 0;
+}
+
+int hipdeflate_stream_inflate_dev(const void *strm, uint64_t nbytes, int frame, const void *chunk_off, uint32_t nchunks,
+				  uint32_t chunk_bytes, uint64_t out_bytes, void *out, uint64_t out_cap,
+				  hipdeflate_stream_summary *summary, void *stream)
+{
+	Ctx &g = cur();
+	int r = ensure();
+	if (r)
+		return r;
+	if (!summary)
+		return HD_E_ARG;
+	memset(summary, 0, sizeof *summary);
+	summary->nchunks = nchunks;
+	summary->bad_chunk = nchunks;
+	if (!stream_frame_ok(frame) || !stream_chunk_ok(chunk_bytes) || ((uintptr_t)strm & 15) || (nbytes && !strm) || !chunk_off ||
+	    nchunks >= STREAM_MAX_PARTS || (out_cap && !out))
+		return HD_E_ARG;
+	const uint32_t hdr = stream_hdr(frame), trl = stream_trl(frame);
+	const uint32_t kind = frame == HD_FRAME_ZLIB ? hd::CHECK_ADLER32 : hd::CHECK_CRC32;
+	// what nchunks and chunk_bytes allow, a stream long enough for its two ends: before any byte is looked at
+	if ((out_bytes + chunk_bytes - 1) / chunk_bytes != nchunks || nbytes < (uint64_t)hdr + 2 + trl) {
+		summary->status = 1;
+		return 0;
+	}
+	hipStream_t st = (hipStream_t)stream;
+	const size_t n = nchunks, ntiles = (n + hd::SCAN_TILE - 1) / hd::SCAN_TILE;
+	std::lock_guard<std::mutex> lk(g.mu_index);
+	// sum[8] | scan tiles | in_off, out_off, prefix [n] | in_len, out_size, out_len, check, status [n]
+	if (g.d_stream.reserve((8 + ntiles + 3 * n) * 8 + 5 * n * 4))
+		return HD_E_NOMEM;
+	uint64_t *sum = (uint64_t *)g.d_stream.p, *tiles = sum + 8, *in_off = tiles + ntiles, *out_off = in_off + n, *prefix = out_off + n;
+	uint32_t *in_len = (uint32_t *)(prefix + n), *out_size = in_len + n, *out_len = out_size + n, *chk = out_len + n;
+	int32_t *status = (int32_t *)(chk + n);
+	// sum[4..5] as u32: the folded check | the lowest table entry at fault | the trailer disagrees | the lowest bad chunk
+	uint32_t *carry = (uint32_t *)(sum + 4), *d_fault = carry + 1, *d_mismatch = carry + 2, *d_bad = carry + 3;
+	uint32_t h[4] = { 0, 0, 0, 0 };
+	HD_CHECK(hipMemsetAsync(sum, 0, 64, st));
+	HD_CHECK(hipMemsetD32Async((hipDeviceptr_t)carry, kind == hd::CHECK_ADLER32 ? 1 : 0, 1, st));
+	HD_CHECK(hipMemsetD32Async((hipDeviceptr_t)d_fault, (int)hd::IDX_NIL, 1, st));
+	HD_CHECK(hipMemsetD32Async((hipDeviceptr_t)d_bad, (int)hd::IDX_NIL, 1, st));
+	hipLaunchKernelGGL(hd::k_stream_check_table, dim3((nchunks + 1 + 255) / 256), dim3(256), 0, st, (const uint8_t *)strm, nbytes,
+			   (const uint64_t *)chunk_off, nchunks, chunk_bytes, out_bytes, frame, in_off, in_len, out_off, out_size, d_fault);
+	HD_CHECK(hipGetLastError());
+	HD_CHECK(hipMemcpyAsync(h, carry, 16, hipMemcpyDeviceToHost, st));
+	HD_CHECK(hipStreamSynchronize(st));
+	if (h[1] != hd::IDX_NIL) {
+		summary->status = 1;
+		summary->bad_chunk = h[1];
+		return 0;
+	}
+	if (out_cap < out_bytes) {
+		summary->status = 3;
+		return 0;
+	}
+	if (nchunks) {
+		if ((r = launch_inflate({ (const uint8_t *)strm, in_off, in_len, nchunks, (uint8_t *)out, out_off, out_size, out_len,
+					  kind == hd::CHECK_ADLER32 ? nullptr : chk, status, g.d_ct, hd::INF_FLUSHED }, st)))
+			return r;
+		if (kind == hd::CHECK_ADLER32)
+			hipLaunchKernelGGL(hd::k_chunk_adler, dim3(nchunks), dim3(64), 0, st, (const uint8_t *)out, (const uint64_t *)out_off,
+					   (const uint32_t *)out_len, (const uint32_t *)out_size, nchunks, chk);
+		hipLaunchKernelGGL(hd::k_members_verify, dim3((nchunks + 255) / 256), dim3(256), 0, st, (const int32_t *)status,
+				   (const uint32_t *)out_len, (const uint32_t *)chk, (const uint32_t *)out_size, (const uint32_t *)chk, nchunks,
+				   d_bad);                                                   // (status and length: the check is the fold's)
+	}
+	if ((r = fold_launch(chk, out_size, nchunks, kind, tiles, prefix, sum + 1, carry, st)))
+		return r;
+	hipLaunchKernelGGL(hd::k_stream_trailer, dim3(1), dim3(64), 0, st, (const uint8_t *)strm, nbytes, frame, out_bytes,
+			   (const uint32_t *)carry, d_mismatch);
+	HD_CHECK(hipGetLastError());
+	HD_CHECK(hipMemcpyAsync(h, carry, 16, hipMemcpyDeviceToHost, st));
+	HD_CHECK(hipStreamSynchronize(st));
+	summary->out_bytes = out_bytes;
+	summary->in_bytes = nbytes;
+	summary->check = h[0];
+	if (h[3] != hd::IDX_NIL) {
+		summary->status = 2;
+		summary->bad_chunk = h[3];
+	} else if (h[2]) {
+		summary->status = 2;
+	}
 	return 0;
 }
 
@@ -2287,6 +2528,35 @@ int hip_inflate(unsigned char *dest, size_t *destLen, const unsigned char *sourc
 int hip_inflate_flush(unsigned char *dest, size_t *destLen, const unsigned char *source, size_t sourceLen)
 {
 	return inflate_one(dest, destLen, source, sourceLen, hd::INF_FLUSHED);
+}
+
+int hip_deflate_stream(unsigned char *dest, size_t *destLen, const unsigned char *source, size_t sourceLen, int level, int frame,
+		       uint32_t chunk_bytes)
+{
+	Ctx &g = cur();
+	int r = ensure();
+	if (r)
+		return r;
+	if (!destLen || (*destLen && !dest) || (sourceLen && !source) || !stream_frame_ok(frame) || !stream_chunk_ok(chunk_bytes))
+		return HD_E_ARG;
+	std::lock_guard<std::mutex> lk(g.mu);
+	if ((r = bind_device(g)))
+		return r;
+	const uint64_t bound = hipdeflate_stream_bound(sourceLen, chunk_bytes, level, frame);
+	const uint64_t cap = *destLen < bound ? *destLen : bound;
+	if (g.d_in.reserve(up16(sourceLen) + 16) || g.d_packed.reserve(up16(cap) + 16))
+		return HD_E_NOMEM;
+	if (sourceLen)
+		HD_CHECK(hipMemcpyAsync(g.d_in.p, source, sourceLen, hipMemcpyHostToDevice, g.stream));
+	hipdeflate_stream_summary s;
+	if ((r = hipdeflate_stream_deflate_dev(g.d_in.p, sourceLen, chunk_bytes, level, frame, g.d_packed.p, cap, nullptr, &s, g.stream)))
+		return r;
+	g.stream_drained(g.stream);
+	if (s.status)
+		return 1;
+	HD_CHECK(hipMemcpy(dest, g.d_packed.p, s.out_bytes, hipMemcpyDeviceToHost));
+	*destLen = s.out_bytes;
+	return 0;
 }
 
 } // extern "C"

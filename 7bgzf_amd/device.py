@@ -166,6 +166,65 @@ def read_ranges(blob, begins, ends, kind=_pkg.RANGE_BYTES):
     return d.read_ranges(blob, begins, ends, kind)
 
 
+def deflate_stream_call(data, level, frame, chunk, dst, dst_cap, chunk_off):
+    """one hipdeflate_stream_deflate_dev: data a 16-byte aligned uint8 tensor, dst a 16-byte aligned uint8 tensor or None,
+    chunk_off an int64 tensor of nchunks + 1 entries or None -> StreamSummary"""
+    summary = _pkg.StreamSummary()
+    rc = _pkg.lib().hipdeflate_stream_deflate_dev(_ptr(data), data.numel(), chunk, level, frame, _ptr(dst), dst_cap,
+                                                  _ptr(chunk_off), ctypes.byref(summary), _stream())
+    _pkg._check(rc, "hipdeflate_stream_deflate_dev")
+    return summary
+
+
+def deflate_stream(data, level=6, frame=_pkg.FRAME_GZIP, chunk=1 << 16):
+    """uint8 tensor -> (stream, chunk_off, StreamSummary): ONE raw / zlib / gzip stream of the whole tensor, coded in
+    independent chunks of `chunk` bytes side by side.  The stream is allocated at hipdeflate_stream_bound and narrowed to
+    out_bytes; chunk_off (int64, nchunks + 1 entries) is the table inflate_stream wants."""
+    n = data.numel()
+    nchunks = (n + chunk - 1) // chunk
+    bound = int(_pkg.lib().hipdeflate_stream_bound(n, chunk, level, frame))
+    if bound == 0:
+        raise ValueError("chunk = %d: a multiple of 16 in [16, 64 MiB]" % chunk)
+    dst = torch.empty(bound, dtype=torch.uint8, device=data.device)
+    chunk_off = torch.zeros(nchunks + 1, dtype=torch.int64, device=data.device)
+    s = deflate_stream_call(data, level, frame, chunk, dst, bound, chunk_off)
+    if s.status:
+        raise _pkg.HipDeflateError("stream encode: status %d, chunk %d" % (s.status, s.bad_chunk))
+    return dst[:s.out_bytes], chunk_off, s
+
+
+def inflate_stream_call(stream, frame, chunk_off, nchunks, chunk, out_bytes, out, out_cap):
+    """one hipdeflate_stream_inflate_dev -> StreamSummary"""
+    summary = _pkg.StreamSummary()
+    rc = _pkg.lib().hipdeflate_stream_inflate_dev(_ptr(stream), stream.numel(), frame, _ptr(chunk_off), nchunks, chunk,
+                                                  out_bytes, _ptr(out), out_cap, ctypes.byref(summary), _stream())
+    _pkg._check(rc, "hipdeflate_stream_inflate_dev")
+    return summary
+
+
+def inflate_stream(stream, chunk_off, chunk, out_bytes, frame=_pkg.FRAME_GZIP):
+    """the inverse of deflate_stream: stream a 16-byte aligned uint8 tensor, chunk_off its table (int64 tensor or a
+    sequence of ints, nchunks + 1 entries) -> uint8 tensor of out_bytes; the chunks are inflated side by side and the
+    result is held to the trailer"""
+    chunk_off = _u64_tensor(chunk_off, stream.device)
+    out = torch.empty(out_bytes, dtype=torch.uint8, device=stream.device)
+    s = inflate_stream_call(stream, frame, chunk_off, chunk_off.numel() - 1, chunk, out_bytes, out, out_bytes)
+    if s.status:
+        why = {1: "not such a stream, or a bad table", 2: "a chunk or the check disagrees", 3: "room too small"}
+        raise _pkg.HipDeflateError("stream decode: %s (status %d, bad_chunk %d of %d)" % (why.get(s.status, "?"), s.status,
+                                                                                         s.bad_chunk, s.nchunks))
+    return out
+
+
+def check_combine(check, lens, kind=_pkg.CHECK_CRC32):
+    """the CRC-32 (kind 0) / Adler-32 (kind 1) of a concatenation from the checks and lengths of its parts: int32 device
+    tensors holding the bits of the u32 values -> int"""
+    result = ctypes.c_uint32()
+    rc = _pkg.lib().hipdeflate_check_combine_dev(_ptr(check), _ptr(lens), check.numel(), kind, ctypes.byref(result), _stream())
+    _pkg._check(rc, "hipdeflate_check_combine_dev")
+    return result.value
+
+
 def device_inflate(comp, in_off, in_len, out, out_off, out_cap, out_len, crc, status):
     nb = in_off.numel()
     rc = _pkg.lib().hipdeflate_batch_inflate_dev(_ptr(comp), _ptr(in_off), _ptr(in_len), nb, _ptr(out), _ptr(out_off),

@@ -330,6 +330,75 @@ int hipdeflate_read_ranges_dev(const void *blob,
 			       void *dst_off /* u64[nqueries] */, void *q_len /* u32[nqueries] */, void *q_status /* i32[nqueries] */,
 			       hipdeflate_range_summary *summary /* HOST */, void *stream);
 
+/* ---- one stream from a device buffer, coded in parallel chunks ----------------------
+ * Role of the single-stream writers of the reference: zlibstdio / zlibrawstdio (zlibrawstdio_compress.h:260-307), the IDAT
+ * of applet/7png.c:296-331, a .gz any tool reads with one inflate().  There one stream is one serial deflate ("one stream =
+ * no block parallelism"); here the buffer is cut into chunks of chunk_bytes, every chunk is coded as a block of its own by
+ * the batch kernels, and the stream is
+ *     header | chunk 0 .. chunk n-1 | 03 00 | trailer
+ *   header   none (HD_FRAME_RAW) | 78 da (HD_FRAME_ZLIB) | the ten bytes HD_FRAME_GZIP writes: 1f 8b 08 00 <mtime = 0> 02 00
+ *   chunk i  in exactly the bytes hipdeflate_batch_deflate_dev(..., HD_FRAME_RAW_FLUSH) gives block i: such chunks concatenate
+ *   trailer  none | Adler-32 big-endian | CRC-32, then nbytes mod 2^32, little-endian
+ * The CRC-32 / Adler-32 of the whole input is folded on the device from the chunks' own (zlib's crc32_combine /
+ * adler32_combine, all chunks at once).  Chunks are independent -- no window across a seam, pigz -i's trade; at levels 1..2 a
+ * chunk longer than HD_SEG_LIMIT is segmented inside as any block is.  nbytes == 0: no chunks, check 0 (CRC-32) / 1 (Adler-32).
+ * frame is HD_FRAME_RAW, HD_FRAME_ZLIB or HD_FRAME_GZIP (anything else, HD_FRAME_LATENCY included: HD_E_ARG); chunk_bytes a
+ * multiple of 16 in [16, 64 MiB]; in, dst and strm 16-byte aligned (else HD_E_ARG).  *summary (host memory): */
+typedef struct hipdeflate_stream_summary {
+	uint64_t out_bytes;   /* encode: bytes of the whole stream (status 3: bytes it needs); decode: bytes written to out */
+	uint64_t in_bytes;    /* encode: nbytes; decode: bytes of stream consumed (trailer included) */
+	uint64_t bad_chunk;   /* status 1/2: lowest chunk at fault; nchunks if it is the whole-stream check, header or terminator */
+	uint32_t nchunks;
+	uint32_t check;       /* CRC-32 (RAW, GZIP) or Adler-32 (ZLIB) of the whole uncompressed data */
+	uint32_t status;      /* 0 ok | 1 not such a stream / bad table | 2 a chunk or the check disagrees | 3 room too small */
+} hipdeflate_stream_summary;
+/* Bytes of dst that always suffice (0 for a chunk_bytes that is refused). */
+uint64_t hipdeflate_stream_bound(uint64_t nbytes, uint32_t chunk_bytes, int level, int frame);
+/* The encoder.  chunk_off (device, u64[nchunks + 1], may be NULL): chunk_off[i] = the stream offset of chunk i,
+ * chunk_off[nchunks] = the offset of the 03 00 -- the table the decoder below wants, a dictzip RA table for a plain stream.
+ * Scratch is the library's: the slots, hipdeflate_bound(chunk_bytes, level) each, of one WINDOW of chunks -- at most
+ * HD_STREAM_WINDOW_BYTES (hipdeflate_params.h) of them, so the scratch does not grow with the input; the stream offset and
+ * the check run on from window to window.  Room: dst_cap below the need gives status 3 with out_bytes = the need -- every
+ * window is still coded to learn it, so dst == NULL with dst_cap == 0 is the sizing call -- and no byte at or behind dst +
+ * dst_cap is written (what is in front of it is unspecified then); hipdeflate_stream_bound always suffices.  Status 2 (a
+ * chunk the batch encoder refused; bad_chunk names the lowest) does not happen with slots of the bound.  Returns 0 whenever
+ * the call ran (the verdict is summary->status), HD_E_* otherwise.  Calls take turns with one another, with
+ * hipdeflate_read_ranges_dev and with the index.  hipdeflate_stall_count() stays 0.  (Synchronises the stream, once a window.) */
+int hipdeflate_stream_deflate_dev(const void *in, uint64_t nbytes, uint32_t chunk_bytes, int level, int frame,
+				  void *dst, uint64_t dst_cap, void *chunk_off /* u64[nchunks + 1], may be NULL */,
+				  hipdeflate_stream_summary *summary /* HOST */, void *stream);
+/* The inverse -- the device-resident form of what a dictzip reader does with its RA table (applet/7dictzip.c:318-323): given
+ * the table, the chunks are inflated side by side, chunk i by the flush-rule batch inflate into out + i * chunk_bytes with
+ * exactly its size as room, and the result is held to the trailer.  Streams of other writers qualify if they are cut the
+ * same way (zlib: Z_FULL_FLUSH behind every chunk_bytes of input, then Z_FINISH with no input left).
+ *   status 1  out_bytes is not what nchunks and chunk_bytes allow (nchunks = ceil(out_bytes / chunk_bytes)); nbytes is too
+ *             short for header, 03 00 and trailer; chunk_off does not ascend strictly inside [header, nbytes - 2 - trailer];
+ *             a chunk of HD_INFLATE_MAX_IN bytes or more; chunk_off[nchunks] is not nbytes - 2 - trailer or the bytes there
+ *             are not 03 00; the header is not one (ZLIB: CM 8, window <= 32 KiB, no dictionary, FCHECK; GZIP: 1f 8b 08 and
+ *             FLG 0).  bad_chunk = the lowest entry of chunk_off at fault, nchunks for its last entry, the header and the
+ *             lengths.  Nothing is inflated.
+ *   status 3  out_cap < out_bytes.  Nothing is inflated.  (Status 1 comes first.)
+ *   status 2  bad_chunk = i: chunk i's inflate status is non-zero or its length is wrong (check is unspecified then);
+ *             bad_chunk = nchunks: every chunk is fine but the folded check, or the gzip ISIZE, disagrees with the trailer.
+ *             HD_FRAME_RAW has no trailer to disagree with.
+ * With status 0 and 2 out_bytes and in_bytes are the arguments', with 1 and 3 they are 0.  The kernels bound every read by
+ * nbytes whatever the table says.  chunk_off holds nchunks + 1 entries.  Returns 0 whenever the call ran.  (Synchronises the
+ * stream; takes turns as the encoder does.) */
+int hipdeflate_stream_inflate_dev(const void *strm, uint64_t nbytes, int frame,
+				  const void *chunk_off, uint32_t nchunks, uint32_t chunk_bytes, uint64_t out_bytes,
+				  void *out, uint64_t out_cap, hipdeflate_stream_summary *summary /* HOST */, void *stream);
+/* the fold on its own: check[] / len[] device arrays of n parts (u32 each, n < 2^31), kind 0 = CRC-32, 1 = Adler-32; *result HOST.
+ * The check of the concatenation of the parts from the parts' own: the role of crc_append (the hosts' serial fold, after
+ * zlib's crc32_combine) with one lane per part -- part i contributes check[i] moved over the S_i bytes behind it, S_i a
+ * 64-bit suffix sum, so the parts may total anything below 2^64.  A part of length 0 is an identity whatever its check says;
+ * n == 0 gives 0 / 1.  (Synchronises the stream.) */
+int hipdeflate_check_combine_dev(const void *check, const void *len, uint32_t n, int kind, uint32_t *result, void *stream);
+/* host-buffer form of the encoder: stages through the device; *destLen in = room, out = bytes; 0, or 1 = does not fit */
+int hip_deflate_stream(unsigned char *dest, size_t *destLen, const unsigned char *source, size_t sourceLen,
+		       int level, int frame, uint32_t chunk_bytes);
+/* test entry: chunks per window of the encoder (0 restores the default) */
+void hipdeflate_test_stream_window(uint32_t chunks);
+
 /* ---- streaming encoder: the host pipeline either side of the kernels ------------
  * Role of the read / compress / write loop of applet/7bgzf.c:159-293 (7migz.c:130-244)
  * for a stream of fixed-size blocks (the last may be short).  `depth` batches are in

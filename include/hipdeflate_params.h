@@ -207,6 +207,10 @@
  * piece at a time, so that one range of gigabytes spreads over the chip like thousands of small ones */
 #define HD_RANGE_PIECE     (256u << 10)
 
+/* hipdeflate_stream_deflate_dev: the input is coded in windows of chunks whose slots -- hipdeflate_bound(chunk_bytes,
+ * level) each -- total at most this much, so that the scratch of the call does not grow with the input */
+#define HD_STREAM_WINDOW_BYTES (1u << 30)
+
 /* result codes of the inflate path = enum libdeflate_result
  * (lib/libdeflate/libdeflate.h:193-208), which libdeflate_inflate
  * (lib/zlibutil.c:194-204) hands straight back to the applet */
