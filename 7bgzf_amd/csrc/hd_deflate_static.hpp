@@ -437,6 +437,8 @@ __global__ __launch_bounds__(64) void k_deflate_static(DeflateArgs a)
 
 	Fn8Ident fid;
 	fid.init(lane);
+	Fn8Cross fcross;                     // the cross-row stages' identity registers: read by fn8_scan_state0 alone
+	fcross.init(lane);
 	HashConsts hk;
 	hk.init(HS);
 	CrcLanes crc;
@@ -828,10 +830,12 @@ __global__ __launch_bounds__(64) void k_deflate_static(DeflateArgs a)
 			Fn8 f;
 			f.lo = sel(livem, jumpA + 0x0200ffffu, 0x03020100u);
 			f.hi = sel(livem, 0x06050403u, 0x07060504u);
-			const Fn8 w = fn8_scan(f, fid);
-			// state entering lane l = (f_{l-1} o ... o f_0)(0): byte 0 of lane l-1 (0 enters lane 0)
-			const uint32_t sin = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)w.lo, 0x138 /* wave_shr:1 */, 0xf, 0xf, true);
-			starts = __ballot((sin & 0xff) == 0) & livem;
+			const uint32_t w0 = fn8_scan_state0(f, fid, fcross);
+			// state entering lane l = (f_{l-1} o ... o f_0)(0): byte 0 of lane l-1, and 0 enters lane 0 -- the mask of
+			// "a state other than 0 behind the lane", one lane up, in scalar registers: the shift brings in the 0 that
+			// lane 0 wants, and the NOT is the s_andn2 that applies livem (a wave_shr:1 of the bytes in front of the
+			// compare is a vector instruction and two wait states)
+			starts = livem & ~(__ballot((w0 & 0xff) != 0) << 1);
 		}
 		// Capped matches the scan took: extend each (left to right) to its true
 		// length, drop the token starts it now covers, and re-thread the chain
@@ -1017,16 +1021,20 @@ __global__ __launch_bounds__(64) void k_deflate_static(DeflateArgs a)
 		// != 0: carry < lanes, and the first start is real -- so level 1 takes the bare s_flbit_i32_b64 (__clzll also answers
 		// for 0: an s_min_u32 ..., 64 behind it in every step)
 		const uint64_t real = starts & ~v;
-		const uint32_t last = 63 - (uint32_t)(K16 ? __clzll((long long)real) : __builtin_clzll(real));
-		const uint32_t E = last + readlane(lenv, last);
+		// Level 1: last - 64 = ~clz (63 - clz - 64), and v_readlane_b32 takes the low six bits of its lane select, which
+		// are last's: E - 64 comes out of the add, and the carry is ONE signed max below
+		const uint32_t last = K16 ? 63 - (uint32_t)__clzll((long long)real) : ~(uint32_t)__builtin_clzll(real);
+		const uint32_t E = last + readlane(lenv, last);              // K16: the end of the last token; level 1: that - 64
 		const uint64_t tm = starts & lanem & ~v;           // tokens: matches + literals inside the block
 		const uint64_t mm = tm & okm;                      // matches
 		// max(E, 64) - 64 in scalar registers (written in C the compiler makes a v_sub ... clamp + v_readfirstlane of
 		// it); tail step: matches are clipped to n
-		if (INNER || lanes == 64)
+		if (!(INNER || lanes == 64))
+			carry = 0;
+		else if (K16)
 			asm("s_max_u32 %0, %1, 64\n\ts_sub_u32 %0, %0, 64" : "=s"(carry) : "s"(E) : "scc");
 		else
-			carry = 0;
+			asm("s_max_i32 %0, %1, 0" : "=s"(carry) : "s"(E) : "scc");
 
 		// ---- 5. queue the step's tokens in position order -------------------
 		// token word: literal byte, or HD_TOKEN_MATCH_TAG | (len - 3) << 16 | (dist - 1), dist - 1 = p - c.

@@ -112,18 +112,19 @@ struct Fn8 {
 };
 
 // Lanes that a DPP stage leaves without a source must see the identity map
-// {0,1,2,3 | 4,5,6,7}.  The shifted value is read with "0 where there is no
-// source" and OR-ed with a per-lane constant that is the identity exactly on
-// those lanes: mov_dpp + or fold into one v_or_b32_dpp, where seeding the
-// destination with the identity would cost an extra v_mov per dword and stage.
+// {0,1,2,3 | 4,5,6,7}.  In the four stages inside a row the shifted value is
+// read with "0 where there is no source" and OR-ed with a per-lane constant
+// that is the identity exactly on those lanes: mov_dpp + or fold into one
+// v_or_b32_dpp, where seeding the destination with the identity would cost an
+// extra v_mov per dword and stage.
 struct Fn8Ident {
-	uint32_t lo[6], hi[6];          // per scan stage
+	uint32_t lo[4], hi[4];          // per in-row scan stage
 	__device__ __forceinline__ void init(uint32_t lane)
 	{
 		const uint32_t r = lane & 15;
-		const bool none[6] = { r < 1, r < 2, r < 4, r < 8, !((lane >> 4) & 1), lane < 32 };
+		const bool none[4] = { r < 1, r < 2, r < 4, r < 8 };
 #pragma unroll
-		for (int k = 0; k < 6; k++) {
+		for (int k = 0; k < 4; k++) {
 			lo[k] = none[k] ? 0x03020100u : 0u;
 			hi[k] = none[k] ? 0x07060504u : 0u;
 		}
@@ -148,20 +149,61 @@ __device__ __forceinline__ Fn8 fn8_compose(Fn8 then, Fn8 first)
 	return r;
 }
 
-// inclusive scan: result at lane l = f_l o ... o f_0
-__device__ __forceinline__ Fn8 fn8_scan(Fn8 w, const Fn8Ident &id)
+// The two stages across the rows (row_bcast:15 into rows 1 and 3, row_bcast:31 into rows 2 and 3) have no seed and no OR.
+// A DPP instruction with a row mask leaves the masked-off rows of its destination alone, and those are exactly the rows
+// that need the identity (every lane of an enabled row has a source).  Written as v_or_b32_dpp like the stages above, the
+// compiler copies the identity constant into the destination first: one v_mov_b32 per dword, stage and step.  Here the
+// destination IS the register that holds the constant: `v_mov_b32_dpp idreg, w row_bcast:15 row_mask:0xa` writes rows 1
+// and 3 of idreg and never touches rows 0 and 2, which hold the identity from init() on, for ever.  Rows 1 and 3 hold
+// whatever the last scan left there and are written again before the v_perm_b32 behind the move reads them.
+// The compiler is told that the register is an INPUT of the statement.  Told the truth ("+v"), it keeps a copy of all
+// three wherever a path that ran no scan meets one that did -- more moves than the seeds were, and four registers, the
+// sixth wavefront of a SIMD.  The lie is sound only while the statement in fn8_scan_state0 is the registers' ONLY reader:
+// a reader that wants 0 on the rows the stage writes would find scan leftovers there.  So the three live in a struct of
+// their own that nothing else takes, and init() hides from the compiler how they were made: it can neither share one
+// with a value it knows to be equal nor make one again from its definition, and a copy, a spill or a reload of one
+// carries the rows that matter unchanged.  The statement needs EXEC = all lanes, as every DPP scan here does.
+struct Fn8Cross {
+	uint32_t lo15, hi15, lo31;      // the identity on the rows their stage masks off; the other rows: anything
+	__device__ __forceinline__ void init(uint32_t lane)
+	{
+		lo15 = (lane & 16) ? 0u : 0x03020100u;
+		hi15 = (lane & 16) ? 0u : 0x07060504u;
+		lo31 = lane < 32 ? 0x03020100u : 0u;
+		asm volatile("" : "+v"(lo15), "+v"(hi15), "+v"(lo31));
+	}
+};
+
+// inclusive scan for a caller that reads only byte 0 of the composed map: byte 0 of the result at lane l is
+// (f_l o ... o f_0)(0), the state BEHIND lane l; the other bytes mean nothing
+// Wait states: a DPP instruction that reads a VGPR the vector instruction in front of it wrote needs two, and inside an
+// asm statement the compiler adds none: s_nop 1 stands in front of the first stage's moves (the v_perm_b32 that wrote
+// their source may be the instruction straight in front of the statement), and the second stage's source has one
+// v_perm_b32 behind its writer, so s_nop 0 completes its two.  v_perm_b32 reading the moved register needs none.
+// (One statement for both stages: the compiler pads the end of every statement with a wait state of its own.)
+__device__ __forceinline__ uint32_t fn8_scan_state0(Fn8 w, const Fn8Ident &id, const Fn8Cross &x)
 {
 	w = fn8_compose(w, fn8_dpp<0x111, 0xf>(w, id.lo[0], id.hi[0]));   // row_shr:1
 	w = fn8_compose(w, fn8_dpp<0x112, 0xf>(w, id.lo[1], id.hi[1]));   // row_shr:2
 	w = fn8_compose(w, fn8_dpp<0x114, 0xf>(w, id.lo[2], id.hi[2]));   // row_shr:4
 	w = fn8_compose(w, fn8_dpp<0x118, 0xf>(w, id.lo[3], id.hi[3]));   // row_shr:8
-	w = fn8_compose(w, fn8_dpp<0x142, 0xa>(w, id.lo[4], id.hi[4]));   // row_bcast:15 -> rows 1,3
-	w = fn8_compose(w, fn8_dpp<0x143, 0xc>(w, id.lo[5], id.hi[5]));   // row_bcast:31 -> rows 2,3
-	return w;
+	// r = w o (w of lane 15 of the row below; rows 0, 2: identity); out = low dword of r o (r of lane 31; rows 0, 1: identity)
+	uint32_t rl, rh, out;
+	asm("s_nop 1\n\t"
+	    "v_mov_b32_dpp %[xl], %[wl] row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"
+	    "v_mov_b32_dpp %[xh], %[wh] row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"
+	    "v_perm_b32 %[rl], %[wh], %[wl], %[xl]\n\t"
+	    "v_perm_b32 %[rh], %[wh], %[wl], %[xh]\n\t"
+	    "s_nop 0\n\t"
+	    "v_mov_b32_dpp %[xm], %[rl] row_bcast:31 row_mask:0xc bank_mask:0xf\n\t"
+	    "v_perm_b32 %[out], %[rh], %[rl], %[xm]"
+	    : [rl] "=&v"(rl), [rh] "=&v"(rh), [out] "=&v"(out)
+	    : [xl] "v"(x.lo15), [xh] "v"(x.hi15), [xm] "v"(x.lo31), [wl] "v"(w.lo), [wh] "v"(w.hi));
+	return out;
 }
 
-// the same scan with the identity seeded by v_mov instead of the 12 registers
-// of Fn8Ident (the dynamic-level kernels sit at their VGPR budget)
+// the whole map (all eight bytes), with the identity seeded by v_mov instead of the registers
+// of Fn8Ident and Fn8Cross (the dynamic-level kernels sit at their VGPR budget)
 template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ Fn8 fn8_dpp_seeded(Fn8 v)
 {

@@ -1,12 +1,16 @@
 #!/usr/bin/env python3
 """Static instruction counts of the level-1 kernel's 16-step group loop, per 64-byte step and by phase.
 
-  python3 tools/valu_by_phase.py > profiles/r09_l1_valu_by_phase.json
+  python3 tools/valu_by_phase.py > profiles/r11_l1_valu_by_phase.json
 
 hipcc -S -gline-tables-only gives every instruction its source line; the lines are mapped to the phases of
 7bgzf_amd/csrc/hd_deflate_static.hpp (fetch / probe / verify / scan / long matches / queue / emit / refill + CRC).
 The loop body holds four unrolled INNER steps; phases that do not run in every step carry their measured frequency
-on the FASTQ-like set (the token queue drains once per ~4.6 steps, the refill runs once per 16)."""
+on the FASTQ-like set (the token queue drains once per ~4.6 steps, the refill runs once per 16).
+
+Beside the counts every phase carries its vector-pipe cycles, "valu_cycles": each vector instruction priced by the rate table
+measured on the device (profiles/r03_valu_rates.json, price() below).  The kernel's vector pipe is about nine tenths busy
+(DESIGN.md 6e), so the cycles, not the count, are what an instruction on the always-run path costs."""
 import collections
 import json
 import os
@@ -17,6 +21,33 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "7bgzf_amd", "csrc")
+
+
+FAST = {"v_add_u32", "v_sub_u32", "v_subrev_u32", "v_and_b32", "v_or_b32", "v_xor_b32", "v_not_b32", "v_mov_b32", "v_lshrrev_b32",
+        "v_add_u16", "v_fma_f32", "v_mul_f32"}
+
+
+def price(t):
+    """SIMD cycles of one wave64 vector instruction, from the reading of profiles/r03_valu_rates.json (>= 2 waves per SIMD):
+    2.3 VOP1/VOP2 of the FAST set on VGPR / inline-constant sources, 2.6 with a 32-bit literal or in the VOP3 encoding,
+    8.3 v_readlane with an SGPR lane select and v_swap, 4.2 everything else (v_perm, DPP, SDWA, v_cndmask, v_cmp, VOP3
+    arithmetic, v_lshlrev, any SGPR source ...)"""
+    op, _, rest = t.partition(" ")
+    args = [a.strip() for a in rest.split(",")]
+    if op == "v_swap_b32" or (op == "v_readlane_b32" and re.match(r"(s\d+|m0)$", args[-1].split()[0])):
+        return 8.3
+    base = re.sub(r"_(e32|e64)$", "", op)
+    if base not in FAST or "row_" in t or "wave_" in t or "sel:" in t or "quad_perm" in t:
+        return 4.2
+    srcs = args[1:]
+    if any(re.match(r"(s\d+|s\[|vcc|exec|m0|ttmp)", a) for a in srcs):
+        return 4.2
+    lit = False
+    for a in srcs:
+        if re.match(r"-?(0x[0-9a-f]+|\d+)$", a):
+            v = int(a, 0)
+            lit = lit or not (-16 <= v <= 64)
+    return 2.6 if lit or op.endswith("_e64") else 2.3
 
 
 def main():
@@ -76,6 +107,7 @@ def main():
             return ph or last                      # sel(), dpp0(): the caller's phase
         return last
     cnt = collections.defaultdict(collections.Counter)
+    cyc = collections.Counter()
     loc, last = (0, 0), P_LOOP
     for i in range(start, end + 1):
         t = lines[i].strip()
@@ -92,20 +124,25 @@ def main():
                 "nop_waitcnt" if op.startswith("s_waitcnt") or op == "s_nop" else "salu" if op.startswith("s_") else "other")
         last = phase(loc, last)
         cnt[last][kind] += 1
+        if kind == "valu":
+            cyc[last] += price(t.split(";")[0].strip())
     steps = 4
     freq = {P_CODES: 1 / 4.6, P_PUT: 1 / 4.6, P_PSUM: 1 / 4.6, P_FLUSH: 1 / 18.4, P_FILL: 0.0, P_LONG: None}
     out = {"kernel": "k_deflate_static<12,11,false>",
            "what": "static instruction counts of the 16-step group loop body (4 unrolled INNER steps), per step, by phase "
                    "(tools/valu_by_phase.py: hipcc -S -gline-tables-only line tables).  runs_per_step: how often the phase's code "
-                   "runs on the FASTQ-like set (the refill sits outside this loop body: once per 16 steps, ~60 VALU).",
+                   "runs on the FASTQ-like set (the refill sits outside this loop body: once per 16 steps, ~60 VALU).  valu_cycles: the phase's "
+                   "vector instructions priced in SIMD cycles by profiles/r03_valu_rates.json (2.3 plain VOP1/VOP2 on VGPRs, 2.6 with a literal, "
+                   "8.3 v_readlane with an SGPR lane, 4.2 everything else).",
            "per_step_static": {}}
     tot, wtot = collections.Counter(), collections.Counter()
     for ph, c in sorted(cnt.items(), key=lambda kv: -kv[1]["valu"]):
         d = {k: round(v / steps, 1) for k, v in sorted(c.items())}
         f = freq.get(ph, 1.0)
+        d["valu_cycles"] = round(cyc[ph] / steps, 1)
         d["runs_per_step"] = "once per long match the parse takes" if f is None else round(f, 3)
         out["per_step_static"][ph] = d
-        for k, v in c.items():
+        for k, v in list(c.items()) + [("valu_cycles", cyc[ph])]:
             tot[k] += v / steps
             if f:
                 wtot[k] += v / steps * f
@@ -113,10 +150,10 @@ def main():
                               "asm statement and are counted in the phase above, with the step's entry test and the loop the compiler keeps round the "
                               "block (s_cmp_lg_u64 + branch).  Run: 1.42 events per step on the FASTQ-like set (twin count), 1.14 hops of the walk per event; "
                               "measured as the PMC figures per step minus the weighted sum of the other phases")
-    out["measured_pmc_per_step"] = ("this kernel (profiles/r09_l1_ab_parent_vs_new.txt; tools/pmc_quick.sh, one counter pass per run, no tracing beside it): "
-                                    "VALU 93.91, SALU 60.32, branch 14.91, LDS 10.83; wave cycles 506.8 (x4 clocks), busy 13.3; an instruction issues in "
-                                    "37.0 % of the wave cycles, the wavefront waits on one in 32.6 %.  "
-                                    "The parent commit in the same way: VALU 95.10, SALU 66.50, branch 17.08, LDS 10.83, wave cycles 529.7, 37.5 % / 31.3 %")
+    out["measured_pmc_per_step"] = ("the parent of this kernel (profiles/r11_l1_pipe_busy_before.json; tools/pmc_quick.sh, one counter pass per run, no tracing beside it): "
+                                    "VALU 93.91, SALU 60.32, branch 14.91, LDS 10.83; wave cycles 506.3 (x4 clocks); vector pipe active 96.59 quad-cycles per step = "
+                                    "91 % of the kernel's cycles per SIMD, scalar pipe 60.33 = 57 %.  The build with items 2a and 2c on top of this kernel (DESIGN.md 6e), in the same way: VALU 88.94, SALU 59.67, "
+                                    "branch 14.91, LDS 10.83, wave cycles 495.6")
     out["sum_static_all_paths_per_step"] = {k: round(v, 1) for k, v in sorted(tot.items())}
     out["sum_weighted_by_frequency_per_step"] = {k: round(v, 1) for k, v in sorted(wtot.items())}
     json.dump(out, sys.stdout, indent=1)
