@@ -30,122 +30,84 @@
  *    in a batch on the device has joined, nobody has joined for HIPDEFLATE_LINGER_US
  *    (8) or HIPDEFLATE_BATCH_US microseconds (default 60) have passed, launches, and
  *    publishes the result; the others spin on the batch's state (HIPDEFLATE_SPIN_US,
- *    default 400, then they sleep on that word; with more callers than cores they sleep at once).  HOOK_CTX batches can be in flight at once (one
+ *    default 400, then they sleep on that word; with more callers than cores they sleep at once).  HD_CB_CTX batches can be in flight at once (one
  *    collecting, the others on the device).  A lone caller does not wait at all.
+ *    That protocol and its policy are hd_call_batch.c's; this file is its client.
  */
 #define _GNU_SOURCE
-#include <errno.h>
+#include <limits.h>
 #include <pthread.h>
 #include <sched.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <strings.h>
-#include <time.h>
 #include <unistd.h>
-#include <limits.h>
-#include <linux/futex.h>
-#include <sys/syscall.h>
 #include "hipdeflate.h"
 #include "hipdeflate_params.h"
+#include "hd_call_batch.h"
 
 #define HOOK_MAX_BATCH 256
-#define HOOK_CTX 8
 #define HOOK_BLOCK 0xff00u           /* what a latency-mode BGZF slot takes (16 x 4080); htslib's BGZF_BLOCK_SIZE */
 
-struct hook_batch {
-	hipdeflate_lat *lat;
-	int sleepers;                /* members of THIS batch asleep on `state` (futex) */
-	/* state: 0 free, 1 collecting, 2 closed (copies in flight / on the device), 3 done.  Changed under g_mu
-	 * (0 -> 1 -> 2, 3 -> 0) or by the batch's leader (2 -> 3); read with acquire loads by spinning members */
-	int state;
-	int n;                       /* blocks reserved (under g_mu while collecting, fixed afterwards) */
-	int ready, taken;            /* blocks copied in / members copied out (atomic counters) */
-	int rc;
-	uint32_t len[HOOK_MAX_BATCH];
-};
+/* HIPDEFLATE_HOOK_STATS=1: where the time of a call goes, printed at exit (tools/hook_bench.c reads it) */
+static struct hd_cb_stats g_st;
 
 /* One ENGINE per (level, frame): the hook's (BGZF members at BGZF_METHOD's level) and, since round 4, one per level and raw
  * frame for the per-block codecs -- hip_deflate / hip_deflate_flush called from the reference's -@N threads
  * (applet/7bgzf.c:211) share launches exactly as htslib's workers do in the hook (16 callers: 3.8 -> 8.6 GB/s at level 1,
- * and 64 callers no longer collapse to 1.2). */
+ * and 64 callers no longer collapse to 1.2).  The batching itself is hd_call_batch.c's, under its compress policy; what a
+ * batch owns here is a latency context: input slot idx, hipdeflate_lat_run, output slot idx. */
 struct hook_eng {
-	pthread_mutex_t mu;
-	pthread_cond_t cv_free;      /* a context became free */
-	struct hook_batch batch[HOOK_CTX];
-	int open;                    /* the batch that is collecting, -1 = none */
-	int active;                  /* callers inside the engine right now (atomic) */
-	int running;                 /* blocks of the batches that are closed and not yet done (under mu) */
-	int inflight;                /* under mu; read without by a leader in its window */
-	int64_t t_returned;          /* when the last batch came back from the device (atomic; 0 = none yet) */
-	int failed;
+	struct hd_cb cb;             /* (first: the client's functions get it back as their engine) */
+	hipdeflate_lat *lat[HD_CB_CTX];
+	uint32_t len[HD_CB_CTX][HOOK_MAX_BATCH];
 	int level, frame;            /* level: the hook's (BGZF_METHOD; a codec engine's is its index); frame: HD_FRAME_BGZF, HD_FRAME_RAW or HD_FRAME_RAW_FLUSH */
 	int loud;                    /* the hook prints codec errors as the reference does (bgzf_compress.c:163-169) */
 };
-#define HOOK_ENG_INIT(fr, ld) { .mu = PTHREAD_MUTEX_INITIALIZER, .cv_free = PTHREAD_COND_INITIALIZER, .open = -1, .level = 1, .frame = (fr), .loud = (ld) }
-static struct hook_eng g_hook = HOOK_ENG_INIT(HD_FRAME_BGZF, 1);
-static struct hook_eng g_codec[10][2] = { [0 ... 9] = { HOOK_ENG_INIT(HD_FRAME_RAW, 0), HOOK_ENG_INIT(HD_FRAME_RAW_FLUSH, 0) } };
+
+/* ---- the engine's client: a batch context is a latency context ----------------------------------------------------- */
+static int hook_open(struct hd_cb *cb, int k)
+{
+	struct hook_eng *e = (struct hook_eng *)cb;
+	/* batch context k lives on entry k of the device list (HIPDEFLATE_DEVICES), round robin */
+	const int ndev = hipdeflate_device_count();
+	e->lat[k] = hipdeflate_lat_open_on(ndev > 0 ? k % ndev : 0, e->level, e->frame | HD_FRAME_LATENCY, HOOK_MAX_BATCH, HOOK_BLOCK);
+	return e->lat[k] ? 0 : -1;                  /* coder missing: the engine fails for good */
+}
+
+static int hook_admit(struct hd_cb *cb, int k, int idx, const void *slen)
+{
+	((struct hook_eng *)cb)->len[k][idx] = (uint32_t)*(const size_t *)slen;
+	return 1;                                   /* every block has its slot */
+}
+
+static int hook_run(struct hd_cb *cb, int k, int n)
+{
+	struct hook_eng *e = (struct hook_eng *)cb;
+	return hipdeflate_lat_run(e->lat[k], e->len[k], (uint32_t)n);
+}
+
+/* (no close: these engines keep their contexts as long as the process lives) */
+static const struct hd_cb_client g_hook_client = { .open = hook_open, .admit = hook_admit, .run = hook_run };
+
+#define HOOK_ENG_INIT(lv, fr, ld) { .cb = HD_CB_INIT(&g_hook_client, &hd_cb_deflate_policy, &g_st, HOOK_MAX_BATCH), .level = (lv), .frame = (fr), .loud = (ld) }
+#define CODEC_ENGS(lv) { HOOK_ENG_INIT(lv, HD_FRAME_RAW, 0), HOOK_ENG_INIT(lv, HD_FRAME_RAW_FLUSH, 0) }
+static struct hook_eng g_hook = HOOK_ENG_INIT(1, HD_FRAME_BGZF, 1);
+static struct hook_eng g_codec[10][2] = { CODEC_ENGS(0), CODEC_ENGS(1), CODEC_ENGS(2), CODEC_ENGS(3), CODEC_ENGS(4),
+					  CODEC_ENGS(5), CODEC_ENGS(6), CODEC_ENGS(7), CODEC_ENGS(8), CODEC_ENGS(9) };
 static pthread_once_t g_env_once = PTHREAD_ONCE_INIT, g_knobs_once = PTHREAD_ONCE_INIT;
-static long g_window_us = 60; /* a leader never waits longer than this for the batch to fill */
-static long g_linger_us = 8;  /* ... nor longer than this after the last caller joined */
-static long g_spin_us = 400;  /* a member spins this long for its batch before it sleeps */
-/* batches on the device at once.  Two run side by side at nearly the price of one at levels 1-2 (hipdeflate_lat_run on 8
- * blocks, level 2: 152 us alone, 173 us each for two), a third and fourth do not (266, 297 us each -- tools/hook_bench.c
- * HOOK_PAR): while two are out, the collecting batch stays open and grows.
- * Round 5: that is the limit for FULL batches (more callers than a batch holds).  A batch that is merely COMPLETE -- every
- * caller that is not on the device has joined -- waits while another is out (g_merge_inflight) and then for that batch's
- * callers to come back (g_rejoin_us): sixteen callers had settled into two groups of eight that took turns, each paying for
- * the other's launch (level 6: two batches of 8 side by side 227-240 us each, one of 16 alone 186: a call 280 -> 215 us) */
-static int g_max_inflight = 2;
-static int g_merge_inflight = 1;
-static int g_merge_callers = 16;  /* ... while at most this many callers are inside the engine; beyond, batches fill by themselves and
-                                   * two side by side win (64 callers, level 6: 403 us a call against 520 merged; 4 / 8 callers:
-                                   * 233 -> 191 / 224 -> 209 us; 16: 257 -> 250; tools/r05_hook_merge.sh, profiles/r05_hook_merge.txt) */
-static long g_rejoin_us = 30; /* after a batch has come back, the collecting one waits this long for the first of its callers */
-static int g_batch_target = HOOK_MAX_BATCH;
-static int g_ncpu = 1;
-/* HIPDEFLATE_HOOK_STATS=1: where the time of a call goes, printed at exit (ns sums; tools/hook_bench.c reads it) */
-static int g_stats;
-static int64_t st_calls, st_batches, st_blocks, st_copy_in, st_window, st_ready, st_run, st_member_wait, st_copy_out, st_ctx_wait;
 
 __attribute__((destructor)) static void hook_stats_print(void)
 {
-	if (!g_stats || !st_calls)
+	if (!g_st.on || !g_st.calls)
 		return;
 	fprintf(stderr, "hipdeflate hook (%d usable CPUs): %lld calls in %lld batches (%.1f blocks each); us per call: wait for a context %.1f, copy in %.1f, "
 		"copy out %.1f, member waits for its batch %.1f; us per batch: leader's window %.1f, others' copies %.1f, device %.1f\n",
-		g_ncpu, (long long)st_calls, (long long)st_batches, st_batches ? (double)st_blocks / st_batches : 0.0,
-		st_ctx_wait / 1e3 / st_calls, st_copy_in / 1e3 / st_calls, st_copy_out / 1e3 / st_calls,
-		st_member_wait / 1e3 / (st_calls - st_batches ? st_calls - st_batches : 1), st_window / 1e3 / (st_batches ? st_batches : 1),
-		st_ready / 1e3 / (st_batches ? st_batches : 1), st_run / 1e3 / (st_batches ? st_batches : 1));
-}
-#define ST_ADD(var, ns) do { if (g_stats) __atomic_add_fetch(&(var), (ns), __ATOMIC_RELAXED); } while (0)
-
-static inline int64_t now_ns(void)
-{
-	struct timespec ts;
-	clock_gettime(CLOCK_MONOTONIC, &ts);
-	return (int64_t)ts.tv_sec * 1000000000LL + ts.tv_nsec;
-}
-
-/* Members that have waited long enough sleep ON THE BATCH'S STATE WORD (futex): the leader's one FUTEX_WAKE releases
- * all of them at once.  (The condition variable of rounds 1-2 handed its waiters over one by one through its mutex --
- * microseconds each: with 64 callers on 16 cores, where members must sleep to leave the CPUs to the leaders, a 27-block
- * batch took 376 us instead of 115 and the CPU reference won that case, 6.24 GB/s against 4.27.) */
-static inline void state_sleep(int *state, int seen)
-{
-	syscall(SYS_futex, state, FUTEX_WAIT_PRIVATE, seen, NULL, NULL, 0);
-}
-static inline void state_wake_all(int *state)
-{
-	syscall(SYS_futex, state, FUTEX_WAKE_PRIVATE, INT_MAX, NULL, NULL, 0);
-}
-
-static inline void cpu_relax(void)
-{
-#if defined(__x86_64__) || defined(__i386__)
-	__builtin_ia32_pause();
-#endif
+		hd_cb_deflate.ncpu, (long long)g_st.calls, (long long)g_st.batches, g_st.batches ? (double)g_st.blocks / g_st.batches : 0.0,
+		g_st.ctx_wait / 1e3 / g_st.calls, g_st.copy_in / 1e3 / g_st.calls, g_st.copy_out / 1e3 / g_st.calls,
+		g_st.member_wait / 1e3 / (g_st.calls - g_st.batches ? g_st.calls - g_st.batches : 1), g_st.window / 1e3 / (g_st.batches ? g_st.batches : 1),
+		g_st.ready / 1e3 / (g_st.batches ? g_st.batches : 1), g_st.run / 1e3 / (g_st.batches ? g_st.batches : 1));
 }
 
 /* CPUs this process may really use: the affinity mask, cut by the cgroup's CPU quota (a container on a 128-core host
@@ -229,42 +191,32 @@ static void parse_env(void)
 
 /* the batcher's knobs: read once, by whichever engine runs first (the hook's method above only when the HOOK is first called:
  * a process may have used the codecs long before it sets BGZF_METHOD) */
+static long knob(const char *name, long deflt, long least)       /* the variable's value where it is set, not empty and >= least */
+{
+	const char *v = getenv(name);
+	return v && *v && atol(v) >= least ? atol(v) : deflt;
+}
+
 static void parse_knobs(void)
 {
-	const char *w = getenv("HIPDEFLATE_BATCH_US");
-	if (w && *w)
-		g_window_us = atol(w);
-	g_ncpu = usable_cpus();
-	const char *lg = getenv("HIPDEFLATE_LINGER_US");
-	if (lg && *lg)
-		g_linger_us = atol(lg);
+	struct hd_cb_deflate_knobs *const g = &hd_cb_deflate;
+	g->window_us = knob("HIPDEFLATE_BATCH_US", g->window_us, LONG_MIN);
+	g->ncpu = usable_cpus();
+	g->linger_us = knob("HIPDEFLATE_LINGER_US", g->linger_us, LONG_MIN);
 	const char *hs = getenv("HIPDEFLATE_HOOK_STATS");
-	g_stats = hs && *hs && *hs != '0';
-	const char *fl = getenv("HIPDEFLATE_INFLIGHT");
-	if (fl && atoi(fl) >= 1)
-		g_max_inflight = atoi(fl);
-	const char *mg = getenv("HIPDEFLATE_MERGE_INFLIGHT");
-	if (mg && atoi(mg) >= 1)
-		g_merge_inflight = atoi(mg);
-	if (g_merge_inflight > g_max_inflight)
-		g_merge_inflight = g_max_inflight;
-	const char *mc = getenv("HIPDEFLATE_MERGE_CALLERS");
-	if (mc && *mc)
-		g_merge_callers = atoi(mc);
-	const char *rj = getenv("HIPDEFLATE_REJOIN_US");
-	if (rj && *rj)
-		g_rejoin_us = atol(rj);
-	const char *sp = getenv("HIPDEFLATE_SPIN_US");
-	if (sp && *sp)
-		g_spin_us = atol(sp);
-	const char *t = getenv("HIPDEFLATE_BATCH_BLOCKS");
-	if (t && *t) {
-		g_batch_target = atoi(t);
-		if (g_batch_target < 1)
-			g_batch_target = 1;
-		if (g_batch_target > HOOK_MAX_BATCH)
-			g_batch_target = HOOK_MAX_BATCH;
-	}
+	g_st.on = hs && *hs && *hs != '0';
+	g->max_inflight = (int)knob("HIPDEFLATE_INFLIGHT", g->max_inflight, 1);
+	g->merge_inflight = (int)knob("HIPDEFLATE_MERGE_INFLIGHT", g->merge_inflight, 1);
+	if (g->merge_inflight > g->max_inflight)
+		g->merge_inflight = g->max_inflight;
+	g->merge_callers = (int)knob("HIPDEFLATE_MERGE_CALLERS", g->merge_callers, LONG_MIN);
+	g->rejoin_us = knob("HIPDEFLATE_REJOIN_US", g->rejoin_us, LONG_MIN);
+	g->spin_us = knob("HIPDEFLATE_SPIN_US", g->spin_us, LONG_MIN);
+	g->batch_target = (int)knob("HIPDEFLATE_BATCH_BLOCKS", HOOK_MAX_BATCH, LONG_MIN);
+	if (g->batch_target < 1)
+		g->batch_target = 1;
+	if (g->batch_target > HOOK_MAX_BATCH)
+		g->batch_target = HOOK_MAX_BATCH;
 }
 
 /* a block the latency slots do not take (longer than 0xff00 bytes: not from htslib): one ordinary call */
@@ -289,7 +241,31 @@ static int code_alone(void *dst, size_t *dlen, const void *src, size_t slen)
 	return ret;
 }
 
-static int eng_compress(struct hook_eng *e, int level, void *_dst, size_t *_dlen, const void *src, size_t slen);
+static int hook_call(struct hook_eng *e, void *_dst, size_t *_dlen, const void *src, size_t slen)
+{
+	struct hd_cb_seat s;
+	if (hd_cb_join(&e->cb, &slen, &s))
+		return -1;                                  /* coder missing */
+	memcpy(hipdeflate_lat_input(e->lat[s.k], (uint32_t)s.idx), src, slen);      /* own block, no lock held */
+	const int rc = hd_cb_wait(&e->cb, &s);
+	int ret;
+	uint32_t olen = 0;
+	int32_t st = 0;
+	const uint8_t *m = hipdeflate_lat_output(e->lat[s.k], (uint32_t)s.idx, &olen, NULL, &st);
+	if (rc || !m) {
+		ret = -1;                                   /* coder missing */
+	} else if (st || olen > *_dlen) {
+		if (e->loud)
+			fprintf(stderr, "hip_deflate %d\n", st ? st : 1);
+		ret = 1;                                    /* codec error, bgzf_compress.c:163-169 */
+	} else {
+		memcpy(_dst, m, olen);                      /* own member, no lock held */
+		*_dlen = olen;
+		ret = 0;
+	}
+	hd_cb_leave(&e->cb, &s);
+	return ret;
+}
 
 int bgzf_compress(void *_dst, size_t *_dlen, const void *src, size_t slen, int level_unused)
 {
@@ -314,12 +290,9 @@ int bgzf_compress(void *_dst, size_t *_dlen, const void *src, size_t slen, int l
 		return -1;
 	if (slen > 0x10000)                         /* a BGZF member cannot hold it */
 		return 1;
-	if (slen > HOOK_BLOCK || __atomic_load_n(&g_hook.failed, __ATOMIC_RELAXED))
-		return g_hook.failed ? -1 : code_alone(_dst, _dlen, src, slen);
-	__atomic_add_fetch(&g_hook.active, 1, __ATOMIC_RELAXED);
-	const int ret = eng_compress(&g_hook, g_hook.level, _dst, _dlen, src, slen);
-	__atomic_sub_fetch(&g_hook.active, 1, __ATOMIC_RELAXED);
-	return ret;
+	if (slen > HOOK_BLOCK || __atomic_load_n(&g_hook.cb.failed, __ATOMIC_RELAXED))
+		return g_hook.cb.failed ? -1 : code_alone(_dst, _dlen, src, slen);
+	return hook_call(&g_hook, _dst, _dlen, src, slen);
 }
 
 /* The per-block codecs' way in (hd_api.hip deflate_one): one block of 1 .. 0xff00 bytes whose room covers the latency form's
@@ -331,191 +304,5 @@ __attribute__((visibility("hidden"))) int hd_codec_batch(unsigned char *dest, si
 	if (level < 0 || level > 9 || !slen || slen > HOOK_BLOCK)
 		return -2;
 	pthread_once(&g_knobs_once, parse_knobs);
-	struct hook_eng *e = &g_codec[level][flush ? 1 : 0];
-	if (__atomic_load_n(&e->failed, __ATOMIC_RELAXED))
-		return -1;
-	__atomic_add_fetch(&e->active, 1, __ATOMIC_RELAXED);
-	const int ret = eng_compress(e, level, dest, destLen, src, slen);
-	__atomic_sub_fetch(&e->active, 1, __ATOMIC_RELAXED);
-	return ret;
-}
-
-static int eng_compress(struct hook_eng *e, int level, void *_dst, size_t *_dlen, const void *src, size_t slen)
-{
-	pthread_mutex_lock(&e->mu);
-	if (e->failed) {
-		pthread_mutex_unlock(&e->mu);
-		return -1;
-	}
-	/* ---- join the collecting batch, or open one ---------------------------------------------- */
-	struct hook_batch *b;
-	const int64_t t_enter = g_stats ? now_ns() : 0;
-	for (;;) {
-		if (e->open >= 0) {
-			b = &e->batch[e->open];
-			break;
-		}
-		int k;
-		for (k = 0; k < HOOK_CTX && __atomic_load_n(&e->batch[k].state, __ATOMIC_ACQUIRE) != 0; k++)
-			;
-		if (k < HOOK_CTX) {
-			b = &e->batch[k];
-			if (!b->lat) {
-				/* batch context k lives on entry k of the device list (HIPDEFLATE_DEVICES), round robin */
-				const int ndev = hipdeflate_device_count();
-				b->lat = hipdeflate_lat_open_on(ndev > 0 ? k % ndev : 0, level, e->frame | HD_FRAME_LATENCY, HOOK_MAX_BATCH,
-								HOOK_BLOCK);
-				if (!b->lat) {
-					e->failed = 1;
-					pthread_mutex_unlock(&e->mu);
-					return -1;                          /* coder missing */
-				}
-			}
-			__atomic_store_n(&b->n, 0, __ATOMIC_RELAXED);
-			__atomic_store_n(&b->ready, 0, __ATOMIC_RELAXED);
-			__atomic_store_n(&b->taken, 0, __ATOMIC_RELAXED);
-			__atomic_store_n(&b->state, 1, __ATOMIC_RELEASE);
-			e->open = k;
-			break;
-		}
-		pthread_cond_wait(&e->cv_free, &e->mu);   /* every context is busy: wait for one to drain */
-	}
-	const int idx = __atomic_fetch_add(&b->n, 1, __ATOMIC_RELAXED);     /* (written under g_mu; the leader's window loop reads it without) */
-	const int leader = idx == 0;
-	b->len[idx] = (uint32_t)slen;
-	/* Everybody who could join has: the callers inside the hook that are not in a batch on the device are all here
-	 * (callers released together by the previous batch come back within microseconds of each other, and count
-	 * as inside while they copy their members out).  Or the batch is full. */
-	const int want = __atomic_load_n(&e->active, __ATOMIC_RELAXED) - e->running;
-	if (b->n >= HOOK_MAX_BATCH || (b->n >= g_batch_target && e->inflight < g_max_inflight) || (b->n >= want && e->inflight < (want + e->running <= g_merge_callers ? g_merge_inflight : g_max_inflight))) {
-		__atomic_store_n(&b->state, 2, __ATOMIC_RELEASE);
-		e->running += b->n;
-		__atomic_add_fetch(&e->inflight, 1, __ATOMIC_RELAXED);
-		e->open = -1;
-	}
-	pthread_mutex_unlock(&e->mu);
-
-	const int64_t t_joined = g_stats ? now_ns() : 0;
-	memcpy(hipdeflate_lat_input(b->lat, (uint32_t)idx), src, slen);      /* own block, no lock held */
-	__atomic_add_fetch(&b->ready, 1, __ATOMIC_RELEASE);
-	const int64_t t_copied = g_stats ? now_ns() : 0;
-	ST_ADD(st_calls, 1);
-	ST_ADD(st_ctx_wait, t_joined - t_enter);
-	ST_ADD(st_copy_in, t_copied - t_joined);
-
-	if (leader) {
-		/* Others join while the window is open; whoever completes the batch (above) closes it.  The leader closes
-		 * it himself when nobody has joined for g_linger_us although callers are missing (they are busy elsewhere),
-		 * or when the window is over. */
-		if (g_window_us > 0) {
-			const int64_t t0 = now_ns(), deadline = t0 + g_window_us * 1000, hard = t0 + 2000000;
-			int64_t t_last = t0;
-			int seen = 1;
-			while (__atomic_load_n(&b->state, __ATOMIC_ACQUIRE) == 1) {
-				const int64_t t = now_ns();
-				const int cur = __atomic_load_n(&b->n, __ATOMIC_RELAXED);
-				if (cur != seen) {
-					seen = cur;
-					t_last = t;
-				}
-				/* (while g_merge_inflight batches are out the window stays open -- 2 ms at most, should one hang --, and
-				 * when one has come back its callers get g_rejoin_us to show up, then the linger counts from join to join) */
-				const int full = __atomic_load_n(&e->inflight, __ATOMIC_RELAXED) >= (cur >= g_batch_target || __atomic_load_n(&e->active, __ATOMIC_RELAXED) > g_merge_callers ? g_max_inflight : g_merge_inflight);
-				const int64_t tr = __atomic_load_n(&e->t_returned, __ATOMIC_RELAXED);
-				const int64_t quiet = tr > t_last ? tr + g_rejoin_us * 1000 : t_last + g_linger_us * 1000;
-				const int64_t dl = tr > t0 && tr + g_window_us * 1000 > deadline ? tr + g_window_us * 1000 : deadline;
-				if ((t >= dl || t >= quiet) && (!full || t >= hard))
-					break;
-				/* with every device slot taken and more callers than CPUs, the leaders in flight and the HIP runtime's
-				 * thread need this CPU more than a spinning window does */
-				if (full && __atomic_load_n(&e->active, __ATOMIC_RELAXED) + 1 >= g_ncpu)
-					sched_yield();
-				else
-					cpu_relax();
-			}
-		}
-		pthread_mutex_lock(&e->mu);
-		if (__atomic_load_n(&b->state, __ATOMIC_RELAXED) == 1) {          /* window over */
-			__atomic_store_n(&b->state, 2, __ATOMIC_RELEASE);
-			e->running += b->n;
-			__atomic_add_fetch(&e->inflight, 1, __ATOMIC_RELAXED);
-			e->open = -1;
-		}
-		const int n = b->n;
-		pthread_mutex_unlock(&e->mu);
-		const int64_t t_closed = g_stats ? now_ns() : 0;
-		while (__atomic_load_n(&b->ready, __ATOMIC_ACQUIRE) < n)     /* the others are still copying in */
-			cpu_relax();
-		const int64_t t_ready = g_stats ? now_ns() : 0;
-		b->rc = hipdeflate_lat_run(b->lat, b->len, (uint32_t)n);
-		__atomic_store_n(&e->t_returned, now_ns(), __ATOMIC_RELAXED);
-		pthread_mutex_lock(&e->mu);
-		e->running -= n;
-		__atomic_sub_fetch(&e->inflight, 1, __ATOMIC_RELAXED);
-		pthread_mutex_unlock(&e->mu);
-		/* (an exchange, i.e. a full fence: the load of `sleepers` below must not pass this store -- a member that
-		 * has counted itself in and still reads state 2 goes to sleep) */
-		(void)__atomic_exchange_n(&b->state, 3, __ATOMIC_SEQ_CST);
-		if (g_stats) {
-			ST_ADD(st_batches, 1);
-			ST_ADD(st_blocks, n);
-			ST_ADD(st_window, t_closed - t_copied);
-			ST_ADD(st_ready, t_ready - t_closed);
-			ST_ADD(st_run, now_ns() - t_ready);
-		}
-		if (__atomic_load_n(&b->sleepers, __ATOMIC_SEQ_CST))
-			state_wake_all(&b->state);
-	} else {
-		/* spin for the batch (all members see it within a cache miss of the leader's store; a condition variable
-		 * hands its waiters over one by one, microseconds each), sleep only when it takes long */
-		/* as many callers as cores, or more: a spinning (or yielding) member only keeps a leader -- or the HIP runtime's
-		 * own thread, which a leader's hipStreamSynchronize waits for -- off its CPU: those members sleep at once (16
-		 * callers on 16 CPUs, hip2: 4.51 -> 4.76 GB/s); otherwise a member spins g_spin_us for its batch first (it
-		 * sees the leader's store within a cache miss) */
-		const int crowded = __atomic_load_n(&e->active, __ATOMIC_RELAXED) + 1 >= g_ncpu;
-		const int64_t deadline = crowded ? 0 : now_ns() + g_spin_us * 1000;
-		int spins = 0, st;
-		while ((st = __atomic_load_n(&b->state, __ATOMIC_ACQUIRE)) != 3) {
-			if (crowded || ((++spins & 63) == 0 && now_ns() > deadline)) {
-				__atomic_add_fetch(&b->sleepers, 1, __ATOMIC_SEQ_CST);
-				/* (the state may be 1 or 2 here; a change to either wakes nobody, so sleep only on what is seen and
-				 * look again: FUTEX_WAIT returns at once when the word has moved on) */
-				if (__atomic_load_n(&b->state, __ATOMIC_SEQ_CST) == st)
-					state_sleep(&b->state, st);
-				__atomic_sub_fetch(&b->sleepers, 1, __ATOMIC_ACQ_REL);
-			} else {
-				cpu_relax();
-			}
-		}
-		if (g_stats)
-			ST_ADD(st_member_wait, now_ns() - t_copied);
-	}
-	const int64_t t_done = g_stats ? now_ns() : 0;
-	const int rc = b->rc;
-	const int nb = b->n;
-
-	int ret;
-	uint32_t olen = 0;
-	int32_t st = 0;
-	const uint8_t *m = hipdeflate_lat_output(b->lat, (uint32_t)idx, &olen, NULL, &st);
-	if (rc || !m) {
-		ret = -1;                                   /* coder missing */
-	} else if (st || olen > *_dlen) {
-		if (e->loud)
-			fprintf(stderr, "hip_deflate %d\n", st ? st : 1);
-		ret = 1;                                    /* codec error, bgzf_compress.c:163-169 */
-	} else {
-		memcpy(_dst, m, olen);                      /* own member, no lock held */
-		*_dlen = olen;
-		ret = 0;
-	}
-	if (g_stats)
-		ST_ADD(st_copy_out, now_ns() - t_done);
-	if (__atomic_add_fetch(&b->taken, 1, __ATOMIC_ACQ_REL) == nb) {
-		pthread_mutex_lock(&e->mu);
-		__atomic_store_n(&b->state, 0, __ATOMIC_RELEASE);   /* drained: the context can collect again */
-		pthread_cond_broadcast(&e->cv_free);
-		pthread_mutex_unlock(&e->mu);
-	}
-	return ret;
+	return hook_call(&g_codec[level][flush ? 1 : 0], dest, destLen, src, slen);
 }

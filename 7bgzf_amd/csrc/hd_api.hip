@@ -7,16 +7,13 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <linux/futex.h>
-#include <sys/syscall.h>
-#include <unistd.h>
-#include <sched.h>
 #include <chrono>
 #include <condition_variable>
 #include <mutex>
 #include <vector>
 
 #include "../../include/hipdeflate.h"
+#include "hd_call_batch.h"
 #include "hd_deflate_static.hpp"
 #include "hd_deflate_dynamic.hpp"
 #include "hd_deflate_wg.hpp"
@@ -2068,6 +2065,15 @@ static bool codec_batching()
 	return on;
 }
 
+// The room the latency form of one block needs at levels 1 .. HD_WG_LEVEL-1, where a block longer than a segment is cut into
+// segments (several wavefronts for the block): their worst case.  0 where nothing is cut: level 0, a block within one
+// segment, and the workgroup levels (one stream in either mode, "latency" only picks the kernels that write it)
+static uint64_t lat_segments_need(int level, size_t sourceLen, int frame)
+{
+	return level >= 1 && level < HD_WG_LEVEL && sourceLen > HD_LAT_SEG_BYTES(level)
+		       ? HD_SEGN_WORST((uint64_t)sourceLen, HD_LAT_SEG_BYTES(level), frame == HD_FRAME_RAW_FLUSH) : 0;
+}
+
 static int deflate_one(unsigned char *dest, size_t *destLen, const unsigned char *source, size_t sourceLen, int level,
 		       int frame)
 {
@@ -2080,10 +2086,8 @@ static int deflate_one(unsigned char *dest, size_t *destLen, const unsigned char
 	// below.  HIPDEFLATE_CODEC_BATCH=0 turns it off (A/B).
 	if (sourceLen && sourceLen <= CODEC_BLOCK && level >= 0 && level <= 9 && codec_batching() && ensure() == 0) {
 		const bool fl = frame == HD_FRAME_RAW_FLUSH;
-		const uint32_t lat = HD_LAT_SEG_BYTES(level);
-		const uint64_t need_lat = level >= 1 && level < HD_WG_LEVEL && sourceLen > lat ? HD_SEGN_WORST((uint64_t)sourceLen, lat, fl) : 0;
 		const uint64_t need_st = HD_STORED_SIZE((uint64_t)sourceLen) + (fl ? 5u : 0u) + 8u;
-		if (*destLen >= need_lat && *destLen >= need_st) {
+		if (*destLen >= lat_segments_need(level, sourceLen, frame) && *destLen >= need_st) {
 			const int r = hd_codec_batch(dest, destLen, source, sourceLen, level, fl ? 1 : 0);
 			if (r == 0 || r == 1)
 				return r;                                /* (-1 / -2: not for a batch, or its engine is down) */
@@ -2092,13 +2096,10 @@ static int deflate_one(unsigned char *dest, size_t *destLen, const unsigned char
 	if (sourceLen <= CODEC_BLOCK && ensure() == 0) {
 		if (hipdeflate_lat *c = codec_acquire(level)) {
 			const size_t cap = *destLen > c->slot ? c->slot : *destLen;
-			const uint32_t lat = HD_LAT_SEG_BYTES(level);
 			// latency form only when the room covers its worst case AND the context has a slot for every segment
-			// (the workgroup levels: one stream in either mode, "latency" only picks the kernels that write it)
+			const uint64_t need = lat_segments_need(level, sourceLen, frame);
 			const bool latency = level >= HD_WG_LEVEL ||
-					     (level >= 1 && sourceLen > lat &&
-					      cap >= HD_SEGN_WORST((uint64_t)sourceLen, lat, frame == HD_FRAME_RAW_FLUSH) &&
-					      HD_SEGN_COUNT((uint32_t)sourceLen, lat) <= c->S);
+					     (need && cap >= need && HD_SEGN_COUNT((uint32_t)sourceLen, HD_LAT_SEG_BYTES(level)) <= c->S);
 			if (sourceLen)
 				memcpy(hipdeflate_lat_input(c, 0), source, sourceLen);
 			const uint32_t len = (uint32_t)sourceLen;
@@ -2124,8 +2125,8 @@ static int deflate_one(unsigned char *dest, size_t *destLen, const unsigned char
 	const size_t cap = *destLen > 0xfffffff0u ? 0xfffffff0u : *destLen;
 	// One block per call: latency mode (several wavefronts for the block) whenever the room covers its worst case;
 	// the ordinary form otherwise, so that -- as libdeflate_deflate -- the call succeeds whenever the stored form fits
-	const uint32_t lat = HD_LAT_SEG_BYTES(level);
-	if (level >= HD_WG_LEVEL || (level >= 1 && sourceLen > lat && cap >= HD_SEGN_WORST((uint64_t)sourceLen, lat, frame == HD_FRAME_RAW_FLUSH)))
+	const uint64_t need = lat_segments_need(level, sourceLen, frame);
+	if (level >= HD_WG_LEVEL || (need && cap >= need))
 		frame |= HD_FRAME_LATENCY;
 	// the slot stride handed to the batch call only needs to cover `cap`
 	int r = hipdeflate_batch_deflate(source, &off, &len, 1, level, frame, dest, up16(cap) ? up16(cap) : 16,
@@ -2156,67 +2157,42 @@ int hip_deflate_flush(unsigned char *dest, size_t *destLen, const unsigned char 
  * stream in and its own output out with no lock held, the kernel reads and writes that memory itself (no copy engine),
  * the first caller of a batch leads it (closes it once every caller that is inside and not already on the device has
  * joined, launches, waits), the others sleep on the batch's state word.  No process-wide lock around the decoding:
- * INFB_CTX batches can be collecting / running side by side, spread over the device list.  A stream or an output
- * larger than a batch's arena goes alone through the host-buffer batch call. */
+ * HD_CB_CTX batches can be collecting / running side by side, spread over the device list.  A stream or an output
+ * larger than a batch's arena goes alone through the host-buffer batch call.  The batching is hd_call_batch.c's, under
+ * its decompress policy; this is its client: what a batch owns, what it admits, its launch. */
 constexpr uint32_t INFB_SLOTS = 64;                           // streams per batch
 constexpr size_t INFB_IN_ARENA = (size_t)5 << 20;             // 64 x (64 KiB + the stored form's overhead) and room to spare
 constexpr size_t INFB_OUT_ARENA = (size_t)4 << 20;            // 64 x 64 KiB
-constexpr int INFB_CTX = 8;
 
-struct InfBatch {
+struct InfBatch {                                             // what batch context k owns
 	int ctx = -1;                                             // entry of the device list
 	hipStream_t st = nullptr;
 	Buf h_in{ nullptr, 0, true }, h_out{ nullptr, 0, true }, h_meta{ nullptr, 0, true };
 	uint8_t *din = nullptr, *dout = nullptr, *dmeta = nullptr;   // device views of the pinned buffers
-	uint32_t state = 0;                                       // futex word: 0 free, 1 collecting, 2 closed (running), 3 done
-	int n = 0;
 	size_t in_used = 0, out_used = 0;
 	uint32_t flags = 0;
-	int ready = 0, taken = 0, sleepers = 0, rc = 0;
 	hd::DecTable table() const { return { h_meta.p, INFB_SLOTS }; }       // pinned, device-visible
 	hd::DecTable dev_table() const { return { dmeta, INFB_SLOTS }; }
 };
-InfBatch g_infb[INFB_CTX];
-std::mutex g_inf_mu;
-std::condition_variable g_inf_free;
-int g_inf_open = -1;                                          // the collecting batch
-int g_inf_active = 0, g_inf_running = 0;                      // callers inside inflate_one / in batches that are closed
-int g_inf_inflight = 0, g_inf_max_inflight = 2;               // closed batches not yet done / HIPDEFLATE_INFLATE_INFLIGHT
-long g_inf_window_ns = 400000, g_inf_linger_ns = 60000;       // HIPDEFLATE_INFLATE_WINDOW_US / _LINGER_US
-int g_inf_failed = 0;
-// "Everybody who is inside has joined" is not enough to close a batch: the reference creates its -@N threads one after the
-// other (applet/7bgzf.c:330-345), tens of microseconds apart, and a batch that closes as soon as everybody INSIDE has joined
-// goes out with the first few of them -- `7bgzf -d -@16` ran 180 launches of 4..8 streams for 1030 blocks, two side by side,
-// where 65 launches of 16 do (profiles/r05_dec_trace.txt).  g_inf_peak remembers how many callers have been inside at once:
-// a batch is complete when it holds max(inside now, that peak) less those on the device; a batch the LINGER time closes
-// short of it takes the peak down a quarter at a time (callers have gone).  A lone caller never waits.
-int g_inf_peak = 0;
-// A batch is ~1.5 ms on the device whatever it holds (one wavefront per stream, the chip is empty), and the device runs two
-// launches side by side but hardly a third (measured on the latency contexts, DESIGN "Hook": 152 us alone, 173 us each for
-// two, 266+ for three): so at most two batches are out, and while they are the collecting batch stays open and grows.
-// Sixteen callers settle into two groups of eight that alternate; without the cap they drifted apart into batches of one
-// to four that queued behind one another (3.0 ms per call where the kernel takes 1.55).
+InfBatch g_infb[HD_CB_CTX];
 
-static void infb_sleep(uint32_t *w, uint32_t seen) { syscall(SYS_futex, w, FUTEX_WAIT_PRIVATE, seen, nullptr, nullptr, 0); }
-static void infb_wake_all(uint32_t *w) { syscall(SYS_futex, w, FUTEX_WAKE_PRIVATE, 0x7fffffff, nullptr, nullptr, 0); }
-static inline int64_t infb_now()
-{
-	return std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
+struct InfCall {                                              // what a caller asks of its batch
+	size_t sourceLen, ocap, in_need, out_need;
+	uint32_t flags;
+};
 
-// (g_inf_mu held) a batch context's memory and stream, once
-static int infb_create(InfBatch &b, int k)
+// a batch context's memory and stream
+static int inf_open(hd_cb *, int k)
 {
-	if (b.st)
-		return 0;
+	InfBatch &b = g_infb[k];
 	static const bool env_once = [] {
 		if (const char *w = getenv("HIPDEFLATE_INFLATE_WINDOW_US"))
-			g_inf_window_ns = atol(w) * 1000;
+			hd_cb_inflate.window_ns = atol(w) * 1000;
 		if (const char *w = getenv("HIPDEFLATE_INFLATE_LINGER_US"))
-			g_inf_linger_ns = atol(w) * 1000;
+			hd_cb_inflate.linger_ns = atol(w) * 1000;
 		if (const char *w = getenv("HIPDEFLATE_INFLATE_INFLIGHT"))
 			if (atoi(w) >= 1)
-				g_inf_max_inflight = atoi(w);
+				hd_cb_inflate.max_inflight = atoi(w);
 		return true;
 	}();
 	(void)env_once;
@@ -2241,22 +2217,62 @@ static int infb_create(InfBatch &b, int k)
 	return 0;
 }
 
-static void infb_drain()                                      // hipdeflate_shutdown(): idle batch contexts are closed
+// a batch holds streams of one `flags` value, as many as its arenas have room for
+static int inf_admit(hd_cb *, int k, int idx, const void *req)
 {
-	std::lock_guard<std::mutex> lk(g_inf_mu);
-	for (InfBatch &b : g_infb) {
-		if (!b.st || __atomic_load_n(&b.state, __ATOMIC_ACQUIRE) != 0)
-			continue;
-		if (g_all[b.ctx].ready)
-			(void)hipSetDevice(g_all[b.ctx].device);
-		(void)hipStreamSynchronize(b.st);
-		(void)hipStreamDestroy(b.st);
-		b.st = nullptr;
-		b.h_in.release();
-		b.h_out.release();
-		b.h_meta.release();
+	InfBatch &b = g_infb[k];
+	const InfCall &c = *(const InfCall *)req;
+	if (idx == 0) {
+		b.in_used = b.out_used = 0;
+		b.flags = c.flags;
+	} else if (b.flags != c.flags || b.in_used + c.in_need > INFB_IN_ARENA || b.out_used + c.out_need > INFB_OUT_ARENA) {
+		return 0;
 	}
-	g_inf_failed = 0;
+	const hd::DecTable t = b.table();
+	t.in_off()[idx] = b.in_used;
+	t.out_off()[idx] = b.out_used;
+	t.in_len()[idx] = (uint32_t)c.sourceLen;
+	t.out_cap()[idx] = (uint32_t)c.ocap;
+	b.in_used += c.in_need;
+	b.out_used += c.out_need;
+	return 1;
+}
+
+static int inf_run(hd_cb *, int k, int n)
+{
+	InfBatch &b = g_infb[k];
+	const OnCtx on(b.ctx);
+	int rc;
+	if ((rc = ensure()) || (rc = bind_device()))
+		return rc;
+	const hd::InflateArgs a = inflate_args(cur(), b.din, b.dev_table(), (uint32_t)n, b.dout, false, b.flags);
+	hipLaunchKernelGGL(hd::k_inflate_lat, dim3((uint32_t)n), dim3(hd::INF_LAT_THREADS), 0, b.st, a);      // (four wavefronts per stream: hd_inflate_lat.hpp)
+	if (hipGetLastError() != hipSuccess || hipStreamSynchronize(b.st) != hipSuccess) {
+		fprintf(stderr, "hipdeflate: hip_inflate: the latency kernel did not run\n");
+		return HD_E_NODEVICE;
+	}
+	return 0;
+}
+
+static void inf_close(hd_cb *, int k)
+{
+	InfBatch &b = g_infb[k];
+	if (g_all[b.ctx].ready)
+		(void)hipSetDevice(g_all[b.ctx].device);
+	(void)hipStreamSynchronize(b.st);
+	(void)hipStreamDestroy(b.st);
+	b.st = nullptr;
+	b.h_in.release();
+	b.h_out.release();
+	b.h_meta.release();
+}
+
+static const hd_cb_client g_infb_client = { inf_open, inf_admit, inf_run, inf_close };
+static hd_cb g_infb_eng = HD_CB_INIT(&g_infb_client, &hd_cb_inflate_policy, nullptr, INFB_SLOTS);
+
+static void infb_drain()                                      // hipdeflate_shutdown(): idle batch contexts are closed, a failure is forgotten
+{
+	hd_cb_drain(&g_infb_eng);
 }
 
 static int inflate_alone(unsigned char *dest, size_t *destLen, const unsigned char *source, size_t sourceLen, uint32_t flags)
@@ -2283,176 +2299,23 @@ static int inflate_one(unsigned char *dest, size_t *destLen, const unsigned char
 	if (in_need > INFB_IN_ARENA / 4 || out_need > INFB_OUT_ARENA / 4)
 		return inflate_alone(dest, destLen, source, sourceLen, flags);
 
-	/* ---- join the collecting batch, or open one ------------------------------------------------------------- */
-	std::unique_lock<std::mutex> lk(g_inf_mu);
-	if (g_inf_failed) {
-		const int f = g_inf_failed;
-		lk.unlock();
+	const InfCall c = { sourceLen, ocap, in_need, out_need, flags };
+	hd_cb_seat s;
+	// HD_E_NOMEM (the batch contexts' pinned memory): this caller and later ones go alone, until hipdeflate_shutdown()
+	if (const int f = hd_cb_join(&g_infb_eng, &c, &s))
 		return f == HD_E_NOMEM ? inflate_alone(dest, destLen, source, sourceLen, flags) : f;
-	}
-	g_inf_active++;
-	InfBatch *b = nullptr;
-	for (;;) {
-		if (g_inf_open >= 0) {
-			b = &g_infb[g_inf_open];
-			if (b->flags == flags && b->n < (int)INFB_SLOTS && b->in_used + in_need <= INFB_IN_ARENA &&
-			    b->out_used + out_need <= INFB_OUT_ARENA)
-				break;
-			// it cannot take this stream: closed as it stands (its leader finds it so), a new one is opened
-			__atomic_store_n(&b->state, 2u, __ATOMIC_RELEASE);
-			g_inf_running += b->n;
-			g_inf_inflight++;
-			g_inf_open = -1;
-		}
-		int k;
-		for (k = 0; k < INFB_CTX && __atomic_load_n(&g_infb[k].state, __ATOMIC_ACQUIRE) != 0; k++)
-			;
-		if (k < INFB_CTX) {
-			b = &g_infb[k];
-			if (const int r = infb_create(*b, k)) {
-				g_inf_failed = r;
-				g_inf_active--;
-				lk.unlock();
-				return r == HD_E_NOMEM ? inflate_alone(dest, destLen, source, sourceLen, flags) : r;
-			}
-			b->n = 0;
-			b->in_used = b->out_used = 0;
-			b->flags = flags;
-			b->rc = 0;
-			__atomic_store_n(&b->ready, 0, __ATOMIC_RELAXED);
-			__atomic_store_n(&b->taken, 0, __ATOMIC_RELAXED);
-			__atomic_store_n(&b->state, 1u, __ATOMIC_RELEASE);
-			g_inf_open = k;
-			break;
-		}
-		g_inf_free.wait(lk);                              // every batch context is busy: wait for one to drain
-	}
-	const int idx = b->n;
-	const bool leader = idx == 0;
-	const size_t my_in = b->in_used, my_out = b->out_used;
-	const hd::DecTable t = b->table();
-	t.in_off()[idx] = my_in;
-	t.out_off()[idx] = my_out;
-	t.in_len()[idx] = (uint32_t)sourceLen;
-	t.out_cap()[idx] = (uint32_t)ocap;
-	b->in_used += in_need;
-	b->out_used += out_need;
-	__atomic_store_n(&b->n, idx + 1, __ATOMIC_RELAXED);
-	// everybody who could join has: the callers inside that are not in a closed batch are all here (or the batch is full)
-	int peak = __atomic_load_n(&g_inf_peak, __ATOMIC_RELAXED);
-	if (g_inf_active > peak)
-		__atomic_store_n(&g_inf_peak, peak = g_inf_active, __ATOMIC_RELAXED);
-	if (b->n >= (int)INFB_SLOTS || (b->n >= peak - g_inf_running && g_inf_inflight < g_inf_max_inflight)) {
-		__atomic_store_n(&b->state, 2u, __ATOMIC_RELEASE);
-		g_inf_running += b->n;
-		g_inf_inflight++;
-		g_inf_open = -1;
-	}
-	lk.unlock();
-
+	const InfBatch &b = g_infb[s.k];
+	const hd::DecTable t = b.table();
 	if (sourceLen)
-		memcpy((uint8_t *)b->h_in.p + my_in, source, sourceLen);      /* own stream, no lock held */
-	__atomic_add_fetch(&b->ready, 1, __ATOMIC_RELEASE);
-
-	if (leader) {
-		// others join while the window is open; whoever completes the batch (above) closes it, or the leader does when
-		// nobody has joined for the linger time although callers are missing, or when the window is over
-		{
-			const int64_t t0 = infb_now(), deadline = t0 + g_inf_window_ns, hard = t0 + 20000000;
-			int64_t t_last = t0;
-			int seen = 1, spins = 0;
-			while (__atomic_load_n(&b->state, __ATOMIC_ACQUIRE) == 1) {
-				const int64_t t = infb_now();
-				const int now_n = __atomic_load_n(&b->n, __ATOMIC_RELAXED);
-				if (now_n != seen) {
-					seen = now_n;
-					t_last = t;
-				}
-				const bool slot = __atomic_load_n(&g_inf_inflight, __ATOMIC_RELAXED) < g_inf_max_inflight;
-				// complete (every caller that is inside and not on the device has joined), or nobody came for the linger
-				// time, or the window is over -- and a launch slot is free (20 ms at most, should a batch hang)
-				const int running = __atomic_load_n(&g_inf_running, __ATOMIC_RELAXED), peak = __atomic_load_n(&g_inf_peak, __ATOMIC_RELAXED);
-				const bool complete = now_n >= std::max(__atomic_load_n(&g_inf_active, __ATOMIC_RELAXED), peak) - running;
-				const bool lingered = t >= deadline || t - t_last >= g_inf_linger_ns;
-				if (((complete || lingered) && slot) || t >= hard) {
-					if (!complete && lingered && slot)       // callers have gone: the peak comes down, a quarter at a time
-						__atomic_store_n(&g_inf_peak, std::max(now_n + running, peak - std::max(1, peak / 4)), __ATOMIC_RELAXED);
-					break;
-				}
-				if (!slot && (++spins & 15) == 0)
-					sched_yield();                       // two batches are out for a millisecond yet: leave the CPU to their callers
-				else
-					__builtin_ia32_pause();
-			}
-		}
-		lk.lock();
-		if (__atomic_load_n(&b->state, __ATOMIC_RELAXED) == 1) {
-			__atomic_store_n(&b->state, 2u, __ATOMIC_RELEASE);
-			g_inf_running += b->n;
-			g_inf_inflight++;
-			g_inf_open = -1;
-		}
-		const int n = b->n;
-		lk.unlock();
-		while (__atomic_load_n(&b->ready, __ATOMIC_ACQUIRE) < n)             /* the others are still copying in */
-			__builtin_ia32_pause();
-		int rc = 0;
-		{
-			const OnCtx on(b->ctx);
-			if (!(rc = ensure()) && !(rc = bind_device())) {
-				const hd::InflateArgs a = inflate_args(cur(), b->din, b->dev_table(), (uint32_t)n, b->dout, false, b->flags);
-				hipLaunchKernelGGL(hd::k_inflate_lat, dim3((uint32_t)n), dim3(hd::INF_LAT_THREADS), 0, b->st, a);      // (four wavefronts per stream: hd_inflate_lat.hpp)
-				if (hipGetLastError() != hipSuccess || hipStreamSynchronize(b->st) != hipSuccess) {
-					fprintf(stderr, "hipdeflate: hip_inflate: the latency kernel did not run\n");
-					rc = HD_E_NODEVICE;
-				}
-			}
-		}
-		b->rc = rc;
-		lk.lock();
-		g_inf_running -= n;
-		g_inf_inflight--;
-		lk.unlock();
-		(void)__atomic_exchange_n(&b->state, 3u, __ATOMIC_SEQ_CST);   /* (a full fence: the load of `sleepers` must not pass it) */
-		if (__atomic_load_n(&b->sleepers, __ATOMIC_SEQ_CST))
-			infb_wake_all(&b->state);
-	} else {
-		// a batch is about a millisecond of device time: look for a moment (a batch of short streams), then sleep on the word
-		const int64_t spin_until = infb_now() + 20000;
-		uint32_t st;
-		int spins = 0;
-		while ((st = __atomic_load_n(&b->state, __ATOMIC_ACQUIRE)) != 3) {
-			if ((++spins & 63) == 0 && infb_now() > spin_until) {
-				__atomic_add_fetch(&b->sleepers, 1, __ATOMIC_SEQ_CST);
-				if (__atomic_load_n(&b->state, __ATOMIC_SEQ_CST) == st)
-					infb_sleep(&b->state, st);
-				__atomic_sub_fetch(&b->sleepers, 1, __ATOMIC_ACQ_REL);
-			} else {
-				__builtin_ia32_pause();
-			}
-		}
+		memcpy((uint8_t *)b.h_in.p + t.in_off()[s.idx], source, sourceLen);      /* own stream, no lock held */
+	int ret = hd_cb_wait(&g_infb_eng, &s);
+	if (!ret && !(ret = t.status()[s.idx])) {
+		const uint32_t olen = t.out_len()[s.idx];
+		if (olen)
+			memcpy(dest, (const uint8_t *)b.h_out.p + t.out_off()[s.idx], olen);   /* own output, no lock held */
+		*destLen = olen;
 	}
-	const int rc = b->rc, nb = b->n;
-	int ret = rc;
-	if (!rc) {
-		const int32_t st = t.status()[idx];
-		const uint32_t olen = t.out_len()[idx];
-		if (st) {
-			ret = st;
-		} else {
-			if (olen)
-				memcpy(dest, (const uint8_t *)b->h_out.p + my_out, olen);   /* own output, no lock held */
-			*destLen = olen;
-		}
-	}
-	const bool last = __atomic_add_fetch(&b->taken, 1, __ATOMIC_ACQ_REL) == nb;
-	lk.lock();
-	g_inf_active--;
-	if (last) {
-		__atomic_store_n(&b->state, 0u, __ATOMIC_RELEASE);                /* drained: the context can collect again */
-		g_inf_free.notify_all();
-	}
-	lk.unlock();
+	hd_cb_leave(&g_infb_eng, &s);
 	return ret;
 }
 

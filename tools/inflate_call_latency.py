@@ -1,6 +1,7 @@
 """what hip_inflate (the zlibutil_code_dec boundary, lib/zlibutil.h:46) costs per 0xff00-byte block, from 1 / 16 / 64 calling
 threads -- the way `7bgzf -d -@N` calls it (applet/7bgzf.c:330-345: a thread per block).  A DEFLATE stream is one wavefront's
-serial work however empty the chip is; concurrent callers share a launch (hd_api.hip, inflate_one).
+serial work however empty the chip is; concurrent callers share a launch (hd_call_batch.c's engine under its
+decompress policy; hd_api.hip's inflate_one is its client).
 usage: python tools/inflate_call_latency.py [out.jsonl]   (on the GPU box; drives 7bgzf_amd/inflate_call_bench)"""
 import importlib, json, os, subprocess, sys, tempfile, zlib
 sys.path.insert(0, '.')
