@@ -29,6 +29,8 @@ constexpr uint32_t INF_LAT_SPINS = 1u << 24;  // polls of a wait between the wav
                                              // never a hang -- hip_inflate answers HD_BAD_DATA, and no test has seen it happen.  (The guards and
                                              // the skipped distance check measured neutral on one box: 898-904 us a lone call either way)
 constexpr uint32_t INF_FQ = 4;               // windows in flight between the front and the sort wavefront
+constexpr uint32_t INF_LAT_LEAD = 32768;     // the sort wavefront's stores stay below (what the back has flushed) + this: half the ring, so what they
+                                             // land on is older than any match source (inflate_stream_pipe, "the lead")
 template <uint32_t RING>
 struct InfLdsPipeT {
 	uint32_t lit[1u << INF_LT_BITS];
@@ -56,6 +58,7 @@ struct InfLdsPipeT {
 	uint32_t fq_head, fq_tail;
 	uint32_t fq_hdr[INF_FQ][8];
 	uint32_t abort;                          // a wait between the wavefronts did not end (INF_LAT_SPINS): everybody leaves, the verdict is an error
+	uint32_t back_flushed;                   // back -> sort: the output position through which the back wavefront has flushed the ring ("the lead", below)
 };
 
 // the decoder, for an output ring of RING bytes (one wavefront; L is the workgroup's LDS).
@@ -78,6 +81,7 @@ __device__ __forceinline__ void inflate_stream_pipe(const InflateArgs &a, LDS &L
 		L.q_head = L.q_tail = 0;
 		L.fq_head = L.fq_tail = 0;
 		L.abort = 0;
+		L.back_flushed = 0;
 		L.sp_head = L.sp_tail = L.sp_ack = L.sp_go = L.sp_start = 0;
 		L.sp_stop = 1;                                   // the spec wavefront starts halted: there are no tables yet (epoch 1 = the first header's)
 	}
@@ -220,6 +224,12 @@ __device__ __forceinline__ void inflate_stream_pipe(const InflateArgs &a, LDS &L
 				crc.fold(ct, flushed / HD_PIECE, true, v);
 			flushed += HD_PIECE;
 		}
+		// (the back wavefront's, and its only: what the sort wavefront's stores may not run further ahead of than INF_LAT_LEAD --
+		// "the lead" at place_window.  Behind the ring's loads above in program order, so behind them in the LDS)
+		asm volatile("" ::: "memory");
+		if (lane == 0)
+			*(lat_word_p)&L.back_flushed = flushed;
+		asm volatile("" ::: "memory");
 	};
 
 
@@ -278,10 +288,20 @@ __device__ __forceinline__ void inflate_stream_pipe(const InflateArgs &a, LDS &L
 		}
 	};
 
-	// ---- what a window's MATCHES become in the ring: the back wavefront's half of a window.  The front has stored the literals
-	// itself (they depend on nothing) and has sorted the matches -- none of that needs the ring --; here the ring holds every
-	// source (64 KiB against distances <= 32 KiB + the few KiB the front is ahead: the "far" paths of hd_inflate.hpp's decoder
-	// do not exist), so what is left is the copying: the statements of that decoder's window, in its order -------------------
+	// ---- what a window's MATCHES become in the ring: the back wavefront's half of a window.  The sort wavefront has stored the
+	// literals itself (they depend on nothing) and has sorted the matches -- none of that needs the ring --; here the ring holds
+	// every source (64 KiB against distances <= 32 KiB + what the sort is ahead: the "far" paths of hd_inflate.hpp's decoder do
+	// not exist), so what is left is the copying: the statements of that decoder's window, in its order.
+	// THE LEAD.  The sort's literal stores are the one writer of the ring that runs ahead of the back wavefront, and the records
+	// between the two bound that lead in number only (one executing, INF_PQ queued, one in the sort's hands, INF_FQ behind it):
+	// windows of <= WIN_OUT_BUDGET bytes make that a few KiB, but a stored block is ONE record of up to 65535 bytes.  The
+	// invariant: nobody writes the ring at an output position >= back_flushed + INF_LAT_LEAD (32 KiB), back_flushed being the
+	// position through which the back has executed AND flushed.  The slot a write lands on held the byte 64 KiB before it: that
+	// byte is then more than 32 KiB behind everything the back has still to execute -- no match of it or of a later record can
+	// read it -- and it has left the ring for the output.  Nor can the back, which writes in order from its own position, write
+	// that slot afterwards.  The back's own writes satisfy this by being in order; the sort waits (at its literal stores) until
+	// its window's last byte does.  The wait ends: with every earlier record executed, back_flushed is within a piece of the
+	// window's first byte.  In a BGZF-sized stream (<= 64 KiB of output) it is never taken ----------------------------------
 	struct WinRec {
 		uint32_t lo0, lo1;                   // per lane and half: match length | distance << 16
 		uint32_t rel0, rel1;                 // a real token's first output byte, relative to the window's
@@ -664,6 +684,7 @@ __device__ __forceinline__ void inflate_stream_pipe(const InflateArgs &a, LDS &L
 	};
 	if (role == 3) {
 		const pipe_word_p head = (pipe_word_p)&L.fq_head;
+		uint32_t since_stored = INF_PQ + 1;       // records pushed since the last stored block's ("the lead", place_window)
 		for (;;) {
 			lat_wait([&]() { return uniform(*head) == fq_n; }, 0);
 			if (uniform(*(lat_word_p)&L.abort))
@@ -681,6 +702,7 @@ __device__ __forceinline__ void inflate_stream_pipe(const InflateArgs &a, LDS &L
 				pipe_push_small(type, x, y);
 				if (type == PIPE_END)
 					return;
+				since_stored = type == PIPE_STORED ? 0 : since_stored + 1;
 				continue;
 			}
 			const uint32_t wpos = x, cum = y;
@@ -704,6 +726,15 @@ __device__ __forceinline__ void inflate_stream_pipe(const InflateArgs &a, LDS &L
 			// the literals: they depend on nothing, and the ring is nobody's at these bytes until the record is out
 			// (lanes without a literal write to their dump slot: no exec juggling, no skip branches)
 			const uint64_t lit0 = real0 & ~is_len0, lit1 = real1 & ~is_len1;
+			// ... and not older output's either: the lead (place_window).  Only behind stored blocks is this ever true.
+			// (A wait given up -- INF_LAT_SPINS, or somebody else's abort -- falls through: the stores and the push below
+			// still happen, into masked ring slots and a queue everybody is leaving; the verdict is the back's HD_BAD_DATA)
+			// The word is looked at only while a stored block is among the last INF_PQ + 1 records pushed: what the back has
+			// not executed yet is at most those (INF_PQ queued, one popped), and that many windows, literals and matches are
+			// 6 x WIN_OUT_BUDGET + a piece = 5 KiB of lead at the most.  A stream without stored blocks never reads it.
+			if (since_stored <= INF_PQ)
+				lat_wait([&]() { return (int32_t)(wpos + cum - INF_LAT_LEAD - uniform(*(lat_word_p)&L.back_flushed)) > 0; }, 0);
+			since_stored++;
 			L.ring[sel(lit0, opos0 & (RING - 1), RING + lane)] = (uint8_t)len0;
 			L.ring[sel(lit1, opos1 & (RING - 1), RING + lane)] = (uint8_t)len1;
 			// the matches, by the way the back wavefront copies them (hd_inflate.hpp's classes without the ring test:

@@ -12,6 +12,10 @@ the verdict each family states are the expected answers.
 says which verdict the plain and the flushed entry points must give, whether zlib can be asked about it (the
 libdeflate-only forms: litlen 286/287, offset 30/31, HLIT > 286, HDIST > 30), and what edges it reaches
 (`stats`, counted from the token lists and code lengths as they are written).
+
+Two corpora, one per kernel geometry: `corpus()` aims at the throughput kernel's 2 KiB ring (k_inflate: RING,
+PIECE, NEAR below), `lat_corpus()` at the latency kernel's 64 KiB ring and its record queues (k_inflate_lat:
+LAT_RING, LAT_FQ, LAT_PQ below).
 """
 import collections
 
@@ -33,6 +37,12 @@ STATIC_DIST = [5] * 32
 RING = 2048                 # INF_RING: the throughput kernel's LDS output ring
 PIECE = 1024                # HD_PIECE: output leaves the ring in 1 KiB pieces
 NEAR = RING - 258 - 64      # INF_NEAR = 1726: a source at most this far back is read from the ring
+
+# the latency kernel's geometry (hd_inflate_lat.hpp), what lat_corpus() aims at
+LAT_RING = 65536            # INF_RING_LAT: its LDS output ring, twice the DEFLATE window
+LAT_FQ = LAT_PQ = 4         # INF_FQ, INF_PQ: records in flight front -> sort and sort -> back
+LAT_WIN = 704               # WIN_OUT_BUDGET: output bytes of one window record at the most
+LAT_MAX_OUT = 1 << 20       # the largest room a call may state and still be decoded by that kernel (hd_api.hip)
 
 
 def len_sym(length):
@@ -376,18 +386,19 @@ def _write_dynamic_header(w, b, lit, dist, st):
 def expand(blocks):
     """The high-precision reference: the output of the token lists, one byte at a time."""
     out = bytearray()
+    put = out.append
     for b in blocks:
         if b.kind == "stored":
             out += b.data
             continue
         for t in b.tokens:
             if isinstance(t, int):
-                out.append(t)
+                put(t)
                 continue
             length, d = t[0], t[1]
             assert 1 <= d <= len(out), "distance %d past the %d bytes produced" % (d, len(out))
             for _ in range(length):
-                out.append(out[-d])
+                put(out[-d])
     return bytes(out)
 
 
@@ -821,3 +832,282 @@ def cached_corpus():
     if _cached is None:
         _cached = corpus()
     return _cached
+
+
+# ---- the second corpus: the latency kernel's geometry (k_inflate_lat, hd_inflate_lat.hpp) -------------------------
+#
+# That kernel keeps the last 64 KiB of output in LDS and deals a stream to four wavefronts: the front parses and
+# hands records on (a window of <= LAT_WIN output bytes, one literal, one match, one stored block of any length,
+# the end), the sort stores a window's literals into the ring and passes every record on, the back executes the
+# records in order.  LAT_FQ records wait between front and sort, LAT_PQ between sort and back.  Three things can
+# go wrong there that corpus() never reaches: an index across the 64 KiB wrap, an output larger than the ring
+# (every stream of corpus() stops before 48,000 bytes or is one stored block), and the sort's literal stores
+# running more than the ring's spare half ahead of the back when the records in between are large stored blocks.
+
+LAT_WRAP_DISTS = [1, 2, 7, 8, 9, 16, 17, 64, 65, 258, 1024, 32767, 32768]
+LAT_LEAD_LITS = 6000        # more than LAT_FQ + LAT_PQ windows of LAT_WIN bytes
+LAT_LEAD_MATCHES = [(258, 32768), (9, 32768), (64, 30000), (17, 16400)]
+LAT_SIZES = [65535, 65536, 65537, 131071, 131072, 131073, 1048575, 1048576, 1048577]
+
+
+def match_fill(rng, out, target):
+    """blocks that bring the output from `out` to `target` cheaply: a stored seed of 300 random bytes if there is
+    no history yet, then one static block of (258, 300) matches and fewer than 258 random literals"""
+    blocks, gap = [], target - out
+    assert gap >= 0
+    if out < 300 and gap:
+        n = min(gap, 300)
+        blocks.append(Block("stored", data=rand_bytes(rng, n)))
+        gap -= n
+    if gap:
+        blocks.append(Block("static", tokens=[(258, 300)] * (gap // 258) + lits(rand_bytes(rng, gap % 258))))
+    return blocks
+
+
+def lat_stats(blocks):
+    """what a block list reaches of the latency kernel's geometry, counted from the lists"""
+    st = collections.Counter()
+    out, run = 0, []                                 # run: the stored blocks directly in front of the next block
+    for b in blocks:
+        if b.kind == "stored":
+            if b.data and out % LAT_RING + len(b.data) > LAT_RING:
+                st["lat_stored_wraps_ring"] += 1
+            if b.data:
+                run.append(len(b.data))
+            out += len(b.data)
+            continue
+        nlit = sum(1 for t in b.tokens if isinstance(t, int))
+        if nlit and run:
+            # what can lie between the back and the sort's stores: the stored records still queued, and the
+            # windows queued with them (counted as LAT_LEAD_LITS bytes whatever the block holds)
+            lead = sum(run[-(LAT_FQ + LAT_PQ + 1):]) + LAT_LEAD_LITS
+            if lead >= LAT_RING:
+                st["lat_inflight_ge_64k"] += 1
+            elif lead >= LAT_RING // 2:
+                st["lat_inflight_32k_64k"] += 1
+        run = []
+        for t in b.tokens:
+            if isinstance(t, int):
+                out += 1
+                continue
+            ln, d = t[0], t[1]
+            if out % LAT_RING + ln > LAT_RING:
+                st["lat_dst_wraps_ring"] += 1
+            if (out - d) % LAT_RING + min(ln, d) > LAT_RING:
+                st["lat_src_wraps_ring"] += 1
+            out += ln
+    if out > LAT_RING:
+        st["lat_out_gt_64k"] += 1
+    if abs(out - LAT_MAX_OUT) <= 1:
+        st["lat_out_1mib"] += 1
+    return st
+
+
+def stored_lead(stream):
+    """the output bytes of the stored blocks a raw DEFLATE stream starts with (0: it starts with a Huffman block),
+    read from the headers: what tells whether an encoder's stream puts large stored records in flight"""
+    pos, total = 0, 0                                # pos: a bit position
+    while 8 * len(stream) - pos >= 3:
+        nxt = stream[(pos >> 3) + 1] if (pos >> 3) + 1 < len(stream) else 0
+        hdr = (stream[pos >> 3] | nxt << 8) >> (pos & 7)
+        if (hdr >> 1) & 3:
+            break
+        p = (pos + 3 + 7) >> 3
+        ln, nl = int.from_bytes(stream[p:p + 2], "little"), int.from_bytes(stream[p + 2:p + 4], "little")
+        assert len(stream) >= p + 4 and ln == nl ^ 0xffff
+        total += ln
+        pos = 8 * (p + 4 + ln)
+        if hdr & 1:
+            break
+    return total
+
+
+def lat_valid(name, family, blocks, chunk=False, extra=None):
+    blocks[-1].final = True
+    c = valid(name, family, blocks, chunk=chunk)
+    c.stats.update(lat_stats(blocks))
+    if extra:
+        c.stats.update(extra)
+    return c
+
+
+def _lat_wrap_items():
+    """(near, far): the matches of lat_wrap as (length, distance, kind, offset of the destination from the wrap).
+    kind d<phase>: the destination starts at wrap + phase; s<phase>: the source does.  phase A = -length // 2,
+    B = -1, 0, 1.  `far` holds the source kinds of the distances whose destination lies clear of the wrap, three
+    queues that share a visit of a wrap with one `near` item.  The full matrix (14 lengths x 13 distances x 8
+    kinds x 3 wraps) does not fit the corpus's budget of output bytes: every (length, distance) is there with its
+    destination across the wrap at both phases that span it, the other kinds are a stride through the matrix."""
+    def phases(ln):
+        return (("A", -(ln // 2)), ("B", -1), ("0", 0), ("1", 1))
+    span = [(ln, d, "d" + p, o) for p in "AB" for d in LAT_WRAP_DISTS for ln in MATCH_LENGTHS
+            for q, o in phases(ln) if q == p]
+    other = [(ln, d, "d" + p, o) for p in "01" for d in LAT_WRAP_DISTS for ln in MATCH_LENGTHS
+             for q, o in phases(ln) if q == p]
+    other += [(ln, d, "s" + p, o + d) for p in "AB01" for d in LAT_WRAP_DISTS if d < 258 for ln in MATCH_LENGTHS
+              for q, o in phases(ln) if q == p]
+    other = [other[(i * 13) % len(other)] for i in range(136)]
+    near = []
+    while span or other:                             # about three spanning ones to one of the others
+        near += span[:3] + other[:1]
+        span, other = span[3:], other[1:]
+    far = []
+    for ds in ((258,), (1024,), (32767, 32768)):
+        q = [(ln, d, "s" + p, o + d) for ln in MATCH_LENGTHS for d in ds for p, o in phases(ln)]
+        far.append([q[(i * 5) % len(q)] for i in range(len(q))])       # (5 is coprime to 56 and 112)
+    return near, far
+
+
+def fam_lat_wrap(rng):
+    """matches whose destination or source lies at and across a multiple of 64 KiB (65536 m, m = 1, 2 in the short
+    streams, m = 1..15 in the long ones), reached with match filler only: no large record is ever in flight, a
+    failure here is a failure of the wrap.  0 / 2 / 37 / 300 literals in front of the match in its own block,
+    static and derived dynamic blocks"""
+    near, far = _lat_wrap_items()
+    cases, k, s = [], 0, 0
+    while near or any(far):
+        long_one = (s % 17) in (0, 2, 5, 7, 10, 12, 15)
+        blocks, out, extra = [], 0, collections.Counter()
+        for m in (range(1, 16) if long_one else (1, 2)):
+            wrap = m * LAT_RING
+            for q in [near] + far:
+                if not q:
+                    continue
+                ln, d, kind, o = q[0]
+                nl = (0, 2, 37, 300)[k % 4]
+                if wrap + o - nl < out:              # the visit's earlier matches are in the way: at a later wrap
+                    continue
+                q.pop(0)
+                blocks += match_fill(rng, out, wrap + o - nl)
+                blocks.append(Block(("static", "dynamic")[(k + k // 4) % 2],
+                                    tokens=lits(rand_bytes(rng, nl)) + [(ln, d)] + lits(rand_bytes(rng, 3))))
+                out = wrap + o + ln + 3
+                extra["lat_wrap_" + kind] += 1
+                extra["lat_wrap_pair_%d_%d" % (ln, d)] += 1
+                extra["lat_wrap_m%d" % m] += 1
+                k += 1
+        cases.append(lat_valid("lat_wrap_%d" % s, "lat_wrap", blocks, extra=extra))
+        s += 1
+        assert s < 120
+    # a stored block of 5,000 bytes across the wrap
+    blocks, out = [], 0
+    for m, back in ((1, 2500), (2, 1), (15, 4999)):
+        blocks += match_fill(rng, out, m * LAT_RING - back) + [Block("stored", data=rand_bytes(rng, 5000))]
+        out = m * LAT_RING - back + 5000
+    blocks.append(Block("static", tokens=[(258, 5000), 1, 2, 3]))
+    cases.append(lat_valid("lat_wrap_stored_5000", "lat_wrap", blocks))
+    # a run of 13..15-bit codewords across it: the scalar path's records, one literal or one match each
+    pool = [int(x) for x in rng.permutation(256)[:40]]
+    for L, m in ((13, 1), (14, 1), (15, 1), (15, 2)):
+        fixed = {256: L, 285: L, pool[0]: L, pool[1]: L}
+        lit = fill_lengths(fixed, pool[2:] + [257, 264, 265, 272, 280, 284], 286)
+        dist = auto_lengths({0: 3, 3: 2, 4: 1, 10: 1, 16: 1, 22: 1}, 30)
+        dsyms = [x for x in range(30) if dist[x]]
+        start = m * LAT_RING - 30
+        run = sym_tokens(rng, [285, pool[0], pool[1]], 60, start, dsyms)
+        other = sym_tokens(rng, [x for x in range(286) if lit[x] and x != 256], 100, start, dsyms)
+        assert sum(1 if isinstance(t, int) else t[0] for t in run) > 30
+        cases.append(lat_valid("lat_wrap_%dbit_run_m%d" % (L, m), "lat_wrap", match_fill(rng, 0, start) +
+                               [Block("dynamic", tokens=run + other, lit_lens=lit, dist_lens=dist)]))
+    # 200 KiB of (258, 1) at one bit per token: the ring wrapped three times by the windows' budget cuts
+    lit = [0] * 286
+    lit[285], lit[256], lit[65], lit[66] = 1, 2, 3, 3
+    n = -(-200 * 1024 // 258)
+    cases.append(lat_valid("lat_wrap_amp_285_1bit_200k", "lat_wrap",
+                           [Block("dynamic", tokens=[65] + [(258, 1)] * n + [66], lit_lens=lit,
+                                  dist_lens=[1] + [0] * 29)]))
+    return cases
+
+
+def _lead_block(rng, kind, match_first=False):
+    body = lits(rand_bytes(rng, LAT_LEAD_LITS))
+    post = lits(rand_bytes(rng, 100))
+    return Block(kind, tokens=LAT_LEAD_MATCHES + body + post if match_first else body + LAT_LEAD_MATCHES + post)
+
+
+def fam_lat_lead(rng):
+    """large stored records in flight, then a Huffman block of 6,000 literals -- more than eight windows: the sort
+    stores them while the back still copies the stored blocks -- then matches that read back into the stored
+    bytes and 100 literals.  Each shape with a static block (no table build: the front is at its fastest) and
+    with a dynamic one"""
+    cases = []
+    for kind in ("static", "dynamic"):
+        for L in (32768, 57344, 61440, 65535):
+            for b in (0, 1000, 40000, LAT_RING + 77):
+                cases.append(lat_valid("lat_lead_one_%d_at_%d_%s" % (L, b, kind), "lat_lead", match_fill(rng, 0, b) +
+                                       [Block("stored", data=rand_bytes(rng, L)), _lead_block(rng, kind)]))
+        for L, ks in ((16383, (4, 5, 9, 12)), (65535, (2, 3, 15))):
+            for n in ks:
+                cases.append(lat_valid("lat_lead_%dx%d_%s" % (n, L, kind), "lat_lead",
+                                       [Block("stored", data=rand_bytes(rng, L)) for _ in range(n)] +
+                                       [_lead_block(rng, kind)]))
+        blocks = []
+        for _ in range(6):
+            blocks += [Block("stored", data=rand_bytes(rng, 65535)), _lead_block(rng, kind)]
+        cases.append(lat_valid("lat_lead_alternating_x6_%s" % kind, "lat_lead", blocks))
+        cases.append(lat_valid("lat_lead_match_first_%s" % kind, "lat_lead",
+                               [Block("stored", data=rand_bytes(rng, 65535)), _lead_block(rng, kind, True)]))
+    return cases
+
+
+_WORDS = [b"the", b"ring", b"holds", b"every", b"source", b"a", b"window", b"of", b"literals", b"goes", b"ahead",
+          b"stored", b"block", b"behind", b"it", b"and", b"back", b"wavefront", b"copies", b"in", b"order"]
+
+
+def _text_tokens(rng, n):
+    """n output bytes that look like text to an encoder: words as literals, earlier phrases as matches"""
+    toks, out = [], 0
+    while out < n:
+        if out > 100 and n - out >= 3 and int(rng.integers(0, 2)):
+            ln = min(int(rng.integers(3, 40)), n - out)
+            toks.append((ln, int(rng.integers(1, out + 1))))
+            out += ln
+        else:
+            w = (_WORDS[int(rng.integers(0, len(_WORDS)))] + b" ")[:n - out]
+            toks += lits(w)
+            out += len(w)
+    return toks
+
+
+def fam_lat_sizes(rng):
+    """outputs at and around the ring's size, twice it, and the largest room the latency kernel takes (one byte
+    more goes to the lone launch of the batch kernel): of match filler, and of stored blocks with a text-like
+    dynamic block behind them"""
+    cases = []
+    for n in LAT_SIZES:
+        cases.append(lat_valid("lat_size_%d_fill" % n, "lat_sizes", match_fill(rng, 0, n)))
+        tail = 3000 + n % 7
+        piece = 65535 if n > 200000 else 16383
+        blocks, left = [], n - tail
+        while left:
+            blocks.append(Block("stored", data=rand_bytes(rng, min(left, piece))))
+            left -= len(blocks[-1].data)
+        cases.append(lat_valid("lat_size_%d_stored_text" % n, "lat_sizes",
+                               blocks + [Block("dynamic", tokens=_text_tokens(rng, tail))]))
+    return cases
+
+
+def lat_corpus(seed=2027):
+    """the families aimed at the latency kernel; cap = exact, plus cap = exact - 1 (INSUFFICIENT_SPACE) for every
+    valid case with output, plus the chunk form of one shape per family"""
+    rng = np.random.default_rng(seed)
+    fams = [fam_lat_wrap(rng), fam_lat_lead(rng), fam_lat_sizes(rng)]
+    cases = [c for f in fams for c in f]
+    for f, pick in zip(fams, ("lat_wrap_1", "lat_lead_one_65535_at_1000_static", "lat_size_131073_stored_text")):
+        c = next(c for c in f if c.name == pick)
+        cases.append(valid("chunk_" + c.name, "chunk_" + c.family, c.blocks, chunk=True))
+        cases[-1].stats.update(lat_stats(c.blocks))
+    tight = [Case(c.name + "_cap_minus1", "cap_minus1", c.stream, len(c.expected) - 1, INSUFFICIENT_SPACE, b"",
+                  chunk=c.chunk) for c in cases if c.expected]
+    return cases + tight
+
+
+_cached_lat = None
+
+
+def cached_lat_corpus():
+    """lat_corpus() once per process"""
+    global _cached_lat
+    if _cached_lat is None:
+        _cached_lat = lat_corpus()
+    return _cached_lat

@@ -100,8 +100,9 @@ def test_hip_inflate_runs_of_long_codewords_between_windows(pkg):
 
 def test_hip_inflate_threads_full_blocks_flush_form_and_oversize(pkg):
     """64 threads x full 0xff00-byte blocks (zlib 1/6/9, our levels 1 and 6), the flush form side by side with the final
-    form (separate batches), one byte of room less (3 = INSUFFICIENT_SPACE), and a 1 MiB member that is larger than a
-    batch's arena (goes alone)."""
+    form (separate batches), one byte of room less (3 = INSUFFICIENT_SPACE), and a 1 MiB member from four threads: a
+    quarter of a batch's arena, the largest call the latency kernel still takes (the path that goes alone starts one
+    byte above: tests/test_gpu_inflate_lat_ring.py's 1 MiB + 1 cases)."""
     s = hdtest.synth()
     blocks = [bytes(s.fastq_like(0xff00, seed=40 + k)) for k in range(6)] + [bytes(s.text_like(0xff00, seed=50 + k)) for k in range(6)]
     jobs = []
