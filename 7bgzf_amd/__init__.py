@@ -84,6 +84,8 @@ EXPORTS = [
     "hipdeflate_check_combine_dev", "hip_deflate_stream", "hipdeflate_test_stream_window",
     "hipdeflate_init_devices", "hipdeflate_device_count", "hipdeflate_use_device",
     "hipdeflate_pipe_open_on", "hipdeflate_unpipe_open_on", "hipdeflate_lat_open_on",
+    "hipdeflate_batch_inflate_size_dev", "hipdeflate_batch_inflate_framed_dev", "hipdeflate_batch_inflate_size",
+    "hipdeflate_batch_inflate_framed",
     "hipdeflate_pipe_members", "hipdeflate_lat_open", "hipdeflate_lat_input", "hipdeflate_lat_run", "hipdeflate_lat_output", "hipdeflate_lat_close",
 ]
 
@@ -154,6 +156,11 @@ def lib():
                                                ctypes.c_uint64, ctypes.c_uint32, _vp, _vp, _vp, _vp]
     L.hipdeflate_batch_inflate_dev.argtypes = [_vp, _vp, _vp, ctypes.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
     L.hipdeflate_batch_inflate_flush_dev.argtypes = L.hipdeflate_batch_inflate_dev.argtypes
+    L.hipdeflate_batch_inflate_size_dev.argtypes = [_vp, _vp, _vp, ctypes.c_uint32, ctypes.c_int, _vp, _vp, _vp, _vp]
+    L.hipdeflate_batch_inflate_framed_dev.argtypes = [_vp, _vp, _vp, ctypes.c_uint32, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                      _vp, _vp]
+    L.hipdeflate_batch_inflate_size.argtypes = [_vp, _vp, _vp, ctypes.c_uint32, ctypes.c_int, _vp, _vp, _vp]
+    L.hipdeflate_batch_inflate_framed.argtypes = [_vp, _vp, _vp, ctypes.c_uint32, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
     L.hipdeflate_scan_sizes_dev.argtypes = [_vp, ctypes.c_uint32, ctypes.c_uint64, _vp, _vp, _vp]
     L.hipdeflate_compact_dev.argtypes = [_vp, ctypes.c_uint64, _vp, _vp, ctypes.c_uint32, _vp, _vp]
     L.hipdeflate_compact_span_dev.argtypes = [_vp, ctypes.c_uint64, _vp, _vp, ctypes.c_uint32, _vp, ctypes.c_uint64, _vp]
@@ -391,6 +398,48 @@ def batch_inflate(streams, caps, want_crc=True, flushed=False):
               _p(crc) if want_crc else None, _p(st)), "hipdeflate_batch_inflate")
     outs = [bytes(out[int(ooff[i]): int(ooff[i]) + int(olen[i])]) if st[i] == 0 else b"" for i in range(nb)]
     return outs, crc, st
+
+
+def _pack_streams(streams):
+    nb = len(streams)
+    ilen = np.array([len(s) for s in streams], dtype=np.uint32)
+    ioff = np.zeros(nb, dtype=np.uint64)
+    if nb:
+        ioff[1:] = np.cumsum(ilen[:-1], dtype=np.uint64)
+    return as_u8(b"".join(bytes(s) for s in streams)), ioff, ilen
+
+
+def batch_inflate_size(streams, frame=FRAME_ZLIB):
+    """The size pass over a list of raw / zlib / gzip members (hipdeflate_batch_inflate_size): nothing is decoded to
+    memory.  -> (out_size array, in_used array, status array)."""
+    src, ioff, ilen = _pack_streams(streams)
+    nb = len(streams)
+    osz = np.zeros(nb, dtype=np.uint32)
+    used = np.zeros(nb, dtype=np.uint32)
+    st = np.zeros(nb, dtype=np.int32)
+    _check(lib().hipdeflate_batch_inflate_size(_p(src), _p(ioff), _p(ilen), nb, frame, _p(osz), _p(used), _p(st)),
+           "hipdeflate_batch_inflate_size")
+    return osz, used, st
+
+
+def batch_inflate_framed(streams, caps, frame=FRAME_ZLIB):
+    """Decode a list of raw / zlib / gzip members, header and trailer included (hipdeflate_batch_inflate_framed).
+    -> (outputs list, check array, in_used array, status array); check is the CRC-32 (raw, gzip) or Adler-32 (zlib)."""
+    src, ioff, ilen = _pack_streams(streams)
+    nb = len(streams)
+    caps = _np(caps, np.uint32)
+    ooff = np.zeros(nb, dtype=np.uint64)
+    if nb:
+        ooff[1:] = np.cumsum(caps[:-1].astype(np.uint64))
+    out = np.zeros(max(int(caps.astype(np.uint64).sum()), 1), dtype=np.uint8)
+    olen = np.zeros(nb, dtype=np.uint32)
+    chk = np.zeros(nb, dtype=np.uint32)
+    used = np.zeros(nb, dtype=np.uint32)
+    st = np.zeros(nb, dtype=np.int32)
+    _check(lib().hipdeflate_batch_inflate_framed(_p(src), _p(ioff), _p(ilen), nb, frame, _p(out), _p(ooff), _p(caps), _p(olen),
+                                                 _p(chk), _p(used), _p(st)), "hipdeflate_batch_inflate_framed")
+    outs = [bytes(out[int(ooff[i]): int(ooff[i]) + int(olen[i])]) if st[i] == 0 else b"" for i in range(nb)]
+    return outs, chk, used, st
 
 
 # ---- container level (role of applet/7bgzf.c _compress / _decompress) --------------

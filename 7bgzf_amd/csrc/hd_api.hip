@@ -20,6 +20,8 @@
 #include "hd_emit_wg.hpp"
 #include "hd_inflate.hpp"
 #include "hd_inflate_lat.hpp"
+#include "hd_inflate_size.hpp"
+#include "hd_frame.hpp"
 #include "hd_compact.hpp"
 #include "hd_index.hpp"
 #include "hd_range.hpp"
@@ -152,12 +154,14 @@ struct Ctx {
 	// device-pointer API scratch (token slabs for the dynamic levels), guarded by mu_dev
 	std::mutex mu_dev;
 	SharedScratch tok, tiles;        // token slabs and segment slots of a launch / the tile sums of a scan
+	SharedScratch frame;             // the payload table of a framed inflate or size pass (hd_frame.hpp)
 	hd::WgBeside beside;             // the workgroup levels' emit kernel beside their parse (hd_deflate_wg.hpp), with tok
 	void stream_drained(hipStream_t st)
 	{
 		std::lock_guard<std::mutex> lk(mu_dev);
 		tok.drained(st);
 		tiles.drained(st);
+		frame.drained(st);
 	}
 	// member index scratch (hd_index.hpp): the bitmap and tile counts of the blob, the candidate list and its successor
 	// tables.  An index call waits for its stream before it returns, so calls take turns by holding mu_index.
@@ -685,6 +689,7 @@ void hipdeflate_shutdown(void)
 		(void)hipStreamDestroy(g.stream);
 		g.tok.reset();
 		g.tiles.reset();
+		g.frame.reset();
 		g.beside.release();
 		g.d_ct = nullptr;
 		g.stream = nullptr;
@@ -886,6 +891,106 @@ int hipdeflate_batch_inflate_flush_dev(const void *in, const void *in_off, const
 {
 	return batch_inflate_dev(in, in_off, in_len, nblocks, out, out_off, out_cap, out_len, crc32, status, stream,
 				 hd::INF_FLUSHED);
+}
+
+/* ---- zlib / gzip members: header, inflate, trailer (hd_frame.hpp), and the size pass (hd_inflate_size.hpp) ---- */
+
+static inline bool member_frame_ok(int frame) { return frame == HD_FRAME_RAW || frame == HD_FRAME_ZLIB || frame == HD_FRAME_GZIP; }
+
+// the payload table of one call in g.frame (the caller holds g.mu_dev and has entered): p_off u64 | p_len, verdict, used, chk u32
+struct FrameTable {
+	uint64_t *p_off;
+	uint32_t *p_len;
+	int32_t *verdict;
+	uint32_t *used, *chk;
+};
+static int frame_table(Ctx &g, uint32_t n, hipStream_t st, FrameTable &t)
+{
+	if (g.frame.buf.grow_keep_old((size_t)n * 24))
+		return HD_E_NOMEM;
+	t.p_off = (uint64_t *)g.frame.buf.p;
+	t.p_len = (uint32_t *)(t.p_off + n);
+	t.verdict = (int32_t *)(t.p_len + n);
+	t.used = (uint32_t *)(t.verdict + n);
+	t.chk = t.used + n;
+	return g.frame.enter(st);
+}
+
+int hipdeflate_batch_inflate_size_dev(const void *in, const void *in_off, const void *in_len, uint32_t nblocks, int frame,
+				      void *out_size, void *in_used, void *status, void *stream)
+{
+	Ctx &g = cur();
+	int r = ensure();
+	if (r)
+		return r;
+	if (!member_frame_ok(frame) || !out_size || !in_used || !status)
+		return HD_E_ARG;
+	if (nblocks == 0)
+		return 0;
+	hipStream_t st = (hipStream_t)stream;
+	if (frame == HD_FRAME_RAW) {                                  // no headers: the caller's tables are the payload table
+		hipLaunchKernelGGL(hd::k_inflate_size, dim3(nblocks), dim3(64), 0, st,
+				   hd::SizeArgs{ (const uint8_t *)in, (const uint64_t *)in_off, (const uint32_t *)in_len, nullptr, nullptr, nblocks,
+						 0u, (uint32_t *)out_size, (uint32_t *)in_used, (int32_t *)status });
+		HD_CHECK(hipGetLastError());
+		return 0;
+	}
+	std::lock_guard<std::mutex> lk(g.mu_dev);
+	FrameTable t;
+	if ((r = frame_table(g, nblocks, st, t)))
+		return r;
+	hipLaunchKernelGGL(hd::k_frame_open, dim3(nblocks), dim3(64), 0, st, (const uint8_t *)in, (const uint64_t *)in_off,
+			   (const uint32_t *)in_len, nblocks, frame, t.p_off, t.p_len, t.verdict);
+	hipLaunchKernelGGL(hd::k_inflate_size, dim3(nblocks), dim3(64), 0, st,
+			   hd::SizeArgs{ (const uint8_t *)in, t.p_off, t.p_len, (const uint64_t *)in_off, t.verdict, nblocks,
+					 frame == HD_FRAME_GZIP ? 8u : 4u, (uint32_t *)out_size, (uint32_t *)in_used, (int32_t *)status });
+	HD_CHECK(hipGetLastError());
+	return g.frame.leave(st);
+}
+
+int hipdeflate_batch_inflate_framed_dev(const void *in, const void *in_off, const void *in_len, uint32_t nblocks, int frame,
+					void *out, const void *out_off, const void *out_cap, void *out_len, void *check,
+					void *in_used, void *status, void *stream)
+{
+	Ctx &g = cur();
+	int r = ensure();
+	if (r)
+		return r;
+	if (!member_frame_ok(frame) || !out_len || !status)
+		return HD_E_ARG;
+	if (nblocks == 0)
+		return 0;
+	hipStream_t st = (hipStream_t)stream;
+	hd::InflateArgs a = { (const uint8_t *)in, (const uint64_t *)in_off, (const uint32_t *)in_len, nblocks, (uint8_t *)out,
+			      (const uint64_t *)out_off, (const uint32_t *)out_cap, (uint32_t *)out_len, (uint32_t *)check,
+			      (int32_t *)status, g.d_ct, 0 };
+	if (frame == HD_FRAME_RAW) {                                  // no header, no trailer: the inflate's answer is the member's
+		if (in_used)
+			hipLaunchKernelGGL(hd::k_inflate_framed, dim3(nblocks), dim3(64), 0, st, hd::InflateFramedArgs{ a, (uint32_t *)in_used });
+		else
+			hipLaunchKernelGGL(hd::k_inflate, dim3(nblocks), dim3(64), 0, st, a);
+		HD_CHECK(hipGetLastError());
+		return 0;
+	}
+	std::lock_guard<std::mutex> lk(g.mu_dev);
+	FrameTable t;
+	if ((r = frame_table(g, nblocks, st, t)))
+		return r;
+	hipLaunchKernelGGL(hd::k_frame_open, dim3(nblocks), dim3(64), 0, st, (const uint8_t *)in, (const uint64_t *)in_off,
+			   (const uint32_t *)in_len, nblocks, frame, t.p_off, t.p_len, t.verdict);
+	a.in_off = t.p_off;
+	a.in_len = t.p_len;
+	a.crc = frame == HD_FRAME_GZIP ? t.chk : nullptr;
+	hipLaunchKernelGGL(hd::k_inflate_framed, dim3(nblocks), dim3(64), 0, st, hd::InflateFramedArgs{ a, t.used });
+	if (frame == HD_FRAME_ZLIB)                                   // (a member whose inflate failed has out_len 0: nothing is read)
+		hipLaunchKernelGGL(hd::k_chunk_adler, dim3(nblocks), dim3(64), 0, st, (const uint8_t *)out, (const uint64_t *)out_off,
+				   (const uint32_t *)out_len, (const uint32_t *)out_cap, nblocks, t.chk);
+	hipLaunchKernelGGL(hd::k_frame_close, dim3((nblocks + 255) / 256), dim3(256), 0, st, (const uint8_t *)in,
+			   (const uint64_t *)in_off, (const uint64_t *)t.p_off, (const int32_t *)t.verdict, (const uint32_t *)t.used,
+			   (const uint32_t *)t.chk, nblocks, frame, (uint32_t *)out_len, (uint32_t *)check, (uint32_t *)in_used,
+			   (int32_t *)status);
+	HD_CHECK(hipGetLastError());
+	return g.frame.leave(st);
 }
 
 int hipdeflate_scan_sizes_dev(const void *out_len, uint32_t nblocks, uint64_t base, void *dst_off, void *total,
@@ -1545,6 +1650,125 @@ int hipdeflate_batch_inflate_flush(const uint8_t *in, const uint64_t *in_off, co
 				   uint32_t *crc32, int32_t *status)
 {
 	return batch_inflate_host(in, in_off, in_len, nblocks, out, out_off, out_cap, out_len, crc32, status, hd::INF_FLUSHED);
+}
+
+// the members packed 16-byte aligned into pinned memory and sent over, their table into h_off / h_len (HD_E_ARG: one is too long)
+static int stage_members(Ctx &g, const uint8_t *in, const uint64_t *in_off, const uint32_t *in_len, uint32_t nblocks,
+			 uint64_t *h_off, uint32_t *h_len)
+{
+	size_t in_total = 0;
+	for (uint32_t i = 0; i < nblocks; i++) {
+		if (in_len[i] >= HD_INFLATE_MAX_IN)
+			return HD_E_ARG;
+		in_total += up16(in_len[i]);
+	}
+	if (g.h_in.reserve(in_total + 16) || g.d_in.reserve(in_total + 16))
+		return HD_E_NOMEM;
+	uint8_t *hin = (uint8_t *)g.h_in.p;
+	size_t io = 0;
+	for (uint32_t i = 0; i < nblocks; i++) {
+		h_off[i] = io;
+		h_len[i] = in_len[i];
+		if (in_len[i])
+			memcpy(hin + io, in + in_off[i], in_len[i]);
+		io += up16(in_len[i]);
+	}
+	HD_CHECK(hipMemcpyAsync(g.d_in.p, hin, in_total, hipMemcpyHostToDevice, g.stream));
+	return 0;
+}
+
+int hipdeflate_batch_inflate_size(const uint8_t *in, const uint64_t *in_off, const uint32_t *in_len, uint32_t nblocks, int frame,
+				  uint32_t *out_size, uint32_t *in_used, int32_t *status)
+{
+	Ctx &g = cur();
+	int r = ensure();
+	if (r)
+		return r;
+	if (!member_frame_ok(frame) || !out_size || !in_used || !status)
+		return HD_E_ARG;
+	if (nblocks == 0)
+		return 0;
+	if (!in_off || !in_len)
+		return HD_E_ARG;
+	std::lock_guard<std::mutex> lk(g.mu);
+	if ((r = bind_device()))
+		return r;
+	// in_off u64 | in_len, out_size, in_used, status u32
+	const size_t n = nblocks, meta_bytes = 24 * n;
+	if (g.h_meta.reserve(meta_bytes) || g.d_meta.reserve(meta_bytes))
+		return HD_E_NOMEM;
+	uint64_t *h_off = (uint64_t *)g.h_meta.p, *d_off = (uint64_t *)g.d_meta.p;
+	uint32_t *h_len = (uint32_t *)(h_off + n), *d_len = (uint32_t *)(d_off + n);
+	if ((r = stage_members(g, in, in_off, in_len, nblocks, h_off, h_len)))
+		return r;
+	HD_CHECK(hipMemcpyAsync(d_off, h_off, 12 * n, hipMemcpyHostToDevice, g.stream));
+	if ((r = hipdeflate_batch_inflate_size_dev(g.d_in.p, d_off, d_len, nblocks, frame, d_len + n, d_len + 2 * n, d_len + 3 * n, g.stream)))
+		return r;
+	HD_CHECK(hipMemcpyAsync(h_len + n, d_len + n, 12 * n, hipMemcpyDeviceToHost, g.stream));
+	HD_CHECK(hipStreamSynchronize(g.stream));
+	g.stream_drained(g.stream);
+	memcpy(out_size, h_len + n, 4 * n);
+	memcpy(in_used, h_len + 2 * n, 4 * n);
+	memcpy(status, h_len + 3 * n, 4 * n);
+	return 0;
+}
+
+int hipdeflate_batch_inflate_framed(const uint8_t *in, const uint64_t *in_off, const uint32_t *in_len, uint32_t nblocks, int frame,
+				    uint8_t *out, const uint64_t *out_off, const uint32_t *out_cap, uint32_t *out_len,
+				    uint32_t *check, uint32_t *in_used, int32_t *status)
+{
+	Ctx &g = cur();
+	int r = ensure();
+	if (r)
+		return r;
+	if (!member_frame_ok(frame) || !out_len || !status)
+		return HD_E_ARG;
+	if (nblocks == 0)
+		return 0;
+	if (!in_off || !in_len || !out_off || !out_cap)
+		return HD_E_ARG;
+	std::lock_guard<std::mutex> lk(g.mu);
+	if ((r = bind_device()))
+		return r;
+	// the decode table, and in_used as one more column behind it
+	const size_t n = nblocks, meta_bytes = hd::DecTable::bytes(n) + 4 * n;
+	size_t out_total = 0;
+	for (uint32_t i = 0; i < nblocks; i++)
+		out_total += up16(out_cap[i]);
+	if (g.h_meta.reserve(meta_bytes) || g.d_meta.reserve(meta_bytes) || g.d_slots.reserve(out_total + 16) ||
+	    g.h_out.reserve(out_total + 16))
+		return HD_E_NOMEM;
+	const hd::DecTable h(g.h_meta.p, n), d(g.d_meta.p, n);
+	uint32_t *h_used = (uint32_t *)((uint8_t *)g.h_meta.p + hd::DecTable::bytes(n));
+	uint32_t *d_used = (uint32_t *)((uint8_t *)g.d_meta.p + hd::DecTable::bytes(n));
+	if ((r = stage_members(g, in, in_off, in_len, nblocks, h.in_off(), h.in_len())))
+		return r;
+	size_t oo = 0;
+	for (uint32_t i = 0; i < nblocks; i++) {
+		h.out_off()[i] = oo;
+		h.out_cap()[i] = out_cap[i];
+		oo += up16(out_cap[i]);
+	}
+	HD_CHECK(table_copy(d, h, h.inputs(), hipMemcpyHostToDevice, g.stream));
+	if ((r = hipdeflate_batch_inflate_framed_dev(g.d_in.p, d.in_off(), d.in_len(), nblocks, frame, g.d_slots.p, d.out_off(), d.out_cap(),
+						     d.out_len(), d.crc(), d_used, d.status(), g.stream)))
+		return r;
+	HD_CHECK(table_copy(h, d, h.results_crc(), hipMemcpyDeviceToHost, g.stream));
+	HD_CHECK(hipMemcpyAsync(h_used, d_used, 4 * n, hipMemcpyDeviceToHost, g.stream));
+	HD_CHECK(hipMemcpyAsync(g.h_out.p, g.d_slots.p, out_total, hipMemcpyDeviceToHost, g.stream));
+	HD_CHECK(hipStreamSynchronize(g.stream));
+	g.stream_drained(g.stream);
+	for (uint32_t i = 0; i < nblocks; i++) {
+		out_len[i] = h.out_len()[i];
+		status[i] = h.status()[i];
+		if (check)
+			check[i] = h.crc()[i];
+		if (in_used)
+			in_used[i] = h_used[i];
+		if (status[i] == 0 && out_len[i])
+			memcpy(out + out_off[i], (const uint8_t *)g.h_out.p + h.out_off()[i], out_len[i]);
+	}
+	return 0;
 }
 
 /* ---- streaming encoder and decoder (SlotRing above) -------------------------------- */

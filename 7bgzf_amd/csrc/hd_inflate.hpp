@@ -42,6 +42,10 @@ struct InflateArgs {
 	const CrcTables *ct;
 	uint32_t flags;
 };
+// k_inflate_framed's: one more result, the bytes of the stream consumed, rounded up to a whole byte (0 on failure)
+struct InflateFramedArgs : InflateArgs {
+	uint32_t *used;
+};
 
 // InflateArgs::flags: a stream may stop after a non-final block once every input byte is used -- the chunks of
 // 7dictzip / 7razf end in a full-flush marker, not in a final block, and the reference reads them with inflaters
@@ -262,9 +266,11 @@ __device__ __noinline__ uint32_t slow_decode(uint64_t bb, const uint16_t *count,
 }
 
 // the decoder, for an output ring of RING bytes (one wavefront; L is the workgroup's LDS)
-template <uint32_t RING>
-__device__ __forceinline__ void inflate_stream(const InflateArgs &a, InfLdsT<RING> &L)
+// Args = InflateFramedArgs: the bytes consumed leave next to out_len (the framed decode finds the trailer there: hd_frame.hpp)
+template <uint32_t RING, class Args = InflateArgs>
+__device__ __forceinline__ void inflate_stream(const Args &a, InfLdsT<RING> &L)
 {
+	constexpr bool USED = std::is_same<Args, InflateFramedArgs>::value;
 	constexpr uint32_t INF_NEAR = RING - 258 - 64;       // dist <= this: source is in the ring
 	const uint32_t lane = threadIdx.x;
 	const uint32_t b = blockIdx.x;
@@ -280,6 +286,8 @@ __device__ __forceinline__ void inflate_stream(const InflateArgs &a, InfLdsT<RIN
 			a.out_len[b] = 0;
 			if (a.crc) a.crc[b] = 0;
 			if (a.status) a.status[b] = HD_BAD_DATA;
+			if constexpr (USED)
+				a.used[b] = 0;
 		}
 		return;
 	}
@@ -1015,6 +1023,8 @@ __device__ __forceinline__ void inflate_stream(const InflateArgs &a, InfLdsT<RIN
 		a.out_len[b] = st == HD_OK ? pos : 0;
 		if (a.status) a.status[b] = st;
 		if (a.crc) a.crc[b] = crcv;
+		if constexpr (USED)
+			a.used[b] = st == HD_OK ? (uint32_t)((consumed_bits() + 7) >> 3) : 0u;
 	}
 	INF_T1(3, t_kernel);
 	INF_CYC_FLUSH;
@@ -1022,6 +1032,15 @@ __device__ __forceinline__ void inflate_stream(const InflateArgs &a, InfLdsT<RIN
 
 // throughput form: thousands of streams per launch, 25 workgroups' worth of LDS per CU
 __global__ __launch_bounds__(64) void k_inflate(InflateArgs a)
+{
+	__shared__ InfLds L;
+	inflate_stream<INF_RING>(a, L);
+}
+
+// ... with the bytes consumed as one more result: an instantiation of its own with arguments of its own, launched by the
+// framed decode alone, so that the kernel every other path launches stays what it was, instruction for instruction (it stands
+// three registers below an occupancy step)
+__global__ __launch_bounds__(64) void k_inflate_framed(InflateFramedArgs a)
 {
 	__shared__ InfLds L;
 	inflate_stream<INF_RING>(a, L);

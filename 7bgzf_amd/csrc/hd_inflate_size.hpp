@@ -1,0 +1,431 @@
+// hd_inflate_size.hpp -- the size pass: how many bytes a DEFLATE stream decodes to, without decoding them.
+//
+// Role: the first of the two inflates of applet/7png.c:114-181, which runs the IDAT stream into a throw-away buffer only
+// to count declen, and the "get decompressed size" call of other device DEFLATE libraries: a stream whose size nobody
+// stated.  One wavefront per stream, hd_inflate.hpp's decoder with everything taken out that moves bytes:
+//
+//   kept   the bit reader, the block headers, build_table / slow_decode and the entry formats, the window decode (every
+//          lane decodes the token at its two bit offsets, the scalar walk follows the chain), the scalar token path for
+//          what a window cannot take, and EVERY verdict of the full decoder: table rejects, over-subscribed codes, input
+//          overrun, LEN / NLEN, a distance past the bytes out so far;
+//   gone   the ring, the window's output budget, the flush, the copies, the CRC, the tables' copy in registers.
+//
+// What is left of the output is its position: 64 bits, and a stream that reaches 2^32 bytes is answered
+// HD_INSUFFICIENT_SPACE where it does -- what the full decoder answers in the largest room its 32-bit tables can state.
+// The distance check `offset > pos` can fail only while fewer than 32 KiB are out and is skipped afterwards, as the
+// front of k_inflate_lat does.  A stored block is a seek.
+//
+// LDS: the two direct tables, the sorted symbols and counts of the slow path, and one union of the code lengths (header)
+// with the stream copy (windows): 4288 bytes = four 1280-byte allocation units, 32 wavefronts per CU (k_inflate: five, 25).
+#pragma once
+#include "hd_inflate.hpp"
+
+namespace hd {
+
+struct SizeArgs {
+	const uint8_t *in;
+	const uint64_t *p_off;           // the DEFLATE payloads: the caller's own tables (HD_FRAME_RAW) or k_frame_open's
+	const uint32_t *p_len;
+	const uint64_t *m_off;           // where each member starts (its header counts into in_used); nullptr: at p_off
+	const int32_t *verdict;          // k_frame_open's verdict on the header; nullptr: no headers
+	uint32_t nblocks;
+	uint32_t trailer;                // bytes behind the stream: 0, 4 (Adler-32: not examined) or 8 (CRC-32: not examined, ISIZE: examined)
+	uint32_t *out_size;
+	uint32_t *in_used;
+	int32_t *status;
+};
+
+struct InfSizeLds {
+	uint32_t lit[1u << INF_LT_BITS];
+	uint32_t off[1u << INF_DT_BITS];
+	uint16_t lit_sorted[288];
+	uint16_t off_sorted[32];
+	uint16_t lit_count[16], off_count[16];
+	union {
+		struct {
+			uint8_t cl[288 + 32 + 138 + 6];   // + worst-case RLE overrun; the table builder's scratch at INF_T_SCRATCH
+			uint8_t pre_lens[32];
+		};
+		uint32_t comp[128];                   // 2 pieces of the compressed stream for the window decoder
+	};
+};
+static_assert(sizeof(InfSizeLds) <= 4 * 1280, "InfSizeLds must stay within four LDS allocation units");
+
+__global__ __launch_bounds__(64) void k_inflate_size(SizeArgs a)
+{
+	__shared__ InfSizeLds L;
+	const uint32_t lane = threadIdx.x;
+	const uint32_t b = blockIdx.x;
+	if (b >= a.nblocks)
+		return;
+	const uint64_t p_off = a.p_off[b];
+	const uint8_t *src = a.in + p_off;
+	const uint32_t n = a.p_len[b];
+	if (n >= HD_INFLATE_MAX_IN || (a.verdict && a.verdict[b])) {
+		// (stream positions are 32-bit bit counts, as in k_inflate: a stream this long is refused whole)
+		if (lane == 0) {
+			a.out_size[b] = 0;
+			a.in_used[b] = 0;
+			a.status[b] = HD_BAD_DATA;
+		}
+		return;
+	}
+
+	// ---- compressed input: hd_inflate.hpp's reader, statement for statement ----
+	const uint32_t mis = (uint32_t)((uintptr_t)src & 3);
+	const uint32_t *src32 = (const uint32_t *)(src - mis);
+	const uint32_t nbytes_al = mis + n;
+	auto load_piece = [&](uint32_t piece) -> uint32_t {
+		const uint32_t d = piece * 64 + lane;
+		uint32_t w = 0;
+		if (d * 4 < nbytes_al) {
+			w = src32[d];
+			const uint32_t valid = nbytes_al - d * 4;
+			if (valid < 4)
+				w &= (1u << (8 * valid)) - 1;
+		}
+		return w;
+	};
+	uint32_t cur_piece = 0;
+	uint32_t cw = load_piece(0), cw_next = load_piece(1);
+	uint32_t dw = 0;
+	uint64_t bb = 0;
+	uint32_t bc = 0;
+	auto next_dword = [&]() -> uint32_t {
+		const uint32_t piece = dw >> 6;
+		if (piece != cur_piece) {
+			cw = cw_next;
+			cur_piece = piece;
+			cw_next = load_piece(piece + 1);
+		}
+		const uint32_t w = readlane(cw, dw & 63);
+		dw++;
+		return w;
+	};
+	auto refill = [&]() {
+		if (bc <= 32) {
+			bb |= (uint64_t)next_dword() << bc;
+			bc += 32;
+		}
+	};
+	auto consumed_bits = [&]() -> int64_t { return (int64_t)dw * 32 - bc - 8 * (int64_t)mis; };
+	const uint32_t over_t = 8 * n + 64 + 8 * mis;
+	auto overrun = [&]() -> bool { return (dw << 5) - bc > over_t; };
+	auto seek_bit = [&](uint32_t B) {              // restart the bit reader at bit B from src32
+		dw = B >> 5;
+		const uint32_t piece = dw >> 6;
+		if (piece != cur_piece) {
+			if (piece == cur_piece + 1)
+				cw = cw_next;
+			else
+				cw = load_piece(piece);
+			cur_piece = piece;
+			cw_next = load_piece(piece + 1);
+		}
+		bb = 0;
+		bc = 0;
+		refill();
+		bb >>= (B & 31);
+		bc -= (B & 31);
+	};
+	refill();
+	bb >>= 8 * mis;
+	bc -= 8 * mis;
+
+	uint64_t pos = 0;                              // bytes the stream has decoded to so far (uniform)
+	constexpr uint64_t POS_LIMIT = 0xffffffffull;  // the largest room a u32 table states: past it the answer is "does not fit"
+
+	// ---- window decode: hd_inflate.hpp's, without its byte work --------------------------------------------------
+	// Every lane decodes the tokens that would start at bit B + lane and B + 64 + lane; the scalar walk (the same
+	// statement) follows the real chain and stops in front of the first token a window cannot take.  There is no budget
+	// to cut at: what the real tokens put out is one prefix sum, and its total moves the position.
+	// Returns 0 = one token through the scalar path, 2 = error (st set).
+	const uint32_t dw_safe = (mis + n) >> 2;
+	uint32_t lds_p0 = 0xfffffff0u;
+	uint32_t pre_piece = 0, pre_idx = 0xfffffff0u;
+	auto run_windows = [&](int32_t &st_out) -> uint32_t {
+		uint32_t B = (dw << 5) - bc;
+		uint32_t result = 0;
+		for (;;) {
+			const uint32_t d0 = B >> 5;
+			if (!(d0 + 7 <= dw_safe))
+				break;
+			const uint32_t p0 = d0 >> 6;
+			if (p0 != lds_p0) {
+				if (p0 == lds_p0 + 1)
+					L.comp[lane] = L.comp[64 + lane];
+				else
+					L.comp[lane] = load_piece(p0);
+				L.comp[64 + lane] = pre_idx == p0 + 1 ? pre_piece : load_piece(p0 + 1);
+				pre_piece = load_piece(p0 + 2);
+				pre_idx = p0 + 2;
+				lds_p0 = p0;
+			}
+			struct Spec {
+				uint32_t offset, outlen, walk;
+				uint64_t is_len;
+			};
+			const uint32_t bl0 = (B & 31) + lane;
+			const uint32_t *wsp = &L.comp[(d0 & 63) + (bl0 >> 5)];
+			const uint32_t ws0 = wsp[0], ws1 = wsp[1], ws2 = wsp[2], ws3 = wsp[3], ws4 = wsp[4];
+			auto spec = [&](uint32_t bl, uint32_t lo, uint32_t mid, uint32_t hi) -> Spec {
+				Spec r;
+				const uint32_t a0 = __builtin_amdgcn_alignbit(mid, lo, bl & 31);
+				const uint32_t bq = __builtin_amdgcn_alignbit(hi, mid, bl & 31);
+				const uint32_t e = L.lit[a0 & ((1u << INF_LT_BITS) - 1)];
+				const uint32_t len1 = e & 15, eb = (e >> 4) & 15;
+				const uint32_t length = (e >> 16) + __builtin_amdgcn_ubfe(a0, len1, eb);
+				const uint32_t t1 = len1 + eb;
+				const uint32_t rest = __builtin_amdgcn_alignbit(bq, a0, t1);
+				const uint32_t dd = L.off[rest & ((1u << INF_DT_BITS) - 1)];
+				const uint32_t kind2 = e & 0x300;
+				r.is_len = __ballot(kind2 == (K_LEN << 8));
+				const uint64_t is_lit = __ballot(kind2 == (K_LIT << 8));
+				const uint32_t ddm = sel(r.is_len, dd, 0u);
+				const uint32_t dlen = ddm & 15, deb = (ddm >> 4) & 15;
+				r.offset = (ddm >> 16) + __builtin_amdgcn_ubfe(rest, dlen, deb);
+				const uint32_t tokbits = t1 + dlen + deb;
+				r.outlen = sel(is_lit, 1u, sel(r.is_len, length, 0u));
+				const uint32_t tb1 = tokbits ? tokbits : 1u;
+				r.walk = tb1 | ((e >> 3) & 64u) | ((ddm >> 3) & 64u);
+				return r;
+			};
+			const Spec s0 = spec(bl0, ws0, ws1, ws2), s1 = spec(bl0 + 64, ws2, ws3, ws4);
+			// (hd_inflate.hpp explains the walk: 3 SALU + 1 branch + 1 v_readlane per token, the stop flag is bit 6 of the word
+			// that is added to the position)
+			uint32_t wb, wm;
+			uint64_t real0, real1;
+			asm volatile("s_mov_b32 %0, 0\n\t"
+				     "s_mov_b64 %1, 0\n\t"
+				     "s_mov_b64 %2, 0\n"
+				     "Lhd_szwalk0_%=:\n\t"
+				     "v_readlane_b32 %3, %4, %0\n\t"
+				     "s_bitset1_b64 %1, %0\n\t"
+				     "s_add_u32 %0, %0, %3\n\t"
+				     "s_cmp_lt_u32 %0, 64\n\t"
+				     "s_cbranch_scc1 Lhd_szwalk0_%=\n\t"
+				     "s_bitcmp1_b32 %3, 6\n\t"
+				     "s_cbranch_scc0 Lhd_szwalk1_%=\n\t"
+				     "s_sub_u32 %0, %0, %3\n\t"
+				     "s_bitset0_b64 %1, %0\n\t"
+				     "s_branch Lhd_szwalk_done_%=\n"
+				     "Lhd_szwalk1_%=:\n\t"
+				     "v_readlane_b32 %3, %5, %0\n\t"
+				     "s_bitset1_b64 %2, %0\n\t"
+				     "s_add_u32 %0, %0, %3\n\t"
+				     "s_cmp_lt_u32 %0, 128\n\t"
+				     "s_cbranch_scc1 Lhd_szwalk1_%=\n\t"
+				     "s_bitcmp1_b32 %3, 6\n\t"
+				     "s_cbranch_scc0 Lhd_szwalk_done_%=\n\t"
+				     "s_sub_u32 %0, %0, %3\n\t"
+				     "s_bitset0_b64 %2, %0\n"
+				     "Lhd_szwalk_done_%=:"
+				     : "=&s"(wb), "=&s"(real0), "=&s"(real1), "=&s"(wm)
+				     : "v"(s0.walk), "v"(s1.walk)
+				     : "scc");
+			if (real0 == 0)
+				break;                                     // the token at B is not for a window: scalar path
+			// (both halves' output lengths in one prefix sum, 16 bits each: 64 x 258 < 2^16)
+			const uint32_t scn = wave_incl_scan(sel(real0, s0.outlen, 0u) | (sel(real1, s1.outlen, 0u) << 16));
+			const uint32_t tot = readlane(scn, 63);
+			if (pos < 32768) {
+				// offset > bytes out so far (decompress_template.h:724): only this early can it be
+				const uint32_t opos0 = (uint32_t)pos + (scn & 0xffff) - s0.outlen;
+				const uint32_t opos1 = (uint32_t)pos + (scn >> 16) + (tot & 0xffff) - s1.outlen;
+				const uint64_t far0 = __ballot(opos0 < s0.offset), far1 = __ballot(opos1 < s1.offset);
+				if ((far0 & real0 & s0.is_len) | (far1 & real1 & s1.is_len)) {
+					st_out = HD_BAD_DATA;
+					result = 2;
+					break;
+				}
+			}
+			pos += (tot & 0xffff) + (tot >> 16);
+			B += wb;
+			if (pos > POS_LIMIT) {
+				st_out = HD_INSUFFICIENT_SPACE;
+				result = 2;
+				break;
+			}
+			if (wm & 64)
+				break;                                     // the walk stopped in front of a long codeword or the end of the block
+		}
+		seek_bit(B);
+		return result;
+	};
+
+	int32_t st = HD_OK;
+	bool static_loaded = false;
+	for (;;) {
+		refill();
+		lds_p0 = 0xfffffff0u;                     // header parsing reuses the LDS behind L.comp
+		const uint32_t bfinal = (uint32_t)bb & 1;
+		const uint32_t btype = ((uint32_t)bb >> 1) & 3;
+		bb >>= 3;
+		bc -= 3;
+
+		if (btype == 0) {
+			// ---- stored (decompress_template.h:234-279): a seek ------------
+			const int64_t cbits = (consumed_bits() + 7) & ~(int64_t)7;
+			if (cbits > 8 * (int64_t)n) { st = HD_BAD_DATA; break; }
+			uint32_t ip = (uint32_t)(cbits >> 3);
+			if (n - ip < 4) { st = HD_BAD_DATA; break; }
+			seek_bit(8 * (mis + ip));
+			refill();
+			const uint32_t len = (uint32_t)bb & 0xffff, nlen = ((uint32_t)bb >> 16) & 0xffff;
+			ip += 4;
+			if (len != (~nlen & 0xffff)) { st = HD_BAD_DATA; break; }
+			if (pos + len > POS_LIMIT) { st = HD_INSUFFICIENT_SPACE; break; }
+			if (len > n - ip) { st = HD_BAD_DATA; break; }
+			pos += len;
+			seek_bit(8 * (mis + ip + len));
+		} else if (btype == 3) {
+			st = HD_BAD_DATA;
+			break;
+		} else {
+			uint32_t nlit = 288, noff = 32;
+			if (btype == 2) {
+				// ---- dynamic header: decompress_template.h:101-232 -------
+				refill();
+				nlit = 257 + ((uint32_t)bb & 31);
+				noff = 1 + (((uint32_t)bb >> 5) & 31);
+				const uint32_t npre = 4 + (((uint32_t)bb >> 10) & 15);
+				bb >>= 14;
+				bc -= 14;
+				if (lane < 19)
+					L.pre_lens[lane] = 0;
+				for (uint32_t i = 0; i < npre; i++) {
+					refill();
+					if (lane == 0)
+						L.pre_lens[k_precode_perm[i]] = (uint8_t)((uint32_t)bb & 7);
+					bb >>= 3;
+					bc -= 3;
+				}
+				if (!uniform(build_table<2>(L.pre_lens, 19, L.lit, 7, L.lit_sorted, nullptr, L.cl + INF_T_SCRATCH, lane))) { st = HD_BAD_DATA; break; }
+				uint8_t *cl = L.cl;
+				uint32_t i = 0, prev = 0;
+				bool bad = false;
+				while (i < nlit + noff) {
+					refill();
+					if (consumed_bits() > 8 * (int64_t)n + 64) { bad = true; break; }
+					const uint32_t e = uniform(L.lit[(uint32_t)bb & 127]);
+					const uint32_t cl_len = e & 15, s = e >> 16;
+					bb >>= cl_len;
+					bc -= cl_len;
+					if (s < 16) {
+						if (lane == 0)
+							cl[i] = (uint8_t)s;
+						prev = s;
+						i++;
+						continue;
+					}
+					uint32_t rep, val = 0;
+					if (s == 16) {
+						if (i == 0) { bad = true; break; }
+						rep = 3 + ((uint32_t)bb & 3);
+						bb >>= 2; bc -= 2;
+						val = prev;
+					} else if (s == 17) {
+						rep = 3 + ((uint32_t)bb & 7);
+						bb >>= 3; bc -= 3;
+						prev = 0;
+					} else {
+						rep = 11 + ((uint32_t)bb & 127);
+						bb >>= 7; bc -= 7;
+						prev = 0;
+					}
+					for (uint32_t k = lane; k < rep; k += 64)
+						cl[i + k] = (uint8_t)val;
+					i += rep;
+				}
+				if (bad || i != nlit + noff) { st = HD_BAD_DATA; break; }
+				static_loaded = false;
+				if (!uniform(build_table<1>(cl + nlit, noff, L.off, INF_DT_BITS, L.off_sorted, L.off_count, L.cl + INF_T_SCRATCH, lane)) ||
+				    !uniform(build_table<0>(cl, nlit, L.lit, INF_LT_BITS, L.lit_sorted, L.lit_count, L.cl + INF_T_SCRATCH, lane))) {
+					st = HD_BAD_DATA;
+					break;
+				}
+			} else if (!static_loaded) {
+				// ---- static code: decompress_template.h:297-330 ----------
+				uint8_t *cl = L.cl;
+				for (uint32_t s = lane; s < 320; s += 64)
+					cl[s] = s < 144 ? 8 : s < 256 ? 9 : s < 280 ? 7 : s < 288 ? 8 : 5;
+				build_table<1>(cl + 288, 32, L.off, INF_DT_BITS, L.off_sorted, L.off_count, L.cl + INF_T_SCRATCH, lane);
+				build_table<0>(cl, 288, L.lit, INF_LT_BITS, L.lit_sorted, L.lit_count, L.cl + INF_T_SCRATCH, lane);
+				static_loaded = true;
+			}
+
+			// ---- symbol loop ----------------------------------------------
+			for (;;) {
+				if (uniform(run_windows(st)))
+					break;
+				// one token through the fully checked scalar path (stream edges, long codes, end of block); the
+				// tables are read from LDS: no copy of them in registers, this kernel answers to occupancy
+				refill();
+				if (overrun()) { st = HD_BAD_DATA; break; }
+				uint32_t e = uniform(L.lit[(uint32_t)bb & ((1u << INF_LT_BITS) - 1)]);
+				if (((e >> 8) & 3) == K_SLOW) {
+					const uint32_t sl = uniform(slow_decode(bb, L.lit_count, L.lit_sorted, lane));
+					e = litlen_entry(sl & 0xffff, sl >> 16);
+				}
+				const uint32_t clen = e & 15;
+				bb >>= clen;
+				bc -= clen;
+				const uint32_t kind = (e >> 8) & 3;
+				if (kind == K_LIT) {
+					if (pos == POS_LIMIT) { st = HD_INSUFFICIENT_SPACE; break; }
+					pos++;
+					continue;
+				}
+				if (kind == K_EOB)
+					break;
+				const uint32_t eb = (e >> 4) & 15;
+				const uint32_t length = (e >> 16) + ((uint32_t)bb & ((1u << eb) - 1));
+				bb >>= eb;
+				bc -= eb;
+				if (length > POS_LIMIT - pos) { st = HD_INSUFFICIENT_SPACE; break; }
+				refill();
+				uint32_t d = uniform(L.off[(uint32_t)bb & ((1u << INF_DT_BITS) - 1)]);
+				if (((d >> 8) & 3) == K_SLOW) {
+					const uint32_t sl = uniform(slow_decode(bb, L.off_count, L.off_sorted, lane));
+					d = offset_entry(sl & 0xffff, sl >> 16);
+				}
+				const uint32_t dlen = d & 15, deb = (d >> 4) & 15;
+				bb >>= dlen;
+				bc -= dlen;
+				const uint32_t offset = (d >> 16) + ((uint32_t)bb & ((1u << deb) - 1));
+				bb >>= deb;
+				bc -= deb;
+				if (offset > pos) { st = HD_BAD_DATA; break; }
+				pos += length;
+			}
+			if (st != HD_OK)
+				break;
+		}
+		if (bfinal)
+			break;
+		if (consumed_bits() > 8 * (int64_t)n + 64) { st = HD_BAD_DATA; break; }
+	}
+	if (st == HD_OK && consumed_bits() > 8 * (int64_t)n)
+		st = HD_BAD_DATA;
+
+	// ---- the verdict: the stream's, and the one field of the trailer that needs no byte of output ----
+	uint32_t used = 0;
+	if (st == HD_OK) {
+		used = (uint32_t)((consumed_bits() + 7) >> 3);
+		if (a.trailer == 8) {
+			// RFC 1952 ISIZE, behind the CRC-32 (gzip_decompress.c:124-127); used <= n, and k_frame_open left 8 bytes behind n
+			const uint8_t *t = src + used + 4;
+			const uint32_t isize = t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16) | ((uint32_t)t[3] << 24);
+			if (isize != (uint32_t)pos)
+				st = HD_BAD_DATA;
+		}
+	}
+	if (lane == 0) {
+		const uint32_t hdr = a.m_off ? (uint32_t)(p_off - a.m_off[b]) : 0u;
+		a.out_size[b] = st == HD_OK ? (uint32_t)pos : 0u;
+		a.in_used[b] = st == HD_OK ? hdr + used + a.trailer : 0u;
+		a.status[b] = st;
+	}
+}
+
+} // namespace hd

@@ -232,6 +232,42 @@ def device_inflate(comp, in_off, in_len, out, out_off, out_cap, out_len, crc, st
     _pkg._check(rc, "hipdeflate_batch_inflate_dev")
 
 
+def inflate_size_call(blob, in_off, in_len, frame, out_size, in_used, status):
+    """one hipdeflate_batch_inflate_size_dev over device tensors"""
+    rc = _pkg.lib().hipdeflate_batch_inflate_size_dev(_ptr(blob), _ptr(in_off), _ptr(in_len), in_off.numel(), frame,
+                                                      _ptr(out_size), _ptr(in_used), _ptr(status), _stream())
+    _pkg._check(rc, "hipdeflate_batch_inflate_size_dev")
+
+
+def inflate_framed_call(blob, in_off, in_len, frame, out, out_off, out_cap, out_len, check, in_used, status):
+    """one hipdeflate_batch_inflate_framed_dev over device tensors (check, in_used: a tensor or None)"""
+    rc = _pkg.lib().hipdeflate_batch_inflate_framed_dev(_ptr(blob), _ptr(in_off), _ptr(in_len), in_off.numel(), frame, _ptr(out),
+                                                        _ptr(out_off), _ptr(out_cap), _ptr(out_len), _ptr(check), _ptr(in_used),
+                                                        _ptr(status), _stream())
+    _pkg._check(rc, "hipdeflate_batch_inflate_framed_dev")
+
+
+def inflate_members(blob, in_off, in_len, frame=_pkg.FRAME_ZLIB):
+    """Decode the raw / zlib / gzip members blob[in_off[i]:in_off[i] + in_len[i]] (uint8 tensor; int64 and int32 device
+    tensors) whose sizes nobody stated: the size pass, the prefix sum of the sizes, ONE allocation, the framed decode.
+    -> (out, out_off, out_len, status): member i is out[out_off[i]:out_off[i] + out_len[i]], status[i] != 0 where it
+    failed (such a member takes no room).  Nothing visits the host but the total."""
+    n = in_off.numel()
+    dev = blob.device
+    out_size, in_used, status = (torch.zeros(n, dtype=torch.int32, device=dev) for _ in range(3))
+    out_off = torch.zeros(n, dtype=torch.int64, device=dev)
+    out_len = torch.zeros(n, dtype=torch.int32, device=dev)
+    total = torch.zeros(1, dtype=torch.int64, device=dev)
+    if n == 0:
+        return torch.empty(0, dtype=torch.uint8, device=dev), out_off, out_len, status
+    inflate_size_call(blob, in_off, in_len, frame, out_size, in_used, status)
+    rc = _pkg.lib().hipdeflate_scan_sizes_dev(_ptr(out_size), n, 0, _ptr(out_off), _ptr(total), _stream())
+    _pkg._check(rc, "hipdeflate_scan_sizes_dev")
+    out = torch.empty(int(total.item()), dtype=torch.uint8, device=dev)
+    inflate_framed_call(blob, in_off, in_len, frame, out, out_off, out_size, out_len, None, None, status)
+    return out, out_off, out_len, status
+
+
 def block_table(total_bytes, block_size, device="cuda"):
     nb = (total_bytes + block_size - 1) // block_size
     off = torch.arange(nb, dtype=torch.int64, device=device) * block_size

@@ -219,6 +219,54 @@ int hipdeflate_batch_inflate_flush_dev(const void *in, const void *in_off,
 				       void *out_len, void *crc32, void *status,
 				       void *stream);
 
+/* ---- zlib and gzip members, and the size pass ----------------------------------------
+ * The decoder's side of HD_FRAME_ZLIB / HD_FRAME_GZIP: nblocks members of RFC 1950 / RFC 1952 (or raw DEFLATE streams,
+ * HD_FRAME_RAW) anywhere in a device buffer -- PNG IDATs, the chunks of an array store, HTTP bodies, plain gzip members
+ * without a length field -- decoded without the host reading a byte.  Role: libdeflate_deflate_decompress_ex,
+ * libdeflate_zlib_decompress_ex (lib/libdeflate/zlib_decompress.c:31-91) and libdeflate_gzip_decompress_ex
+ * (gzip_decompress.c:30-133), by frame, per member; and for the size pass the first of the two inflates of
+ * applet/7png.c:114-181, which decodes a stream into a throw-away buffer only to learn its size.
+ * frame is HD_FRAME_RAW, HD_FRAME_ZLIB or HD_FRAME_GZIP (anything else, HD_FRAME_LATENCY included: HD_E_ARG).  Member i is
+ * in[in_off[i] .. +in_len[i]), at any byte offset; bytes behind its trailer are allowed.  All arrays are device arrays
+ * (in_off, out_off u64; the others u32, status i32), the calls are asynchronous as hipdeflate_batch_inflate_dev is.
+ *
+ * hipdeflate_batch_inflate_framed_dev: status[i] is what the reference function answers for member i with out_cap[i]
+ * bytes of room -- 0, 1 bad data (header, stream or trailer), 3 does not fit (decided before any check, as there):
+ *   gzip   18 bytes at least; 1f 8b 08; a reserved FLG bit (0xe0) is bad data; FEXTRA, FNAME, FCOMMENT and FHCRC must each
+ *          leave 8 bytes behind them; FHCRC is skipped, not verified; the CRC-32 and ISIZE (mod 2^32) of the trailer must hold;
+ *   zlib   6 bytes at least; FCHECK; CM 8; CINFO <= 7; FDICT is refused; the Adler-32 of the trailer must hold;
+ *   the stream may use at most in_len[i] - header - trailer bytes, and the trailer is read at the byte it really ended on.
+ * out_len[i] = bytes produced; check[i] (may be NULL) = the CRC-32 (RAW, GZIP) or Adler-32 (ZLIB) of the output;
+ * in_used[i] (may be NULL) = header + stream rounded up to a whole byte + trailer, the reference's actual_in_nbytes: added
+ * to in_off[i] it is where a member behind this one starts (the walk over concatenated members stays with the caller).
+ * All three are 0 for a member that fails.  No byte at or behind in_off[i] + in_len[i] is read, whatever a header
+ * claims; no byte of out outside [out_off[i], out_off[i] + out_len[i]) is written, beyond what
+ * hipdeflate_batch_inflate_dev writes: the decoded prefix of a member that fails, inside its room.  A member of
+ * HD_INFLATE_MAX_IN bytes or more has status 1.  out_len and status must not be NULL.
+ *
+ * hipdeflate_batch_inflate_size_dev writes nothing but its three result arrays (none may be NULL): status[i] is the framed
+ * call's with unlimited room, minus the one thing that needs the bytes -- the CRC-32 / Adler-32 value is not examined (the
+ * gzip ISIZE is); out_size[i] = the decoded length, in_used[i] as above.  A member that decodes to 2^32 bytes or more has
+ * status 3; a member that fails has out_size and in_used 0.  Status 0 therefore means that the framed call with out_cap[i]
+ * = out_size[i] can only fail on the check value.  A kernel of its own (one wavefront per member, no window, no output):
+ * cheaper than inflating into scratch.
+ * Scratch (the payload table, 24 bytes a member) is the library's, grow-only; calls on different streams take turns.
+ * nblocks == 0: returns 0 and writes nothing. */
+int hipdeflate_batch_inflate_size_dev(const void *in, const void *in_off, const void *in_len, uint32_t nblocks, int frame,
+				      void *out_size /* u32[n] */, void *in_used /* u32[n] */, void *status /* i32[n] */,
+				      void *stream);
+int hipdeflate_batch_inflate_framed_dev(const void *in, const void *in_off, const void *in_len, uint32_t nblocks, int frame,
+					void *out, const void *out_off, const void *out_cap,
+					void *out_len, void *check /* u32[n], may be NULL */, void *in_used /* may be NULL */,
+					void *status, void *stream);
+/* the host-buffer forms: staged through the device as hipdeflate_batch_inflate is; HD_E_ARG for a member of
+ * HD_INFLATE_MAX_IN bytes or more */
+int hipdeflate_batch_inflate_size(const uint8_t *in, const uint64_t *in_off, const uint32_t *in_len, uint32_t nblocks, int frame,
+				  uint32_t *out_size, uint32_t *in_used, int32_t *status);
+int hipdeflate_batch_inflate_framed(const uint8_t *in, const uint64_t *in_off, const uint32_t *in_len, uint32_t nblocks, int frame,
+				    uint8_t *out, const uint64_t *out_off, const uint32_t *out_cap,
+				    uint32_t *out_len, uint32_t *check, uint32_t *in_used, int32_t *status);
+
 /* Gather the variable-length members produced by batch_deflate_dev into one
  * contiguous stream: member i (out_len[i] bytes at slots + i*stride) goes to
  * dst + dst_off[i], where dst_off is the exclusive prefix sum of out_len (plus
