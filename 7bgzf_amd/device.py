@@ -250,8 +250,10 @@ def inflate_framed_call(blob, in_off, in_len, frame, out, out_off, out_cap, out_
 def inflate_members(blob, in_off, in_len, frame=_pkg.FRAME_ZLIB):
     """Decode the raw / zlib / gzip members blob[in_off[i]:in_off[i] + in_len[i]] (uint8 tensor; int64 and int32 device
     tensors) whose sizes nobody stated: the size pass, the prefix sum of the sizes, ONE allocation, the framed decode.
-    -> (out, out_off, out_len, status): member i is out[out_off[i]:out_off[i] + out_len[i]], status[i] != 0 where it
-    failed (such a member takes no room).  Nothing visits the host but the total."""
+    -> (out, out_off, out_len, status): member i is out[out_off[i]:out_off[i] + out_len[i]], status[i] != 0 and
+    out_len[i] == 0 where it failed.  A member the size pass refuses (header, stream, gzip ISIZE) takes no room; one that
+    fails only in the decode -- a wrong CRC-32 or Adler-32, which the size pass does not examine -- keeps the room of its
+    stated size, out_off[i + 1] - out_off[i], holding whatever was decoded.  Nothing visits the host but the total."""
     n = in_off.numel()
     dev = blob.device
     out_size, in_used, status = (torch.zeros(n, dtype=torch.int32, device=dev) for _ in range(3))

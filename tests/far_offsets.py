@@ -400,3 +400,95 @@ def check_stream(mem, exp, tile_stream, equal=None):
 def gzip_isize(stream_tail):
     """the ISIZE field of the last four bytes of a gzip stream"""
     return int.from_bytes(bytes(stream_tail)[-4:], "little")
+
+
+# ---- long streams: one inflate at the ends of its own 32-bit counters (families G and G2) ------------------------------
+
+def static_code(w, sym):
+    """one litlen symbol in the static code (RFC 1951 3.2.6)"""
+    if sym < 144:
+        w.huff(0x30 + sym, 8)
+    elif sym < 256:
+        w.huff(0x190 + sym - 144, 9)
+    elif sym < 280:
+        w.huff(sym - 256, 7)
+    else:
+        w.huff(0xc0 + sym - 280, 8)
+
+
+def static_match(w, length, dist):
+    import deflate_gen as dg
+    ls, ds = dg.len_sym(length), dg.dist_sym(dist)
+    static_code(w, ls)
+    w.bits(length - dg.LEN_BASE[ls - 257], dg.LEN_EXTRA[ls - 257])
+    w.huff(ds, 5)
+    w.bits(dist - dg.DIST_BASE[ds], dg.DIST_EXTRA[ds])
+
+
+def long_input_stream(nbytes, rng):
+    """a stream of exactly nbytes bytes: stored blocks of 65535 noise bytes (one block, tiled), a shorter one, and a final
+    static block of three literals -> (stream as numpy, the 65535-byte pattern, how often it repeats, the rest of the output)"""
+    import deflate_gen as dg
+    w = dg.BitWriter()
+    w.bits(1, 1)
+    w.bits(1, 2)
+    for ch in b"end":
+        static_code(w, ch)
+    static_code(w, 256)
+    last = w.value()
+    pattern = rng.integers(0, 256, 65535, dtype=np.uint8)
+    block = np.concatenate([np.frombuffer(b"\x00\xff\xff\x00\x00", dtype=np.uint8), pattern])
+    reps, left = divmod(nbytes - len(last), len(block))
+    assert 5 <= left
+    part = rng.integers(0, 256, left - 5, dtype=np.uint8)
+    head = np.frombuffer(b"\x00" + int(left - 5).to_bytes(2, "little") + int((left - 5) ^ 0xffff).to_bytes(2, "little"), dtype=np.uint8)
+    stream = np.concatenate([np.tile(block, reps), head, part, np.frombuffer(last, dtype=np.uint8)])
+    assert len(stream) == nbytes
+    return stream, pattern, reps, part.tobytes() + b"end"
+
+
+def long_output_stream(total):
+    """a small stream of `total` bytes of output: one stored block of 32 KiB of noise, then static-Huffman matches of length
+    258 at distance 32768 -- 26 bits each, so four of them are a 13-byte period of the stream, tiled -- a last match or two
+    for the remainder and the end of block -> (stream as numpy, the 32 KiB pattern)"""
+    import deflate_gen as dg
+    pattern = np.random.default_rng(31).integers(0, 256, 32768, dtype=np.uint8)
+    assert total % 32768 == 0 and total >= 32768 + 258 * 12
+    n258, rem = divmod(total - 32768, 258)
+    tail = []
+    if 0 < rem < 3:
+        n258, rem = n258 - 1, rem + 258
+        tail = [rem // 2, rem - rem // 2]
+    elif rem:
+        tail = [rem]
+    periods, extra = divmod(n258, 4)
+    w = dg.BitWriter()                                   # the final block with TWO periods: head byte | period | the rest
+    w.bits(1, 1)
+    w.bits(1, 2)
+    for length in [258] * (8 + extra) + tail:
+        static_match(w, length, 32768)
+    static_code(w, 256)
+    sample = w.value()
+    assert sample[1:14] == sample[14:27] or extra + len(tail) == 0
+    head = b"\x00\x00\x80\xff\x7f" + pattern.tobytes() + sample[:1]
+    stream = np.concatenate([np.frombuffer(head, dtype=np.uint8), np.tile(np.frombuffer(sample[1:14], dtype=np.uint8), periods - 1),
+                             np.frombuffer(sample[14:], dtype=np.uint8)])
+    return stream, pattern
+
+
+def framed_long_member(frame, stream, pattern, reps, rest=b""):
+    """a long stream of this file in a frame (0 raw, 4 zlib, 5 gzip: framed_gen's plain headers), its check value and ISIZE
+    by construction -- the output is `pattern` reps times and `rest`, so the CRC-32 / Adler-32 is stream_model.fold of the
+    parts' -> (member as numpy, check, bytes of output)"""
+    import framed_gen
+    kind, pat = sm.KIND[frame], pattern.tobytes()
+    lens = [len(pat)] * reps + ([len(rest)] if rest else [])
+    checks = [sm.part_check(pat, kind)] * reps + ([sm.part_check(rest, kind)] if rest else [])
+    check, total = sm.fold(checks, lens, kind), sum(lens)
+    head = {sm.FRAME_RAW: b"", sm.FRAME_ZLIB: framed_gen.zlib_header(), sm.FRAME_GZIP: framed_gen.gzip_header()}[frame]
+    member = np.concatenate([np.frombuffer(head, dtype=np.uint8), stream,
+                             np.frombuffer(sm.trailer(frame, check, total), dtype=np.uint8)])
+    return member, check, total
+
+
+LONG_OVERHEAD = {sm.FRAME_RAW: 0, sm.FRAME_ZLIB: 2 + 4, sm.FRAME_GZIP: 10 + 8}     # header + trailer of framed_long_member

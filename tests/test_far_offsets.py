@@ -7,6 +7,7 @@ import zlib
 import numpy as np
 import pytest
 
+import far_framed as ff
 import far_offsets as fo
 import hdtest
 import member_index_model as mm
@@ -321,3 +322,115 @@ def test_stream_checker_rejects_a_narrow_running_position(what):
     bad = fo.check_stream(mem, e, t.stream) + fo.check_table(table, e["chunk_off"], "chunk_off")
     assert (bad == []) == (what == "exact"), bad
     assert per == 5
+
+
+# ---- the framed family (D2, G2): the layout through a stand-in, the trailer's address through the mutants ---------------
+
+def _framed_standin(src, dst, frame, launch, caps, trailer=fo.exact, header_len=fo.exact):
+    """a stand-in for hipdeflate_batch_inflate_framed_dev: the member is read at in_off, framed_model.framed decides --
+    but the trailer is fetched the way k_frame_close fetches it, byte by byte at (in_off + header) + consumed + k, through
+    `trailer`; header_len stands for the narrowing of p_off - in_off on the way into in_used"""
+    M = ff.M
+    got = []
+    for p, cap in zip(launch, caps):
+        m = src.read(p.a.offset, p.a.length)
+        pos, foot = M.open_member(m, frame), M.FOOTER[frame]
+        if pos is not None and foot:
+            r, _, bits = M.oracle_inflate_bits(m[pos:len(m) - foot], cap)
+            if r == 0:
+                at = pos + (bits + 7) // 8
+                t = b"".join(src.read(p.a.offset + at + k, 1, trailer) for k in range(foot))
+                m = m[:at] + t + m[at + foot:]
+        st, n, used, check, data = M.framed(m, frame, cap)
+        if st == 0:
+            p_off = p.a.offset + pos
+            used = header_len(p_off - p.a.offset) + (used - pos)
+            dst.write(p.b.offset, data)
+        got.append((st, n, used, check))
+    return got
+
+
+def _standin_launch(frame, launch, short=None, **how):
+    src, dst = fo.Sparse(ff.BIG), fo.Sparse(ff.BIG)
+    caps = ff.caps_of(launch, short)
+    in_regs, regs = ff.lay_input(src, launch), ff.lay_output(dst, launch, caps)
+    sizes = [ff.M.size(src.read(p.a.offset, p.a.length), frame) for p in launch]
+    got = _framed_standin(src, dst, frame, launch, caps, **how)
+    return ff.size_problems(launch, sizes) + ff.framed_problems(launch, caps, got, dst, regs, src, in_regs)
+
+
+@pytest.mark.parametrize("frame", [0, 4, 5], ids=["raw", "zlib", "gzip"])
+def test_framed_layout_passes_its_own_expectations_through_an_exact_stand_in(frame):
+    """section D2's layout, members and checker without a GPU: every launch, the launches with out_cap one short, and the
+    conditions that keep it a far-offset test"""
+    launches = ff.launches(frame)
+    refused_far = ff.honest(launches)
+    assert refused_far >= (8 if frame == ff.M.GZIP else 4)
+    assert [len(l) for l in launches] == [8, 8, 8, 8] + [4] * (frame == ff.M.GZIP)
+    for launch in launches:
+        assert _standin_launch(frame, launch) == []
+        for p in launch:
+            if p.case.name in ("crc_flip", "isize_flip", "adler_flip", "bad_id", "reserved", "no_nul", "bad_fcheck", "cut1"):
+                assert ff.want_framed(p.case, p.case.room)[:4] == (1, 0, 0, 0) and p.a.offset >= fo.P32, p.case.name
+            if p.case.name == "garbage7":
+                assert ff.want_framed(p.case, p.case.room)[2] == len(p.case.data) - 7
+            if p.case.name == "pair":
+                assert ff.want_size(p.case)[2] == len(p.case.data) - len(p.case.follow[0])
+    for launch in launches[:2]:                       # the boundary outputs at 2^32 - 100 and at 2^32, one byte short
+        short = ff.boundary_position(launch)
+        assert launch[short].b.kind in ("straddle", "starts_at")
+        assert _standin_launch(frame, launch, short=short) == []
+        assert ff.want_framed(launch[short].case, launch[short].case.room - 1)[:4] == (3, 0, 0, 0)
+    if frame == ff.M.GZIP:
+        by = {p.case.name: p for l in launches for p in l if p.a.kind in fo.BOUNDARY}
+        assert by["name300"].a.offset == 2 ** 32 - 100 and by["extra65535"].a.offset + len(by["extra65535"].case.data) == 2 ** 32
+        assert ff.M.open_member(by["name300"].case.data, frame) == 311 and ff.M.open_member(by["extra65535"].case.data, frame) == 12 + 65535
+
+
+@pytest.mark.parametrize("mutant", MUTANTS, ids=lambda f: f.__name__)
+def test_framed_checker_rejects_a_narrow_trailer_address(mutant):
+    """the one address of the framed family the block cases do not have: the gzip member of 104 bytes from 2^32 - 100 has its
+    CRC-32 below 2^32 and its ISIZE at it, the zlib member of 102 bytes its Adler-32 cut 2 | 2.  A trailer read byte by byte
+    through a narrowed address finds the alias sentinels (or nothing) where the upper bytes should be."""
+    for frame, name in ((ff.M.GZIP, "g104"), (ff.M.ZLIB, "z102")):
+        launch = next(l for l in ff.launches(frame) if any(p.case.name == name and p.a.kind == "straddle" for p in l))
+        p = next(p for p in launch if p.case.name == name)
+        assert p.a.offset == 2 ** 32 - 100 and p.a.offset + p.a.length == 2 ** 32 + (4 if frame == ff.M.GZIP else 2)
+        assert _standin_launch(frame, launch) == []
+        bad = _standin_launch(frame, launch, trailer=mutant)
+        caught = {b[1] for b in bad if b[0] == "framed"}
+        far_ok = {q.case.name for q in launch if q.a.offset >= fo.P32 and ff.want_framed(q.case, q.case.room)[0] == 0}
+        assert name in caught and caught >= far_ok, (frame, bad)
+
+
+def test_in_used_may_narrow_the_header_length():
+    """k_frame_close and k_inflate_size form in_used from (uint32_t)(p_off - in_off): the narrowing of a DIFFERENCE of two
+    64-bit offsets of one member, which is the header's length (< 2^28) whatever the offsets are.  mask32 on it changes
+    nothing -- this is not a narrowed address and needs no fix."""
+    for frame in ff.FRAMES:
+        for launch in ff.launches(frame):
+            assert _standin_launch(frame, launch, header_len=fo.mask32) == []
+
+
+@pytest.mark.parametrize("frame", [0, 4, 5], ids=["raw", "zlib", "gzip"])
+def test_long_streams_in_a_frame_are_what_the_gpu_tests_take_them_for(frame):
+    """section G2 and H rest on members whose check value and ISIZE are by construction: the same wrapping at a scale zlib
+    and the model can follow"""
+    import framed_model as M
+    over = fo.LONG_OVERHEAD[frame]
+    host, pattern, reps, rest = fo.long_input_stream(200000 - over, np.random.default_rng(28))
+    member, check, total = fo.framed_long_member(frame, host, pattern, reps, rest)
+    m = member.tobytes()
+    plain = pattern.tobytes() * reps + rest
+    assert len(m) == 200000 and total == len(plain) and zlib.decompress(m, sm.WBITS[frame]) == plain
+    assert M.size(m, frame) == (0, total, 200000) and M.framed(m, frame, total)[:4] == (0, total, 200000, check)
+    if frame == M.GZIP:
+        off = m[:-4] + ((total + 1) & 0xffffffff).to_bytes(4, "little")
+        assert M.size(off, frame) == (1, 0, 0)
+    total = 32768 * 8
+    stream, pattern = fo.long_output_stream(total)
+    member, check, n = fo.framed_long_member(frame, stream, pattern, 8)
+    m = member.tobytes()
+    assert n == total and zlib.decompress(m, sm.WBITS[frame]) == pattern.tobytes() * 8
+    assert M.size(m, frame) == (0, total, len(m)) and M.framed(m, frame, total)[:4] == (0, total, len(m), check)
+    assert M.framed(m, frame, total - 1)[:4] == (3, 0, 0, 0)

@@ -13,12 +13,24 @@ Which test holds which 64-bit quantity to a value >= 2^32 whose bytes are at tha
   dst_off, span_base          test_scan_and_gather_at_far_addresses (slots and destination past 2^32, base 2^40 + 5)
   in_off / out_off of the     test_inflate_far_input_and_far_output
   inflate
+  a member's header address,  test_members_far_input_and_far_output (tests/far_framed.py: raw, zlib and gzip members at every
+  the payload table (p_off),  edge of a 6.06 GiB input -- a name scanned across 2^32, header and payload 64 KiB apart at 2^32, a
+  the trailer's address       gzip trailer cut 4 | 4 and a zlib trailer cut 2 | 2 by 2^32, refused members on far rows)
+  p_off + used, in_used,
+  out_off of the framed       the same (outputs at ANOTHER edge of a 6.06 GiB output, one of 300,000 bytes read back from HBM at
+  decode, the Adler pass      a far out_off; zlib members: k_chunk_adler over out + out_off); in_off + in_used as a 64-bit tensor
+  the host forms' host        test_host_forms_with_far_host_offsets
+  offsets
   index pos / in_off /        test_index_and_run_on_a_container_past_4gib, test_ranged_reads_past_4gib (also a virtual
   end_offset / out_bytes,     offset's coffset and a range's dst_off)
   chunk_off, the stream's     test_one_stream_past_4gib
   in_bytes / out_bytes, ISIZE
   the 32-bit counters of one  test_inflate_input_of_max_in, test_inflate_output_past_2_31 (and its 128 MiB form, which the
   inflate (bit position, out) oracle can still follow: test_inflate_output_of_128_mib)
+  the size pass's bit         test_size_pass_input_of_max_in (stored-block seeks up to bit 2^31, ISIZE read at src + used + 4),
+  position, `used` near 2^28  test_framed_decode_input_of_max_in (in_used and the trailer's address at 2^28 - 1)
+  inflate_members' prefix     test_inflate_members_prefix_sum_past_4gib (out_off up to 2^32 + 64 MiB + 70,100 from the scan,
+  sum                         a member that straddles 2^32, a refused member with and without room)
 
 Every test asserts the free device memory it needs before it allocates (it fails, never skips) and frees its buffers."""
 import ctypes
@@ -31,7 +43,9 @@ import numpy as np
 import pytest
 
 import encode_room as er
+import far_framed as ff
 import far_offsets as fo
+import framed_model as fm
 import hdtest
 import member_index_model as mm
 import range_read_model as rm
@@ -522,6 +536,84 @@ def test_inflate_far_input_and_far_output(pkg, torch, dev, room, flushed):
     del src, out
 
 
+# ---- D2. raw, zlib and gzip members: far input, far output ---------------------------------------------------------------
+
+def run_members(torch, dev, frame, launch, src, out, short=None, bare=False):
+    """one launch of far_framed.launches(): the size pass and the framed call over the same shuffled tables (bare: the framed
+    call alone, check and in_used both NULL), then, where a member has another behind it, that one from in_off + in_used
+    -- formed on the device as a 64-bit tensor.  short: the position whose out_cap is one below its output.
+    -> the problems found"""
+    n = len(launch)
+    caps = ff.caps_of(launch, short)
+    in_regs = ff.lay_input(src, launch, write=lambda mem, at, data: put(torch, mem, at, data))
+    regs = ff.lay_output(out, launch, caps)
+    in_off, in_len = u64(torch, [p.a.offset for p in launch]), u32(torch, [p.a.length for p in launch])
+    out_off, out_cap = u64(torch, [p.b.offset for p in launch]), u32(torch, caps)
+    osz, used0, st0, olen, chk, used, st = (torch.full((n,), -7, dtype=torch.int32, device="cuda") for _ in range(7))
+    bad = []
+    if not bare:
+        dev.inflate_size_call(src, in_off, in_len, frame, osz, used0, st0)
+        torch.cuda.synchronize()
+        bad += ff.size_problems(launch, list(zip(st0.cpu().tolist(), host_u32(osz), host_u32(used0))))
+    dev.inflate_framed_call(src, in_off, in_len, frame, out, out_off, out_cap, olen, None if bare else chk, None if bare else used, st)
+    torch.cuda.synchronize()
+    none = [None] * n
+    got = list(zip(st.cpu().tolist(), host_u32(olen), none if bare else host_u32(used), none if bare else host_u32(chk)))
+    bad += ff.framed_problems(launch, caps, got, out, regs, src, in_regs)
+    for i, p in enumerate(launch):
+        if p.b2 is None or bare or bad:
+            continue
+        m2, d2 = p.case.follow
+        off2 = in_off[i:i + 1] + used0[i:i + 1].to(torch.int64)          # where the second member starts: never on the host
+        len2 = in_len[i:i + 1] - used0[i:i + 1]
+        assert int(off2.item()) == p.a.offset + len(p.case.data) - len(m2) and int(len2.item()) == len(m2)
+        r = [torch.full((1,), -7, dtype=torch.int32, device="cuda") for _ in range(7)]
+        dev.inflate_size_call(src, off2, len2, frame, r[0], r[1], r[2])
+        o2, c2 = u64(torch, [p.b2.offset]), u32(torch, [len(d2)])
+        dev.inflate_framed_call(src, off2, len2, frame, out, o2, c2, r[3], r[4], r[5], r[6])
+        torch.cuda.synchronize()
+        w = fm.framed(m2, frame, len(d2))
+        assert w[4] == d2
+        if (r[2].item(), host_u32(r[0])[0], host_u32(r[1])[0]) != fm.size(m2, frame):
+            bad.append(("size of the second", p.a.kind))
+        if (r[6].item(), host_u32(r[3])[0], host_u32(r[5])[0], host_u32(r[4])[0]) != w[:4]:
+            bad.append(("framed second", p.a.kind, p.b2.kind))
+        bad += fo.check_rows(out, [(p.b2.offset, d2)], regs)
+    return bad
+
+
+@pytest.mark.timeout(300)
+@pytest.mark.parametrize("frame", ff.FRAMES, ids=[ff.FRAME_NAMES[f] for f in ff.FRAMES])
+def test_members_far_input_and_far_output(pkg, torch, dev, room, frame):
+    """hipdeflate_batch_inflate_size_dev and hipdeflate_batch_inflate_framed_dev (through device.inflate_size_call /
+    inflate_framed_call): members at the edge offsets of a 6.06 GiB input, out_off at the edge offsets of a 6.06 GiB output
+    (tests/far_framed.py: the layout, pinned on the CPU by test_far_offsets.py).  Held to framed_model: (status, out_size,
+    in_used) of the size pass and (status, out_len, in_used, check) of the framed call for every member, the bytes, the
+    guards around and the aliases of every far room, the sentinel-filled aliases of the input.  Among the members: a gzip
+    name whose NUL lies behind 2^32, an extra field of 65535 bytes that ends at 2^32, trailers cut by 2^32 (gzip 4 | 4, zlib
+    2 | 2), refused headers and trailers on far rows between valid neighbours, a name without NUL whose scan must stop at a
+    far in_off + in_len, and a pair whose second member is found by in_used.  Once with check and in_used NULL; the
+    launches whose boundary output starts at 2^32 and straddles it once more with out_cap one short: status 3, the guard
+    behind the room intact."""
+    room(2 * BIG)
+    launches = ff.launches(frame)
+    refused_far = ff.honest(launches)                 # >= 10 far inputs and outputs, an output > 64 KiB at out_off >= 2^32
+    assert refused_far >= (6 if frame == fm.GZIP else 4)
+    src, out = empty(torch, BIG), empty(torch, BIG)
+    for launch in launches:
+        bad = run_members(torch, dev, frame, launch, src, out)
+        assert bad == [], (frame, [p.case.name for p in launch], bad)
+    assert run_members(torch, dev, frame, launches[2], src, out, bare=True) == []
+    for launch in launches[:2]:
+        short = ff.boundary_position(launch)
+        assert launch[short].b.kind in ("straddle", "starts_at")
+        assert ff.want_framed(launch[short].case, launch[short].case.room - 1)[:4] == (3, 0, 0, 0)
+        bad = run_members(torch, dev, frame, launch, src, out, short=short)
+        assert bad == [], (frame, launch[short].case.name, bad)
+    assert pkg.lib().hipdeflate_stall_count() == 0
+    del src, out
+
+
 # ---- E. member index, verify and ranged read on a container past 4 GiB --------------------------------------------------
 
 E_TILE = (64 << 20) - 4080                           # repeat k starts at k * E_TILE: 2^32 lies 64 * 4080 bytes into repeat 64
@@ -841,47 +933,8 @@ def test_one_stream_past_4gib(pkg, torch, dev, room, level, frame, text_share, w
 MAX_IN = 1 << 28                                     # include/hipdeflate_params.h HD_INFLATE_MAX_IN
 
 
-def static_code(w, sym):
-    """one litlen symbol in the static code (RFC 1951 3.2.6)"""
-    if sym < 144:
-        w.huff(0x30 + sym, 8)
-    elif sym < 256:
-        w.huff(0x190 + sym - 144, 9)
-    elif sym < 280:
-        w.huff(sym - 256, 7)
-    else:
-        w.huff(0xc0 + sym - 280, 8)
-
-
-def static_match(w, length, dist):
-    import deflate_gen as dg
-    ls, ds = dg.len_sym(length), dg.dist_sym(dist)
-    static_code(w, ls)
-    w.bits(length - dg.LEN_BASE[ls - 257], dg.LEN_EXTRA[ls - 257])
-    w.huff(ds, 5)
-    w.bits(dist - dg.DIST_BASE[ds], dg.DIST_EXTRA[ds])
-
-
-def long_input_stream(nbytes, rng):
-    """a stream of exactly nbytes bytes: stored blocks of 65535 noise bytes (one block, tiled), a shorter one, and a final
-    static block of three literals -> (stream as numpy, the 65535-byte pattern, how often it repeats, the rest of the output)"""
-    import deflate_gen as dg
-    w = dg.BitWriter()
-    w.bits(1, 1)
-    w.bits(1, 2)
-    for ch in b"end":
-        static_code(w, ch)
-    static_code(w, 256)
-    last = w.value()
-    pattern = rng.integers(0, 256, 65535, dtype=np.uint8)
-    block = np.concatenate([np.frombuffer(b"\x00\xff\xff\x00\x00", dtype=np.uint8), pattern])
-    reps, left = divmod(nbytes - len(last), len(block))
-    assert 5 <= left
-    part = rng.integers(0, 256, left - 5, dtype=np.uint8)
-    head = np.frombuffer(b"\x00" + int(left - 5).to_bytes(2, "little") + int((left - 5) ^ 0xffff).to_bytes(2, "little"), dtype=np.uint8)
-    stream = np.concatenate([np.tile(block, reps), head, part, np.frombuffer(last, dtype=np.uint8)])
-    assert len(stream) == nbytes
-    return stream, pattern, reps, part.tobytes() + b"end"
+static_code, static_match = fo.static_code, fo.static_match                # (the generators live in far_offsets.py: the CPU pins use them too)
+long_input_stream, long_output_stream = fo.long_input_stream, fo.long_output_stream
 
 
 @pytest.mark.timeout(300)
@@ -926,35 +979,6 @@ def test_inflate_input_of_max_in(pkg, torch, dev, room):
         assert fn(p(big), p(one[0]), p(one[1]), 1, p(room_), p(one[2]), p(one[3]), p(one[4]), p(one[5]), p(one[6])) == pkg.HD_E_ARG
     n = ctypes.c_size_t(4096)
     assert pkg.lib().hip_inflate(p(room_), ctypes.byref(n), p(big), MAX_IN) == pkg.HD_E_ARG
-
-
-def long_output_stream(total):
-    """a small stream of `total` bytes of output: one stored block of 32 KiB of noise, then static-Huffman matches of length
-    258 at distance 32768 -- 26 bits each, so four of them are a 13-byte period of the stream, tiled -- a last match or two
-    for the remainder and the end of block -> (stream as numpy, the 32 KiB pattern)"""
-    import deflate_gen as dg
-    pattern = np.random.default_rng(31).integers(0, 256, 32768, dtype=np.uint8)
-    assert total % 32768 == 0 and total >= 32768 + 258 * 12
-    n258, rem = divmod(total - 32768, 258)
-    tail = []
-    if 0 < rem < 3:
-        n258, rem = n258 - 1, rem + 258
-        tail = [rem // 2, rem - rem // 2]
-    elif rem:
-        tail = [rem]
-    periods, extra = divmod(n258, 4)
-    w = dg.BitWriter()                                   # the final block with TWO periods: head byte | period | the rest
-    w.bits(1, 1)
-    w.bits(1, 2)
-    for length in [258] * (8 + extra) + tail:
-        static_match(w, length, 32768)
-    static_code(w, 256)
-    sample = w.value()
-    assert sample[1:14] == sample[14:27] or extra + len(tail) == 0
-    head = b"\x00\x00\x80\xff\x7f" + pattern.tobytes() + sample[:1]
-    stream = np.concatenate([np.frombuffer(head, dtype=np.uint8), np.tile(np.frombuffer(sample[1:14], dtype=np.uint8), periods - 1),
-                             np.frombuffer(sample[14:], dtype=np.uint8)])
-    return stream, pattern
 
 
 def run_long_output(pkg, torch, dev, total, short):
@@ -1024,3 +1048,224 @@ def test_inflate_output_past_2_31(pkg, torch, dev, room, short):
         assert res[0] == 3
     else:
         check_long_output(torch, G2_TOTAL, res)
+
+
+# ---- G2. the size pass and the framed decode at the end of the 32-bit bit position ---------------------------------------
+
+def max_in_member(torch, frame):
+    """the stream of test_inflate_input_of_max_in in a frame, HD_INFLATE_MAX_IN - 1 bytes with header and trailer, on the
+    device in a buffer of HD_INFLATE_MAX_IN + 16 -> (src, pattern, reps, rest, check, total)"""
+    host, pattern, reps, rest = long_input_stream(MAX_IN - 1 - fo.LONG_OVERHEAD[frame], np.random.default_rng(28))
+    member, check, total = fo.framed_long_member(frame, host, pattern, reps, rest)
+    assert len(member) == MAX_IN - 1 and total == reps * 65535 + len(rest)
+    src = empty(torch, MAX_IN + 16)
+    src[:MAX_IN - 1] = torch.from_numpy(member).cuda()
+    src[MAX_IN - 1:] = 0
+    return src, pattern, reps, rest, check, total
+
+
+def timed(torch, call):
+    import time
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    call()
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0
+
+
+@pytest.mark.timeout(1, func_only=True)
+@pytest.mark.parametrize("frame", ff.FRAMES, ids=[ff.FRAME_NAMES[f] for f in ff.FRAMES])
+def test_size_pass_input_of_max_in(pkg, torch, dev, room, frame):
+    """k_inflate_size on a member of HD_INFLATE_MAX_IN - 1 bytes: 4096 stored blocks, each a seek of its own 32-bit bit
+    reader, up to bit 2^31 - 8 and some; the answer is (0, total, HD_INFLATE_MAX_IN - 1), by construction (the CPU pin:
+    test_long_streams_in_a_frame_are_what_the_gpu_tests_take_them_for).  gzip: with ISIZE off by one the status is 1 -- the
+    read at src + used + 4 with used near 2^28.  raw: a real buffer of exactly HD_INFLATE_MAX_IN bytes answers status 1
+    and zeros from both _dev calls and leaves a sentinel-filled output alone.
+    Time (printed at every run), first measured on an MI355X: the call 0.0044 s (raw), 0.0045 s (zlib, gzip) -- nearly all of it
+    stored-block seeks; the whole test with the 256 MiB it makes and uploads 0.17 / 0.15 / 0.18 s.  The timeout is three
+    times the slowest, in whole seconds, on the test's own body."""
+    import time
+    t_test = time.perf_counter()
+    room(2 * MAX_IN)
+    src, pattern, reps, rest, check, total = max_in_member(torch, frame)
+    zero, n_in = u64(torch, [0]), u32(torch, [MAX_IN - 1])
+    osz, used, st = (torch.full((1,), -7, dtype=torch.int32, device="cuda") for _ in range(3))
+    dt = timed(torch, lambda: dev.inflate_size_call(src, zero, n_in, frame, osz, used, st))
+    print("size pass over a %s member of 2^28 - 1 bytes: %.4f s" % (ff.FRAME_NAMES[frame], dt))
+    assert (st.item(), host_u32(osz)[0], host_u32(used)[0]) == (0, total, MAX_IN - 1)
+    if frame == fm.GZIP:
+        put(torch, src, MAX_IN - 1 - 4, ((total + 1) & 0xffffffff).to_bytes(4, "little"))
+        dev.inflate_size_call(src, zero, n_in, frame, osz, used, st)
+        torch.cuda.synchronize()
+        assert (st.item(), host_u32(osz)[0], host_u32(used)[0]) == (1, 0, 0)
+    if frame == fm.RAW:
+        n_max, cap = u32(torch, [MAX_IN]), u32(torch, [4096])
+        out = torch.full((4096,), SENT, dtype=torch.uint8, device="cuda")
+        olen, chk = (torch.full((1,), -7, dtype=torch.int32, device="cuda") for _ in range(2))
+        dev.inflate_size_call(src, zero, n_max, frame, osz, used, st)
+        torch.cuda.synchronize()
+        assert (st.item(), host_u32(osz)[0], host_u32(used)[0]) == (1, 0, 0)
+        dev.inflate_framed_call(src, zero, n_max, frame, out, zero, cap, olen, chk, used, st)
+        torch.cuda.synchronize()
+        assert (st.item(), host_u32(olen)[0], host_u32(used)[0], host_u32(chk)[0]) == (1, 0, 0, 0) and bool((out == SENT).all())
+    assert pkg.lib().hipdeflate_stall_count() == 0
+    del src
+    print("the whole test: %.2f s" % (time.perf_counter() - t_test))
+
+
+@pytest.mark.timeout(5, func_only=True)
+@pytest.mark.parametrize("frame", [fm.GZIP, fm.ZLIB], ids=["gzip", "zlib"])
+def test_framed_decode_input_of_max_in(pkg, torch, dev, room, frame):
+    """k_frame_open, k_inflate_framed, k_chunk_adler (zlib) and k_frame_close on the same member: (0, total, in_used =
+    HD_INFLATE_MAX_IN - 1, check), the bytes consumed and the trailer's address both near 2^28; the output is the 65535-byte
+    pattern 4096 times and the rest (compared through a reshaped view), the guard behind it intact.
+    Time (printed at every run), first measured on an MI355X: the call 1.26 s (gzip), 1.29 s (zlib: k_chunk_adler's one
+    wavefront over 256 MiB is the 0.03 s), the whole test 1.45 s either way -- 256 MiB of stored blocks through one wavefront
+    are well under 10 s, so both frames stay.  The timeout is three times 1.45 s, in whole seconds, on the test's own body."""
+    import time
+    t_test = time.perf_counter()
+    room(3 * MAX_IN)
+    src, pattern, reps, rest, check, total = max_in_member(torch, frame)
+    out = empty(torch, total + fo.GUARD)
+    out[:total] = 0
+    out[total:] = SENT
+    zero, n_in, cap = u64(torch, [0]), u32(torch, [MAX_IN - 1]), u32(torch, [total])
+    olen, chk, used, st = (torch.full((1,), -7, dtype=torch.int32, device="cuda") for _ in range(4))
+    dt = timed(torch, lambda: dev.inflate_framed_call(src, zero, n_in, frame, out, zero, cap, olen, chk, used, st))
+    print("framed decode of a %s member of 2^28 - 1 bytes: %.4f s" % (ff.FRAME_NAMES[frame], dt))
+    assert (st.item(), host_u32(olen)[0], host_u32(used)[0], host_u32(chk)[0]) == (0, total, MAX_IN - 1, check)
+    pat = torch.from_numpy(pattern).cuda()
+    assert bool((out[:reps * 65535].view(reps, 65535) == pat[None, :]).all())
+    assert fo.to_bytes(out[reps * 65535:total]) == rest and bool((out[total:] == SENT).all())
+    assert pkg.lib().hipdeflate_stall_count() == 0
+    del src, out
+    print("the whole test: %.2f s" % (time.perf_counter() - t_test))
+
+
+# ---- H. device.inflate_members: the prefix sum it hands to the decoder passes 2^32 --------------------------------------
+
+H_BIG = 64 << 20
+
+
+@pytest.mark.timeout(4, func_only=True)
+@pytest.mark.parametrize("frame", [fm.GZIP, fm.ZLIB], ids=["gzip", "zlib"])
+def test_inflate_members_prefix_sum_past_4gib(pkg, torch, dev, room, frame):
+    """device.inflate_members -- the size pass, hipdeflate_scan_sizes_dev, one allocation, the framed decode -- over 69 rows:
+      0       100 bytes of text, made by zlib
+      1..64   long_output_stream(64 MiB) in the frame, all rows pointing at ONE copy: row 64's output starts at 2^32 - 64 MiB
+              + 100 and straddles 2^32
+      65      gzip: the same member with ISIZE off by one; zlib: with a bad FCHECK.  The size pass refuses it: no room
+      66      70,000 FASTQ-like bytes, made by zlib: out_off 2^32 + 100
+      67      the 64 MiB member with one bit of its CRC-32 (Adler-32) flipped: the size pass accepts it, the decode refuses
+              it -- status 1, out_len 0, and its 64 MiB of room are allocated
+      68      5 bytes, made by zlib
+    (three copies of the 64 MiB member's 0.85 MB in the blob, 2.6 MB.)  out_off is the exclusive prefix sum of the model's
+    size-pass sizes, out.numel() their sum, status and out_len the framed model's in exactly that room; the 64 MiB rows
+    are compared through a (2048, 32768) view against the pattern, the small rows as bytes.
+    Time (printed at every run), first measured on an MI355X: the call -- both passes, 66 wavefronts side by side on 64 MiB
+    each -- 0.455 s (gzip), 0.521 s (zlib); the whole test, with the model's three 64 MiB decodes on the host, 1.20 / 0.81 s.
+    The timeout is three times 1.20 s, in whole seconds, on the test's own body."""
+    import time
+    t_test = time.perf_counter()
+    room(6 * GIB)
+    stream, pattern = long_output_stream(H_BIG)
+    member, check, total = fo.framed_long_member(frame, stream, pattern, H_BIG // 32768)
+    big = member.tobytes()
+    assert total == H_BIG
+    c = corpus()
+    wbits = sm.WBITS[frame]
+
+    def made(d):
+        z = zlib.compressobj(6, zlib.DEFLATED, wbits)
+        return z.compress(d) + z.flush()
+    small = [c["text"][:100], c["fastq"][:70000], c["text"][5000:5005]]
+    if frame == fm.GZIP:
+        refused_early = big[:-4] + ((H_BIG + 1) & 0xffffffff).to_bytes(4, "little")
+        refused_late = big[:-8] + bytes([big[-8] ^ 0x10]) + big[-7:]
+    else:
+        refused_early = big[:1] + bytes([big[1] ^ 1]) + big[2:]
+        refused_late = big[:-4] + bytes([big[-4] ^ 0x10]) + big[-3:]
+    distinct = [made(small[0]), big, refused_early, made(small[1]), refused_late, made(small[2])]
+    which = [0] + [1] * 64 + [2, 3, 4, 5]
+    blob, offs = bytearray(), []
+    for i, m in enumerate(distinct):
+        blob += bytes(range(1, 1 + (i * 5 - len(blob)) % 16))
+        offs.append(len(blob))
+        blob += m
+    blob += bytes(range(1, 65))
+    sizes = [fm.size(m, frame) for m in distinct]
+    wants = [fm.framed(m, frame, s[1]) for m, s in zip(distinct, sizes)]
+    assert [s[0] for s in sizes] == [0, 0, 1, 0, 0, 0] and sizes[1][1] == sizes[4][1] == H_BIG
+    assert wants[1][:4] == (0, H_BIG, len(big), check) and wants[4][:4] == (1, 0, 0, 0)
+    assert [w[4] for w in (wants[0], wants[3], wants[5])] == small
+    want_size = np.array([sizes[k][1] for k in which], dtype=np.uint64)
+    want_off = np.concatenate([np.zeros(1, dtype=np.uint64), np.cumsum(want_size)[:-1]])
+    assert int(want_off[64]) == P32 - H_BIG + 100 and int(want_off[65]) == int(want_off[66]) == P32 + 100
+    assert int(want_off[68]) == P32 + 100 + 70000 + H_BIG
+    d_blob = torch.from_numpy(np.frombuffer(bytes(blob), dtype=np.uint8).copy()).cuda()
+    in_off, in_len = u64(torch, [offs[k] for k in which]), u32(torch, [len(distinct[k]) for k in which])
+    res = []
+    dt = timed(torch, lambda: res.extend(dev.inflate_members(d_blob, in_off, in_len, frame)))
+    print("inflate_members, 66 members of 64 MiB among 69 (%s): %.3f s" % (ff.FRAME_NAMES[frame], dt))
+    out, out_off, out_len, status = res
+    assert out.numel() == int(want_size.sum()) == 65 * H_BIG + 70105
+    assert fo.check_table(out_off.cpu().numpy().view(np.uint64), want_off, "out_off") == []
+    assert status.cpu().tolist() == [wants[k][0] for k in which] and status[67].item() == 1
+    assert host_u32(out_len) == [wants[k][1] for k in which] and host_u32(out_len)[67] == 0
+    pat = torch.from_numpy(pattern).cuda()
+    for row in range(1, 65):
+        at = int(want_off[row])
+        assert bool((out[at:at + H_BIG].view(H_BIG // 32768, 32768) == pat[None, :]).all()), row
+    assert fo.check_rows(out, [(int(want_off[r]), wants[which[r]][4]) for r in (0, 66, 68)], []) == []
+    assert pkg.lib().hipdeflate_stall_count() == 0
+    del out, res
+    print("the whole test: %.2f s" % (time.perf_counter() - t_test))
+
+
+# ---- I. the host-buffer forms: 64-bit offsets into host memory ----------------------------------------------------------
+
+I_SIZE = P32 + (8 << 20)
+I_MEMBERS = {fm.GZIP: ("all_fields", "name300", "fastq70k", "five"), fm.ZLIB: ("fastq70k", "garbage7", "text300k", "five")}
+
+
+@pytest.mark.timeout(120)
+@pytest.mark.parametrize("frame", [fm.GZIP, fm.ZLIB], ids=["gzip", "zlib"])
+def test_host_forms_with_far_host_offsets(pkg, frame):
+    """hipdeflate_batch_inflate_size and hipdeflate_batch_inflate_framed (through the library itself: the list wrappers cannot
+    state an offset) on two host arrays of 2^32 + 8 MiB whose pages are never touched but where the members are: a member
+    ending at, straddling, starting at and just behind offset 2^32 of the input, its output at the same kind of the output
+    between 4096-byte sentinel guards, a low-offset control beside each.  The answers and the bytes are the model's."""
+    with open("/proc/meminfo") as f:
+        avail = next(int(line.split()[1]) * 1024 for line in f if line.startswith("MemAvailable:"))
+    assert avail >= 2 * I_SIZE, "needs %.1f GiB of host memory, %.1f are available" % (2 * I_SIZE / GIB, avail / GIB)
+    L = pkg.lib()
+    hin, hout = np.empty(I_SIZE, dtype=np.uint8), np.empty(I_SIZE, dtype=np.uint8)
+    p = lambda a: a.ctypes.data_as(ctypes.c_void_p)       # noqa: E731
+    c = ff.cases(frame)
+    control = c["twin1"]
+    for kind, name in zip(fo.BOUNDARY, I_MEMBERS[frame]):
+        ms = [c[name], control]
+        a = [fo.edge_offset(kind, len(ms[0].data), I_SIZE), fo.edge_offset("low", len(control.data), I_SIZE)]
+        b = [fo.edge_offset(kind, ms[0].room, I_SIZE), fo.edge_offset("low", control.room, I_SIZE)]
+        assert fo.is_far(a[0], len(ms[0].data)) and fo.is_far(b[0], ms[0].room)
+        for m, ai, bi in zip(ms, a, b):
+            hin[ai:ai + len(m.data)] = np.frombuffer(m.data, dtype=np.uint8)
+            hin[ai + len(m.data):ai + len(m.data) + 16] = 0x77
+            hout[bi - fo.GUARD:bi] = SENT
+            hout[bi:bi + m.room] = 0
+            hout[bi + m.room:bi + m.room + fo.GUARD] = SENT
+        in_off, in_len = np.array(a, dtype=np.uint64), np.array([len(m.data) for m in ms], dtype=np.uint32)
+        out_off, cap = np.array(b, dtype=np.uint64), np.array([m.room for m in ms], dtype=np.uint32)
+        r = [np.full(2, 0xfffffff9, dtype=np.uint32) for _ in range(6)]
+        st0, st = np.full(2, -7, dtype=np.int32), np.full(2, -7, dtype=np.int32)
+        assert L.hipdeflate_batch_inflate_size(p(hin), p(in_off), p(in_len), 2, frame, p(r[0]), p(r[1]), p(st0)) == 0
+        assert [(int(st0[i]), int(r[0][i]), int(r[1][i])) for i in range(2)] == [ff.want_size(m) for m in ms], (kind, name)
+        assert L.hipdeflate_batch_inflate_framed(p(hin), p(in_off), p(in_len), 2, frame, p(hout), p(out_off), p(cap), p(r[2]), p(r[3]),
+                                                 p(r[4]), p(st)) == 0
+        wants = [ff.want_framed(m, m.room) for m in ms]
+        assert [(int(st[i]), int(r[2][i]), int(r[4][i]), int(r[3][i])) for i in range(2)] == [w[:4] for w in wants], (kind, name)
+        for m, w, bi in zip(ms, wants, b):
+            assert w[0] == 0 and hout[bi:bi + m.room].tobytes() == w[4] == m.plain, (kind, m.name)
+            assert np.all(hout[bi - fo.GUARD:bi] == SENT) and np.all(hout[bi + m.room:bi + m.room + fo.GUARD] == SENT), (kind, m.name)
+    assert L.hipdeflate_stall_count() == 0
+    del hin, hout
