@@ -57,6 +57,12 @@ class StreamSummary(ctypes.Structure):
                 ("nchunks", ctypes.c_uint32), ("check", ctypes.c_uint32), ("status", ctypes.c_uint32)]
 
 
+class StreamIndexSummary(ctypes.Structure):
+    """hipdeflate_stream_index_summary (include/hipdeflate.h)"""
+    _fields_ = [("nchunks", ctypes.c_uint64), ("out_bytes", ctypes.c_uint64), ("end_offset", ctypes.c_uint64),
+                ("ncandidates", ctypes.c_uint64), ("hdr_bytes", ctypes.c_uint32), ("status", ctypes.c_uint32)]
+
+
 STREAM_WINDOW_BYTES = 1 << 30        # include/hipdeflate_params.h HD_STREAM_WINDOW_BYTES: slots of one window of the stream encoder
 CHECK_CRC32, CHECK_ADLER32 = 0, 1    # `kind` of hipdeflate_check_combine_dev
 RANGE_BYTES, RANGE_VOFFSET = 0, 1    # HD_RANGE_*: what the begin / end of a ranged read are
@@ -82,6 +88,7 @@ EXPORTS = [
     "hipdeflate_read_ranges_dev",
     "hipdeflate_stream_bound", "hipdeflate_stream_deflate_dev", "hipdeflate_stream_inflate_dev",
     "hipdeflate_check_combine_dev", "hip_deflate_stream", "hipdeflate_test_stream_window",
+    "hipdeflate_stream_index_dev", "hipdeflate_stream_inflate_table_dev", "hip_inflate_stream",
     "hipdeflate_init_devices", "hipdeflate_device_count", "hipdeflate_use_device",
     "hipdeflate_pipe_open_on", "hipdeflate_unpipe_open_on", "hipdeflate_lat_open_on",
     "hipdeflate_batch_inflate_size_dev", "hipdeflate_batch_inflate_framed_dev", "hipdeflate_batch_inflate_size",
@@ -177,6 +184,11 @@ def lib():
                                                 ctypes.c_uint64, _vp, ctypes.c_uint64, ctypes.POINTER(StreamSummary), _vp]
     L.hipdeflate_check_combine_dev.argtypes = [_vp, _vp, ctypes.c_uint32, ctypes.c_int, ctypes.POINTER(ctypes.c_uint32), _vp]
     L.hip_deflate_stream.argtypes = [_vp, sz_p, _vp, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_uint32]
+    L.hipdeflate_stream_index_dev.argtypes = [_vp, ctypes.c_uint64, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp, _vp, _vp,
+                                              ctypes.POINTER(StreamIndexSummary), _vp]
+    L.hipdeflate_stream_inflate_table_dev.argtypes = [_vp, ctypes.c_uint64, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.c_uint32, _vp,
+                                                      ctypes.c_uint64, ctypes.POINTER(StreamSummary), _vp]
+    L.hip_inflate_stream.argtypes = [_vp, sz_p, _vp, ctypes.c_size_t, ctypes.c_int, sz_p]
     L.hipdeflate_test_stream_window.argtypes = [ctypes.c_uint32]
     L.hipdeflate_test_stream_window.restype = None
     L.hipdeflate_pipe_open.restype = _vp
@@ -275,6 +287,17 @@ def hip_deflate_stream(data, level=6, frame=FRAME_GZIP, chunk=1 << 16, cap=None)
     n = ctypes.c_size_t(cap)
     r = lib().hip_deflate_stream(_p(dst), ctypes.byref(n), _p(src), len(src), level, frame, chunk)
     return r, bytes(dst[: n.value]) if r == 0 else b""
+
+
+def hip_inflate_stream(data, cap, frame=FRAME_GZIP):
+    """-> (ret, bytes, need, in_used): ONE raw / zlib / gzip stream in flush form, indexed and decoded in parallel chunks on
+    the device (hipdeflate_stream_index_dev and hipdeflate_stream_inflate_table_dev behind host buffers); cap: the room.
+    need: the bytes the stream decodes to where ret is 0 or 3; in_used: the stream's bytes, trailer included"""
+    src = as_u8(data)
+    dst = np.zeros(max(cap, 1), dtype=np.uint8)
+    n, used = ctypes.c_size_t(cap), ctypes.c_size_t(0)
+    r = lib().hip_inflate_stream(_p(dst), ctypes.byref(n), _p(src), len(src), frame, ctypes.byref(used))
+    return r, bytes(dst[: n.value]) if r == 0 else b"", n.value, used.value
 
 
 def hip_inflate(data, cap):

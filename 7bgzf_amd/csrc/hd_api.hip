@@ -1416,6 +1416,56 @@ int hipdeflate_stream_deflate_dev(const void *in, uint64_t nbytes, uint32_t chun
 	return 0;
 }
 
+// The decode behind the table check, for hipdeflate_stream_inflate_dev and hipdeflate_stream_inflate_table_dev: row i by the
+// flush-rule inflate into out + out_off[i] with out_size[i] as room, every row held to its size, the rows' checks folded and
+// held to the trailer that ends at nbytes.  sum[4..5] as u32: the folded check (0 / 1 before the call) | - | the trailer
+// disagrees | the lowest bad row (0xffffffff before the call).  The caller has set summary->nchunks and bad_chunk.
+struct StreamRows {
+	const uint64_t *in_off;
+	const uint32_t *in_len;
+	const uint64_t *out_off;
+	const uint32_t *out_size;
+	uint32_t *out_len, *chk;
+	int32_t *status;
+	uint64_t *tiles, *prefix, *sum;
+};
+static int stream_decode_rows(Ctx &g, const void *strm, uint64_t nbytes, int frame, const StreamRows &t, uint32_t nchunks,
+			      uint64_t out_bytes, void *out, hipdeflate_stream_summary *summary, hipStream_t st)
+{
+	int r;
+	const uint32_t kind = frame == HD_FRAME_ZLIB ? hd::CHECK_ADLER32 : hd::CHECK_CRC32;
+	uint32_t *carry = (uint32_t *)(t.sum + 4), *d_mismatch = carry + 2, *d_bad = carry + 3;
+	uint32_t h[4] = { 0, 0, 0, 0 };
+	if (nchunks) {
+		if ((r = launch_inflate({ (const uint8_t *)strm, t.in_off, t.in_len, nchunks, (uint8_t *)out, t.out_off, t.out_size, t.out_len,
+					  kind == hd::CHECK_ADLER32 ? nullptr : t.chk, t.status, g.d_ct, hd::INF_FLUSHED }, st)))
+			return r;
+		if (kind == hd::CHECK_ADLER32)
+			hipLaunchKernelGGL(hd::k_chunk_adler, dim3(nchunks), dim3(64), 0, st, (const uint8_t *)out, t.out_off,
+					   (const uint32_t *)t.out_len, t.out_size, nchunks, t.chk);
+		hipLaunchKernelGGL(hd::k_members_verify, dim3((nchunks + 255) / 256), dim3(256), 0, st, (const int32_t *)t.status,
+				   (const uint32_t *)t.out_len, (const uint32_t *)t.chk, t.out_size, (const uint32_t *)t.chk, nchunks,
+				   d_bad);                                                   // (status and length: the check is the fold's)
+	}
+	if ((r = fold_launch(t.chk, t.out_size, nchunks, kind, t.tiles, t.prefix, t.sum + 1, carry, st)))
+		return r;
+	hipLaunchKernelGGL(hd::k_stream_trailer, dim3(1), dim3(64), 0, st, (const uint8_t *)strm, nbytes, frame, out_bytes,
+			   (const uint32_t *)carry, d_mismatch);
+	HD_CHECK(hipGetLastError());
+	HD_CHECK(hipMemcpyAsync(h, carry, 16, hipMemcpyDeviceToHost, st));
+	HD_CHECK(hipStreamSynchronize(st));
+	summary->out_bytes = out_bytes;
+	summary->in_bytes = nbytes;
+	summary->check = h[0];
+	if (h[3] != hd::IDX_NIL) {
+		summary->status = 2;
+		summary->bad_chunk = h[3];
+	} else if (h[2]) {
+		summary->status = 2;
+	}
+	return 0;
+}
+
 int hipdeflate_stream_inflate_dev(const void *strm, uint64_t nbytes, int frame, const void *chunk_off, uint32_t nchunks,
 				  uint32_t chunk_bytes, uint64_t out_bytes, void *out, uint64_t out_cap,
 				  hipdeflate_stream_summary *summary, void *stream)
@@ -1449,7 +1499,7 @@ int hipdeflate_stream_inflate_dev(const void *strm, uint64_t nbytes, int frame, 
 	uint32_t *in_len = (uint32_t *)(prefix + n), *out_size = in_len + n, *out_len = out_size + n, *chk = out_len + n;
 	int32_t *status = (int32_t *)(chk + n);
 	// sum[4..5] as u32: the folded check | the lowest table entry at fault | the trailer disagrees | the lowest bad chunk
-	uint32_t *carry = (uint32_t *)(sum + 4), *d_fault = carry + 1, *d_mismatch = carry + 2, *d_bad = carry + 3;
+	uint32_t *carry = (uint32_t *)(sum + 4), *d_fault = carry + 1, *d_bad = carry + 3;
 	uint32_t h[4] = { 0, 0, 0, 0 };
 	HD_CHECK(hipMemsetAsync(sum, 0, 64, st));
 	HD_CHECK(hipMemsetD32Async((hipDeviceptr_t)carry, kind == hd::CHECK_ADLER32 ? 1 : 0, 1, st));
@@ -1469,34 +1519,242 @@ int hipdeflate_stream_inflate_dev(const void *strm, uint64_t nbytes, int frame, 
 		summary->status = 3;
 		return 0;
 	}
-	if (nchunks) {
-		if ((r = launch_inflate({ (const uint8_t *)strm, in_off, in_len, nchunks, (uint8_t *)out, out_off, out_size, out_len,
-					  kind == hd::CHECK_ADLER32 ? nullptr : chk, status, g.d_ct, hd::INF_FLUSHED }, st)))
-			return r;
-		if (kind == hd::CHECK_ADLER32)
-			hipLaunchKernelGGL(hd::k_chunk_adler, dim3(nchunks), dim3(64), 0, st, (const uint8_t *)out, (const uint64_t *)out_off,
-					   (const uint32_t *)out_len, (const uint32_t *)out_size, nchunks, chk);
-		hipLaunchKernelGGL(hd::k_members_verify, dim3((nchunks + 255) / 256), dim3(256), 0, st, (const int32_t *)status,
-				   (const uint32_t *)out_len, (const uint32_t *)chk, (const uint32_t *)out_size, (const uint32_t *)chk, nchunks,
-				   d_bad);                                                   // (status and length: the check is the fold's)
+	return stream_decode_rows(g, strm, nbytes, frame, { in_off, in_len, out_off, out_size, out_len, chk, status, tiles, prefix, sum },
+				  nchunks, out_bytes, out, summary, st);
+}
+
+/* ---- ... and a stream nobody kept a table for: the index of its flush points (hd_stream.hpp) ---- */
+
+// The header of the stream by k_frame_open's rules, on the first min(nbytes, HD_INFLATE_MAX_IN - 1) bytes: *hdr its length.
+// -> 0, 1 the rules refuse it, 2 nbytes is below the frame's header and trailer.  w: eight u64 of device scratch.
+// (Synchronises the stream.)
+static int stream_open(const void *strm, uint64_t nbytes, int frame, uint64_t *w, hipStream_t st, uint32_t *hdr, uint32_t *verdict)
+{
+	*hdr = 0;
+	*verdict = 0;
+	if (frame == HD_FRAME_RAW)
+		return 0;
+	if (nbytes < (frame == HD_FRAME_GZIP ? 18u : 6u)) {
+		*verdict = 2;
+		return 0;
 	}
-	if ((r = fold_launch(chk, out_size, nchunks, kind, tiles, prefix, sum + 1, carry, st)))
-		return r;
-	hipLaunchKernelGGL(hd::k_stream_trailer, dim3(1), dim3(64), 0, st, (const uint8_t *)strm, nbytes, frame, out_bytes,
-			   (const uint32_t *)carry, d_mismatch);
+	// w[0] the member's offset | w[1] its payload's | w[2] as u32: the member's length, the payload's | w[3] as i32: the verdict
+	const uint32_t n = nbytes < HD_INFLATE_MAX_IN ? (uint32_t)nbytes : HD_INFLATE_MAX_IN - 1;
+	HD_CHECK(hipMemsetAsync(w, 0, 32, st));
+	HD_CHECK(hipMemsetD32Async((hipDeviceptr_t)(w + 2), (int)n, 1, st));
+	hipLaunchKernelGGL(hd::k_frame_open, dim3(1), dim3(64), 0, st, (const uint8_t *)strm, (const uint64_t *)w, (const uint32_t *)(w + 2), 1u,
+			   frame, w + 1, (uint32_t *)(w + 2) + 1, (int32_t *)(w + 3));
 	HD_CHECK(hipGetLastError());
-	HD_CHECK(hipMemcpyAsync(h, carry, 16, hipMemcpyDeviceToHost, st));
+	uint64_t h[4];
+	HD_CHECK(hipMemcpyAsync(h, w, 32, hipMemcpyDeviceToHost, st));
 	HD_CHECK(hipStreamSynchronize(st));
-	summary->out_bytes = out_bytes;
-	summary->in_bytes = nbytes;
-	summary->check = h[0];
-	if (h[3] != hd::IDX_NIL) {
-		summary->status = 2;
-		summary->bad_chunk = h[3];
-	} else if (h[2]) {
-		summary->status = 2;
-	}
+	if ((uint32_t)h[3])
+		*verdict = 1;
+	else
+		*hdr = (uint32_t)h[1];
 	return 0;
+}
+
+// own: the tables are the library's, made as large as the stream needs once that is known -- in_off, out_off u64[n] |
+// in_len, out_size u32[n] in *own, n = summary->nchunks -- and the four table arguments are not looked at
+static int stream_index(Ctx &g, const void *strm, uint64_t nbytes, int frame, uint32_t max_chunks, uint32_t max_chunk_in, void *in_off,
+			void *in_len, void *out_size, void *out_off, hipdeflate_stream_index_summary *summary, hipStream_t st, Buf *own)
+{
+	int r;
+	const uint8_t *src = (const uint8_t *)strm;
+	const uint32_t trl = stream_trl(frame);
+	if (max_chunk_in == 0)
+		max_chunk_in = HD_INFLATE_MAX_IN - 1;
+	std::lock_guard<std::mutex> lk(g.mu_index);
+	if (g.d_index.reserve(128))
+		return HD_E_NOMEM;
+	uint32_t hdr = 0, refused = 0;
+	if ((r = stream_open(strm, nbytes, frame, (uint64_t *)g.d_index.p + 8, st, &hdr, &refused)))
+		return r;
+	summary->hdr_bytes = hdr;
+	summary->end_offset = hdr;
+	if (refused) {
+		summary->status = refused;
+		return 0;
+	}
+	summary->ncandidates = 1;                                                // the first payload byte, whatever it is
+	const uint64_t payload_end = nbytes - trl;                               // (k_frame_open: hdr + trl <= nbytes)
+	if (payload_end == hdr) {
+		summary->status = 2;
+		return 0;
+	}
+	// pass 1 and 2: the sorted candidate list.  The passes' nbytes is the last payload byte: a marker there makes no candidate
+	const uint64_t scan_n = payload_end - 1;
+	const uint64_t nwords = (scan_n + hd::IDX_WORD - 1) / hd::IDX_WORD;
+	const uint64_t ntb64 = (nwords + hd::IDX_TILE_WORDS - 1) / hd::IDX_TILE_WORDS;
+	if (ntb64 > 0x7fffffffu)
+		return HD_E_ARG;
+	const uint32_t ntb = (uint32_t)ntb64;
+	const size_t scan_tiles_a = (ntb + hd::SCAN_TILE - 1) / hd::SCAN_TILE;
+	// sum[8] | the header's [8] | scan tiles | tile_off | bitmap | tile_cnt
+	if (g.d_index.reserve(128 + (scan_tiles_a + ntb + nwords) * 8 + (size_t)ntb * 4))
+		return HD_E_NOMEM;
+	uint64_t *sum = (uint64_t *)g.d_index.p, *tiles_a = sum + 16, *tile_off = tiles_a + scan_tiles_a;
+	uint64_t *bitmap = tile_off + ntb;
+	uint32_t *tile_cnt = (uint32_t *)(bitmap + nwords);
+	uint64_t h[4] = { 0, 0, 0, 0 };
+	HD_CHECK(hipMemsetAsync(sum, 0, 64, st));
+	if (ntb) {
+		hipLaunchKernelGGL(hd::k_stream_flag, dim3(ntb), dim3(256), 0, st, src, scan_n, (uint64_t)hdr, bitmap, tile_cnt);
+		index_scan(tile_cnt, ntb, tiles_a, tile_off, sum + 4, st);
+		HD_CHECK(hipGetLastError());
+		HD_CHECK(hipMemcpyAsync(h, sum + 4, 8, hipMemcpyDeviceToHost, st));
+		HD_CHECK(hipStreamSynchronize(st));
+	}
+	if (h[0] >= 0x7fffffffu)                                                 // candidate indices, and ncand + 255, stay well inside 32 bits
+		return HD_E_NOMEM;
+	const uint32_t ncand = (uint32_t)h[0] + 1;
+	summary->ncandidates = ncand;
+	const size_t scan_tiles_b = ((size_t)ncand + hd::SCAN_TILE - 1) / hd::SCAN_TILE + ((size_t)ncand + hd::SCAN_TILE - 1) / hd::SCAN_TILE;
+	const size_t nc = ((size_t)ncand + 3) & ~(size_t)3;
+	// scan tiles | pos | succ[2] (later: rank) | mark | in_used | out_size | status | stop
+	if (g.d_cand.reserve((scan_tiles_b + nc * 2) * 8 + nc * 20))
+		return HD_E_NOMEM;
+	uint64_t *tiles_b = (uint64_t *)g.d_cand.p, *pos = tiles_b + scan_tiles_b, *rank = pos + nc;
+	uint32_t *succ0 = (uint32_t *)rank, *succ1 = succ0 + nc, *mark = succ1 + nc, *used = mark + nc, *osize = used + nc;
+	int32_t *pstat = (int32_t *)(osize + nc);
+	uint32_t *stop = (uint32_t *)(pstat + nc);
+	const uint32_t nwg = (ncand + 255) / 256;
+	HD_CHECK(hipMemsetAsync(pos, 0, 8, st));
+	HD_CHECK(hipMemsetD32Async((hipDeviceptr_t)pos, (int)hdr, 1, st));
+	if (ncand > 1)
+		hipLaunchKernelGGL(hd::k_stream_write, dim3(ntb), dim3(256), 0, st, src, scan_n, (uint64_t)hdr, (const uint64_t *)bitmap, nwords,
+				   (const uint64_t *)tile_off, pos + 1);
+	// one bounded decode per candidate
+	hipLaunchKernelGGL(hd::k_inflate_piece, dim3(ncand), dim3(64), 0, st,
+			   hd::PieceArgs{ src, (const uint64_t *)pos, ncand, max_chunk_in, payload_end, osize, used, pstat, stop });
+	hipLaunchKernelGGL(hd::k_stream_links, dim3(nwg), dim3(256), 0, st, (const uint64_t *)pos, (const uint32_t *)used,
+			   (const uint32_t *)stop, ncand, succ0, mark);
+	// the true chain: rounds until 2^rounds >= ncand (a chain has at most ncand rows)
+	for (uint64_t reach = 1; reach < ncand; reach *= 2) {
+		hipLaunchKernelGGL(hd::k_index_jump, dim3(nwg), dim3(256), 0, st, (const uint32_t *)succ0, succ1, (const uint32_t *)used, mark,
+				   ncand);
+		std::swap(succ0, succ1);
+	}
+	index_scan(mark, ncand, tiles_b, rank, sum + 0, st);                     // (the successor tables are dead: rank takes their place)
+	HD_CHECK(hipGetLastError());
+	HD_CHECK(hipMemcpyAsync(h, sum, 8, hipMemcpyDeviceToHost, st));
+	HD_CHECK(hipStreamSynchronize(st));
+	const uint64_t nrows = h[0];
+	if (own) {
+		if (own->reserve((size_t)nrows * 24 + 64))
+			return HD_E_NOMEM;
+		max_chunks = (uint32_t)nrows;
+		in_off = own->p;
+		out_off = (uint64_t *)in_off + nrows;
+		in_len = (uint64_t *)out_off + nrows;
+		out_size = (uint32_t *)in_len + nrows;
+	}
+	if (nrows) {
+		const uint32_t ntab = (uint32_t)(nrows < max_chunks ? nrows : max_chunks);
+		hipLaunchKernelGGL(hd::k_stream_rows, dim3(nwg), dim3(256), 0, st, (const uint64_t *)pos, (const uint32_t *)used,
+				   (const uint32_t *)osize, (const uint32_t *)mark, (const uint64_t *)rank, ncand, nrows, max_chunks,
+				   (uint64_t *)in_off, (uint32_t *)in_len, (uint32_t *)out_size, sum + 5);
+		if (ntab)
+			index_scan((const uint32_t *)out_size, ntab, tiles_b, (uint64_t *)out_off, sum + 1, st);
+	}
+	hipLaunchKernelGGL(hd::k_stream_verdict, dim3(1), dim3(1), 0, st, (const uint64_t *)pos, (const uint32_t *)used, (const int32_t *)pstat,
+			   (const uint32_t *)stop, ncand, nrows, max_chunks, max_chunk_in, payload_end, trl, sum);
+	HD_CHECK(hipGetLastError());
+	HD_CHECK(hipMemcpyAsync(h, sum, 32, hipMemcpyDeviceToHost, st));
+	HD_CHECK(hipStreamSynchronize(st));
+	summary->nchunks = h[0];
+	summary->out_bytes = h[1];
+	summary->end_offset = h[2];
+	summary->status = (uint32_t)h[3];
+	return 0;
+}
+
+int hipdeflate_stream_index_dev(const void *strm, uint64_t nbytes, int frame, uint32_t max_chunks, uint32_t max_chunk_in, void *in_off,
+				void *in_len, void *out_size, void *out_off, hipdeflate_stream_index_summary *summary, void *stream)
+{
+	Ctx &g = cur();
+	int r = ensure();
+	if (r)
+		return r;
+	if (!summary)
+		return HD_E_ARG;
+	memset(summary, 0, sizeof *summary);
+	if (!stream_frame_ok(frame) || ((uintptr_t)strm & 15) || (nbytes && !strm) || max_chunk_in >= HD_INFLATE_MAX_IN ||
+	    (max_chunks && (!in_off || !in_len || !out_size || !out_off)))
+		return HD_E_ARG;
+	return stream_index(g, strm, nbytes, frame, max_chunks, max_chunk_in, in_off, in_len, out_size, out_off, summary, (hipStream_t)stream,
+			    nullptr);
+}
+
+int hipdeflate_stream_inflate_table_dev(const void *strm, uint64_t nbytes, int frame, const void *in_off, const void *in_len,
+					const void *out_size, const void *out_off, uint32_t nchunks, void *out, uint64_t out_cap,
+					hipdeflate_stream_summary *summary, void *stream)
+{
+	Ctx &g = cur();
+	int r = ensure();
+	if (r)
+		return r;
+	if (!summary)
+		return HD_E_ARG;
+	memset(summary, 0, sizeof *summary);
+	summary->nchunks = nchunks;
+	summary->bad_chunk = nchunks;
+	if (!stream_frame_ok(frame) || ((uintptr_t)strm & 15) || (nbytes && !strm) || nchunks >= STREAM_MAX_PARTS || (out_cap && !out) ||
+	    (nchunks && (!in_off || !in_len || !out_size || !out_off)))
+		return HD_E_ARG;
+	if (nchunks == 0) {                                           // a stream has its final block, and that is a row
+		summary->status = 1;
+		return 0;
+	}
+	hipStream_t st = (hipStream_t)stream;
+	const uint32_t trl = stream_trl(frame);
+	const uint32_t kind = frame == HD_FRAME_ZLIB ? hd::CHECK_ADLER32 : hd::CHECK_CRC32;
+	const size_t n = nchunks, ntiles = (n + hd::SCAN_TILE - 1) / hd::SCAN_TILE;
+	std::lock_guard<std::mutex> lk(g.mu_index);
+	// sum[8] | the header's [8], then where the rows end [2] | scan tiles | prefix [n] | out_len, check, status [n]
+	if (g.d_stream.reserve((18 + ntiles + n) * 8 + 3 * n * 4))
+		return HD_E_NOMEM;
+	uint64_t *sum = (uint64_t *)g.d_stream.p, *ends = sum + 16, *tiles = ends + 2, *prefix = tiles + ntiles;
+	uint32_t *out_len = (uint32_t *)(prefix + n), *chk = out_len + n;
+	int32_t *status = (int32_t *)(chk + n);
+	uint32_t hdr = 0, refused = 0;
+	if ((r = stream_open(strm, nbytes, frame, sum + 8, st, &hdr, &refused)))
+		return r;
+	if (refused) {
+		summary->status = 1;
+		return 0;
+	}
+	uint32_t *carry = (uint32_t *)(sum + 4), *d_fault = carry + 1, *d_bad = carry + 3;
+	HD_CHECK(hipMemsetAsync(sum, 0, 64, st));
+	HD_CHECK(hipMemsetAsync(ends, 0, 16, st));
+	HD_CHECK(hipMemsetD32Async((hipDeviceptr_t)carry, kind == hd::CHECK_ADLER32 ? 1 : 0, 1, st));
+	HD_CHECK(hipMemsetD32Async((hipDeviceptr_t)d_fault, (int)hd::IDX_NIL, 1, st));
+	HD_CHECK(hipMemsetD32Async((hipDeviceptr_t)d_bad, (int)hd::IDX_NIL, 1, st));
+	hipLaunchKernelGGL(hd::k_stream_check_rows, dim3((nchunks + 255) / 256), dim3(256), 0, st, (const uint64_t *)in_off,
+			   (const uint32_t *)in_len, (const uint32_t *)out_size, (const uint64_t *)out_off, nchunks, (uint64_t)hdr, nbytes - trl,
+			   d_fault, ends);
+	HD_CHECK(hipGetLastError());
+	uint32_t h[4] = { 0, 0, 0, 0 };
+	uint64_t e[2] = { 0, 0 };
+	HD_CHECK(hipMemcpyAsync(h, carry, 16, hipMemcpyDeviceToHost, st));
+	HD_CHECK(hipMemcpyAsync(e, ends, 16, hipMemcpyDeviceToHost, st));
+	HD_CHECK(hipStreamSynchronize(st));
+	if (h[1] != hd::IDX_NIL) {
+		summary->status = 1;
+		summary->bad_chunk = h[1];
+		return 0;
+	}
+	if (out_cap < e[1]) {
+		summary->status = 3;
+		summary->out_bytes = e[1];
+		return 0;
+	}
+	// the trailer lies behind the last row, wherever the caller's buffer ends
+	return stream_decode_rows(g, strm, e[0] + trl, frame,
+				  { (const uint64_t *)in_off, (const uint32_t *)in_len, (const uint64_t *)out_off, (const uint32_t *)out_size, out_len,
+				    chk, status, tiles, prefix, sum },
+				  nchunks, e[1], out, summary, st);
 }
 
 /* ---- host-pointer API ------------------------------------------------------ */
@@ -2643,6 +2901,52 @@ int hip_deflate_stream(unsigned char *dest, size_t *destLen, const unsigned char
 		return 1;
 	HD_CHECK(hipMemcpy(dest, g.d_packed.p, s.out_bytes, hipMemcpyDeviceToHost));
 	*destLen = s.out_bytes;
+	return 0;
+}
+
+int hip_inflate_stream(unsigned char *dest, size_t *destLen, const unsigned char *source, size_t sourceLen, int frame, size_t *in_used)
+{
+	Ctx &g = cur();
+	int r = ensure();
+	if (r)
+		return r;
+	if (!destLen || (*destLen && !dest) || (sourceLen && !source) || !stream_frame_ok(frame))
+		return HD_E_ARG;
+	std::lock_guard<std::mutex> lk(g.mu);
+	if ((r = bind_device(g)))
+		return r;
+	if (g.d_in.reserve(up16(sourceLen) + 16))
+		return HD_E_NOMEM;
+	if (sourceLen)
+		HD_CHECK(hipMemcpyAsync(g.d_in.p, source, sourceLen, hipMemcpyHostToDevice, g.stream));
+	// stage, index, decode: the table stays on the device, in d_meta, as large as the stream needs
+	hipdeflate_stream_index_summary xs;
+	memset(&xs, 0, sizeof xs);
+	if ((r = stream_index(g, g.d_in.p, sourceLen, frame, 0, 0, nullptr, nullptr, nullptr, nullptr, &xs, g.stream, &g.d_meta)))
+		return r;
+	g.stream_drained(g.stream);
+	if (in_used)
+		*in_used = xs.end_offset;
+	if (xs.status)
+		return 1;
+	if (xs.out_bytes > *destLen) {
+		*destLen = xs.out_bytes;
+		return 3;
+	}
+	if (g.d_packed.reserve(up16(xs.out_bytes) + 16))
+		return HD_E_NOMEM;
+	const uint64_t n = xs.nchunks;
+	const uint64_t *in_off = (const uint64_t *)g.d_meta.p, *out_off = in_off + n;
+	const uint32_t *in_len = (const uint32_t *)(out_off + n), *out_size = in_len + n;
+	hipdeflate_stream_summary s;
+	if ((r = hipdeflate_stream_inflate_table_dev(g.d_in.p, xs.end_offset, frame, in_off, in_len, out_size, out_off, (uint32_t)n,
+						     g.d_packed.p, xs.out_bytes, &s, g.stream)))
+		return r;
+	if (s.status)
+		return 1;
+	if (xs.out_bytes)
+		HD_CHECK(hipMemcpy(dest, g.d_packed.p, xs.out_bytes, hipMemcpyDeviceToHost));
+	*destLen = xs.out_bytes;
 	return 0;
 }
 

@@ -51,8 +51,17 @@ __device__ __forceinline__ uint32_t index_match16(const uint32_t (&d)[5])
 	return m;
 }
 
+// The matcher of the two passes is a parameter: m(d, o) = the bits k of the granule at o whose position o + k matches, and
+// a match at position q makes the candidate q + M::SHIFT.  MatchMember is the member index's: a candidate is where the
+// gzip magic starts.  (hd_stream.hpp has the other one.)
+struct MatchMember {
+	static constexpr uint32_t SHIFT = 0;
+	__device__ __forceinline__ uint32_t operator()(const uint32_t (&d)[5], uint64_t) const { return index_match16(d); }
+};
+
 // pass 1: per 1 KiB word a ballot of the 16-byte granules that hold a candidate, per tile the candidate count
-__global__ __launch_bounds__(256) void k_index_flag(const uint8_t *blob, uint64_t nbytes, uint64_t *bitmap, uint32_t *tile_cnt)
+template <class M>
+__device__ __forceinline__ void index_flag_body(const uint8_t *blob, uint64_t nbytes, uint64_t *bitmap, uint32_t *tile_cnt, const M &match)
 {
 	__shared__ uint32_t wcnt[4];
 	const uint32_t t = threadIdx.x, lane = t & 63, w = t >> 6;
@@ -65,7 +74,7 @@ __global__ __launch_bounds__(256) void k_index_flag(const uint8_t *blob, uint64_
 			break;
 		uint32_t d[5];
 		index_load20(blob, nbytes, base + lane * 16, d);
-		const uint32_t m = index_match16(d);
+		const uint32_t m = match(d, base + lane * 16);
 		cnt += __popc(m);
 		const uint64_t any = __ballot(m != 0);
 		if (lane == 0)
@@ -82,8 +91,9 @@ __global__ __launch_bounds__(256) void k_index_flag(const uint8_t *blob, uint64_
 
 // pass 2: thread t of tile b owns bitmap word b * 256 + t; it re-reads the flagged granules only, and the candidates
 // of the tile go to pos[tile_off[b]...] in ascending order
-__global__ __launch_bounds__(256) void k_index_write(const uint8_t *blob, uint64_t nbytes, const uint64_t *bitmap,
-						      uint64_t nwords, const uint64_t *tile_off, uint64_t *pos)
+template <class M>
+__device__ __forceinline__ void index_write_body(const uint8_t *blob, uint64_t nbytes, const uint64_t *bitmap, uint64_t nwords,
+						 const uint64_t *tile_off, uint64_t *pos, const M &match)
 {
 	__shared__ uint32_t wtot[4];
 	const uint32_t t = threadIdx.x, lane = t & 63, w = t >> 6;
@@ -91,9 +101,10 @@ __global__ __launch_bounds__(256) void k_index_write(const uint8_t *blob, uint64
 	const uint64_t bits = wi < nwords ? bitmap[wi] : 0;
 	uint32_t c = 0;
 	for (uint64_t b = bits; b; b &= b - 1) {
+		const uint64_t o = wi * IDX_WORD + (uint32_t)__ffsll((long long)b) * 16 - 16;
 		uint32_t d[5];
-		index_load20(blob, nbytes, wi * IDX_WORD + (uint32_t)__ffsll((long long)b) * 16 - 16, d);
-		c += __popc(index_match16(d));
+		index_load20(blob, nbytes, o, d);
+		c += __popc(match(d, o));
 	}
 	const uint32_t incl = wave_incl_scan(c);
 	if (lane == 63)
@@ -106,9 +117,20 @@ __global__ __launch_bounds__(256) void k_index_write(const uint8_t *blob, uint64
 		const uint64_t o = wi * IDX_WORD + (uint32_t)__ffsll((long long)b) * 16 - 16;
 		uint32_t d[5];
 		index_load20(blob, nbytes, o, d);
-		for (uint32_t m = index_match16(d); m; m &= m - 1)
-			pos[at++] = o + (uint32_t)__ffs((int)m) - 1;
+		for (uint32_t m = match(d, o); m; m &= m - 1)
+			pos[at++] = o + (uint32_t)__ffs((int)m) - 1 + M::SHIFT;
 	}
+}
+
+__global__ __launch_bounds__(256) void k_index_flag(const uint8_t *blob, uint64_t nbytes, uint64_t *bitmap, uint32_t *tile_cnt)
+{
+	index_flag_body(blob, nbytes, bitmap, tile_cnt, MatchMember{});
+}
+
+__global__ __launch_bounds__(256) void k_index_write(const uint8_t *blob, uint64_t nbytes, const uint64_t *bitmap,
+						      uint64_t nwords, const uint64_t *tile_off, uint64_t *pos)
+{
+	index_write_body(blob, nbytes, bitmap, nwords, tile_off, pos, MatchMember{});
 }
 
 struct Member {

@@ -51,24 +51,55 @@ struct InfSizeLds {
 };
 static_assert(sizeof(InfSizeLds) <= 4 * 1280, "InfSizeLds must stay within four LDS allocation units");
 
-__global__ __launch_bounds__(64) void k_inflate_size(SizeArgs a)
+// The piece form (k_inflate_piece): the same decoder started at a candidate of the stream index (hd_stream.hpp), which
+// stops at whichever comes first -- a flush point, the end of a non-final stored block with LEN == 0, or the end of a
+// final block -- and says which.  Its input is the candidate's bytes up to the end of the payload region, max_in at
+// the most.  Every verdict of the size pass is kept, and one is told apart: PIECE_CUT where the decoder needed a bit at
+// or behind the end of its input (bits there read as 0; whatever the decoder makes of them, the verdict is this one).
+struct PieceArgs {
+	const uint8_t *in;
+	const uint64_t *pos;             // the candidates, ascending
+	uint32_t ncand;
+	uint32_t max_in;                 // < HD_INFLATE_MAX_IN
+	uint64_t payload_end;            // > pos[i] for every i
+	uint32_t *out_size;
+	uint32_t *in_used;               // whole bytes, 0 where the piece does not decode
+	int32_t *status;                 // HD_OK | HD_BAD_DATA | HD_INSUFFICIENT_SPACE | PIECE_CUT
+	uint32_t *stop;                  // PIECE_FLUSH | PIECE_FINAL, 0 where the piece does not decode
+};
+constexpr int32_t PIECE_CUT = 4;
+constexpr uint32_t PIECE_FLUSH = 1, PIECE_FINAL = 2;
+
+template <bool PIECE, class Args> __device__ __forceinline__ void inflate_size_body(const Args &a)
 {
 	__shared__ InfSizeLds L;
 	const uint32_t lane = threadIdx.x;
 	const uint32_t b = blockIdx.x;
-	if (b >= a.nblocks)
-		return;
-	const uint64_t p_off = a.p_off[b];
+	uint64_t p_off;
+	uint32_t n;
+	if constexpr (PIECE) {
+		if (b >= a.ncand)
+			return;
+		p_off = a.pos[b];
+		const uint64_t left = a.payload_end - p_off;
+		n = left < a.max_in ? (uint32_t)left : a.max_in;
+	} else {
+		if (b >= a.nblocks)
+			return;
+		p_off = a.p_off[b];
+		n = a.p_len[b];
+	}
 	const uint8_t *src = a.in + p_off;
-	const uint32_t n = a.p_len[b];
-	if (n >= HD_INFLATE_MAX_IN || (a.verdict && a.verdict[b])) {
-		// (stream positions are 32-bit bit counts, as in k_inflate: a stream this long is refused whole)
-		if (lane == 0) {
-			a.out_size[b] = 0;
-			a.in_used[b] = 0;
-			a.status[b] = HD_BAD_DATA;
+	if constexpr (!PIECE) {
+		if (n >= HD_INFLATE_MAX_IN || (a.verdict && a.verdict[b])) {
+			// (stream positions are 32-bit bit counts, as in k_inflate: a stream this long is refused whole)
+			if (lane == 0) {
+				a.out_size[b] = 0;
+				a.in_used[b] = 0;
+				a.status[b] = HD_BAD_DATA;
+			}
+			return;
 		}
-		return;
 	}
 
 	// ---- compressed input: hd_inflate.hpp's reader, statement for statement ----
@@ -255,6 +286,8 @@ __global__ __launch_bounds__(64) void k_inflate_size(SizeArgs a)
 
 	int32_t st = HD_OK;
 	bool static_loaded = false;
+	uint32_t stop = 0;                            // (piece form) the stop it hit
+	bool cut = false;                             // (piece form) a stored block's LEN / NLEN or payload reaches past the input
 	for (;;) {
 		refill();
 		lds_p0 = 0xfffffff0u;                     // header parsing reuses the LDS behind L.comp
@@ -268,16 +301,22 @@ __global__ __launch_bounds__(64) void k_inflate_size(SizeArgs a)
 			const int64_t cbits = (consumed_bits() + 7) & ~(int64_t)7;
 			if (cbits > 8 * (int64_t)n) { st = HD_BAD_DATA; break; }
 			uint32_t ip = (uint32_t)(cbits >> 3);
-			if (n - ip < 4) { st = HD_BAD_DATA; break; }
+			if (n - ip < 4) { st = HD_BAD_DATA; cut = true; break; }
 			seek_bit(8 * (mis + ip));
 			refill();
 			const uint32_t len = (uint32_t)bb & 0xffff, nlen = ((uint32_t)bb >> 16) & 0xffff;
 			ip += 4;
 			if (len != (~nlen & 0xffff)) { st = HD_BAD_DATA; break; }
 			if (pos + len > POS_LIMIT) { st = HD_INSUFFICIENT_SPACE; break; }
-			if (len > n - ip) { st = HD_BAD_DATA; break; }
+			if (len > n - ip) { st = HD_BAD_DATA; cut = true; break; }
 			pos += len;
 			seek_bit(8 * (mis + ip + len));
+			if constexpr (PIECE) {
+				if (!bfinal && len == 0) {
+					stop = PIECE_FLUSH;
+					break;
+				}
+			}
 		} else if (btype == 3) {
 			st = HD_BAD_DATA;
 			break;
@@ -401,31 +440,50 @@ __global__ __launch_bounds__(64) void k_inflate_size(SizeArgs a)
 			if (st != HD_OK)
 				break;
 		}
-		if (bfinal)
+		if (bfinal) {
+			if constexpr (PIECE)
+				stop = PIECE_FINAL;
 			break;
+		}
 		if (consumed_bits() > 8 * (int64_t)n + 64) { st = HD_BAD_DATA; break; }
 	}
-	if (st == HD_OK && consumed_bits() > 8 * (int64_t)n)
-		st = HD_BAD_DATA;
+	if constexpr (PIECE) {
+		// with the decoder's position past the input -- at a stop it reached through the zero bits, or at the failure they
+		// led to -- the piece is cut, whatever else the decoder found there
+		if (cut || consumed_bits() > 8 * (int64_t)n)
+			st = PIECE_CUT;
+		if (lane == 0) {
+			a.out_size[b] = st == HD_OK ? (uint32_t)pos : 0u;
+			a.in_used[b] = st == HD_OK ? (uint32_t)((consumed_bits() + 7) >> 3) : 0u;
+			a.status[b] = st;
+			a.stop[b] = st == HD_OK ? stop : 0u;
+		}
+	} else {
+		if (st == HD_OK && consumed_bits() > 8 * (int64_t)n)
+			st = HD_BAD_DATA;
 
-	// ---- the verdict: the stream's, and the one field of the trailer that needs no byte of output ----
-	uint32_t used = 0;
-	if (st == HD_OK) {
-		used = (uint32_t)((consumed_bits() + 7) >> 3);
-		if (a.trailer == 8) {
-			// RFC 1952 ISIZE, behind the CRC-32 (gzip_decompress.c:124-127); used <= n, and k_frame_open left 8 bytes behind n
-			const uint8_t *t = src + used + 4;
-			const uint32_t isize = t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16) | ((uint32_t)t[3] << 24);
-			if (isize != (uint32_t)pos)
-				st = HD_BAD_DATA;
+		// ---- the verdict: the stream's, and the one field of the trailer that needs no byte of output ----
+		uint32_t used = 0;
+		if (st == HD_OK) {
+			used = (uint32_t)((consumed_bits() + 7) >> 3);
+			if (a.trailer == 8) {
+				// RFC 1952 ISIZE, behind the CRC-32 (gzip_decompress.c:124-127); used <= n, and k_frame_open left 8 bytes behind n
+				const uint8_t *t = src + used + 4;
+				const uint32_t isize = t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16) | ((uint32_t)t[3] << 24);
+				if (isize != (uint32_t)pos)
+					st = HD_BAD_DATA;
+			}
+		}
+		if (lane == 0) {
+			const uint32_t hdr = a.m_off ? (uint32_t)(p_off - a.m_off[b]) : 0u;
+			a.out_size[b] = st == HD_OK ? (uint32_t)pos : 0u;
+			a.in_used[b] = st == HD_OK ? hdr + used + a.trailer : 0u;
+			a.status[b] = st;
 		}
 	}
-	if (lane == 0) {
-		const uint32_t hdr = a.m_off ? (uint32_t)(p_off - a.m_off[b]) : 0u;
-		a.out_size[b] = st == HD_OK ? (uint32_t)pos : 0u;
-		a.in_used[b] = st == HD_OK ? hdr + used + a.trailer : 0u;
-		a.status[b] = st;
-	}
 }
+
+__global__ __launch_bounds__(64) void k_inflate_size(SizeArgs a) { inflate_size_body<false>(a); }
+__global__ __launch_bounds__(64) void k_inflate_piece(PieceArgs a) { inflate_size_body<true>(a); }
 
 } // namespace hd

@@ -14,6 +14,7 @@
 #pragma once
 #include "hd_compact.hpp"
 #include "hd_index.hpp"
+#include "hd_inflate_size.hpp"
 
 namespace hd {
 
@@ -281,6 +282,149 @@ __global__ void k_stream_trailer(const uint8_t *strm, uint64_t nbytes, int frame
 		bad = crc != c || isize != (uint32_t)out_bytes;
 	}
 	*mismatch = bad;
+}
+
+// ---- the index of a stream nobody kept a table for -----------------------------------------------------------------------
+// A chunk in flush form ends in an empty stored block, and that block's last four bytes are 00 00 ff ff on a byte boundary.
+// This is hd_index.hpp's problem again, with a decoder in the place of the header rules:
+//   1. k_stream_flag / k_stream_write: one streaming read of the payload region finds every position with those four bytes
+//      in front of it; with the first payload byte they are the sorted candidate list;
+//   2. k_inflate_piece (hd_inflate_size.hpp), one wavefront per candidate, decodes from there to the first flush point or
+//      final block; its distance check makes a chunk that reaches back over its own start bad data from that start;
+//   3. k_stream_links: a piece that ends in a flush point links to the candidate at its end;
+//   4. k_index_jump marks what candidate 0 reaches, a prefix count ranks it, k_stream_rows writes the tables;
+//   5. k_stream_verdict names where the chain stopped and why.
+
+// bit k: the four bytes at o + k are 00 00 ff ff and o + k >= lo; the candidate is the byte behind them.  The passes get
+// the payload's end less one as their nbytes, so a marker that ends on the last payload byte, or runs into the trailer,
+// makes no candidate.
+struct MatchFlush {
+	static constexpr uint32_t SHIFT = 4;
+	uint64_t lo;
+	__device__ __forceinline__ uint32_t operator()(const uint32_t (&d)[5], uint64_t o) const
+	{
+		uint32_t m = 0;
+#pragma unroll
+		for (uint32_t k = 0; k < 16; k++) {
+			const uint32_t w = (k & 3) ? __builtin_amdgcn_alignbyte(d[(k >> 2) + 1], d[k >> 2], k & 3) : d[k >> 2];
+			m |= (uint32_t)(w == 0xffff0000u) << k;
+		}
+		if (o < lo)
+			m = lo - o >= 16 ? 0u : m & ~((1u << (uint32_t)(lo - o)) - 1u);
+		return m;
+	}
+};
+
+__global__ __launch_bounds__(256) void k_stream_flag(const uint8_t *strm, uint64_t nbytes, uint64_t lo, uint64_t *bitmap, uint32_t *tile_cnt)
+{
+	index_flag_body(strm, nbytes, bitmap, tile_cnt, MatchFlush{ lo });
+}
+
+__global__ __launch_bounds__(256) void k_stream_write(const uint8_t *strm, uint64_t nbytes, uint64_t lo, const uint64_t *bitmap,
+						       uint64_t nwords, const uint64_t *tile_off, uint64_t *pos)
+{
+	index_write_body(strm, nbytes, bitmap, nwords, tile_off, pos, MatchFlush{ lo });
+}
+
+// the candidate at offset `at` among pos[from .. ncand), IDX_NIL if there is none
+__device__ __forceinline__ uint32_t stream_find(const uint64_t *pos, uint32_t from, uint32_t ncand, uint64_t at)
+{
+	uint32_t lo = from, hi = ncand;
+	while (lo < hi) {
+		const uint32_t mid = lo + ((hi - lo) >> 1);
+		if (pos[mid] < at)
+			lo = mid + 1;
+		else
+			hi = mid;
+	}
+	return lo < ncand && pos[lo] == at ? lo : IDX_NIL;
+}
+
+// one lane per candidate: a piece that ended in a flush point links to the candidate behind it (there is one unless the
+// payload ends there), everything else to nil.  in_used[] is 0 where a piece does not decode.
+__global__ __launch_bounds__(256) void k_stream_links(const uint64_t *pos, const uint32_t *in_used, const uint32_t *stop, uint32_t ncand,
+						       uint32_t *succ, uint32_t *mark)
+{
+	const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+	if (i >= ncand)
+		return;
+	succ[i] = stop[i] == PIECE_FLUSH ? stream_find(pos, i + 1, ncand, pos[i] + in_used[i]) : IDX_NIL;
+	mark[i] = i == 0 && in_used[i];                      // the head of the true chain
+}
+
+// the marked candidates in rank order -> the rows; the last one is named in *last
+__global__ __launch_bounds__(256) void k_stream_rows(const uint64_t *pos, const uint32_t *in_used, const uint32_t *osize,
+						      const uint32_t *mark, const uint64_t *rank, uint32_t ncand, uint64_t nrows,
+						      uint32_t max_chunks, uint64_t *in_off, uint32_t *in_len, uint32_t *out_size, uint64_t *last)
+{
+	const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+	if (i >= ncand || !mark[i])
+		return;
+	const uint64_t r = rank[i];
+	if (r < max_chunks) {
+		in_off[r] = pos[i];
+		in_len[r] = in_used[i];
+		out_size[r] = osize[i];
+	}
+	if (r + 1 == nrows)
+		*last = i;
+}
+
+// sum[] = { nchunks, out_bytes, end_offset, status, -, the last row's candidate }.  The chain ends well in a piece that
+// ended in a final block (the trailer's bytes lie behind it: no piece reads past the payload's end); it is cut where a
+// flush point is the payload's last byte; otherwise it stopped in front of a piece that does not decode, and that piece is
+// cut if its verdict is PIECE_CUT with the payload's end as its bound, bad in every other case.
+__global__ void k_stream_verdict(const uint64_t *pos, const uint32_t *in_used, const int32_t *status, const uint32_t *stop,
+				 uint32_t ncand, uint64_t nrows, uint32_t max_chunks, uint32_t max_in, uint64_t payload_end, uint32_t trailer,
+				 uint64_t *sum)
+{
+	uint32_t c = 0;                                       // the piece the chain stopped in front of
+	uint64_t end = 0, st = 0;
+	if (nrows) {
+		const uint32_t last = (uint32_t)sum[5];
+		end = pos[last] + in_used[last];
+		if (stop[last] == PIECE_FINAL) {
+			end += trailer;
+			c = IDX_NIL;
+		} else {
+			c = stream_find(pos, last + 1, ncand, end);
+			if (c == IDX_NIL)
+				st = 2;
+		}
+	}
+	if (c != IDX_NIL) {
+		end = pos[c];
+		st = status[c] == PIECE_CUT && payload_end - end <= max_in ? 2 : 1;
+	}
+	if (nrows > max_chunks)
+		st = 3;
+	sum[0] = nrows;
+	sum[2] = end;
+	sum[3] = st;
+}
+
+// The check in front of the decode on a caller's table of uneven rows, one lane per row: a row lies in the payload region
+// [lo, payload_end), is shorter than HD_INFLATE_MAX_IN and ends at or in front of its successor; out_off is the exclusive
+// prefix sum of out_size.  *bad (0xffffffff before the launch) takes the lowest row at fault; ends[] = where the last row
+// ends in the stream and in the output.
+__global__ __launch_bounds__(256) void k_stream_check_rows(const uint64_t *in_off, const uint32_t *in_len, const uint32_t *out_size,
+							    const uint64_t *out_off, uint32_t n, uint64_t lo, uint64_t payload_end,
+							    uint32_t *bad, uint64_t *ends)
+{
+	const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+	if (i >= n)
+		return;
+	const uint64_t o = in_off[i], q = out_off[i];
+	const uint32_t len = in_len[i], size = out_size[i];
+	bool fault = len >= HD_INFLATE_MAX_IN || o < lo || o > payload_end || len > payload_end - o || (i == 0 && q != 0);
+	if (i + 1 < n) {
+		fault = fault || in_off[i + 1] < o || in_off[i + 1] - o < len || out_off[i + 1] - q != size || out_off[i + 1] < q;
+	} else {
+		ends[0] = o + len;
+		ends[1] = q + size;
+	}
+	if (fault)
+		atomicMin(bad, i);
 }
 
 } // namespace hd

@@ -216,6 +216,62 @@ def inflate_stream(stream, chunk_off, chunk, out_bytes, frame=_pkg.FRAME_GZIP):
     return out
 
 
+def index_stream_call(stream, frame, max_chunks, max_chunk_in, in_off, in_len, out_size, out_off):
+    """one hipdeflate_stream_index_dev: stream a 16-byte aligned uint8 tensor, the four tables int64 / int32 tensors of
+    max_chunks entries (None with max_chunks == 0: the sizing call) -> StreamIndexSummary"""
+    summary = _pkg.StreamIndexSummary()
+    rc = _pkg.lib().hipdeflate_stream_index_dev(_ptr(stream), stream.numel(), frame, max_chunks, max_chunk_in, _ptr(in_off),
+                                                _ptr(in_len), _ptr(out_size), _ptr(out_off), ctypes.byref(summary), _stream())
+    _pkg._check(rc, "hipdeflate_stream_index_dev")
+    return summary
+
+
+def index_stream(stream, frame=_pkg.FRAME_GZIP, max_chunks=None, max_chunk_in=0):
+    """the chunk table of a stream in flush form whose table nobody kept -> (in_off, in_len, out_size, out_off,
+    StreamIndexSummary): device tensors of max_chunks entries, of which min(nchunks, max_chunks) are filled.  Without
+    max_chunks the tables get one row per 64 stream bytes, and where a stream has more (status 3 names the number) it is
+    indexed again on tables of that size."""
+    dev = stream.device
+
+    def run(n):
+        t = (torch.zeros(n, dtype=torch.int64, device=dev), torch.zeros(n, dtype=torch.int32, device=dev),
+             torch.zeros(n, dtype=torch.int32, device=dev), torch.zeros(n, dtype=torch.int64, device=dev))
+        return t + (index_stream_call(stream, frame, n, max_chunk_in, *t),)
+
+    if max_chunks is not None:
+        return run(max_chunks)
+    r = run(stream.numel() // 64 + 16)
+    return run(r[4].nchunks) if r[4].status == 3 else r
+
+
+def inflate_stream_table_call(stream, frame, in_off, in_len, out_size, out_off, nchunks, out, out_cap):
+    """one hipdeflate_stream_inflate_table_dev -> StreamSummary"""
+    summary = _pkg.StreamSummary()
+    rc = _pkg.lib().hipdeflate_stream_inflate_table_dev(_ptr(stream), stream.numel(), frame, _ptr(in_off), _ptr(in_len),
+                                                        _ptr(out_size), _ptr(out_off), nchunks, _ptr(out), out_cap,
+                                                        ctypes.byref(summary), _stream())
+    _pkg._check(rc, "hipdeflate_stream_inflate_table_dev")
+    return summary
+
+
+def inflate_stream_auto(stream, frame=_pkg.FRAME_GZIP):
+    """a raw / zlib / gzip stream in flush form, 16-byte aligned uint8 tensor -> (uint8 tensor of its contents,
+    StreamIndexSummary): index, one allocation, the chunks inflated side by side and held to the trailer.  Only the two
+    summaries visit the host.  Bytes behind the trailer are left alone: summary.end_offset says where they start."""
+    in_off, in_len, out_size, out_off, x = index_stream(stream, frame)
+    if x.status:
+        why = {1: "a piece does not decode, or the header is refused", 2: "the stream is cut"}
+        raise _pkg.HipDeflateError("stream index: %s at offset %d (status %d, %d chunks)" % (why.get(x.status, "?"), x.end_offset,
+                                                                                            x.status, x.nchunks))
+    out = torch.empty(x.out_bytes, dtype=torch.uint8, device=stream.device)
+    s = inflate_stream_table_call(stream, frame, in_off, in_len, out_size, out_off, x.nchunks, out, x.out_bytes)
+    if s.status:
+        why = {1: "a bad table", 2: "a chunk or the check disagrees", 3: "room too small"}
+        raise _pkg.HipDeflateError("stream decode: %s (status %d, bad_chunk %d of %d)" % (why.get(s.status, "?"), s.status,
+                                                                                         s.bad_chunk, s.nchunks))
+    return out, x
+
+
 def check_combine(check, lens, kind=_pkg.CHECK_CRC32):
     """the CRC-32 (kind 0) / Adler-32 (kind 1) of a concatenation from the checks and lengths of its parts: int32 device
     tensors holding the bits of the u32 values -> int"""

@@ -435,6 +435,86 @@ int hipdeflate_stream_deflate_dev(const void *in, uint64_t nbytes, uint32_t chun
 int hipdeflate_stream_inflate_dev(const void *strm, uint64_t nbytes, int frame,
 				  const void *chunk_off, uint32_t nchunks, uint32_t chunk_bytes, uint64_t out_bytes,
 				  void *out, uint64_t out_cap, hipdeflate_stream_summary *summary /* HOST */, void *stream);
+/* ---- ... and the same decode for a stream whose table nobody kept ----------------------
+ * A .gz, zlib or raw stream written in flush form -- by the encoder above, by zlib with Z_FULL_FLUSH, by pigz -i, a dictzip
+ * file without its RA field -- carries its own table: every chunk ends in an empty stored block, whose last four bytes are
+ * 00 00 ff ff on a byte boundary.  hipdeflate_stream_index_dev finds it, by the method of the member index: one streaming
+ * read of the payload region [header, nbytes - trailer) lists every position with those four bytes in front of it, plus
+ * the first payload byte (candidate 0); one wavefront per candidate decodes, writing no byte, from there to whichever
+ * comes first -- a FLUSH POINT, the end of a non-final stored block with LEN == 0, or the end of a FINAL block -- over at
+ * most min(max_chunk_in, what is left of the payload region) bytes; a piece that ends in a flush point names the candidate
+ * behind it, and the chain from candidate 0 alone decides.  Markers inside a chunk -- in a stored payload, or by chance --
+ * cost a decode and change nothing.  A chunk whose matches reach back over its own start (a sync flush, which keeps the
+ * window) does not decode from that start: the chain stops there with status 1 and is never decoded wrong.  A stream
+ * without flush points is one row.  Row i of the table:
+ *   in_off[i]   (u64) where the piece starts          in_len[i]   (u32) its exact length, marker included
+ *   out_size[i] (u32) bytes it decodes to             out_off[i]  (u64) exclusive prefix sum of out_size
+ * all four device arrays of max_chunks entries.  The final piece is a row of its own: for a stream of the encoder above rows
+ * 0..n-1 are the chunks, row n is the 03 00 with size 0, and in_off[0..n] equals its chunk_off[0..n] -- where the encoder codes
+ * every chunk whole.  At levels 1..2 it codes a chunk longer than HD_SEG_LIMIT as full-flush segments; every segment is a row
+ * then, and chunk_off is a subsequence of in_off.  Rows of size 0 (two flushes in a row) stay in the table.  *summary (host
+ * memory): */
+typedef struct hipdeflate_stream_index_summary {
+	uint64_t nchunks;      /* rows in the table (status 3: rows the stream has) */
+	uint64_t out_bytes;    /* sum of out_size over the table */
+	uint64_t end_offset;   /* status 0: first byte behind the trailer; else where the chain stopped */
+	uint64_t ncandidates;
+	uint32_t hdr_bytes;
+	uint32_t status;       /* 0 ok | 1 the piece at end_offset does not decode (bad data, reaches back over its start, longer than
+	                          max_chunk_in, 2^32 bytes of output) or the header is refused | 2 the stream is cut: no final block
+	                          before the bytes run out, or no room for the trailer | 3 table too small */
+} hipdeflate_stream_index_summary;
+/* frame is HD_FRAME_RAW (no header), HD_FRAME_ZLIB or HD_FRAME_GZIP; the header is held to the rules of
+ * hipdeflate_batch_inflate_framed_dev (gzip: FEXTRA / FNAME / FCOMMENT / FHCRC allowed, so files of gzip and pigz qualify), on
+ * the first HD_INFLATE_MAX_IN - 1 bytes of the stream at the most.  strm must be 16-byte aligned; no byte at or behind strm +
+ * nbytes is read.  A marker that would put a candidate at or behind nbytes - trailer does not count.  max_chunk_in bounds
+ * one piece's input; 0 means HD_INFLATE_MAX_IN - 1, which is also the most (more: HD_E_ARG).
+ *   status 0  the chain's last row ended in a final block, and the trailer's bytes lie behind it.  Bytes behind the trailer
+ *             are allowed and are not looked at: end_offset says where a following member would start, and the walk over
+ *             concatenated members is the caller's.  The trailer's contents are not examined (the decode below does that).
+ *   status 1  the piece that starts at end_offset does not decode: bad data, a distance past the bytes the piece has put out,
+ *             2^32 bytes of output, or more than max_chunk_in bytes of input with payload left behind them; or the header is
+ *             refused (end_offset 0, hdr_bytes 0, ncandidates 0).
+ *   status 2  the piece that starts at end_offset needed a bit at or behind nbytes - trailer, or a flush point is the last
+ *             payload byte (end_offset = nbytes - trailer then); or nbytes is below the frame's header and trailer (18 / 6
+ *             bytes, end_offset 0, ncandidates 0).  A stream cut short anywhere, trailer included, ends like this unless the
+ *             cut leaves an element the rules refuse.
+ *   status 3  more rows than max_chunks: the first max_chunks rows are in the table, nothing is written past them, nchunks is
+ *             the number the stream has, out_bytes the sum over the table, and end_offset and the verdict that status 3
+ *             replaces are those of the whole chain -- max_chunks == 0 with NULL tables is the sizing call.
+ * With status 1 or 2 the rows in front of end_offset are in the table and usable with hipdeflate_batch_inflate_flush_dev.
+ * Returns 0 whenever the index ran (the verdict is summary->status), HD_E_* otherwise.  Scratch -- the bitmap, the candidate
+ * list, five words a candidate -- is the library's, grow-only; calls take turns with the member index and the other stream
+ * calls.  Work: one streaming read, one piece decode per candidate, O(log candidates) passes over the list.  An honest
+ * writer leaves about one marker by chance per 2^32 compressed bytes, and more only where stored payloads hold the four
+ * bytes; a stream made to hurt -- stored payloads full of markers -- buys one decode of at most max_chunk_in bytes per
+ * candidate, of which most end within a block header, and never a wrong table.  (Synchronises the stream.) */
+int hipdeflate_stream_index_dev(const void *strm, uint64_t nbytes, int frame, uint32_t max_chunks, uint32_t max_chunk_in,
+				void *in_off /* u64 */, void *in_len /* u32 */, void *out_size /* u32 */, void *out_off /* u64 */,
+				hipdeflate_stream_index_summary *summary /* HOST */, void *stream);
+/* The decode on such a table: hipdeflate_stream_inflate_dev behind its table check, for rows of uneven size.  Row i goes by
+ * the flush-rule batch inflate into out + out_off[i] with exactly out_size[i] as room, the rows' checks are folded, and the
+ * result is held to the trailer, which is read behind the last row (in_off[n-1] + in_len[n-1]), wherever nbytes is.  The
+ * four tables are device arrays of nchunks entries, in the index's layout.  Status and fields are hipdeflate_stream_summary's:
+ *   status 1  nchunks is 0 (a stream has its final row); the header is refused or nbytes too short for header and trailer;
+ *             a row starts in front of the header, ends behind nbytes - trailer, overlaps its successor or comes after it, or
+ *             has HD_INFLATE_MAX_IN bytes or more; out_off is not the exclusive prefix sum of out_size.  bad_chunk = the
+ *             lowest row at fault, nchunks for the header and the lengths.  Nothing is inflated.
+ *   status 3  out_cap < out_off[n-1] + out_size[n-1]; out_bytes is that need.  Nothing is inflated.  (Status 1 comes first.)
+ *   status 2  bad_chunk = i: row i's inflate status is non-zero or its length is not out_size[i] (check is unspecified then);
+ *             bad_chunk = nchunks: every row is fine but the folded check, or the gzip ISIZE, disagrees with the trailer.
+ * With status 0 and 2 out_bytes is the rows' total and in_bytes the offset behind the trailer.  No read and no write depends
+ * on what the table claims beyond what the check has held it to.  strm 16-byte aligned, out of any alignment.  Returns 0
+ * whenever the call ran.  (Synchronises the stream; takes turns as the index does.) */
+int hipdeflate_stream_inflate_table_dev(const void *strm, uint64_t nbytes, int frame,
+					const void *in_off, const void *in_len, const void *out_size, const void *out_off,
+					uint32_t nchunks, void *out, uint64_t out_cap,
+					hipdeflate_stream_summary *summary /* HOST */, void *stream);
+/* host-buffer form: stage, index, decode; the table stays on the device and the scratch grows with the stream.  *destLen in =
+ * room, out = bytes.  0; 1 = not such a stream (index status 1 or 2) or it disagrees with its trailer; 3 = the room is too
+ * small, *destLen = the need.  *in_used (may be NULL) = the index's end_offset: with 0 and 3 the first byte behind the trailer. */
+int hip_inflate_stream(unsigned char *dest, size_t *destLen, const unsigned char *source, size_t sourceLen, int frame,
+		       size_t *in_used);
 /* the fold on its own: check[] / len[] device arrays of n parts (u32 each, n < 2^31), kind 0 = CRC-32, 1 = Adler-32; *result HOST.
  * The check of the concatenation of the parts from the parts' own: the role of crc_append (the hosts' serial fold, after
  * zlib's crc32_combine) with one lane per part -- part i contributes check[i] moved over the S_i bytes behind it, S_i a
