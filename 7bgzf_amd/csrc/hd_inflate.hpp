@@ -22,9 +22,14 @@
 //   * output goes through an LDS ring; finished 1 KiB pieces leave as 16 B per
 //     lane stores; a match copy is 64 bytes per step across the lanes, from the
 //     ring when the source is near, from HBM (already flushed) when it is far.
+//
+// SHARED AND COPIED.  The entry formats, build_table and slow_decode are hd_inflate_common.hpp's, as for the latency
+// decoder (hd_inflate_lat.hpp) and the size pass (hd_inflate_size.hpp).  Those two also take from there everything that
+// reads a stream: InfReader, inflate_dynamic_header / inflate_static_tables, spec_token, window_walk.  inflate_stream
+// below keeps its own copy of each, marked "(own copy of ...)" where it stands: DESIGN.md 4.3c has the measurements.  A
+// rule changed in hd_inflate_common.hpp is changed here as well; tests/test_gpu_inflate_agree.py holds the two to each other.
 #pragma once
-#include <type_traits>
-#include "hd_device.hpp"
+#include "hd_inflate_common.hpp"
 
 namespace hd {
 
@@ -52,68 +57,10 @@ struct InflateFramedArgs : InflateArgs {
 // that report "out of input" as success (zlib_inflate, lib/zlibutil.c:289-291; igzip_inflate, zlibutil_igzip.c:111)
 constexpr uint32_t INF_FLUSHED = 1;
 
-#ifdef HD_INFLATE_STATS
-// experiment build only (tools/exp_inflate_stats.sh): where the tokens go
-__device__ unsigned long long g_inf_stats[8];
-__device__ unsigned long long g_inf_stats2[8];      // matches of the windows: [0] all [1] lane groups of 8 [2] of 16 [3] simple, one at a time [4] far, one at a time [5] general (fed by the window, overlapping, > 64 bytes)
-#define INF_STAT2(k, v) atomicAdd(&g_inf_stats2[k], lane == 0 ? (unsigned long long)(v) : 0ull)
-#define INF_U64(m) (((uint64_t)uniform((uint32_t)((m) >> 32)) << 32) | uniform((uint32_t)(m)))
-__device__ unsigned long long g_inf_cycles[8];       // [0] block headers + table build, [1] windows, [2] scalar token path, [3] whole kernel
-// (every lane adds, lane 0 the value and the others zero: an `if (lane == 0)` around the atomic makes the compiler treat the
-// lane masks that live across it as divergent, and the window code keeps them in scalar registers)
-#define INF_STAT(k, v) atomicAdd(&g_inf_stats[k], lane == 0 ? (unsigned long long)(v) : 0ull)
-#define INF_T0(t) const unsigned long long t = __builtin_amdgcn_s_memtime()
-// (cycles are summed in scalar registers and leave once per wave)
-#define INF_T1(k, t) do { inf_cyc[k] += __builtin_amdgcn_s_memtime() - (t); } while (0)
-#define INF_CYC_DECL unsigned long long inf_cyc[4] = { 0, 0, 0, 0 }
-#define INF_CYC_FLUSH do { for (int k_ = 0; k_ < 4; k_++) atomicAdd(&g_inf_cycles[k_], lane == 0 ? inf_cyc[k_] : 0ull); } while (0)
-#else
-#define INF_STAT(k, v) do { } while (0)
-#define INF_STAT2(k, v) do { } while (0)
-#define INF_T0(t) do { } while (0)
-#define INF_T1(k, t) do { } while (0)
-#define INF_CYC_DECL do { } while (0)
-#define INF_CYC_FLUSH do { } while (0)
-#endif
-
-constexpr uint32_t INF_LT_BITS = 9;      // litlen direct table (8 VGPRs once loaded)
-constexpr uint32_t INF_DT_BITS = 8;      // offset direct table
 constexpr uint32_t INF_RING    = 2048;   // LDS output ring of the throughput kernel: small on purpose, occupancy beats window
                                          // (8 KiB: 36 GB/s, 2 KiB: 49 GB/s on the libdeflate-6 stream)
 constexpr uint32_t INF_RING_LAT = 65536; // ... of the latency kernel (k_inflate_lat: a few streams on an empty chip, hip_inflate):
                                          // every match source of a block is in LDS, nothing waits for flushed output
-
-// table entry: [31:16] value (literal / length base / offset base)
-//              [9:8] kind  [7:4] extra-bit count  [3:0] codeword length
-constexpr uint32_t K_LIT = 0, K_LEN = 1, K_EOB = 2, K_SLOW = 3;
-
-// order in which the precode lengths are stored (RFC 1951 3.2.7;
-// decompress_template.h:91-93)
-__constant__ uint8_t k_precode_perm[19] = { 16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15 };
-
-__device__ __forceinline__ uint32_t litlen_entry(uint32_t sym, uint32_t len)
-{
-	if (sym < 256)
-		return (sym << 16) | (K_LIT << 8) | len;
-	if (sym == 256)
-		return (K_EOB << 8) | len;
-	// lengths: deflate_decompress.c:563-577 (286, 287 decode as 258)
-	uint32_t s = sym - 257, base, eb;
-	if (s < 8) { base = 3 + s; eb = 0; }
-	else if (s >= 28) { base = 258; eb = 0; }
-	else { eb = (s >> 2) - 1; base = 3 + ((4 + (s & 3)) << eb); }
-	return (base << 16) | (K_LEN << 8) | (eb << 4) | len;
-}
-
-__device__ __forceinline__ uint32_t offset_entry(uint32_t sym, uint32_t len)
-{
-	// deflate_decompress.c:612-627 (30, 31 decode as 24577 + 13 bits)
-	uint32_t base, eb;
-	if (sym < 4) { base = 1 + sym; eb = 0; }
-	else if (sym >= 30) { base = 24577; eb = 13; }
-	else { eb = (sym >> 1) - 1; base = 1 + ((2 + (sym & 1)) << eb); }
-	return (base << 16) | (eb << 4) | len;
-}
 
 // 6400 bytes = five 1280-byte allocation units = 25 waves per CU (7200 were six units, 21 waves; this
 // kernel answers to occupancy: 16 waves measured 85 GB/s where 21 gave 102).  What is live only while a
@@ -145,125 +92,6 @@ struct InfLdsT {
 };
 using InfLds = InfLdsT<INF_RING>;
 static_assert(sizeof(InfLds) == 6400, "InfLds must stay within five LDS allocation units");
-constexpr uint32_t INF_T_SCRATCH = 320;      // byte offset in cl of { u32 cnt[16]; u16 first[16]; u16 offs[16]; }
-
-// Build one decode table from code lengths (all 64 lanes).  Returns false for
-// what build_decode_table() rejects (deflate_decompress.c:799-853).
-//   nsyms <= 288; tbits = direct table bits; kind 0 litlen / 1 offset / 2 precode
-// Per-length counters live in LDS (one lane per code length), not in registers:
-// sixteen-element uniform arrays would cost 64 SGPRs and spill the symbol loop.
-template <int KIND>
-__device__ __noinline__ uint32_t build_table(const uint8_t *lens, uint32_t nsyms, uint32_t *table, uint32_t tbits,
-					  uint16_t *sorted, uint16_t *count_out, uint8_t *scratch, uint32_t lane)
-{
-	// per-length counters; once the counts are read they serve as the running rank bases
-	uint32_t *t_cnt = (uint32_t *)scratch, *t_base = t_cnt;
-	uint16_t *t_first = (uint16_t *)(scratch + 64), *t_offs = t_first + 16;
-	if (lane < 16)
-		t_cnt[lane] = 0;
-	for (uint32_t base = 0; base < nsyms; base += 64) {
-		const uint32_t s = base + lane;
-		const uint32_t len = s < nsyms ? lens[s] : 0;
-		if (len)
-			atomicAdd(&t_cnt[len], 1u);
-	}
-	// lane l (1..15) derives its length's first codeword, sorted offset and codespace share
-	uint32_t code = 0, o = 0, mine = 0;
-	if (lane >= 1 && lane < 16) {
-		for (uint32_t l = 1; l <= lane; l++) {
-			code = (code + (l > 1 ? t_cnt[l - 1] : 0)) << 1;
-			if (l < lane)
-				o += t_cnt[l];
-		}
-		mine = t_cnt[lane];
-		t_first[lane] = (uint16_t)code;       // < 2^15 for every code that passes the checks below
-		t_offs[lane] = (uint16_t)o;
-	}
-	if (lane < 16)
-		t_base[lane] = 0;                     // (all lanes are past the loop that read the counts)
-	if (count_out && lane < 16)
-		count_out[lane] = (uint16_t)mine;
-	const uint32_t used = readlane(wave_incl_scan((lane >= 1 && lane < 16) ? mine << (15 - lane) : 0u), 63);
-	const uint64_t present = __ballot(mine != 0);
-	const uint32_t maxlen = present ? 63 - (uint32_t)__clzll((long long)present) : 0;
-	const uint32_t ones = readlane(mine, 1);
-	if (used > (1u << 15))
-		return 0;                         // overfull
-	bool degenerate = false;
-	if (used < (1u << 15)) {                  // incomplete
-		if (used != 0 && !(ones == 1 && maxlen == 1))
-			return 0;
-		degenerate = true;
-	}
-	uint32_t one_sym = 0;                 // the symbol owning the single 1-bit codeword, if any
-	for (uint32_t base = 0; base < nsyms; base += 64) {
-		const uint32_t s = base + lane;
-		const uint32_t len = s < nsyms ? lens[s] : 0;
-		// rank inside the length class, in symbol order: one ballot per length present
-		uint32_t rank = 0;
-		uint64_t rem = __ballot(len != 0);
-		while (rem) {
-			const uint32_t lead = (uint32_t)__ffsll((unsigned long long)rem) - 1;
-			const uint32_t lc = readlane(len, lead);
-			const uint64_t m = __ballot(len == lc);
-			const uint32_t b0 = uniform(t_base[lc]);
-			if (len == lc)
-				rank = b0 + __popcll(m & ((1ull << lane) - 1));
-			if (lane == lead)
-				t_base[lc] = b0 + __popcll(m);
-			if (lc == 1)
-				one_sym = base + lead;
-			rem &= ~m;
-		}
-		if (len) {
-			sorted[t_offs[len] + rank] = (uint16_t)s;
-			const uint32_t cw = t_first[len] + rank;        // MSB-first codeword
-			const uint32_t rev = __brev(cw) >> (32 - len);
-			if (!degenerate) {
-				if (len <= tbits) {
-					const uint32_t e = KIND == 0 ? litlen_entry(s, len)
-							 : KIND == 1 ? offset_entry(s, len)
-								     : ((s << 16) | len);
-					for (uint32_t i = rev; i < (1u << tbits); i += 1u << len)
-						table[i] = e;
-				} else {
-					table[rev & ((1u << tbits) - 1)] = K_SLOW << 8;
-				}
-			}
-		}
-	}
-	if (degenerate) {
-		// empty code -> symbol 0; single 1-bit codeword -> that symbol, for both
-		// bit values (deflate_decompress.c:816-849)
-		const uint32_t sym = used ? one_sym : 0;
-		const uint32_t e = KIND == 0 ? litlen_entry(sym, 1) : KIND == 1 ? offset_entry(sym, 1) : ((sym << 16) | 1);
-		for (uint32_t i = lane; i < (1u << tbits); i += 64)
-			table[i] = e;
-	}
-	return 1;
-}
-
-// Canonical decode for codewords longer than the direct table; returns symbol | length << 16.
-// All fifteen lengths are tried at once: lane l holds count[l], two prefix sums give its length's first
-// codeword (first[l] = sum_{k<l} count[k] << (l - k), i.e. the Kraft sum in 2^-15 units shifted back) and
-// its offset into the sorted symbols, one ballot finds the length that matches.  (The bit-serial loop it
-// replaces paid an LDS round trip per length: ~1 M such tokens per GiB of a libdeflate-6 stream.)
-__device__ __noinline__ uint32_t slow_decode(uint64_t bb, const uint16_t *count, const uint16_t *sorted, uint32_t lane)
-{
-	const bool in = lane >= 1 && lane < 16;
-	const uint32_t l = lane & 15;
-	const uint32_t cnt = in ? count[l] : 0u;
-	const uint32_t scaled = cnt << (15 - l);
-	const uint32_t first = (wave_incl_scan(scaled) - scaled) >> (15 - l);
-	const uint32_t offs = wave_incl_scan(cnt) - cnt;
-	const uint32_t code = __brev((uint32_t)bb) >> (32 - (l ? l : 1));     // the first l stream bits, MSB first
-	const uint32_t d = code - first;
-	const uint64_t hit = __ballot(in && d < cnt);
-	if (!hit)
-		return 15u << 16;
-	const uint32_t len = (uint32_t)__ffsll((unsigned long long)hit) - 1;
-	return (uint32_t)sorted[readlane(offs + d, len)] | (len << 16);
-}
 
 // the decoder, for an output ring of RING bytes (one wavefront; L is the workgroup's LDS)
 // Args = InflateFramedArgs: the bytes consumed leave next to out_len (the framed decode finds the trailer there: hd_frame.hpp)
@@ -297,7 +125,7 @@ __device__ __forceinline__ void inflate_stream(const Args &a, InfLdsT<RING> &L)
 	const bool want_crc = a.crc != nullptr;
 	const bool dst_aligned = (((uintptr_t)dst) & 15) == 0;
 
-	// ---- compressed input: 256-byte pieces, one dword per lane -----------
+	// ---- compressed input: 256-byte pieces, one dword per lane (own copy of InfReader: 77 VGPRs either way, 0.5 % slower with the shared one) ----
 	const uint32_t mis = (uint32_t)((uintptr_t)src & 3);
 	const uint32_t *src32 = (const uint32_t *)(src - mis);
 	const uint32_t nbytes_al = mis + n;                  // valid bytes from src32
@@ -435,6 +263,7 @@ __device__ __forceinline__ void inflate_stream(const Args &a, InfLdsT<RING> &L)
 			const uint32_t bl0 = (B & 31) + lane;
 			const uint32_t *wsp = &L.comp[(d0 & 63) + (bl0 >> 5)];
 			const uint32_t ws0 = wsp[0], ws1 = wsp[1], ws2 = wsp[2], ws3 = wsp[3], ws4 = wsp[4];
+			// (own copy of spec_token: adopted only together with the reader, which cost 0.5 %)
 			auto spec = [&](uint32_t bl, uint32_t lo, uint32_t mid, uint32_t hi) -> Spec {   // bl = bit offset from dword d0
 				Spec r;
 				const uint32_t a = __builtin_amdgcn_alignbit(mid, lo, bl & 31);
@@ -465,6 +294,7 @@ __device__ __forceinline__ void inflate_stream(const Args &a, InfLdsT<RING> &L)
 			};
 			const Spec s0 = spec(bl0, ws0, ws1, ws2), s1 = spec(bl0 + 64, ws2, ws3, ws4);
 
+			// (own copy of window_walk, as spec_token above.)
 			// The real chain from bit 0 of the window.  This walk is the hottest scalar
 			// code of the kernel (the CU has one scalar ALU) and the compiler spends ~20
 			// instructions per token on it, so it is written out: 3 SALU + 1 branch
@@ -754,7 +584,7 @@ __device__ __forceinline__ void inflate_stream(const Args &a, InfLdsT<RING> &L)
 			if ((wm & 64) && !over)
 				break;
 		}
-		// hand the position back to the scalar reader
+		// hand the position back to the scalar reader (own copy of InfReader::seek_bit)
 		dw = B >> 5;
 		if ((dw >> 6) != cur_piece) {
 			const uint32_t piece = dw >> 6;
@@ -826,7 +656,7 @@ __device__ __forceinline__ void inflate_stream(const Args &a, InfLdsT<RING> &L)
 		} else {
 			uint32_t nlit = 288, noff = 32;
 			if (btype == 2) {
-				// ---- dynamic header: decompress_template.h:101-232 -------
+				// ---- dynamic header: decompress_template.h:101-232 (own copy of inflate_dynamic_header: 81 VGPRs with the shared one, the step is 80) ----
 				refill();
 				nlit = 257 + ((uint32_t)bb & 31);
 				noff = 1 + (((uint32_t)bb >> 5) & 31);
@@ -887,7 +717,7 @@ __device__ __forceinline__ void inflate_stream(const Args &a, InfLdsT<RING> &L)
 					break;
 				}
 			} else if (!static_loaded) {
-				// ---- static code: decompress_template.h:297-330 ----------
+				// ---- static code: decompress_template.h:297-330 (own copy of inflate_static_tables: 85 VGPRs with the shared one) ----
 				uint8_t *cl = L.cl;
 				for (uint32_t s = lane; s < 320; s += 64)
 					cl[s] = s < 144 ? 8 : s < 256 ? 9 : s < 280 ? 7 : s < 288 ? 8 : 5;
@@ -908,7 +738,7 @@ __device__ __forceinline__ void inflate_stream(const Args &a, InfLdsT<RING> &L)
 						break;
 				}
 				INF_T0(t_tok);
-				// one token through the fully checked scalar path (stream edges, long codes)
+				// one token through the fully checked scalar path (stream edges, long codes): each decoder's own, a shared function lost in all three
 				// one flush site for the whole symbol loop (at most 1023 + 258 bytes pending)
 				if (pos - flushed >= HD_PIECE)
 					flush_pieces();

@@ -2,13 +2,17 @@
 // waiting -- lib/zlibutil.c:194-204 as applet/7bgzf.c:330-345 calls it, a thread per block): FOUR wavefronts per stream.
 //
 // The same decoder as hd_inflate.hpp's inflate_stream -- same tables, same windows, same scalar path, the same verdicts -- with
-// its statements dealt to four wavefronts of one workgroup, each on a SIMD of its own (the comments at inflate_stream_pipe):
+// its work dealt to four wavefronts of one workgroup, each on a SIMD of its own (the comments at inflate_stream_pipe):
 //   spec   decodes the token that WOULD start at every bit position of the stream, ahead of everybody (an LDS ring of words)
 //   front  owns the bit reader, the headers and tables, every verdict: reads the words under its window, walks the real chain,
 //          sums the output positions -- what decides where the next window starts -- and hands the rest over
 //   sort   stores the window's literals, sorts its matches by the way they are copied, writes the record
 //   back   copies the matches, flushes the ring, folds the CRC, writes the verdict
-// It is a copy of that function, restructured, and not a template parameter of it: the throughput kernel is bound by vector
+// What READS the stream is shared with the other decoders and used directly (hd_inflate_common.hpp): the bit reader
+// (InfReader), the block headers, the speculative decode of a position (spec_token, packed into the spec ring's word) and the
+// walk (window_walk); the scalar path's token decode is a copy, marked where it stands.  What PLACES the tokens -- the records between the
+// wavefronts, window placement, the ring, the flush, the CRC -- is this file's own, a deliberate restructured copy of the
+// throughput decoder's and not a template parameter of it: that kernel is bound by vector
 // issue at six wavefronts per SIMD, three registers below the step that costs one, and the same restructure applied to it in
 // place -- placement behind a lambda, then inline again with only the scalar writers and the tail as lambdas -- cost it 6 % and
 // 4 % on one box (profiles/r05_inflate_ab.txt).  And this copy is free to be what the latency kernel wants: its ring holds the
@@ -68,7 +72,7 @@ struct InfLdsPipeT {
 // (literals, lane-group copies, match copies, flush, CRC).  So the front wavefront (threads 0..63) owns the bit reader, the
 // tables and every verdict, and keeps the output position as a number only; whatever writes the ring -- a window's tokens, a
 // literal or match of the scalar path, a stored block -- goes to the back wavefront (threads 64..127) as a record through
-// LDS, INF_PQ in flight.  Statement for statement the decoder of hd_inflate.hpp: only who executes which half differs.
+// LDS, INF_PQ in flight.  The decoder of hd_inflate.hpp: only who executes which half differs.
 enum { PIPE_WINDOW = 0, PIPE_LITERAL = 1, PIPE_MATCH = 2, PIPE_STORED = 3, PIPE_END = 4 };
 template <uint32_t RING, class LDS>
 __device__ __forceinline__ void inflate_stream_pipe(const InflateArgs &a, LDS &L)
@@ -144,67 +148,7 @@ __device__ __forceinline__ void inflate_stream_pipe(const InflateArgs &a, LDS &L
 	const bool want_crc = a.crc != nullptr;
 	const bool dst_aligned = (((uintptr_t)dst) & 15) == 0;
 
-	// ---- compressed input: 256-byte pieces, one dword per lane -----------
-	const uint32_t mis = (uint32_t)((uintptr_t)src & 3);
-	const uint32_t *src32 = (const uint32_t *)(src - mis);
-	const uint32_t nbytes_al = mis + n;                  // valid bytes from src32
-	auto load_piece = [&](uint32_t piece) -> uint32_t {
-		const uint32_t d = piece * 64 + lane;
-		uint32_t w = 0;
-		if (d * 4 < nbytes_al) {
-			w = src32[d];
-			const uint32_t valid = nbytes_al - d * 4;    // bytes of this dword inside the stream
-			if (valid < 4)
-				w &= (1u << (8 * valid)) - 1;
-		}
-		return w;
-	};
-	uint32_t cur_piece = 0;
-	uint32_t cw = load_piece(0), cw_next = load_piece(1);
-	uint32_t dw = 0;                 // next dword index to feed the bit buffer
-	uint64_t bb = 0;                 // bit buffer (uniform)
-	uint32_t bc = 0;                 // valid bits in bb
-
-	auto next_dword = [&]() -> uint32_t {
-		const uint32_t piece = dw >> 6;
-		if (piece != cur_piece) {        // uniform branch: step to the next piece
-			cw = cw_next;
-			cur_piece = piece;
-			cw_next = load_piece(piece + 1);
-		}
-		const uint32_t w = readlane(cw, dw & 63);
-		dw++;
-		return w;
-	};
-	auto refill = [&]() {
-		if (bc <= 32) {
-			bb |= (uint64_t)next_dword() << bc;
-			bc += 32;
-		}
-	};
-	auto consumed_bits = [&]() -> int64_t { return (int64_t)dw * 32 - bc - 8 * (int64_t)mis; };
-	// consumed_bits() > 8 n + 64 in 32-bit arithmetic (n < 2^28): (dw << 5) - bc > over_t
-	const uint32_t over_t = 8 * n + 64 + 8 * mis;
-	auto overrun = [&]() -> bool { return (dw << 5) - bc > over_t; };
-	auto seek_byte = [&](uint32_t byteoff) {       // restart the bit reader at src + byteoff
-		const uint32_t o = mis + byteoff;
-		dw = o >> 2;
-		const uint32_t piece = dw >> 6;
-		if (piece != cur_piece) {
-			cur_piece = piece;
-			cw = load_piece(piece);
-			cw_next = load_piece(piece + 1);
-		}
-		bb = 0;
-		bc = 0;
-		refill();
-		bb >>= 8 * (o & 3);
-		bc -= 8 * (o & 3);
-	};
-	// skip the mis-alignment bytes
-	refill();
-	bb >>= 8 * mis;
-	bc -= 8 * mis;
+	InfReader R(src, n, lane);                           // the bit reader (hd_inflate_common.hpp): the front's; the spec wavefront loads pieces through it
 
 	// ---- output ring + flush ---------------------------------------------
 	uint32_t pos = 0, flushed = 0;
@@ -246,7 +190,7 @@ __device__ __forceinline__ void inflate_stream_pipe(const InflateArgs &a, LDS &L
 	// output budget of one window: pending <= 1023 + 704 = 1727 <= RING - 64 - 257, so a source is
 	// either wholly in the ring (wend - src <= RING - 64) or wholly flushed to HBM
 	constexpr uint32_t WIN_OUT_BUDGET = 704;
-	const uint32_t dw_safe = (mis + n) >> 2;      // dwords below this are whole
+	const uint32_t dw_safe = R.nbytes_al >> 2;     // dwords below this are whole
 
 	// ---- the scalar path's writers (PIPE: the back wavefront's) -----------------------------------------------------------------
 	auto copy_stored = [&](uint32_t ip, uint32_t len) {
@@ -560,7 +504,7 @@ __device__ __forceinline__ void inflate_stream_pipe(const InflateArgs &a, LDS &L
 		const spec_word_p stopw = (spec_word_p)&L.sp_stop, gow = (spec_word_p)&L.sp_go, tailw = (spec_word_p)&L.sp_tail;
 		uint32_t epoch = 0, c = 0;
 		uint32_t s_p0 = 0xfffffff0u, s_pre = 0, s_pre_idx = 0xfffffff0u;
-		const uint32_t c_end = (((mis + n) >> 2) >> 1) + 2;           // chunks from here on lie behind the stream's last whole dwords
+		const uint32_t c_end = ((R.nbytes_al >> 2) >> 1) + 2;           // chunks from here on lie behind the stream's last whole dwords
 		for (;;) {
 			const uint32_t want = uniform(*stopw);
 			if (want != epoch) {
@@ -593,33 +537,17 @@ __device__ __forceinline__ void inflate_stream_pipe(const InflateArgs &a, LDS &L
 				if (p0 == s_p0 + 1)
 					L.comp[lane] = L.comp[64 + lane];
 				else
-					L.comp[lane] = load_piece(p0);
-				L.comp[64 + lane] = s_pre_idx == p0 + 1 ? s_pre : load_piece(p0 + 1);
-				s_pre = load_piece(p0 + 2);
+					L.comp[lane] = R.load_piece(p0);
+				L.comp[64 + lane] = s_pre_idx == p0 + 1 ? s_pre : R.load_piece(p0 + 1);
+				s_pre = R.load_piece(p0 + 2);
 				s_pre_idx = p0 + 2;
 				s_p0 = p0;
 			}
 			const uint32_t *wsp = &L.comp[(d0 & 63) + (lane >> 5)];
 			const uint32_t ws0 = wsp[0], ws1 = wsp[1], ws2 = wsp[2], ws3 = wsp[3], ws4 = wsp[4];
-			auto spec_word = [&](uint32_t bl, uint32_t lo, uint32_t mid, uint32_t hi) -> uint32_t {   // bl = bit offset from dword d0
-				const uint32_t a = __builtin_amdgcn_alignbit(mid, lo, bl & 31);
-				const uint32_t bq = __builtin_amdgcn_alignbit(hi, mid, bl & 31);
-				const uint32_t e = L.lit[a & ((1u << INF_LT_BITS) - 1)];
-				const uint32_t len1 = e & 15, eb = (e >> 4) & 15;
-				// (a literal's entry has no extra bits: the sum is the literal then)
-				const uint32_t lenlit = (e >> 16) + __builtin_amdgcn_ubfe(a, len1, eb);
-				const uint32_t t1 = len1 + eb;                 // <= 9 + 5
-				const uint32_t rest = __builtin_amdgcn_alignbit(bq, a, t1);
-				const uint32_t dd = L.off[rest & ((1u << INF_DT_BITS) - 1)];
-				const uint32_t ddm = (e & 0x300) == (K_LEN << 8) ? dd : 0u;
-				const uint32_t dlen = ddm & 15, deb = (ddm >> 4) & 15;
-				const uint32_t offset = (ddm >> 16) + __builtin_amdgcn_ubfe(rest, dlen, deb);
-				const uint32_t tokbits = t1 + dlen + deb;
-				// bit 6 = the walk stops in front of this token: bit 9 of either entry (K_EOB and K_SLOW have it) moved down
-				const uint32_t tb1 = tokbits ? tokbits : 1u;
-				return tb1 | ((e >> 3) & 64u) | ((ddm >> 3) & 64u) | ((lenlit & 511u) << 7) | (offset << 16);
-			};
-			const uint32_t w0 = spec_word(lane, ws0, ws1, ws2), w1 = spec_word(lane + 64, ws2, ws3, ws4);
+			// (a literal's entry has no extra bits: its "length" is the literal then)
+			auto spec_word = [&](const InfSpec &t) { return t.walk | ((t.length & 511u) << 7) | (t.offset << 16); };
+			const uint32_t w0 = spec_word(spec_token(L, lane, ws0, ws1, ws2)), w1 = spec_word(spec_token(L, lane + 64, ws2, ws3, ws4));
 			L.spec[(64 * c + lane) & (INF_SPEC_POS - 1)] = w0;
 			L.spec[(64 * c + 64 + lane) & (INF_SPEC_POS - 1)] = w1;
 			asm volatile("" ::: "memory");
@@ -643,7 +571,7 @@ __device__ __forceinline__ void inflate_stream_pipe(const InflateArgs &a, LDS &L
 		asm volatile("" ::: "memory");
 	};
 	auto spec_go = [&]() {
-		const uint32_t c0 = (((dw << 5) - bc) >> 6) & ~1u;           // the (even) chunk under the block's first token
+		const uint32_t c0 = (R.bit_pos() >> 6) & ~1u;           // the (even) chunk under the block's first token
 		asm volatile("" ::: "memory");
 		if (lane == 0) {
 			*(spec_word_p)&L.sp_start = c0;
@@ -752,7 +680,7 @@ __device__ __forceinline__ void inflate_stream_pipe(const InflateArgs &a, LDS &L
 	}
 
 	auto run_windows = [&](int32_t &st_out) -> uint32_t {
-		uint32_t B = (dw << 5) - bc;              // absolute bit position from src32
+		uint32_t B = R.bit_pos();                 // absolute bit position from src32
 		uint32_t result = 0;
 		for (;;) {
 			// (flushing the ring is the back wavefront's; here pos is a number)
@@ -784,11 +712,7 @@ __device__ __forceinline__ void inflate_stream_pipe(const InflateArgs &a, LDS &L
 				}
 				asm volatile("" ::: "memory");
 			}
-			struct Spec {
-				uint32_t length, offset, outlen, walk;   // length: a match's, or a literal's byte
-				uint64_t is_len, is_lit;             // lane masks
-			};
-			Spec s0, s1;
+			InfSpec s0, s1;                          // (without .e: length is a match's, or a literal's byte)
 			{
 				const uint32_t w0 = L.spec[(B + lane) & (INF_SPEC_POS - 1)], w1 = L.spec[(B + 64 + lane) & (INF_SPEC_POS - 1)];
 				asm volatile("" ::: "memory");
@@ -801,48 +725,10 @@ __device__ __forceinline__ void inflate_stream_pipe(const InflateArgs &a, LDS &L
 				s1.outlen = sel(s1.is_len, s1.length, 1u);
 			}
 
-			// The real chain from bit 0 of the window.  This walk is the hottest scalar
-			// code of the kernel (the CU has one scalar ALU) and the compiler spends ~20
-			// instructions per token on it, so it is written out: 4 SALU + 2 branches
-			// + 1 v_readlane per token (the lane select of v_readlane and s_bitset1 take
-			// the low 6 bits, so the second half runs on b itself).  It stops in front of
-			// the first token the window cannot take; that one goes to the scalar loop.
-			// (A lane select written by the SALU needs no wait states before v_readlane,
-			// only one written by the VALU does.)
 			PIPE_P(0);                                   // the wait for the spec wavefront's words, their fields
 			uint32_t b, wm;
 			uint64_t real0, real1;
-			// (round 5: the stop flag is bit 6 of the word that is ADDED to the position -- a token the walk must stop in front of
-			// throws it out of the half by itself, and the half's loop needs no test of its own for it: five instructions and one
-			// branch per token instead of seven and two; behind the loop the last word says whether its token has to be taken back)
-			asm volatile("s_mov_b32 %0, 0\n\t"
-				     "s_mov_b64 %1, 0\n\t"
-				     "s_mov_b64 %2, 0\n"
-				     "Lhd_walk0_%=:\n\t"
-				     "v_readlane_b32 %3, %4, %0\n\t"
-				     "s_bitset1_b64 %1, %0\n\t"
-				     "s_add_u32 %0, %0, %3\n\t"
-				     "s_cmp_lt_u32 %0, 64\n\t"
-				     "s_cbranch_scc1 Lhd_walk0_%=\n\t"
-				     "s_bitcmp1_b32 %3, 6\n\t"
-				     "s_cbranch_scc0 Lhd_walk1_%=\n\t"
-				     "s_sub_u32 %0, %0, %3\n\t"
-				     "s_bitset0_b64 %1, %0\n\t"
-				     "s_branch Lhd_walk_done_%=\n"
-				     "Lhd_walk1_%=:\n\t"
-				     "v_readlane_b32 %3, %5, %0\n\t"
-				     "s_bitset1_b64 %2, %0\n\t"
-				     "s_add_u32 %0, %0, %3\n\t"
-				     "s_cmp_lt_u32 %0, 128\n\t"
-				     "s_cbranch_scc1 Lhd_walk1_%=\n\t"
-				     "s_bitcmp1_b32 %3, 6\n\t"
-				     "s_cbranch_scc0 Lhd_walk_done_%=\n\t"
-				     "s_sub_u32 %0, %0, %3\n\t"
-				     "s_bitset0_b64 %2, %0\n"
-				     "Lhd_walk_done_%=:"
-				     : "=&s"(b), "=&s"(real0), "=&s"(real1), "=&s"(wm)
-				     : "v"(s0.walk), "v"(s1.walk)
-				     : "scc");
+			window_walk(s0.walk, s1.walk, b, real0, real1, wm);  // the real chain from bit 0 of the window
 			// output positions; cut in front of the first token that would overrun the budget.  (Conditions are
 			// 64-bit lane masks: the ballot of ONE compare each, combined in scalar code, back to the lanes
 			// through sel() -- hd_device.hpp "lane masks".)
@@ -903,22 +789,7 @@ __device__ __forceinline__ void inflate_stream_pipe(const InflateArgs &a, LDS &L
 			if ((wm & 64) && !over)
 				break;
 		}
-		// hand the position back to the scalar reader
-		dw = B >> 5;
-		if ((dw >> 6) != cur_piece) {
-			const uint32_t piece = dw >> 6;
-			if (piece == cur_piece + 1)
-				cw = cw_next;
-			else
-				cw = load_piece(piece);
-			cur_piece = piece;
-			cw_next = load_piece(piece + 1);
-		}
-		bb = 0;
-		bc = 0;
-		refill();
-		bb >>= (B & 31);
-		bc -= (B & 31);
+		R.seek_bit(B);                            // hand the position back to the scalar reader
 		return result;
 	};
 
@@ -936,102 +807,37 @@ __device__ __forceinline__ void inflate_stream_pipe(const InflateArgs &a, LDS &L
 	};
 
 	for (;;) {
-		refill();
-		const uint32_t bfinal = (uint32_t)bb & 1;
-		const uint32_t btype = ((uint32_t)bb >> 1) & 3;
-		bb >>= 3;
-		bc -= 3;
+		R.refill();
+		const uint32_t bfinal = (uint32_t)R.bb & 1;
+		const uint32_t btype = ((uint32_t)R.bb >> 1) & 3;
+		R.drop(3);
 
 		if (btype == 0) {
 			// ---- stored: decompress_template.h:234-279 -------------------
-			int64_t cbits = (consumed_bits() + 7) & ~(int64_t)7;
+			int64_t cbits = (R.consumed_bits() + 7) & ~(int64_t)7;
 			if (cbits > 8 * (int64_t)n) { st = HD_BAD_DATA; break; }
 			uint32_t ip = (uint32_t)(cbits >> 3);
 			if (n - ip < 4) { st = HD_BAD_DATA; break; }
-			seek_byte(ip);
-			refill();
-			const uint32_t len = (uint32_t)bb & 0xffff, nlen = ((uint32_t)bb >> 16) & 0xffff;
+			R.seek_byte(ip);
+			R.refill();
+			const uint32_t len = (uint32_t)R.bb & 0xffff, nlen = ((uint32_t)R.bb >> 16) & 0xffff;
 			ip += 4;
 			if (len != (~nlen & 0xffff)) { st = HD_BAD_DATA; break; }
 			if (len > cap - pos) { st = HD_INSUFFICIENT_SPACE; break; }
 			if (len > n - ip) { st = HD_BAD_DATA; break; }
 			fq_push(PIPE_STORED, ip, len, 0, 0, 0);
 			pos += len;
-			seek_byte(ip + len);
+			R.seek_byte(ip + len);
 		} else if (btype == 3) {
 			st = HD_BAD_DATA;
 			break;
 		} else {
-			uint32_t nlit = 288, noff = 32;
 			spec_halt();                              // the tables are about to change: the spec wavefront stands still
 			if (btype == 2) {
-				// ---- dynamic header: decompress_template.h:101-232 -------
-				refill();
-				nlit = 257 + ((uint32_t)bb & 31);
-				noff = 1 + (((uint32_t)bb >> 5) & 31);
-				const uint32_t npre = 4 + (((uint32_t)bb >> 10) & 15);
-				bb >>= 14;
-				bc -= 14;
-				if (lane < 19)
-					L.pre_lens[lane] = 0;
-				for (uint32_t i = 0; i < npre; i++) {
-					refill();
-					if (lane == 0)
-						L.pre_lens[k_precode_perm[i]] = (uint8_t)((uint32_t)bb & 7);
-					bb >>= 3;
-					bc -= 3;
-				}
-				if (!uniform(build_table<2>(L.pre_lens, 19, L.lit, 7, L.lit_sorted, nullptr, L.cl + INF_T_SCRATCH, lane))) { st = HD_BAD_DATA; break; }
-				uint8_t *cl = L.cl;
-				uint32_t i = 0, prev = 0;
-				bool bad = false;
-				while (i < nlit + noff) {
-					refill();
-					if (consumed_bits() > 8 * (int64_t)n + 64) { bad = true; break; }
-					const uint32_t e = uniform(L.lit[(uint32_t)bb & 127]);
-					const uint32_t cl_len = e & 15, s = e >> 16;
-					bb >>= cl_len;
-					bc -= cl_len;
-					if (s < 16) {
-						if (lane == 0)
-							cl[i] = (uint8_t)s;
-						prev = s;
-						i++;
-						continue;
-					}
-					uint32_t rep, val = 0;
-					if (s == 16) {
-						if (i == 0) { bad = true; break; }
-						rep = 3 + ((uint32_t)bb & 3);
-						bb >>= 2; bc -= 2;
-						val = prev;
-					} else if (s == 17) {
-						rep = 3 + ((uint32_t)bb & 7);
-						bb >>= 3; bc -= 3;
-						prev = 0;
-					} else {
-						rep = 11 + ((uint32_t)bb & 127);
-						bb >>= 7; bc -= 7;
-						prev = 0;
-					}
-					for (uint32_t k = lane; k < rep; k += 64)
-						cl[i + k] = (uint8_t)val;
-					i += rep;
-				}
-				if (bad || i != nlit + noff) { st = HD_BAD_DATA; break; }
+				if (!inflate_dynamic_header(R, L, n, lane)) { st = HD_BAD_DATA; break; }
 				static_loaded = false;
-				if (!uniform(build_table<1>(cl + nlit, noff, L.off, INF_DT_BITS, L.off_sorted, L.off_count, L.cl + INF_T_SCRATCH, lane)) ||
-				    !uniform(build_table<0>(cl, nlit, L.lit, INF_LT_BITS, L.lit_sorted, L.lit_count, L.cl + INF_T_SCRATCH, lane))) {
-					st = HD_BAD_DATA;
-					break;
-				}
 			} else if (!static_loaded) {
-				// ---- static code: decompress_template.h:297-330 ----------
-				uint8_t *cl = L.cl;
-				for (uint32_t s = lane; s < 320; s += 64)
-					cl[s] = s < 144 ? 8 : s < 256 ? 9 : s < 280 ? 7 : s < 288 ? 8 : 5;
-				build_table<1>(cl + 288, 32, L.off, INF_DT_BITS, L.off_sorted, L.off_count, L.cl + INF_T_SCRATCH, lane);
-				build_table<0>(cl, 288, L.lit, INF_LT_BITS, L.lit_sorted, L.lit_count, L.cl + INF_T_SCRATCH, lane);
+				inflate_static_tables(L, lane);
 				static_loaded = true;
 			}
 
@@ -1046,17 +852,18 @@ __device__ __forceinline__ void inflate_stream_pipe(const InflateArgs &a, LDS &L
 				}
 				// one token through the fully checked scalar path (stream edges, long codes)
 				// one flush site for the whole symbol loop (at most 1023 + 258 bytes pending)
-				refill();
-				if (overrun()) { st = HD_BAD_DATA; break; }
-				const uint32_t li = (uint32_t)bb & ((1u << INF_LT_BITS) - 1);
+				// own copy of the token decode, as in inflate_stream and the size pass: a shared function cost the lone call 2 %
+				R.refill();
+				if (R.overrun()) { st = HD_BAD_DATA; break; }
+				const uint32_t li = (uint32_t)R.bb & ((1u << INF_LT_BITS) - 1);
 				uint32_t e = readlane(LT[li >> 6], li & 63);
 				if (((e >> 8) & 3) == K_SLOW) {
-					const uint32_t sl = uniform(slow_decode(bb, L.lit_count, L.lit_sorted, lane));
+					const uint32_t sl = uniform(slow_decode(R.bb, L.lit_count, L.lit_sorted, lane));
 					e = litlen_entry(sl & 0xffff, sl >> 16);
 				}
 				const uint32_t clen = e & 15;
-				bb >>= clen;
-				bc -= clen;
+				R.bb >>= clen;
+				R.bc -= clen;
 				const uint32_t kind = (e >> 8) & 3;
 				if (kind == K_LIT) {
 					if (pos == cap) { st = HD_INSUFFICIENT_SPACE; break; }
@@ -1068,23 +875,23 @@ __device__ __forceinline__ void inflate_stream_pipe(const InflateArgs &a, LDS &L
 					break;
 				}
 				const uint32_t eb = (e >> 4) & 15;
-				const uint32_t length = (e >> 16) + ((uint32_t)bb & ((1u << eb) - 1));
-				bb >>= eb;
-				bc -= eb;
+				const uint32_t length = (e >> 16) + ((uint32_t)R.bb & ((1u << eb) - 1));
+				R.bb >>= eb;
+				R.bc -= eb;
 				if (length > cap - pos) { st = HD_INSUFFICIENT_SPACE; break; }
-				refill();
-				const uint32_t di = (uint32_t)bb & ((1u << INF_DT_BITS) - 1);
+				R.refill();
+				const uint32_t di = (uint32_t)R.bb & ((1u << INF_DT_BITS) - 1);
 				uint32_t d = uniform(L.off[di]);                 // (LDS: one token in 130 comes this way, its copy in four registers cost a wave)
 				if (((d >> 8) & 3) == K_SLOW) {
-					const uint32_t sl = uniform(slow_decode(bb, L.off_count, L.off_sorted, lane));
+					const uint32_t sl = uniform(slow_decode(R.bb, L.off_count, L.off_sorted, lane));
 					d = offset_entry(sl & 0xffff, sl >> 16);
 				}
 				const uint32_t dlen = d & 15, deb = (d >> 4) & 15;
-				bb >>= dlen;
-				bc -= dlen;
-				const uint32_t offset = (d >> 16) + ((uint32_t)bb & ((1u << deb) - 1));
-				bb >>= deb;
-				bc -= deb;
+				R.bb >>= dlen;
+				R.bc -= dlen;
+				const uint32_t offset = (d >> 16) + ((uint32_t)R.bb & ((1u << deb) - 1));
+				R.bb >>= deb;
+				R.bc -= deb;
 				if (offset > pos) { st = HD_BAD_DATA; break; }
 
 				fq_push(PIPE_MATCH, length, offset, 0, 0, 0);
@@ -1095,11 +902,11 @@ __device__ __forceinline__ void inflate_stream_pipe(const InflateArgs &a, LDS &L
 		}
 		if (bfinal)
 			break;
-		if ((a.flags & INF_FLUSHED) && consumed_bits() <= 8 * (int64_t)n && consumed_bits() + 7 >= 8 * (int64_t)n)
+		if ((a.flags & INF_FLUSHED) && R.consumed_bits() <= 8 * (int64_t)n && R.consumed_bits() + 7 >= 8 * (int64_t)n)
 			break;
-		if (consumed_bits() > 8 * (int64_t)n + 64) { st = HD_BAD_DATA; break; }
+		if (R.consumed_bits() > 8 * (int64_t)n + 64) { st = HD_BAD_DATA; break; }
 	}
-	if (st == HD_OK && consumed_bits() > 8 * (int64_t)n)
+	if (st == HD_OK && R.consumed_bits() > 8 * (int64_t)n)
 		st = HD_BAD_DATA;
 
 	spec_end();

@@ -2,12 +2,13 @@
 //
 // Role: the first of the two inflates of applet/7png.c:114-181, which runs the IDAT stream into a throw-away buffer only
 // to count declen, and the "get decompressed size" call of other device DEFLATE libraries: a stream whose size nobody
-// stated.  One wavefront per stream, hd_inflate.hpp's decoder with everything taken out that moves bytes:
+// stated.  One wavefront per stream, the throughput decoder (hd_inflate.hpp) with everything taken out that moves bytes:
 //
-//   kept   the bit reader, the block headers, build_table / slow_decode and the entry formats, the window decode (every
-//          lane decodes the token at its two bit offsets, the scalar walk follows the chain), the scalar token path for
-//          what a window cannot take, and EVERY verdict of the full decoder: table rejects, over-subscribed codes, input
-//          overrun, LEN / NLEN, a distance past the bytes out so far;
+//   kept   everything that READS the stream, and it is the shared code of hd_inflate_common.hpp, used directly: the bit
+//          reader (InfReader), the block headers (inflate_dynamic_header / inflate_static_tables over build_table), the
+//          window decode (spec_token per lane, window_walk along the chain); the checked token of the scalar path is a
+//          copy of the full decoder's, its litlen lookup from LDS -- so EVERY verdict of the full decoder: table rejects,
+//          over-subscribed codes, input overrun, a distance past the bytes out so far; LEN / NLEN is checked here;
 //   gone   the ring, the window's output budget, the flush, the copies, the CRC, the tables' copy in registers.
 //
 // What is left of the output is its position: 64 bits, and a stream that reaches 2^32 bytes is answered
@@ -16,7 +17,8 @@
 // front of k_inflate_lat does.  A stored block is a seek.
 //
 // LDS: the two direct tables, the sorted symbols and counts of the slow path, and one union of the code lengths (header)
-// with the stream copy (windows): 4288 bytes = four 1280-byte allocation units, 32 wavefronts per CU (k_inflate: five, 25).
+// with the stream copy (windows): 4288 bytes = four 1280-byte allocation units, 32 wavefronts per CU (k_inflate: five, 25);
+// at most 64 VGPRs keep the registers from being the tighter bound (tests/test_abi.py holds both).
 #pragma once
 #include "hd_inflate.hpp"
 
@@ -102,80 +104,20 @@ template <bool PIECE, class Args> __device__ __forceinline__ void inflate_size_b
 		}
 	}
 
-	// ---- compressed input: hd_inflate.hpp's reader, statement for statement ----
-	const uint32_t mis = (uint32_t)((uintptr_t)src & 3);
-	const uint32_t *src32 = (const uint32_t *)(src - mis);
-	const uint32_t nbytes_al = mis + n;
-	auto load_piece = [&](uint32_t piece) -> uint32_t {
-		const uint32_t d = piece * 64 + lane;
-		uint32_t w = 0;
-		if (d * 4 < nbytes_al) {
-			w = src32[d];
-			const uint32_t valid = nbytes_al - d * 4;
-			if (valid < 4)
-				w &= (1u << (8 * valid)) - 1;
-		}
-		return w;
-	};
-	uint32_t cur_piece = 0;
-	uint32_t cw = load_piece(0), cw_next = load_piece(1);
-	uint32_t dw = 0;
-	uint64_t bb = 0;
-	uint32_t bc = 0;
-	auto next_dword = [&]() -> uint32_t {
-		const uint32_t piece = dw >> 6;
-		if (piece != cur_piece) {
-			cw = cw_next;
-			cur_piece = piece;
-			cw_next = load_piece(piece + 1);
-		}
-		const uint32_t w = readlane(cw, dw & 63);
-		dw++;
-		return w;
-	};
-	auto refill = [&]() {
-		if (bc <= 32) {
-			bb |= (uint64_t)next_dword() << bc;
-			bc += 32;
-		}
-	};
-	auto consumed_bits = [&]() -> int64_t { return (int64_t)dw * 32 - bc - 8 * (int64_t)mis; };
-	const uint32_t over_t = 8 * n + 64 + 8 * mis;
-	auto overrun = [&]() -> bool { return (dw << 5) - bc > over_t; };
-	auto seek_bit = [&](uint32_t B) {              // restart the bit reader at bit B from src32
-		dw = B >> 5;
-		const uint32_t piece = dw >> 6;
-		if (piece != cur_piece) {
-			if (piece == cur_piece + 1)
-				cw = cw_next;
-			else
-				cw = load_piece(piece);
-			cur_piece = piece;
-			cw_next = load_piece(piece + 1);
-		}
-		bb = 0;
-		bc = 0;
-		refill();
-		bb >>= (B & 31);
-		bc -= (B & 31);
-	};
-	refill();
-	bb >>= 8 * mis;
-	bc -= 8 * mis;
-
+	InfReader R(src, n, lane);
 	uint64_t pos = 0;                              // bytes the stream has decoded to so far (uniform)
 	constexpr uint64_t POS_LIMIT = 0xffffffffull;  // the largest room a u32 table states: past it the answer is "does not fit"
 
-	// ---- window decode: hd_inflate.hpp's, without its byte work --------------------------------------------------
+	// ---- window decode: the throughput decoder's, without its byte work --------------------------------------------------
 	// Every lane decodes the tokens that would start at bit B + lane and B + 64 + lane; the scalar walk (the same
 	// statement) follows the real chain and stops in front of the first token a window cannot take.  There is no budget
 	// to cut at: what the real tokens put out is one prefix sum, and its total moves the position.
 	// Returns 0 = one token through the scalar path, 2 = error (st set).
-	const uint32_t dw_safe = (mis + n) >> 2;
+	const uint32_t dw_safe = R.nbytes_al >> 2;
 	uint32_t lds_p0 = 0xfffffff0u;
 	uint32_t pre_piece = 0, pre_idx = 0xfffffff0u;
 	auto run_windows = [&](int32_t &st_out) -> uint32_t {
-		uint32_t B = (dw << 5) - bc;
+		uint32_t B = R.bit_pos();
 		uint32_t result = 0;
 		for (;;) {
 			const uint32_t d0 = B >> 5;
@@ -186,74 +128,20 @@ template <bool PIECE, class Args> __device__ __forceinline__ void inflate_size_b
 				if (p0 == lds_p0 + 1)
 					L.comp[lane] = L.comp[64 + lane];
 				else
-					L.comp[lane] = load_piece(p0);
-				L.comp[64 + lane] = pre_idx == p0 + 1 ? pre_piece : load_piece(p0 + 1);
-				pre_piece = load_piece(p0 + 2);
+					L.comp[lane] = R.load_piece(p0);
+				L.comp[64 + lane] = pre_idx == p0 + 1 ? pre_piece : R.load_piece(p0 + 1);
+				pre_piece = R.load_piece(p0 + 2);
 				pre_idx = p0 + 2;
 				lds_p0 = p0;
 			}
-			struct Spec {
-				uint32_t offset, outlen, walk;
-				uint64_t is_len;
-			};
 			const uint32_t bl0 = (B & 31) + lane;
 			const uint32_t *wsp = &L.comp[(d0 & 63) + (bl0 >> 5)];
 			const uint32_t ws0 = wsp[0], ws1 = wsp[1], ws2 = wsp[2], ws3 = wsp[3], ws4 = wsp[4];
-			auto spec = [&](uint32_t bl, uint32_t lo, uint32_t mid, uint32_t hi) -> Spec {
-				Spec r;
-				const uint32_t a0 = __builtin_amdgcn_alignbit(mid, lo, bl & 31);
-				const uint32_t bq = __builtin_amdgcn_alignbit(hi, mid, bl & 31);
-				const uint32_t e = L.lit[a0 & ((1u << INF_LT_BITS) - 1)];
-				const uint32_t len1 = e & 15, eb = (e >> 4) & 15;
-				const uint32_t length = (e >> 16) + __builtin_amdgcn_ubfe(a0, len1, eb);
-				const uint32_t t1 = len1 + eb;
-				const uint32_t rest = __builtin_amdgcn_alignbit(bq, a0, t1);
-				const uint32_t dd = L.off[rest & ((1u << INF_DT_BITS) - 1)];
-				const uint32_t kind2 = e & 0x300;
-				r.is_len = __ballot(kind2 == (K_LEN << 8));
-				const uint64_t is_lit = __ballot(kind2 == (K_LIT << 8));
-				const uint32_t ddm = sel(r.is_len, dd, 0u);
-				const uint32_t dlen = ddm & 15, deb = (ddm >> 4) & 15;
-				r.offset = (ddm >> 16) + __builtin_amdgcn_ubfe(rest, dlen, deb);
-				const uint32_t tokbits = t1 + dlen + deb;
-				r.outlen = sel(is_lit, 1u, sel(r.is_len, length, 0u));
-				const uint32_t tb1 = tokbits ? tokbits : 1u;
-				r.walk = tb1 | ((e >> 3) & 64u) | ((ddm >> 3) & 64u);
-				return r;
-			};
-			const Spec s0 = spec(bl0, ws0, ws1, ws2), s1 = spec(bl0 + 64, ws2, ws3, ws4);
-			// (hd_inflate.hpp explains the walk: 3 SALU + 1 branch + 1 v_readlane per token, the stop flag is bit 6 of the word
-			// that is added to the position)
+			// (the fields that place bytes -- the entry, the literals' mask -- are not looked at: the compiler drops them)
+			const InfSpec s0 = spec_token(L, bl0, ws0, ws1, ws2), s1 = spec_token(L, bl0 + 64, ws2, ws3, ws4);
 			uint32_t wb, wm;
 			uint64_t real0, real1;
-			asm volatile("s_mov_b32 %0, 0\n\t"
-				     "s_mov_b64 %1, 0\n\t"
-				     "s_mov_b64 %2, 0\n"
-				     "Lhd_szwalk0_%=:\n\t"
-				     "v_readlane_b32 %3, %4, %0\n\t"
-				     "s_bitset1_b64 %1, %0\n\t"
-				     "s_add_u32 %0, %0, %3\n\t"
-				     "s_cmp_lt_u32 %0, 64\n\t"
-				     "s_cbranch_scc1 Lhd_szwalk0_%=\n\t"
-				     "s_bitcmp1_b32 %3, 6\n\t"
-				     "s_cbranch_scc0 Lhd_szwalk1_%=\n\t"
-				     "s_sub_u32 %0, %0, %3\n\t"
-				     "s_bitset0_b64 %1, %0\n\t"
-				     "s_branch Lhd_szwalk_done_%=\n"
-				     "Lhd_szwalk1_%=:\n\t"
-				     "v_readlane_b32 %3, %5, %0\n\t"
-				     "s_bitset1_b64 %2, %0\n\t"
-				     "s_add_u32 %0, %0, %3\n\t"
-				     "s_cmp_lt_u32 %0, 128\n\t"
-				     "s_cbranch_scc1 Lhd_szwalk1_%=\n\t"
-				     "s_bitcmp1_b32 %3, 6\n\t"
-				     "s_cbranch_scc0 Lhd_szwalk_done_%=\n\t"
-				     "s_sub_u32 %0, %0, %3\n\t"
-				     "s_bitset0_b64 %2, %0\n"
-				     "Lhd_szwalk_done_%=:"
-				     : "=&s"(wb), "=&s"(real0), "=&s"(real1), "=&s"(wm)
-				     : "v"(s0.walk), "v"(s1.walk)
-				     : "scc");
+			window_walk(s0.walk, s1.walk, wb, real0, real1, wm);
 			if (real0 == 0)
 				break;                                     // the token at B is not for a window: scalar path
 			// (both halves' output lengths in one prefix sum, 16 bits each: 64 x 258 < 2^16)
@@ -280,7 +168,7 @@ template <bool PIECE, class Args> __device__ __forceinline__ void inflate_size_b
 			if (wm & 64)
 				break;                                     // the walk stopped in front of a long codeword or the end of the block
 		}
-		seek_bit(B);
+		R.seek_bit(B);
 		return result;
 	};
 
@@ -289,28 +177,27 @@ template <bool PIECE, class Args> __device__ __forceinline__ void inflate_size_b
 	uint32_t stop = 0;                            // (piece form) the stop it hit
 	bool cut = false;                             // (piece form) a stored block's LEN / NLEN or payload reaches past the input
 	for (;;) {
-		refill();
+		R.refill();
 		lds_p0 = 0xfffffff0u;                     // header parsing reuses the LDS behind L.comp
-		const uint32_t bfinal = (uint32_t)bb & 1;
-		const uint32_t btype = ((uint32_t)bb >> 1) & 3;
-		bb >>= 3;
-		bc -= 3;
+		const uint32_t bfinal = (uint32_t)R.bb & 1;
+		const uint32_t btype = ((uint32_t)R.bb >> 1) & 3;
+		R.drop(3);
 
 		if (btype == 0) {
 			// ---- stored (decompress_template.h:234-279): a seek ------------
-			const int64_t cbits = (consumed_bits() + 7) & ~(int64_t)7;
+			const int64_t cbits = (R.consumed_bits() + 7) & ~(int64_t)7;
 			if (cbits > 8 * (int64_t)n) { st = HD_BAD_DATA; break; }
 			uint32_t ip = (uint32_t)(cbits >> 3);
 			if (n - ip < 4) { st = HD_BAD_DATA; cut = true; break; }
-			seek_bit(8 * (mis + ip));
-			refill();
-			const uint32_t len = (uint32_t)bb & 0xffff, nlen = ((uint32_t)bb >> 16) & 0xffff;
+			R.seek_byte(ip);
+			R.refill();
+			const uint32_t len = (uint32_t)R.bb & 0xffff, nlen = ((uint32_t)R.bb >> 16) & 0xffff;
 			ip += 4;
 			if (len != (~nlen & 0xffff)) { st = HD_BAD_DATA; break; }
 			if (pos + len > POS_LIMIT) { st = HD_INSUFFICIENT_SPACE; break; }
 			if (len > n - ip) { st = HD_BAD_DATA; cut = true; break; }
 			pos += len;
-			seek_bit(8 * (mis + ip + len));
+			R.seek_byte(ip + len);
 			if constexpr (PIECE) {
 				if (!bfinal && len == 0) {
 					stop = PIECE_FLUSH;
@@ -321,75 +208,11 @@ template <bool PIECE, class Args> __device__ __forceinline__ void inflate_size_b
 			st = HD_BAD_DATA;
 			break;
 		} else {
-			uint32_t nlit = 288, noff = 32;
 			if (btype == 2) {
-				// ---- dynamic header: decompress_template.h:101-232 -------
-				refill();
-				nlit = 257 + ((uint32_t)bb & 31);
-				noff = 1 + (((uint32_t)bb >> 5) & 31);
-				const uint32_t npre = 4 + (((uint32_t)bb >> 10) & 15);
-				bb >>= 14;
-				bc -= 14;
-				if (lane < 19)
-					L.pre_lens[lane] = 0;
-				for (uint32_t i = 0; i < npre; i++) {
-					refill();
-					if (lane == 0)
-						L.pre_lens[k_precode_perm[i]] = (uint8_t)((uint32_t)bb & 7);
-					bb >>= 3;
-					bc -= 3;
-				}
-				if (!uniform(build_table<2>(L.pre_lens, 19, L.lit, 7, L.lit_sorted, nullptr, L.cl + INF_T_SCRATCH, lane))) { st = HD_BAD_DATA; break; }
-				uint8_t *cl = L.cl;
-				uint32_t i = 0, prev = 0;
-				bool bad = false;
-				while (i < nlit + noff) {
-					refill();
-					if (consumed_bits() > 8 * (int64_t)n + 64) { bad = true; break; }
-					const uint32_t e = uniform(L.lit[(uint32_t)bb & 127]);
-					const uint32_t cl_len = e & 15, s = e >> 16;
-					bb >>= cl_len;
-					bc -= cl_len;
-					if (s < 16) {
-						if (lane == 0)
-							cl[i] = (uint8_t)s;
-						prev = s;
-						i++;
-						continue;
-					}
-					uint32_t rep, val = 0;
-					if (s == 16) {
-						if (i == 0) { bad = true; break; }
-						rep = 3 + ((uint32_t)bb & 3);
-						bb >>= 2; bc -= 2;
-						val = prev;
-					} else if (s == 17) {
-						rep = 3 + ((uint32_t)bb & 7);
-						bb >>= 3; bc -= 3;
-						prev = 0;
-					} else {
-						rep = 11 + ((uint32_t)bb & 127);
-						bb >>= 7; bc -= 7;
-						prev = 0;
-					}
-					for (uint32_t k = lane; k < rep; k += 64)
-						cl[i + k] = (uint8_t)val;
-					i += rep;
-				}
-				if (bad || i != nlit + noff) { st = HD_BAD_DATA; break; }
+				if (!inflate_dynamic_header(R, L, n, lane)) { st = HD_BAD_DATA; break; }
 				static_loaded = false;
-				if (!uniform(build_table<1>(cl + nlit, noff, L.off, INF_DT_BITS, L.off_sorted, L.off_count, L.cl + INF_T_SCRATCH, lane)) ||
-				    !uniform(build_table<0>(cl, nlit, L.lit, INF_LT_BITS, L.lit_sorted, L.lit_count, L.cl + INF_T_SCRATCH, lane))) {
-					st = HD_BAD_DATA;
-					break;
-				}
 			} else if (!static_loaded) {
-				// ---- static code: decompress_template.h:297-330 ----------
-				uint8_t *cl = L.cl;
-				for (uint32_t s = lane; s < 320; s += 64)
-					cl[s] = s < 144 ? 8 : s < 256 ? 9 : s < 280 ? 7 : s < 288 ? 8 : 5;
-				build_table<1>(cl + 288, 32, L.off, INF_DT_BITS, L.off_sorted, L.off_count, L.cl + INF_T_SCRATCH, lane);
-				build_table<0>(cl, 288, L.lit, INF_LT_BITS, L.lit_sorted, L.lit_count, L.cl + INF_T_SCRATCH, lane);
+				inflate_static_tables(L, lane);
 				static_loaded = true;
 			}
 
@@ -398,17 +221,16 @@ template <bool PIECE, class Args> __device__ __forceinline__ void inflate_size_b
 				if (uniform(run_windows(st)))
 					break;
 				// one token through the fully checked scalar path (stream edges, long codes, end of block); the
-				// tables are read from LDS: no copy of them in registers, this kernel answers to occupancy
-				refill();
-				if (overrun()) { st = HD_BAD_DATA; break; }
-				uint32_t e = uniform(L.lit[(uint32_t)bb & ((1u << INF_LT_BITS) - 1)]);
+				// tables are read from LDS: no copy of them in registers, this kernel answers to occupancy.  (pos <= POS_LIMIT
+				// here).  Own copy of the token decode, as in inflate_stream and inflate_stream_pipe: a shared function lost 0.3-0.9 % here
+				R.refill();
+				if (R.overrun()) { st = HD_BAD_DATA; break; }
+				uint32_t e = uniform(L.lit[(uint32_t)R.bb & ((1u << INF_LT_BITS) - 1)]);
 				if (((e >> 8) & 3) == K_SLOW) {
-					const uint32_t sl = uniform(slow_decode(bb, L.lit_count, L.lit_sorted, lane));
+					const uint32_t sl = uniform(slow_decode(R.bb, L.lit_count, L.lit_sorted, lane));
 					e = litlen_entry(sl & 0xffff, sl >> 16);
 				}
-				const uint32_t clen = e & 15;
-				bb >>= clen;
-				bc -= clen;
+				R.drop(e & 15);
 				const uint32_t kind = (e >> 8) & 3;
 				if (kind == K_LIT) {
 					if (pos == POS_LIMIT) { st = HD_INSUFFICIENT_SPACE; break; }
@@ -418,23 +240,20 @@ template <bool PIECE, class Args> __device__ __forceinline__ void inflate_size_b
 				if (kind == K_EOB)
 					break;
 				const uint32_t eb = (e >> 4) & 15;
-				const uint32_t length = (e >> 16) + ((uint32_t)bb & ((1u << eb) - 1));
-				bb >>= eb;
-				bc -= eb;
+				const uint32_t length = (e >> 16) + ((uint32_t)R.bb & ((1u << eb) - 1));
+				R.drop(eb);
 				if (length > POS_LIMIT - pos) { st = HD_INSUFFICIENT_SPACE; break; }
-				refill();
-				uint32_t d = uniform(L.off[(uint32_t)bb & ((1u << INF_DT_BITS) - 1)]);
+				R.refill();
+				uint32_t d = uniform(L.off[(uint32_t)R.bb & ((1u << INF_DT_BITS) - 1)]);
 				if (((d >> 8) & 3) == K_SLOW) {
-					const uint32_t sl = uniform(slow_decode(bb, L.off_count, L.off_sorted, lane));
+					const uint32_t sl = uniform(slow_decode(R.bb, L.off_count, L.off_sorted, lane));
 					d = offset_entry(sl & 0xffff, sl >> 16);
 				}
-				const uint32_t dlen = d & 15, deb = (d >> 4) & 15;
-				bb >>= dlen;
-				bc -= dlen;
-				const uint32_t offset = (d >> 16) + ((uint32_t)bb & ((1u << deb) - 1));
-				bb >>= deb;
-				bc -= deb;
-				if (offset > pos) { st = HD_BAD_DATA; break; }
+				const uint32_t deb = (d >> 4) & 15;
+				R.drop(d & 15);
+				const uint32_t offset = (d >> 16) + ((uint32_t)R.bb & ((1u << deb) - 1));
+				R.drop(deb);
+				if (offset > pos) { st = HD_BAD_DATA; break; }       // decompress_template.h:724
 				pos += length;
 			}
 			if (st != HD_OK)
@@ -445,27 +264,27 @@ template <bool PIECE, class Args> __device__ __forceinline__ void inflate_size_b
 				stop = PIECE_FINAL;
 			break;
 		}
-		if (consumed_bits() > 8 * (int64_t)n + 64) { st = HD_BAD_DATA; break; }
+		if (R.consumed_bits() > 8 * (int64_t)n + 64) { st = HD_BAD_DATA; break; }
 	}
 	if constexpr (PIECE) {
 		// with the decoder's position past the input -- at a stop it reached through the zero bits, or at the failure they
 		// led to -- the piece is cut, whatever else the decoder found there
-		if (cut || consumed_bits() > 8 * (int64_t)n)
+		if (cut || R.consumed_bits() > 8 * (int64_t)n)
 			st = PIECE_CUT;
 		if (lane == 0) {
 			a.out_size[b] = st == HD_OK ? (uint32_t)pos : 0u;
-			a.in_used[b] = st == HD_OK ? (uint32_t)((consumed_bits() + 7) >> 3) : 0u;
+			a.in_used[b] = st == HD_OK ? (uint32_t)((R.consumed_bits() + 7) >> 3) : 0u;
 			a.status[b] = st;
 			a.stop[b] = st == HD_OK ? stop : 0u;
 		}
 	} else {
-		if (st == HD_OK && consumed_bits() > 8 * (int64_t)n)
+		if (st == HD_OK && R.consumed_bits() > 8 * (int64_t)n)
 			st = HD_BAD_DATA;
 
 		// ---- the verdict: the stream's, and the one field of the trailer that needs no byte of output ----
 		uint32_t used = 0;
 		if (st == HD_OK) {
-			used = (uint32_t)((consumed_bits() + 7) >> 3);
+			used = (uint32_t)((R.consumed_bits() + 7) >> 3);
 			if (a.trailer == 8) {
 				// RFC 1952 ISIZE, behind the CRC-32 (gzip_decompress.c:124-127); used <= n, and k_frame_open left 8 bytes behind n
 				const uint8_t *t = src + used + 4;

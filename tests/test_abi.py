@@ -199,6 +199,16 @@ def test_kernel_resource_budgets_by_template_args():
         assert v["VGPRs"] <= 96 and units <= 7, (k, v)          # parse_slots()
     (v,) = inf.values()
     assert v["VGPRs"] <= 80 and v["LDS Size"] <= 6400, v         # five LDS units (25 per CU), 6 waves per SIMD: 24 waves per CU
+    # ... and the same line for its instantiation with the bytes consumed (the framed decode's)
+    inf_framed = {k: v for k, v in kernels.items() if "k_inflate_framedE" in k}
+    assert len(inf_framed) == 1, list(kernels)
+    (v,) = inf_framed.values()
+    assert v["VGPRs"] <= 80 and v["LDS Size"] <= 6400, v
+    # the size pass and the piece decoder (hd_inflate_size.hpp): four LDS units, 32 wavefronts per CU = 8 per SIMD
+    inf_size = {k: v for k, v in kernels.items() if "k_inflate_sizeE" in k or "k_inflate_pieceE" in k}
+    assert len(inf_size) == 2, list(kernels)
+    for k, v in inf_size.items():
+        assert v["VGPRs"] <= 64 and -(-v["LDS Size"] // 1280) <= 4, (k, v)
     (v,) = inf_lat.values()
     # the whole window in LDS + the queues and the spec ring of its four wavefronts: ONE workgroup per CU (a stream wants the CU's
     # four SIMDs for its four wavefronts; a batch holds at most 64 streams and two batches are out at once: 128 workgroups, 256 CUs)
