@@ -93,6 +93,7 @@ EXPORTS = [
     "hipdeflate_pipe_open_on", "hipdeflate_unpipe_open_on", "hipdeflate_lat_open_on",
     "hipdeflate_batch_inflate_size_dev", "hipdeflate_batch_inflate_framed_dev", "hipdeflate_batch_inflate_size",
     "hipdeflate_batch_inflate_framed",
+    "hipdeflate_test_compact_grid",
     "hipdeflate_pipe_members", "hipdeflate_lat_open", "hipdeflate_lat_input", "hipdeflate_lat_run", "hipdeflate_lat_output", "hipdeflate_lat_close",
 ]
 
@@ -220,6 +221,8 @@ def lib():
     L.hipdeflate_test_build_lengths.argtypes = [_vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _vp]
     L.hipdeflate_test_beside.argtypes = [ctypes.c_int, ctypes.c_uint32]
     L.hipdeflate_test_beside.restype = None
+    L.hipdeflate_test_compact_grid.argtypes = []
+    L.hipdeflate_test_compact_grid.restype = ctypes.c_uint32
     _lib = L
     return L
 

@@ -139,6 +139,24 @@ struct SharedScratch {
 	}
 };
 
+// The last encode launch of the device-pointer API: what a gather asks to learn, on the host, whether an encode kernel of
+// the library's own is still running beside it (compact_beside below).  Guarded by Ctx::mu_enc.
+struct LastEncode {
+	hipEvent_t ev = nullptr;         // recorded right behind the launch; created once, no timing
+	hipStream_t stream = nullptr;    // (compared only, never used: the caller may have destroyed it since)
+	const void *out = nullptr;       // the slots it writes
+	int level = 0;
+	uint32_t nblocks = 0;
+	bool valid = false;
+	void reset()
+	{
+		if (ev)
+			(void)hipEventDestroy(ev);
+		ev = nullptr;
+		valid = false;
+	}
+};
+
 struct Ctx {
 	bool ready = false;
 	int failed = 0;
@@ -156,6 +174,11 @@ struct Ctx {
 	SharedScratch tok, tiles;        // token slabs and segment slots of a launch / the tile sums of a scan
 	SharedScratch frame;             // the payload table of a framed inflate or size pass (hd_frame.hpp)
 	hd::WgBeside beside;             // the workgroup levels' emit kernel beside their parse (hd_deflate_wg.hpp), with tok
+	// the last encode launch and the grid of the last gather (hipdeflate_test_compact_grid), behind a mutex of their own:
+	// level 1 launches without mu_dev
+	std::mutex mu_enc;
+	LastEncode enc;
+	uint32_t compact_grid = 0;
 	void stream_drained(hipStream_t st)
 	{
 		std::lock_guard<std::mutex> lk(mu_dev);
@@ -690,6 +713,7 @@ void hipdeflate_shutdown(void)
 		g.tok.reset();
 		g.tiles.reset();
 		g.frame.reset();
+		g.enc.reset();
 		g.beside.release();
 		g.d_ct = nullptr;
 		g.stream = nullptr;
@@ -743,6 +767,71 @@ static bool beside_allowed()
 	// (read at every launch -- a launch is >= 512 blocks --, so a test can switch it)
 	return !on("HIPDEFLATE_NO_BESIDE") && !on("HIP_LAUNCH_BLOCKING") && !on("AMD_SERIALIZE_KERNEL") && !on("ROCPROF_COUNTER_COLLECTION") &&
 	       !getenv("ROCPROF_COUNTERS");
+}
+
+// The gather BESIDE an encode kernel.  A stream of batches (bench.py, any caller with two buffer sets) gathers batch k in
+// a second stream while the encode kernel of batch k + 1 runs, and what the gather takes from that kernel follows the
+// bytes it keeps in flight.  Such a gather has the encode kernel's whole time to spare, so it gets the
+// small grid (hd_compact.hpp); nothing on the device waits for anything: the rate is fixed at the launch, by what the
+// host knows of the library's own last encode launch.
+constexpr uint32_t ENCODE_L1_WAVES_PER_CU = 21;               // six LDS units a wavefront (hd_deflate_static.hpp)
+static bool stream_capturing(hipStream_t st)
+{
+	hipStreamCaptureStatus s = hipStreamCaptureStatusNone;
+	if (hipStreamIsCapturing(st, &s) != hipSuccess) {
+		(void)hipGetLastError();                             // (not this launch's error: the answer is "do not ask further")
+		return true;
+	}
+	return s != hipStreamCaptureStatusNone;
+}
+
+// right behind launch_deflate of the device-pointer entry.  A failure here costs the next gathers their small grid only.
+static void note_encode(Ctx &g, hipStream_t st, const void *out, int level, uint32_t nblocks)
+{
+	if (!nblocks || stream_capturing(st))
+		return;
+	std::lock_guard<std::mutex> lk(g.mu_enc);
+	LastEncode &e = g.enc;
+	e.valid = false;
+	if (!e.ev && hipEventCreateWithFlags(&e.ev, hipEventDisableTiming) != hipSuccess) {
+		e.ev = nullptr;
+		(void)hipGetLastError();
+		return;
+	}
+	if (hipEventRecord(e.ev, st) != hipSuccess) {
+		(void)hipGetLastError();
+		return;
+	}
+	e.stream = st;
+	e.out = out;
+	e.level = level;
+	e.nblocks = nblocks;
+	e.valid = true;
+}
+
+// HIPDEFLATE_GATHER_GRID=full|beside|auto (default auto), read at every launch like beside_allowed()'s variables
+static bool compact_beside(Ctx &g, const void *slots, hipStream_t st)
+{
+	const char *v = getenv("HIPDEFLATE_GATHER_GRID");
+	if (v && !strcmp(v, "full"))
+		return false;
+	if (v && !strcmp(v, "beside"))
+		return true;
+	if (stream_capturing(st))
+		return false;
+	std::lock_guard<std::mutex> lk(g.mu_enc);
+	const LastEncode &e = g.enc;
+	// another stream's, other slots (a gather that waits for its own producer has nothing beside it, as far as the library
+	// can know), a real encode (level 0 is a copy the throttled gather would outlast several times) that fills the device
+	// (CUs x 21 level-1 wavefronts at once: a smaller launch is over before the gather has started) ...
+	if (!e.valid || e.stream == st || e.out == slots || e.level < 1 ||
+	    e.nblocks < (uint64_t)hd::compact_device_cus() * ENCODE_L1_WAVES_PER_CU)
+		return false;
+	// ... and still queued or running
+	const hipError_t q = hipEventQuery(e.ev);
+	if (q != hipSuccess)
+		(void)hipGetLastError();                             // (the runtime keeps "not ready" as the thread's last error)
+	return q == hipErrorNotReady;
 }
 
 // The segments of a launch (hd_segment.hpp): a slot that could hold a block longer than the segment limit -- HD_SEG_LIMIT;
@@ -806,8 +895,12 @@ static int batch_deflate_dev_impl(const void *in, const void *in_off, const void
 					 out_stride, out_cap, (uint32_t *)out_len, (uint32_t *)crc32, (int32_t *)status,
 					 hd::split_max_block(out_stride, out_cap), max_in);
 	const uint64_t need = scratch_need(nblocks, a.split_max, level, latency);
-	if (!need)
-		return launch_deflate(a, level, st);
+	if (!need) {
+		if ((r = launch_deflate(a, level, st)))
+			return r;
+		note_encode(g, st, out, level, nblocks);
+		return 0;
+	}
 	// token slabs of the dynamic levels, segment slots of large blocks: library-owned, grow-only
 	std::lock_guard<std::mutex> lk(g.mu_dev);
 	// (a re-allocation must not pull the rug from under launches in flight: the old scratch stays alive)
@@ -833,6 +926,7 @@ static int batch_deflate_dev_impl(const void *in, const void *in_off, const void
 	}
 	if ((r = launch_deflate(a, level, st)))
 		return r;
+	note_encode(g, st, out, level, nblocks);
 	return g.tok.leave(st);
 }
 
@@ -1025,6 +1119,7 @@ int hipdeflate_scan_sizes_dev(const void *out_len, uint32_t nblocks, uint64_t ba
 int hipdeflate_compact_dev(const void *slots, uint64_t stride, const void *out_len, const void *dst_off,
 			   uint32_t nblocks, void *dst, void *stream)
 {
+	Ctx &g = cur();
 	int r = ensure();
 	if (r)
 		return r;
@@ -1032,9 +1127,12 @@ int hipdeflate_compact_dev(const void *slots, uint64_t stride, const void *out_l
 		return 0;
 	if ((stride & 3) || ((uintptr_t)slots & 3))
 		return HD_E_ARG;
-	hd::launch_compact((const uint8_t *)slots, stride, (const uint32_t *)out_len, (const uint64_t *)dst_off, nblocks,
-			   (uint8_t *)dst, (hipStream_t)stream);
+	hipStream_t st = (hipStream_t)stream;
+	const uint32_t grid = hd::launch_compact((const uint8_t *)slots, stride, (const uint32_t *)out_len, (const uint64_t *)dst_off,
+						 nblocks, (uint8_t *)dst, st, compact_beside(g, slots, st));
 	HD_CHECK(hipGetLastError());
+	std::lock_guard<std::mutex> lk(g.mu_enc);
+	g.compact_grid = grid;
 	return 0;
 }
 
@@ -2805,6 +2903,13 @@ void hipdeflate_test_beside(int keep, uint32_t sub_cap)
 {
 	g_test_beside_keep = keep < 0 ? 0u : (uint32_t)keep > hd::BESIDE_KEEP_MAX ? hd::BESIDE_KEEP_MAX : (uint32_t)keep;
 	hd::wg_sub_test() = sub_cap;
+}
+
+uint32_t hipdeflate_test_compact_grid(void)
+{
+	Ctx &g = cur();
+	std::lock_guard<std::mutex> lk(g.mu_enc);
+	return g.compact_grid;
 }
 
 #ifdef HD_EMIT_STATS

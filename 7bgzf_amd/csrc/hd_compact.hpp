@@ -160,6 +160,15 @@ constexpr bool COMPACT_NT = HD_COMPACT_NT != 0;                     // nontempor
 // keeps in flight, not with the instructions it issues: 3 x 4 KiB per CU is the least that still copies, alone, as fast
 // as one wavefront per member did (DESIGN.md 6d has the sweep).
 constexpr uint32_t COMPACT_WAVES_PER_CU = HD_COMPACT_WAVES_PER_CU;
+// The small grid, wavefronts per TWO CUs (so that half a wavefront per CU can be written down): what a gather gets that
+// the library itself launches while an encode kernel of its own is still running in another stream (hd_api.hip
+// compact_beside).  Such a gather has that kernel's whole time to spare and need not be fast, only gentle: throttled
+// like this it takes a fraction of what the full grid takes from the encoder (DESIGN.md 6d has the sweep).
+#ifndef HD_COMPACT_BESIDE_WAVES_PER_2CU
+#define HD_COMPACT_BESIDE_WAVES_PER_2CU 1
+#endif
+constexpr uint32_t COMPACT_BESIDE_WAVES_PER_2CU = HD_COMPACT_BESIDE_WAVES_PER_2CU;
+static_assert(COMPACT_BESIDE_WAVES_PER_2CU >= 1 && COMPACT_BESIDE_WAVES_PER_2CU <= 2 * COMPACT_WAVES_PER_CU, "the small grid is not above the full one");
 
 typedef uint32_t compact_u32x4 __attribute__((ext_vector_type(4)));
 typedef compact_u32x4 compact_u32x4_any __attribute__((aligned(1)));   // a source line: wherever the destination's alignment puts it
@@ -272,12 +281,18 @@ inline uint32_t compact_device_cus()
 	return c;
 }
 
-// a launch of fewer members than the persistent grid holds is one wavefront per member
-inline void launch_compact(const uint8_t *slots, uint64_t stride, const uint32_t *len, const uint64_t *dst_off, uint32_t n,
-			   uint8_t *dst, hipStream_t st)
+// a launch of fewer members than the persistent grid holds is one wavefront per member.  beside: the small grid (the
+// same kernel, fewer wavefronts: every one of them takes more members).  -> the grid of the launch
+inline uint32_t launch_compact(const uint8_t *slots, uint64_t stride, const uint32_t *len, const uint64_t *dst_off, uint32_t n,
+			       uint8_t *dst, hipStream_t st, bool beside = false)
 {
-	const uint64_t cap = (uint64_t)compact_device_cus() * COMPACT_WAVES_PER_CU;
-	hipLaunchKernelGGL(k_compact, dim3(n < cap ? n : (uint32_t)cap), dim3(64), 0, st, slots, stride, len, dst_off, n, dst);
+	const uint64_t cus = compact_device_cus();
+	uint64_t cap = beside ? cus * COMPACT_BESIDE_WAVES_PER_2CU / 2 : cus * COMPACT_WAVES_PER_CU;
+	if (!cap)
+		cap = 1;
+	const uint32_t grid = n < cap ? n : (uint32_t)cap;
+	hipLaunchKernelGGL(k_compact, dim3(grid), dim3(64), 0, st, slots, stride, len, dst_off, n, dst);
+	return grid;
 }
 
 // RFC 1950 members (HD_FRAME_ZLIB): the Adler-32 of every block's input, written big-endian

@@ -648,6 +648,12 @@ int hipdeflate_test_build_lengths(const uint32_t *freq, uint32_t nvec, uint32_t 
  * walks the path of a 16 GiB one (two record buffers, the gates between sub-batches).  The bytes do not depend on either.  Process-wide;
  * (3, 0) restores the defaults. */
 void hipdeflate_test_beside(int keep, uint32_t sub_cap);
+/* test entry: the grid (wavefronts) of the last gather kernel that hipdeflate_compact_dev / hipdeflate_compact_span_dev launched
+ * on the calling thread's device context; 0 before the first.  A gather launched while an encode of hipdeflate_batch_deflate_dev
+ * (level >= 1, enough blocks to fill the device) is still queued or running in ANOTHER stream, into other slots than the
+ * gather's, runs on a small grid: it has that kernel's time to spare and takes less from it.
+ * HIPDEFLATE_GATHER_GRID=full|beside|auto (default auto; read at every launch) forces either grid.  The bytes do not depend on it. */
+uint32_t hipdeflate_test_compact_grid(void);
 
 #ifdef __cplusplus
 }

@@ -12,7 +12,12 @@ the gather (and the 0.1 ms of scan) takes from the encoder.  pipeline_ms_per_ste
 last gather drained inside it, as bench.py times its steps: if it is not encode_beside plus a twentieth of a
 gather, the two streams did not run beside each other.  One JSON line:
 
-  python tools/gather_beside.py [--steps 10] [--warmup 2] [--level 1] [--gib 16]
+  python tools/gather_beside.py [--steps 10] [--warmup 2] [--level 1] [--gib 16] [--data fastq|text|random] [--lib FILE]
+
+--lib: another build of the library than the package's own (parent against new from one checkout).  The grid the library
+chose for the gathers of legs 2 and 3 (hipdeflate_test_compact_grid, where the build has it) is on the line as
+gather_beside_grid / gather_alone_grid; HIPDEFLATE_GATHER_GRID=full|beside in the environment forces either, which is how
+the rows of a sweep over HD_COMPACT_BESIDE_WAVES_PER_2CU are made: one build per value, run under `beside`.
 """
 import argparse
 import json
@@ -30,11 +35,14 @@ def stats(ms):
     return {"avg": round(sum(ms) / len(ms), 3), "min": round(min(ms), 3), "max": round(max(ms), 3), "n": len(ms)}
 
 
-def setup(gib=16.0, tile_mib=64, first_record=0):
+def setup(gib=16.0, tile_mib=64, first_record=0, data_kind="fastq", lib=None):
     """-> (Bench, data, off, ln, encs, packs): what bench.py's encode() sets up before its timed region"""
     args = argparse.Namespace(gpus=1, gib=gib, tile_mib=tile_mib, first_record=first_record)
+    if lib:
+        import importlib
+        importlib.import_module("7bgzf_amd").LIB_PATH = os.path.abspath(lib)       # before the first lib()
     B = bench.Bench(args)
-    _, data, _ = B.make_data("fastq", bench.BGZF_BLOCK, whole_blocks=False)
+    _, data, _ = B.make_data(data_kind, bench.BGZF_BLOCK, whole_blocks=False)
     off, ln = B.dev.block_table(data.numel(), bench.BGZF_BLOCK)
     nb = off.numel()
     encs = [B.dev.DeviceDeflate(nb, slot=65536) for _ in range(2)]
@@ -46,6 +54,60 @@ def setup(gib=16.0, tile_mib=64, first_record=0):
     # the step takes the sum of the two)
     B.side = B.torch.cuda.Stream()
     return B, data, off, ln, encs, packs
+
+
+def last_grid(B):
+    """the grid of the library's last gather launch (None: a build without the hook)"""
+    f = getattr(B.pkg.lib(), "hipdeflate_test_compact_grid", None)
+    return int(f()) & 0xffffffff if f is not None else None
+
+
+def pipeline(torch, main, side, encs, packs, encode, after_gather=None):
+    """bench.py's software pipeline over two buffer sets -> (step, drain): step(keep_e, keep_g) queues the encode of the
+    next pass on `main` (encode(i) fills encs[i]) and then, on `side`, scan and gather of the pass before it into packs[i];
+    drain(keep_g) gathers the last pass, which has no encoder beside it.  The lists receive the event pairs round the
+    encode and round the gather; after_gather(i) is called right behind every gather's launch."""
+    coded = [torch.cuda.Event(), torch.cuda.Event()]
+    gathered = [torch.cuda.Event(), torch.cuda.Event()]
+    state = {"k": 0, "pending": None}
+
+    def ev():
+        return torch.cuda.Event(enable_timing=True)
+
+    def gather(i, keep):
+        with torch.cuda.stream(side):
+            side.wait_event(coded[i])
+            encs[i].scan()
+            g0, g1 = ev(), ev()
+            g0.record(side)
+            encs[i].compact(packs[i])
+            g1.record(side)
+            gathered[i].record(side)
+        if after_gather is not None:
+            after_gather(i)
+        keep.append((g0, g1))
+
+    def step(keep_e, keep_g):
+        i = state["k"] & 1
+        state["k"] += 1
+        e0, e1 = ev(), ev()
+        main.wait_event(gathered[i])
+        e0.record()
+        encode(i)
+        e1.record()
+        coded[i].record(main)
+        if state["pending"] is not None:
+            gather(state["pending"], keep_g)
+        state["pending"] = i
+        keep_e.append((e0, e1))
+
+    def drain(keep_g):
+        if state["pending"] is not None:
+            gather(state["pending"], keep_g)
+            state["pending"] = None
+        main.wait_stream(side)
+
+    return step, drain
 
 
 def measure(B, data, off, ln, encs, packs, steps=10, warmup=2, level=1):
@@ -71,40 +133,8 @@ def measure(B, data, off, ln, encs, packs, steps=10, warmup=2, level=1):
     enc_alone = [a.elapsed_time(b) for a, b in alone]
 
     # ---- leg 2: bench.py's pipeline ---------------------------------------------------------------------------
-    coded = [torch.cuda.Event(), torch.cuda.Event()]
-    gathered = [torch.cuda.Event(), torch.cuda.Event()]
-    state = {"k": 0, "pending": None}
-
-    def gather(i, keep):
-        with torch.cuda.stream(side):
-            side.wait_event(coded[i])
-            encs[i].scan()
-            g0, g1 = ev(), ev()
-            g0.record(side)
-            encs[i].compact(packs[i])
-            g1.record(side)
-            gathered[i].record(side)
-        keep.append((g0, g1))
-
-    def step(keep_e, keep_g):
-        i = state["k"] & 1
-        state["k"] += 1
-        e0, e1 = ev(), ev()
-        main.wait_event(gathered[i])
-        e0.record()
-        encs[i].run(data, off, ln, level=level, frame=frame)
-        e1.record()
-        coded[i].record(main)
-        if state["pending"] is not None:
-            gather(state["pending"], keep_g)
-        state["pending"] = i
-        keep_e.append((e0, e1))
-
-    def drain(keep_g):
-        if state["pending"] is not None:
-            gather(state["pending"], keep_g)
-            state["pending"] = None
-        main.wait_stream(side)
+    step, drain = pipeline(torch, main, side, encs, packs,
+                           lambda i: encs[i].run(data, off, ln, level=level, frame=frame))
 
     for _ in range(warmup):
         step([], [])
@@ -114,6 +144,7 @@ def measure(B, data, off, ln, encs, packs, steps=10, warmup=2, level=1):
     t0 = time.perf_counter()
     for _ in range(steps):
         step(be, bg)
+    grid_beside = last_grid(B)
     lone = []
     drain(lone)                                  # the last gather has no encoder beside it: kept out of the figure
     torch.cuda.synchronize()
@@ -136,6 +167,7 @@ def measure(B, data, off, ln, encs, packs, steps=10, warmup=2, level=1):
         ga.append((g0, g1))
     torch.cuda.synchronize()
     gat_alone = [a.elapsed_time(b) for a, b in ga]
+    grid_alone = last_grid(B)
 
     assert int(encs[0].status.abs().sum()) == 0 and int(encs[1].status.abs().sum()) == 0
     comp = int(encs[0].total.item())
@@ -143,6 +175,8 @@ def measure(B, data, off, ln, encs, packs, steps=10, warmup=2, level=1):
            "gather_alone_ms": stats(gat_alone), "gather_beside_ms": stats(gat_beside),
            "encode_beside_minus_alone_ms": round(stats(enc_beside)["avg"] - stats(enc_alone)["avg"], 3),
            "pipeline_ms_per_step": round(wall_ms, 3),
+           "gather_beside_grid": grid_beside, "gather_alone_grid": grid_alone,
+           "gather_grid_env": os.environ.get("HIPDEFLATE_GATHER_GRID", ""),
            "gather_alone_GBps_copied": round(comp / (stats(gat_alone)["avg"] * 1e-3) / 1e9, 1),
            "members": int(off.numel()), "input_bytes": int(data.numel()), "gathered_bytes": comp,
            "level": level, "steps": steps, "warmup": warmup}
@@ -155,9 +189,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--level", type=int, default=1)
     ap.add_argument("--gib", type=float, default=16.0)
+    ap.add_argument("--data", default="fastq", choices=["fastq", "text", "random"])
+    ap.add_argument("--lib", default=None, help="another build of libhipdeflate.so than the package's own")
     a = ap.parse_args()
-    B, data, off, ln, encs, packs = setup(gib=a.gib)
-    print(json.dumps(measure(B, data, off, ln, encs, packs, a.steps, a.warmup, a.level)), flush=True)
+    B, data, off, ln, encs, packs = setup(gib=a.gib, data_kind=a.data, lib=a.lib)
+    res = measure(B, data, off, ln, encs, packs, a.steps, a.warmup, a.level)
+    res["data"] = a.data
+    print(json.dumps(res), flush=True)
 
 
 if __name__ == "__main__":
