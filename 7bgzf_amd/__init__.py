@@ -89,6 +89,8 @@ EXPORTS = [
     "hipdeflate_stream_bound", "hipdeflate_stream_deflate_dev", "hipdeflate_stream_inflate_dev",
     "hipdeflate_check_combine_dev", "hip_deflate_stream", "hipdeflate_test_stream_window",
     "hipdeflate_stream_index_dev", "hipdeflate_stream_inflate_table_dev", "hip_inflate_stream",
+    "hipdeflate_stream_index_carry_dev", "hipdeflate_stream_inflate_carry_dev", "hip_inflate_stream_carry",
+    "hipdeflate_test_carry_group", "hipdeflate_test_carry_times",
     "hipdeflate_init_devices", "hipdeflate_device_count", "hipdeflate_use_device",
     "hipdeflate_pipe_open_on", "hipdeflate_unpipe_open_on", "hipdeflate_lat_open_on",
     "hipdeflate_batch_inflate_size_dev", "hipdeflate_batch_inflate_framed_dev", "hipdeflate_batch_inflate_size",
@@ -192,6 +194,15 @@ def lib():
     L.hip_inflate_stream.argtypes = [_vp, sz_p, _vp, ctypes.c_size_t, ctypes.c_int, sz_p]
     L.hipdeflate_test_stream_window.argtypes = [ctypes.c_uint32]
     L.hipdeflate_test_stream_window.restype = None
+    L.hipdeflate_stream_index_carry_dev.argtypes = [_vp, ctypes.c_uint64, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp, _vp,
+                                                    _vp, _vp, ctypes.POINTER(StreamIndexSummary), _vp]
+    L.hipdeflate_stream_inflate_carry_dev.argtypes = [_vp, ctypes.c_uint64, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint32, _vp,
+                                                      ctypes.c_uint64, ctypes.POINTER(StreamSummary), _vp]
+    L.hip_inflate_stream_carry.argtypes = [_vp, sz_p, _vp, ctypes.c_size_t, ctypes.c_int, sz_p]
+    L.hipdeflate_test_carry_group.argtypes = [ctypes.c_uint64]
+    L.hipdeflate_test_carry_group.restype = None
+    L.hipdeflate_test_carry_times.argtypes = [ctypes.POINTER(ctypes.c_double)]
+    L.hipdeflate_test_carry_times.restype = None
     L.hipdeflate_pipe_open.restype = _vp
     L.hipdeflate_pipe_open.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int]
     L.hipdeflate_pipe_input.restype = _vp
@@ -300,6 +311,16 @@ def hip_inflate_stream(data, cap, frame=FRAME_GZIP):
     dst = np.zeros(max(cap, 1), dtype=np.uint8)
     n, used = ctypes.c_size_t(cap), ctypes.c_size_t(0)
     r = lib().hip_inflate_stream(_p(dst), ctypes.byref(n), _p(src), len(src), frame, ctypes.byref(used))
+    return r, bytes(dst[: n.value]) if r == 0 else b"", n.value, used.value
+
+
+def hip_inflate_stream_carry(data, cap, frame=FRAME_GZIP):
+    """hip_inflate_stream for a stream whose flushes carry the window (pigz, zlib's Z_SYNC_FLUSH): the carry index and the
+    carry decode behind host buffers -> (ret, bytes, need, in_used), as hip_inflate_stream gives them"""
+    src = as_u8(data)
+    dst = np.zeros(max(cap, 1), dtype=np.uint8)
+    n, used = ctypes.c_size_t(cap), ctypes.c_size_t(0)
+    r = lib().hip_inflate_stream_carry(_p(dst), ctypes.byref(n), _p(src), len(src), frame, ctypes.byref(used))
     return r, bytes(dst[: n.value]) if r == 0 else b"", n.value, used.value
 
 

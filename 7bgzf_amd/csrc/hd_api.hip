@@ -26,6 +26,7 @@
 #include "hd_index.hpp"
 #include "hd_range.hpp"
 #include "hd_stream.hpp"
+#include "hd_carry.hpp"
 #include "hd_segment.hpp"
 #include "hd_tables.hpp"
 
@@ -1654,9 +1655,12 @@ static int stream_open(const void *strm, uint64_t nbytes, int frame, uint64_t *w
 }
 
 // own: the tables are the library's, made as large as the stream needs once that is known -- in_off, out_off u64[n] |
-// in_len, out_size u32[n] in *own, n = summary->nchunks -- and the four table arguments are not looked at
+// in_len, out_size u32[n] (carry: | reach u32[n]) in *own, n = the chain's rows (summary->nchunks where the status is 0) --
+// and the table arguments are not looked at.  carry: the index of hd_carry.hpp -- k_carry_piece in the place of
+// k_inflate_piece, the reach column, and the reach rule behind the verdict.
 static int stream_index(Ctx &g, const void *strm, uint64_t nbytes, int frame, uint32_t max_chunks, uint32_t max_chunk_in, void *in_off,
-			void *in_len, void *out_size, void *out_off, hipdeflate_stream_index_summary *summary, hipStream_t st, Buf *own)
+			void *in_len, void *out_size, void *out_off, hipdeflate_stream_index_summary *summary, hipStream_t st, Buf *own,
+			bool carry = false, void *reach = nullptr)
 {
 	int r;
 	const uint8_t *src = (const uint8_t *)strm;
@@ -1711,12 +1715,13 @@ static int stream_index(Ctx &g, const void *strm, uint64_t nbytes, int frame, ui
 	const size_t scan_tiles_b = ((size_t)ncand + hd::SCAN_TILE - 1) / hd::SCAN_TILE + ((size_t)ncand + hd::SCAN_TILE - 1) / hd::SCAN_TILE;
 	const size_t nc = ((size_t)ncand + 3) & ~(size_t)3;
 	// scan tiles | pos | succ[2] (later: rank) | mark | in_used | out_size | status | stop
-	if (g.d_cand.reserve((scan_tiles_b + nc * 2) * 8 + nc * 20))
+	if (g.d_cand.reserve((scan_tiles_b + nc * 2) * 8 + nc * (carry ? 24 : 20)))
 		return HD_E_NOMEM;
 	uint64_t *tiles_b = (uint64_t *)g.d_cand.p, *pos = tiles_b + scan_tiles_b, *rank = pos + nc;
 	uint32_t *succ0 = (uint32_t *)rank, *succ1 = succ0 + nc, *mark = succ1 + nc, *used = mark + nc, *osize = used + nc;
 	int32_t *pstat = (int32_t *)(osize + nc);
 	uint32_t *stop = (uint32_t *)(pstat + nc);
+	uint32_t *preach = stop + nc;                                            // (carry) every candidate's reach
 	const uint32_t nwg = (ncand + 255) / 256;
 	HD_CHECK(hipMemsetAsync(pos, 0, 8, st));
 	HD_CHECK(hipMemsetD32Async((hipDeviceptr_t)pos, (int)hdr, 1, st));
@@ -1724,8 +1729,12 @@ static int stream_index(Ctx &g, const void *strm, uint64_t nbytes, int frame, ui
 		hipLaunchKernelGGL(hd::k_stream_write, dim3(ntb), dim3(256), 0, st, src, scan_n, (uint64_t)hdr, (const uint64_t *)bitmap, nwords,
 				   (const uint64_t *)tile_off, pos + 1);
 	// one bounded decode per candidate
-	hipLaunchKernelGGL(hd::k_inflate_piece, dim3(ncand), dim3(64), 0, st,
-			   hd::PieceArgs{ src, (const uint64_t *)pos, ncand, max_chunk_in, payload_end, osize, used, pstat, stop });
+	if (carry)
+		hipLaunchKernelGGL(hd::k_carry_piece, dim3(ncand), dim3(64), 0, st,
+				   hd::CarryPieceArgs{ { src, (const uint64_t *)pos, ncand, max_chunk_in, payload_end, osize, used, pstat, stop }, preach });
+	else
+		hipLaunchKernelGGL(hd::k_inflate_piece, dim3(ncand), dim3(64), 0, st,
+				   hd::PieceArgs{ src, (const uint64_t *)pos, ncand, max_chunk_in, payload_end, osize, used, pstat, stop });
 	hipLaunchKernelGGL(hd::k_stream_links, dim3(nwg), dim3(256), 0, st, (const uint64_t *)pos, (const uint32_t *)used,
 			   (const uint32_t *)stop, ncand, succ0, mark);
 	// the true chain: rounds until 2^rounds >= ncand (a chain has at most ncand rows)
@@ -1740,24 +1749,37 @@ static int stream_index(Ctx &g, const void *strm, uint64_t nbytes, int frame, ui
 	HD_CHECK(hipStreamSynchronize(st));
 	const uint64_t nrows = h[0];
 	if (own) {
-		if (own->reserve((size_t)nrows * 24 + 64))
+		if (own->reserve((size_t)nrows * (carry ? 28 : 24) + 64))
 			return HD_E_NOMEM;
 		max_chunks = (uint32_t)nrows;
 		in_off = own->p;
 		out_off = (uint64_t *)in_off + nrows;
 		in_len = (uint64_t *)out_off + nrows;
 		out_size = (uint32_t *)in_len + nrows;
+		reach = (uint32_t *)out_size + nrows;
 	}
+	const uint32_t ntab = (uint32_t)(nrows < max_chunks ? nrows : max_chunks);
 	if (nrows) {
-		const uint32_t ntab = (uint32_t)(nrows < max_chunks ? nrows : max_chunks);
 		hipLaunchKernelGGL(hd::k_stream_rows, dim3(nwg), dim3(256), 0, st, (const uint64_t *)pos, (const uint32_t *)used,
 				   (const uint32_t *)osize, (const uint32_t *)mark, (const uint64_t *)rank, ncand, nrows, max_chunks,
 				   (uint64_t *)in_off, (uint32_t *)in_len, (uint32_t *)out_size, sum + 5);
 		if (ntab)
 			index_scan((const uint32_t *)out_size, ntab, tiles_b, (uint64_t *)out_off, sum + 1, st);
+		if (carry && ntab)
+			hipLaunchKernelGGL(hd::k_carry_reach_rows, dim3(nwg), dim3(256), 0, st, (const uint32_t *)preach, (const uint32_t *)mark,
+					   (const uint64_t *)rank, ncand, max_chunks, (uint32_t *)reach);
 	}
 	hipLaunchKernelGGL(hd::k_stream_verdict, dim3(1), dim3(1), 0, st, (const uint64_t *)pos, (const uint32_t *)used, (const int32_t *)pstat,
 			   (const uint32_t *)stop, ncand, nrows, max_chunks, max_chunk_in, payload_end, trl, sum);
+	if (carry && ntab) {
+		// the reach rule, on the rows in the table: sum[6] as u32 = the first row that reaches back over the stream's start
+		uint32_t *first = (uint32_t *)(sum + 6);
+		HD_CHECK(hipMemsetD32Async((hipDeviceptr_t)first, (int)hd::IDX_NIL, 1, st));
+		hipLaunchKernelGGL(hd::k_carry_check_reach, dim3((ntab + 255) / 256), dim3(256), 0, st, (const uint32_t *)reach,
+				   (const uint64_t *)out_off, ntab, 0xffffffffu, first);
+		hipLaunchKernelGGL(hd::k_carry_cut, dim3(1), dim3(64), 0, st, (const uint32_t *)first, (const uint64_t *)in_off,
+				   (const uint64_t *)out_off, sum);
+	}
 	HD_CHECK(hipGetLastError());
 	HD_CHECK(hipMemcpyAsync(h, sum, 32, hipMemcpyDeviceToHost, st));
 	HD_CHECK(hipStreamSynchronize(st));
@@ -1853,6 +1875,226 @@ int hipdeflate_stream_inflate_table_dev(const void *strm, uint64_t nbytes, int f
 				  { (const uint64_t *)in_off, (const uint32_t *)in_len, (const uint64_t *)out_off, (const uint32_t *)out_size, out_len,
 				    chk, status, tiles, prefix, sum },
 				  nchunks, e[1], out, summary, st);
+}
+
+/* ---- ... and a stream cut by sync flushes, which carry the window across the cut (hd_carry.hpp) ---- */
+
+static uint64_t g_test_carry_group = 0;                       // hipdeflate_test_carry_group
+void hipdeflate_test_carry_group(uint64_t bytes) { g_test_carry_group = bytes; }
+
+// hipdeflate_test_carry_times: milliseconds of the marker path's passes -- decode, tails, resolve, check and fold -- by
+// events around the launches of every group, while it is on (tools/stream_carry_bench.py)
+static bool g_carry_timed = false;
+static double g_carry_ms[4] = { 0, 0, 0, 0 };
+void hipdeflate_test_carry_times(double *ms4)
+{
+	for (int k = 0; k < 4; k++) {
+		if (ms4)
+			ms4[k] = g_carry_ms[k];
+		g_carry_ms[k] = 0;
+	}
+	g_carry_timed = ms4 != nullptr;
+}
+struct CarryTimer {
+	hipEvent_t ev[5] = { nullptr, nullptr, nullptr, nullptr, nullptr };
+	bool on;
+	explicit CarryTimer(bool on_) : on(on_)
+	{
+		for (int k = 0; on && k < 5; k++)
+			if (hipEventCreate(&ev[k]) != hipSuccess)
+				on = false;
+	}
+	void mark(int k, hipStream_t st)
+	{
+		if (on)
+			(void)hipEventRecord(ev[k], st);
+	}
+	void add(double *ms)
+	{
+		if (!on || hipEventSynchronize(ev[4]) != hipSuccess)
+			return;
+		for (int k = 0; k < 4; k++) {
+			float t = 0;
+			if (hipEventElapsedTime(&t, ev[k], ev[k + 1]) == hipSuccess)
+				ms[k] += t;
+		}
+	}
+	~CarryTimer()
+	{
+		for (int k = 0; k < 5; k++)
+			if (ev[k])
+				(void)hipEventDestroy(ev[k]);
+	}
+};
+
+int hipdeflate_stream_index_carry_dev(const void *strm, uint64_t nbytes, int frame, uint32_t max_chunks, uint32_t max_chunk_in, void *in_off,
+				      void *in_len, void *out_size, void *out_off, void *reach, hipdeflate_stream_index_summary *summary,
+				      void *stream)
+{
+	Ctx &g = cur();
+	int r = ensure();
+	if (r)
+		return r;
+	if (!summary)
+		return HD_E_ARG;
+	memset(summary, 0, sizeof *summary);
+	if (!stream_frame_ok(frame) || ((uintptr_t)strm & 15) || (nbytes && !strm) || max_chunk_in >= HD_INFLATE_MAX_IN ||
+	    (max_chunks && (!in_off || !in_len || !out_size || !out_off || !reach)))
+		return HD_E_ARG;
+	return stream_index(g, strm, nbytes, frame, max_chunks, max_chunk_in, in_off, in_len, out_size, out_off, summary, (hipStream_t)stream,
+			    nullptr, true, reach);
+}
+
+int hipdeflate_stream_inflate_carry_dev(const void *strm, uint64_t nbytes, int frame, const void *in_off, const void *in_len,
+					const void *out_size, const void *out_off, const void *reach, uint32_t nchunks, void *out,
+					uint64_t out_cap, hipdeflate_stream_summary *summary, void *stream)
+{
+	Ctx &g = cur();
+	int r = ensure();
+	if (r)
+		return r;
+	if (!summary)
+		return HD_E_ARG;
+	memset(summary, 0, sizeof *summary);
+	summary->nchunks = nchunks;
+	summary->bad_chunk = nchunks;
+	if (!stream_frame_ok(frame) || ((uintptr_t)strm & 15) || (nbytes && !strm) || nchunks >= STREAM_MAX_PARTS || (out_cap && !out) ||
+	    (nchunks && (!in_off || !in_len || !out_size || !out_off || !reach)))
+		return HD_E_ARG;
+	if (nchunks == 0) {                                           // a stream has its final block, and that is a row
+		summary->status = 1;
+		return 0;
+	}
+	hipStream_t st = (hipStream_t)stream;
+	const uint32_t trl = stream_trl(frame);
+	const uint32_t kind = frame == HD_FRAME_ZLIB ? hd::CHECK_ADLER32 : hd::CHECK_CRC32;
+	const size_t n = nchunks, ntiles = (n + hd::SCAN_TILE - 1) / hd::SCAN_TILE;
+	const uint64_t *t_in_off = (const uint64_t *)in_off, *t_out_off = (const uint64_t *)out_off;
+	const uint32_t *t_in_len = (const uint32_t *)in_len, *t_out_size = (const uint32_t *)out_size, *t_reach = (const uint32_t *)reach;
+	std::lock_guard<std::mutex> lk(g.mu_index);
+	// sum[8] | the header's [8], then where the rows end [2], the group's record [4] | scan tiles | prefix [n] | out_len, check, status [n]
+	if (g.d_stream.reserve((22 + ntiles + n) * 8 + 3 * n * 4))
+		return HD_E_NOMEM;
+	uint64_t *sum = (uint64_t *)g.d_stream.p, *ends = sum + 16, *rec = ends + 2, *tiles = rec + 4, *prefix = tiles + ntiles;
+	uint32_t *out_len = (uint32_t *)(prefix + n), *chk = out_len + n;
+	int32_t *status = (int32_t *)(chk + n);
+	uint32_t hdr = 0, refused = 0;
+	if ((r = stream_open(strm, nbytes, frame, sum + 8, st, &hdr, &refused)))
+		return r;
+	if (refused) {
+		summary->status = 1;
+		return 0;
+	}
+	// sum[4..5] as u32: the folded check | the lowest row of the table at fault | the trailer disagrees | the lowest bad row
+	uint32_t *carry = (uint32_t *)(sum + 4), *d_fault = carry + 1, *d_mismatch = carry + 2, *d_bad = carry + 3;
+	HD_CHECK(hipMemsetAsync(sum, 0, 64, st));
+	HD_CHECK(hipMemsetAsync(ends, 0, 16, st));
+	HD_CHECK(hipMemsetD32Async((hipDeviceptr_t)carry, kind == hd::CHECK_ADLER32 ? 1 : 0, 1, st));
+	HD_CHECK(hipMemsetD32Async((hipDeviceptr_t)d_fault, (int)hd::IDX_NIL, 1, st));
+	HD_CHECK(hipMemsetD32Async((hipDeviceptr_t)d_bad, (int)hd::IDX_NIL, 1, st));
+	hipLaunchKernelGGL(hd::k_stream_check_rows, dim3((nchunks + 255) / 256), dim3(256), 0, st, t_in_off, t_in_len, t_out_size, t_out_off,
+			   nchunks, (uint64_t)hdr, nbytes - trl, d_fault, ends);
+	hipLaunchKernelGGL(hd::k_carry_check_reach, dim3((nchunks + 255) / 256), dim3(256), 0, st, t_reach, t_out_off, nchunks,
+			   hd::CARRY_WINDOW, d_fault);
+	HD_CHECK(hipGetLastError());
+	uint32_t h[4] = { 0, 0, 0, 0 };
+	uint64_t e[2] = { 0, 0 };
+	HD_CHECK(hipMemcpyAsync(h, carry, 16, hipMemcpyDeviceToHost, st));
+	HD_CHECK(hipMemcpyAsync(e, ends, 16, hipMemcpyDeviceToHost, st));
+	HD_CHECK(hipStreamSynchronize(st));
+	if (h[1] != hd::IDX_NIL) {
+		summary->status = 1;
+		summary->bad_chunk = h[1];
+		return 0;
+	}
+	if (out_cap < e[1]) {
+		summary->status = 3;
+		summary->out_bytes = e[1];
+		return 0;
+	}
+	// group by group, in stream order: the check runs on in *carry, the lowest bad row in *d_bad
+	const uint64_t group_bytes = g_test_carry_group ? g_test_carry_group : HD_CARRY_GROUP_BYTES;
+	for (uint32_t r0 = 0; r0 < nchunks;) {
+		uint64_t gr[4];
+		hipLaunchKernelGGL(hd::k_carry_group, dim3(1), dim3(256), 0, st, t_out_off, t_out_size, t_reach, r0, nchunks, group_bytes, rec);
+		HD_CHECK(hipGetLastError());
+		HD_CHECK(hipMemcpyAsync(gr, rec, 32, hipMemcpyDeviceToHost, st));
+		HD_CHECK(hipMemcpyAsync(h, carry, 16, hipMemcpyDeviceToHost, st));
+		HD_CHECK(hipStreamSynchronize(st));
+		if (h[3] != hd::IDX_NIL)
+			break;                                                    // a row of an earlier group is bad: the verdict is in
+		const uint32_t r1 = (uint32_t)gr[0], nr = r1 - r0;
+		const uint64_t begin = gr[2], gbytes = gr[3] - gr[2];
+		if (gr[1] == 0) {
+			// no row of the group reaches back: the flush-rule batch inflate into place, as stream_decode_rows does it
+			if ((r = launch_inflate({ (const uint8_t *)strm, t_in_off + r0, t_in_len + r0, nr, (uint8_t *)out, t_out_off + r0,
+						  t_out_size + r0, out_len + r0, kind == hd::CHECK_ADLER32 ? nullptr : chk + r0, status + r0,
+						  g.d_ct, hd::INF_FLUSHED }, st)))
+				return r;
+			if (kind == hd::CHECK_ADLER32)
+				hipLaunchKernelGGL(hd::k_chunk_adler, dim3(nr), dim3(64), 0, st, (const uint8_t *)out, t_out_off + r0,
+						   (const uint32_t *)(out_len + r0), t_out_size + r0, nr, chk + r0);
+			hipLaunchKernelGGL(hd::k_carry_verify, dim3((nr + 255) / 256), dim3(256), 0, st, (const int32_t *)status,
+					   (const uint32_t *)out_len, t_out_size, r0, nr, d_bad);
+			if ((r = fold_launch(chk + r0, t_out_size + r0, nr, kind, tiles, prefix, sum + 1, carry, st)))
+				return r;
+		} else {
+			// the marker path: symbols | the check's pieces: off, prefix u64[np], scan tiles | len, check u32[np]
+			const uint64_t np64 = (gbytes + HD_CARRY_CHECK_PIECE - 1) / HD_CARRY_CHECK_PIECE;
+			if (np64 >= STREAM_MAX_PARTS)
+				return HD_E_NOMEM;
+			const uint32_t np = (uint32_t)np64;
+			const size_t sym_bytes = (size_t)((2 * gbytes + 15) & ~(uint64_t)15), ptiles_n = ((size_t)np + hd::SCAN_TILE - 1) / hd::SCAN_TILE;
+			if (gbytes > (uint64_t)1 << 40 || g.d_stream_slots.reserve(sym_bytes + ((size_t)np * 2 + ptiles_n) * 8 + (size_t)np * 8 + 16))
+				return HD_E_NOMEM;
+			uint16_t *sym = (uint16_t *)g.d_stream_slots.p;
+			uint64_t *poff = (uint64_t *)((uint8_t *)g.d_stream_slots.p + sym_bytes), *pprefix = poff + np, *ptiles = pprefix + np;
+			uint32_t *plen = (uint32_t *)(ptiles + ptiles_n), *pchk = plen + np;
+			CarryTimer tm(g_carry_timed);
+			tm.mark(0, st);
+			hipLaunchKernelGGL(hd::k_carry_decode, dim3(nr), dim3(64), 0, st,
+					   hd::CarryDecodeArgs{ (const uint8_t *)strm, t_in_off, t_in_len, t_out_size, t_out_off, t_reach, r0, nr, begin,
+								sym, out_len, status });
+			const hd::CarryRowsArgs ra{ sym, begin, t_out_off, t_out_size, out_len, status, r0, nr, (uint8_t *)out };
+			tm.mark(1, st);
+			hipLaunchKernelGGL(hd::k_carry_tails, dim3(1), dim3(hd::CARRY_TAIL_THREADS), 0, st, ra);
+			tm.mark(2, st);
+			hipLaunchKernelGGL(hd::k_carry_resolve, dim3(nr), dim3(256), 0, st, ra);
+			tm.mark(3, st);
+			hipLaunchKernelGGL(hd::k_carry_verify, dim3((nr + 255) / 256), dim3(256), 0, st, (const int32_t *)status,
+					   (const uint32_t *)out_len, t_out_size, r0, nr, d_bad);
+			if (np) {
+				hipLaunchKernelGGL(hd::k_carry_parts, dim3((np + 255) / 256), dim3(256), 0, st, begin, gr[3], np, poff, plen);
+				if (kind == hd::CHECK_ADLER32)
+					hipLaunchKernelGGL(hd::k_chunk_adler, dim3(np), dim3(64), 0, st, (const uint8_t *)out, (const uint64_t *)poff,
+							   (const uint32_t *)plen, (const uint32_t *)nullptr, np, pchk);
+				else
+					hipLaunchKernelGGL(hd::k_carry_crc, dim3(np), dim3(64), 0, st, (const CrcTables *)g.d_ct, (const uint8_t *)out,
+							   (const uint64_t *)poff, (const uint32_t *)plen, np, pchk);
+				if ((r = fold_launch(pchk, plen, np, kind, ptiles, pprefix, sum + 1, carry, st)))
+					return r;
+			}
+			tm.mark(4, st);
+			tm.add(g_carry_ms);
+		}
+		r0 = r1;
+	}
+	// the trailer lies behind the last row, wherever the caller's buffer ends
+	hipLaunchKernelGGL(hd::k_stream_trailer, dim3(1), dim3(64), 0, st, (const uint8_t *)strm, e[0] + trl, frame, e[1], (const uint32_t *)carry,
+			   d_mismatch);
+	HD_CHECK(hipGetLastError());
+	HD_CHECK(hipMemcpyAsync(h, carry, 16, hipMemcpyDeviceToHost, st));
+	HD_CHECK(hipStreamSynchronize(st));
+	summary->out_bytes = e[1];
+	summary->in_bytes = e[0] + trl;
+	summary->check = h[0];
+	if (h[3] != hd::IDX_NIL) {
+		summary->status = 2;
+		summary->bad_chunk = h[3];
+	} else if (h[2]) {
+		summary->status = 2;
+	}
+	return 0;
 }
 
 /* ---- host-pointer API ------------------------------------------------------ */
@@ -3045,6 +3287,52 @@ int hip_inflate_stream(unsigned char *dest, size_t *destLen, const unsigned char
 	const uint32_t *in_len = (const uint32_t *)(out_off + n), *out_size = in_len + n;
 	hipdeflate_stream_summary s;
 	if ((r = hipdeflate_stream_inflate_table_dev(g.d_in.p, xs.end_offset, frame, in_off, in_len, out_size, out_off, (uint32_t)n,
+						     g.d_packed.p, xs.out_bytes, &s, g.stream)))
+		return r;
+	if (s.status)
+		return 1;
+	if (xs.out_bytes)
+		HD_CHECK(hipMemcpy(dest, g.d_packed.p, xs.out_bytes, hipMemcpyDeviceToHost));
+	*destLen = xs.out_bytes;
+	return 0;
+}
+
+// hip_inflate_stream for a stream whose flushes carry the window: the carry index and the carry decode behind the staging
+int hip_inflate_stream_carry(unsigned char *dest, size_t *destLen, const unsigned char *source, size_t sourceLen, int frame, size_t *in_used)
+{
+	Ctx &g = cur();
+	int r = ensure();
+	if (r)
+		return r;
+	if (!destLen || (*destLen && !dest) || (sourceLen && !source) || !stream_frame_ok(frame))
+		return HD_E_ARG;
+	std::lock_guard<std::mutex> lk(g.mu);
+	if ((r = bind_device(g)))
+		return r;
+	if (g.d_in.reserve(up16(sourceLen) + 16))
+		return HD_E_NOMEM;
+	if (sourceLen)
+		HD_CHECK(hipMemcpyAsync(g.d_in.p, source, sourceLen, hipMemcpyHostToDevice, g.stream));
+	hipdeflate_stream_index_summary xs;
+	memset(&xs, 0, sizeof xs);
+	if ((r = stream_index(g, g.d_in.p, sourceLen, frame, 0, 0, nullptr, nullptr, nullptr, nullptr, &xs, g.stream, &g.d_meta, true)))
+		return r;
+	g.stream_drained(g.stream);
+	if (in_used)
+		*in_used = xs.end_offset;
+	if (xs.status)
+		return 1;
+	if (xs.out_bytes > *destLen) {
+		*destLen = xs.out_bytes;
+		return 3;
+	}
+	if (g.d_packed.reserve(up16(xs.out_bytes) + 16))
+		return HD_E_NOMEM;
+	const uint64_t n = xs.nchunks;                               // (status 0: the chain's rows, which the table's layout goes by)
+	const uint64_t *in_off = (const uint64_t *)g.d_meta.p, *out_off = in_off + n;
+	const uint32_t *in_len = (const uint32_t *)(out_off + n), *out_size = in_len + n, *reach = out_size + n;
+	hipdeflate_stream_summary s;
+	if ((r = hipdeflate_stream_inflate_carry_dev(g.d_in.p, xs.end_offset, frame, in_off, in_len, out_size, out_off, reach, (uint32_t)n,
 						     g.d_packed.p, xs.out_bytes, &s, g.stream)))
 		return r;
 	if (s.status)

@@ -71,8 +71,14 @@ struct PieceArgs {
 };
 constexpr int32_t PIECE_CUT = 4;
 constexpr uint32_t PIECE_FLUSH = 1, PIECE_FINAL = 2;
+// The carried form (k_carry_piece, hd_carry.hpp): a piece of a stream whose writer kept the window across the flush.  A
+// distance past the bytes the piece has put out is no fault then -- 32768 is DEFLATE's most, and the bytes in front of the
+// piece are another row's -- and reach[] takes the furthest one: 0 where the piece stands alone.
+struct CarryPieceArgs : PieceArgs {
+	uint32_t *reach;
+};
 
-template <bool PIECE, class Args> __device__ __forceinline__ void inflate_size_body(const Args &a)
+template <bool PIECE, class Args, bool CARRY = false> __device__ __forceinline__ void inflate_size_body(const Args &a)
 {
 	__shared__ InfSizeLds L;
 	const uint32_t lane = threadIdx.x;
@@ -106,6 +112,7 @@ template <bool PIECE, class Args> __device__ __forceinline__ void inflate_size_b
 
 	InfReader R(src, n, lane);
 	uint64_t pos = 0;                              // bytes the stream has decoded to so far (uniform)
+	[[maybe_unused]] uint32_t reach = 0;           // (carried form) the furthest a match went back over the piece's first byte
 	constexpr uint64_t POS_LIMIT = 0xffffffffull;  // the largest room a u32 table states: past it the answer is "does not fit"
 
 	// ---- window decode: the throughput decoder's, without its byte work --------------------------------------------------
@@ -153,9 +160,17 @@ template <bool PIECE, class Args> __device__ __forceinline__ void inflate_size_b
 				const uint32_t opos1 = (uint32_t)pos + (scn >> 16) + (tot & 0xffff) - s1.outlen;
 				const uint64_t far0 = __ballot(opos0 < s0.offset), far1 = __ballot(opos1 < s1.offset);
 				if ((far0 & real0 & s0.is_len) | (far1 & real1 & s1.is_len)) {
-					st_out = HD_BAD_DATA;
-					result = 2;
-					break;
+					if constexpr (CARRY) {
+						uint32_t r = max(sel(far0 & real0 & s0.is_len, s0.offset - opos0, 0u),
+								 sel(far1 & real1 & s1.is_len, s1.offset - opos1, 0u));
+						for (int o = 32; o > 0; o >>= 1)
+							r = max(r, (uint32_t)__shfl_xor((int)r, o, 64));
+						reach = max(reach, uniform(r));
+					} else {
+						st_out = HD_BAD_DATA;
+						result = 2;
+						break;
+					}
 				}
 			}
 			pos += (tot & 0xffff) + (tot >> 16);
@@ -253,7 +268,14 @@ template <bool PIECE, class Args> __device__ __forceinline__ void inflate_size_b
 				R.drop(d & 15);
 				const uint32_t offset = (d >> 16) + ((uint32_t)R.bb & ((1u << deb) - 1));
 				R.drop(deb);
-				if (offset > pos) { st = HD_BAD_DATA; break; }       // decompress_template.h:724
+				if (offset > pos) {                                  // decompress_template.h:724
+					if constexpr (CARRY) {
+						reach = max(reach, offset - (uint32_t)pos);
+					} else {
+						st = HD_BAD_DATA;
+						break;
+					}
+				}
 				pos += length;
 			}
 			if (st != HD_OK)
@@ -276,6 +298,8 @@ template <bool PIECE, class Args> __device__ __forceinline__ void inflate_size_b
 			a.in_used[b] = st == HD_OK ? (uint32_t)((R.consumed_bits() + 7) >> 3) : 0u;
 			a.status[b] = st;
 			a.stop[b] = st == HD_OK ? stop : 0u;
+			if constexpr (CARRY)
+				a.reach[b] = st == HD_OK ? reach : 0u;
 		}
 	} else {
 		if (st == HD_OK && R.consumed_bits() > 8 * (int64_t)n)

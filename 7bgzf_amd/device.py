@@ -272,6 +272,61 @@ def inflate_stream_auto(stream, frame=_pkg.FRAME_GZIP):
     return out, x
 
 
+def index_stream_carry_call(stream, frame, max_chunks, max_chunk_in, in_off, in_len, out_size, out_off, reach):
+    """one hipdeflate_stream_index_carry_dev: index_stream_call with the reach table (int32 tensor of max_chunks entries)
+    -> StreamIndexSummary"""
+    summary = _pkg.StreamIndexSummary()
+    rc = _pkg.lib().hipdeflate_stream_index_carry_dev(_ptr(stream), stream.numel(), frame, max_chunks, max_chunk_in, _ptr(in_off),
+                                                      _ptr(in_len), _ptr(out_size), _ptr(out_off), _ptr(reach),
+                                                      ctypes.byref(summary), _stream())
+    _pkg._check(rc, "hipdeflate_stream_index_carry_dev")
+    return summary
+
+
+def index_stream_carry(stream, frame=_pkg.FRAME_GZIP, max_chunks=None, max_chunk_in=0):
+    """index_stream for a stream whose flushes carry the window -> (in_off, in_len, out_size, out_off, reach,
+    StreamIndexSummary); indexed again on tables of the stream's size where the first ones are too small (status 3)"""
+    dev = stream.device
+
+    def run(n):
+        t = (torch.zeros(n, dtype=torch.int64, device=dev), torch.zeros(n, dtype=torch.int32, device=dev),
+             torch.zeros(n, dtype=torch.int32, device=dev), torch.zeros(n, dtype=torch.int64, device=dev),
+             torch.zeros(n, dtype=torch.int32, device=dev))
+        return t + (index_stream_carry_call(stream, frame, n, max_chunk_in, *t),)
+
+    if max_chunks is not None:
+        return run(max_chunks)
+    r = run(stream.numel() // 64 + 16)
+    return run(r[5].nchunks) if r[5].status == 3 else r
+
+
+def inflate_stream_carry_call(stream, frame, in_off, in_len, out_size, out_off, reach, nchunks, out, out_cap):
+    """one hipdeflate_stream_inflate_carry_dev -> StreamSummary"""
+    summary = _pkg.StreamSummary()
+    rc = _pkg.lib().hipdeflate_stream_inflate_carry_dev(_ptr(stream), stream.numel(), frame, _ptr(in_off), _ptr(in_len),
+                                                        _ptr(out_size), _ptr(out_off), _ptr(reach), nchunks, _ptr(out), out_cap,
+                                                        ctypes.byref(summary), _stream())
+    _pkg._check(rc, "hipdeflate_stream_inflate_carry_dev")
+    return summary
+
+
+def inflate_stream_carry(stream, frame=_pkg.FRAME_GZIP):
+    """inflate_stream_auto for a stream whose flushes carry the window (pigz, zlib's Z_SYNC_FLUSH) -> (uint8 tensor of its
+    contents, StreamIndexSummary): the carry index, one allocation, the rows decoded side by side and held to the trailer"""
+    in_off, in_len, out_size, out_off, reach, x = index_stream_carry(stream, frame)
+    if x.status:
+        why = {1: "a piece does not decode, or the header is refused", 2: "the stream is cut"}
+        raise _pkg.HipDeflateError("stream index: %s at offset %d (status %d, %d chunks)" % (why.get(x.status, "?"), x.end_offset,
+                                                                                            x.status, x.nchunks))
+    out = torch.empty(x.out_bytes, dtype=torch.uint8, device=stream.device)
+    s = inflate_stream_carry_call(stream, frame, in_off, in_len, out_size, out_off, reach, x.nchunks, out, x.out_bytes)
+    if s.status:
+        why = {1: "a bad table", 2: "a chunk or the check disagrees", 3: "room too small"}
+        raise _pkg.HipDeflateError("stream decode: %s (status %d, bad_chunk %d of %d)" % (why.get(s.status, "?"), s.status,
+                                                                                         s.bad_chunk, s.nchunks))
+    return out, x
+
+
 def check_combine(check, lens, kind=_pkg.CHECK_CRC32):
     """the CRC-32 (kind 0) / Adler-32 (kind 1) of a concatenation from the checks and lengths of its parts: int32 device
     tensors holding the bits of the u32 values -> int"""

@@ -515,6 +515,63 @@ int hipdeflate_stream_inflate_table_dev(const void *strm, uint64_t nbytes, int f
  * small, *destLen = the need.  *in_used (may be NULL) = the index's end_offset: with 0 and 3 the first byte behind the trailer. */
 int hip_inflate_stream(unsigned char *dest, size_t *destLen, const unsigned char *source, size_t sourceLen, int frame,
 		       size_t *in_used);
+/* ---- ... and a stream whose flushes CARRY the window: pigz, zlib's Z_SYNC_FLUSH ----------------------
+ * The writers people have -- pigz in its default mode, every zlib writer that calls deflate(Z_SYNC_FLUSH), a dictzip-like
+ * writer that did not reset the window -- end a chunk in the same empty stored block, but the next chunk's matches reach
+ * into the 32 KiB in front of it.  The index above stops at the first such chunk (status 1).  The two calls below decode
+ * such a stream side by side all the same, by the two-pass marker method of pugz / rapidgzip.
+ *
+ * hipdeflate_stream_index_carry_dev is hipdeflate_stream_index_dev -- the same method, candidates, summary, max_chunk_in and
+ * header rules -- with one more table, reach (u32[max_chunks]): reach[i] = the furthest a match of row i goes back over the
+ * row's first byte, 0 for a row that stands alone, 32768 at the most.  A distance past the bytes a piece has put out is no
+ * longer a reason not to decode it (no distance is bad by itself: 32768 is DEFLATE's most); instead, behind the chain and
+ * the prefix sum, the first row of the table with reach[i] > out_off[i] -- it reaches back over the start of the stream --
+ * ends the chain: status 1, end_offset = in_off[i], nchunks = i, out_bytes = out_off[i], and the rows in front stay
+ * usable.  A stream whose first token reaches back is status 1 with nchunks 0, as before.  With more rows than max_chunks
+ * the reach rule is applied to the rows in the table only: a row there that breaks it gives the verdict just stated, and
+ * otherwise the answer is status 3 with nchunks = the chain's length, as above -- a second call with a table of that size
+ * gives the final verdict.  On every stream for which hipdeflate_stream_index_dev answers status 0 this call answers the
+ * same summary and the same four tables, with reach all 0. */
+int hipdeflate_stream_index_carry_dev(const void *strm, uint64_t nbytes, int frame, uint32_t max_chunks, uint32_t max_chunk_in,
+				      void *in_off /* u64 */, void *in_len /* u32 */, void *out_size /* u32 */, void *out_off /* u64 */,
+				      void *reach /* u32 */, hipdeflate_stream_index_summary *summary /* HOST */, void *stream);
+/* The decode on such a table: hipdeflate_stream_inflate_table_dev with the reach column, the same summary and statuses, in
+ * this order:
+ *   status 1  everything hipdeflate_stream_inflate_table_dev answers status 1 for; or reach[i] > 32768 or reach[i] >
+ *             out_off[i].  bad_chunk = the lowest row at fault by either rule.  Nothing is decoded.
+ *   status 3  out_cap < out_off[n-1] + out_size[n-1]; out_bytes is that need.  Nothing is decoded.
+ *   status 2  bad_chunk = i: row i does not decode by the flush rule, is not out_size[i] long, or reaches further back than
+ *             reach[i] says; bad_chunk = nchunks: every row is fine but the folded check, or the gzip ISIZE, disagrees with
+ *             the trailer.
+ * The table is a hint that is checked, never trusted: a row writes at most out_size[i] bytes at out_off[i], and names a
+ * byte in front of itself only within reach[i], which the check has held to the bytes the stream has there.  The rows are
+ * taken in GROUPS, in stream order: the consecutive rows whose out_off lies in the same multiple of HD_CARRY_GROUP_BYTES
+ * (hipdeflate_params.h; a row is never split), the largest reach of a group taken on the device, one small record per
+ * group read by the host.  A group in which no row reaches back goes through the flush-rule batch inflate into place
+ * exactly as hipdeflate_stream_inflate_table_dev does it -- a plain single-member .gz and every full-flush stream take
+ * only this path, and it needs no scratch.  Any other group takes three launches, none of which waits for another
+ * workgroup: every row decoded by one wavefront into 16-bit SYMBOLS (a byte, or "the byte this far in front of my start");
+ * one workgroup that walks the rows in order with the running 32 KiB window in LDS and makes every row's last 32 KiB
+ * final; all rows side by side turning the rest of their symbols into bytes.  The CRC-32 (RAW, GZIP) / Adler-32 (ZLIB) of
+ * such a group is taken from its bytes in pieces of HD_CARRY_CHECK_PIECE behind the third launch, and folded; the check
+ * runs on from group to group.  Scratch: 2 bytes per output byte of the largest group that takes the marker path, the
+ * library's, grow-only; HD_E_NOMEM if it cannot grow.  With status 2 the bytes of out are unspecified, and groups behind
+ * the bad row's may not have been decoded.  strm 16-byte aligned, out of any alignment.  Returns 0 whenever the call ran.
+ * (Synchronises the stream, once a group; takes turns as the index does.) */
+int hipdeflate_stream_inflate_carry_dev(const void *strm, uint64_t nbytes, int frame,
+					const void *in_off, const void *in_len, const void *out_size, const void *out_off,
+					const void *reach, uint32_t nchunks, void *out, uint64_t out_cap,
+					hipdeflate_stream_summary *summary /* HOST */, void *stream);
+/* host-buffer form: hip_inflate_stream with the carry index and the carry decode; the same arguments and return values */
+int hip_inflate_stream_carry(unsigned char *dest, size_t *destLen, const unsigned char *source, size_t sourceLen, int frame,
+			     size_t *in_used);
+/* test entry: the group size of hipdeflate_stream_inflate_carry_dev in bytes (0 restores HD_CARRY_GROUP_BYTES), so that a
+ * stream of a few hundred KiB walks several groups; the decoded bytes do not depend on it */
+void hipdeflate_test_carry_group(uint64_t bytes);
+/* test entry: ms4[0..3] = the milliseconds the marker path's passes -- decode, tails, resolve, check and fold -- took since
+ * the last call, by events around their launches (one more wait per group while it is on); the call turns the timing on,
+ * NULL turns it off */
+void hipdeflate_test_carry_times(double *ms4);
 /* the fold on its own: check[] / len[] device arrays of n parts (u32 each, n < 2^31), kind 0 = CRC-32, 1 = Adler-32; *result HOST.
  * The check of the concatenation of the parts from the parts' own: the role of crc_append (the hosts' serial fold, after
  * zlib's crc32_combine) with one lane per part -- part i contributes check[i] moved over the S_i bytes behind it, S_i a

@@ -211,6 +211,12 @@
  * level) each -- total at most this much, so that the scratch of the call does not grow with the input */
 #define HD_STREAM_WINDOW_BYTES (1u << 30)
 
+/* hipdeflate_stream_inflate_carry_dev: the rows are decoded in GROUPS, the consecutive rows whose out_off lies in the same
+ * multiple of this many bytes (a row is never split), so that the symbol scratch -- 2 bytes per output byte of the largest
+ * group -- does not grow with the stream; and the check of a group's bytes is taken in pieces of HD_CARRY_CHECK_PIECE */
+#define HD_CARRY_GROUP_BYTES   (256u << 20)
+#define HD_CARRY_CHECK_PIECE   (64u << 10)
+
 /* result codes of the inflate path = enum libdeflate_result
  * (lib/libdeflate/libdeflate.h:193-208), which libdeflate_inflate
  * (lib/zlibutil.c:194-204) hands straight back to the applet */
