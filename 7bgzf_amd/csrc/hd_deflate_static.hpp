@@ -14,7 +14,9 @@
 //   (conflicts inside a step are re-written until the largest position holds the
 //   slot); candidates are verified against the LDS ring window, 8 bytes per lane;
 //   the greedy choice of token starts is a DPP prefix scan over 8-state
-//   transition functions (two v_perm_b32 per composition); the rare matches whose
+//   transition functions (two v_perm_b32 per composition; every lane's function is
+//   elementary -- the lanes the last step's match covers are literals -- so the
+//   scan's first three stages shift one dword, not two); the rare matches whose
 //   8 bytes all agree are extended cooperatively, 64 bytes per ballot; the step's
 //   tokens are compacted into a queue -- a register, filled by a cross-lane push
 //   whose result joins it one step later, so that no step waits for it --
@@ -826,10 +828,13 @@ __global__ __launch_bounds__(64) void k_deflate_static(DeflateArgs a)
 		}
 		uint64_t starts;
 		{
-			// fn8_make: {a, 0, 1, 2 | 3, 4, 5, 6} with a = jump - 1, the identity on covered lanes
+			// fn8_make: {a, 0, 1, 2 | 3, 4, 5, 6} with a = jump - 1; the lanes the last match covers are literals
+			// (a = 0), not the identity: state 0 enters lane 0 and a literal hands it on, so the first live lane sees
+			// 0 either way and livem masks the covered lanes' own "starts" below.  Every map being elementary, the
+			// upper dword is one constant for the wave and the scan's first three stages know theirs (Fn8Ident)
 			Fn8 f;
-			f.lo = sel(livem, jumpA + 0x0200ffffu, 0x03020100u);
-			f.hi = sel(livem, 0x06050403u, 0x07060504u);
+			f.lo = sel(livem, jumpA + 0x0200ffffu, 0x02010000u);
+			f.hi = 0x06050403u;
 			const uint32_t w0 = fn8_scan_state0(f, fid, fcross);
 			// state entering lane l = (f_{l-1} o ... o f_0)(0): byte 0 of lane l-1, and 0 enters lane 0 -- the mask of
 			// "a state other than 0 behind the lane", one lane up, in scalar registers: the shift brings in the 0 that

@@ -117,6 +117,17 @@ struct Fn8 {
 // that is the identity exactly on those lanes: mov_dpp + or fold into one
 // v_or_b32_dpp, where seeding the destination with the identity would cost an
 // extra v_mov per dword and stage.
+//
+// fn8_scan_state0 is fed elementary maps only (every lane {a,0,1,2 | 3,4,5,6}: the caller makes the lanes the last
+// step's match covers literals, not the identity -- state 0 enters lane 0 and a literal hands 0 on).  A composite F of
+// k elementary maps has F(r) = r - k for every r >= k, so while k <= 4 its upper dword is {4-k, 5-k, 6-k, 7-k} whatever
+// the data.  In front of the stage that shifts by d = 1, 2, 4 a lane of row position r covers min(r + 1, d) lanes, so
+// the upper dword that stage would fetch from row position r - d covers k = min(r - d + 1, d) of them (r < d: no source,
+// k = 0, the identity): a function of the lane number alone.  hi[0..2] hold that whole selector, and the three stages
+// issue no DPP instruction for the upper dword.  hi[3] (row_shr:8 shifts maps of 8 lanes: data) is the OR constant.
+// (In the stages that shift by 1 and 2 the upper-dword LOOKUP yields a lane constant as well -- its result covers
+// min(r + 1, 2 d) <= 4 lanes -- and could go for two more instructions a step; the listing tests hold a scan to its
+// eleven v_perm_b32, so they stay: the named follow-up)
 struct Fn8Ident {
 	uint32_t lo[4], hi[4];          // per in-row scan stage
 	__device__ __forceinline__ void init(uint32_t lane)
@@ -124,10 +135,16 @@ struct Fn8Ident {
 		const uint32_t r = lane & 15;
 		const bool none[4] = { r < 1, r < 2, r < 4, r < 8 };
 #pragma unroll
-		for (int k = 0; k < 4; k++) {
+		for (int k = 0; k < 4; k++)
 			lo[k] = none[k] ? 0x03020100u : 0u;
-			hi[k] = none[k] ? 0x07060504u : 0u;
-		}
+		// lanes the shifted map covers: 0 where the stage has no source
+		const uint32_t k0 = r < 1 ? 0u : 1u;
+		const uint32_t k1 = r < 2 ? 0u : r < 3 ? 1u : 2u;
+		const uint32_t k2 = r < 4 ? 0u : r < 7 ? r - 3 : 4u;
+		hi[0] = 0x07060504u - 0x01010101u * k0;
+		hi[1] = 0x07060504u - 0x01010101u * k1;
+		hi[2] = 0x07060504u - 0x01010101u * k2;
+		hi[3] = none[3] ? 0x07060504u : 0u;
 	}
 };
 
@@ -137,6 +154,16 @@ __device__ __forceinline__ Fn8 fn8_dpp(Fn8 v, uint32_t id_lo, uint32_t id_hi)
 	Fn8 r;
 	r.lo = dpp0<CTRL, ROW_MASK, 0xf>(v.lo) | id_lo;
 	r.hi = dpp0<CTRL, ROW_MASK, 0xf>(v.hi) | id_hi;
+	return r;
+}
+
+// ... of elementary maps, shifted by 1, 2 or 4 lanes: the upper dword is the lane's constant (Fn8Ident), not fetched
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ Fn8 fn8_dpp_lo(Fn8 v, uint32_t id_lo, uint32_t sel_hi)
+{
+	Fn8 r;
+	r.lo = dpp0<CTRL, ROW_MASK, 0xf>(v.lo) | id_lo;
+	r.hi = sel_hi;
 	return r;
 }
 
@@ -175,7 +202,8 @@ struct Fn8Cross {
 };
 
 // inclusive scan for a caller that reads only byte 0 of the composed map: byte 0 of the result at lane l is
-// (f_l o ... o f_0)(0), the state BEHIND lane l; the other bytes mean nothing
+// (f_l o ... o f_0)(0), the state BEHIND lane l; the other bytes mean nothing.  Every lane's map must be elementary
+// ({a,0,1,2 | 3,4,5,6}, never the identity): the first three stages take the shifted upper dword from Fn8Ident
 // Wait states: a DPP instruction that reads a VGPR the vector instruction in front of it wrote needs two, and inside an
 // asm statement the compiler adds none: s_nop 1 stands in front of the first stage's moves (the v_perm_b32 that wrote
 // their source may be the instruction straight in front of the statement), and the second stage's source has one
@@ -183,10 +211,10 @@ struct Fn8Cross {
 // (One statement for both stages: the compiler pads the end of every statement with a wait state of its own.)
 __device__ __forceinline__ uint32_t fn8_scan_state0(Fn8 w, const Fn8Ident &id, const Fn8Cross &x)
 {
-	w = fn8_compose(w, fn8_dpp<0x111, 0xf>(w, id.lo[0], id.hi[0]));   // row_shr:1
-	w = fn8_compose(w, fn8_dpp<0x112, 0xf>(w, id.lo[1], id.hi[1]));   // row_shr:2
-	w = fn8_compose(w, fn8_dpp<0x114, 0xf>(w, id.lo[2], id.hi[2]));   // row_shr:4
-	w = fn8_compose(w, fn8_dpp<0x118, 0xf>(w, id.lo[3], id.hi[3]));   // row_shr:8
+	w = fn8_compose(w, fn8_dpp_lo<0x111, 0xf>(w, id.lo[0], id.hi[0]));   // row_shr:1
+	w = fn8_compose(w, fn8_dpp_lo<0x112, 0xf>(w, id.lo[1], id.hi[1]));   // row_shr:2
+	w = fn8_compose(w, fn8_dpp_lo<0x114, 0xf>(w, id.lo[2], id.hi[2]));   // row_shr:4
+	w = fn8_compose(w, fn8_dpp<0x118, 0xf>(w, id.lo[3], id.hi[3]));      // row_shr:8
 	// r = w o (w of lane 15 of the row below; rows 0, 2: identity); out = low dword of r o (r of lane 31; rows 0, 1: identity)
 	uint32_t rl, rh, out;
 	asm("s_nop 1\n\t"

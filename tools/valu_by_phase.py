@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Static instruction counts of the level-1 kernel's 16-step group loop, per 64-byte step and by phase.
 
-  python3 tools/valu_by_phase.py > profiles/r11_l1_valu_by_phase.json
+  python3 tools/valu_by_phase.py > profiles/r13_l1_valu_by_phase.json
 
 hipcc -S -gline-tables-only gives every instruction its source line; the lines are mapped to the phases of
 7bgzf_amd/csrc/hd_deflate_static.hpp (fetch / probe / verify / scan / long matches / queue / emit / refill + CRC).
@@ -150,10 +150,10 @@ def main():
                               "asm statement and are counted in the phase above, with the step's entry test and the loop the compiler keeps round the "
                               "block (s_cmp_lg_u64 + branch).  Run: 1.42 events per step on the FASTQ-like set (twin count), 1.14 hops of the walk per event; "
                               "measured as the PMC figures per step minus the weighted sum of the other phases")
-    out["measured_pmc_per_step"] = ("the parent of this kernel (profiles/r11_l1_pipe_busy_before.json; tools/pmc_quick.sh, one counter pass per run, no tracing beside it): "
-                                    "VALU 93.91, SALU 60.32, branch 14.91, LDS 10.83; wave cycles 506.3 (x4 clocks); vector pipe active 96.59 quad-cycles per step = "
-                                    "91 % of the kernel's cycles per SIMD, scalar pipe 60.33 = 57 %.  The build with items 2a and 2c on top of this kernel (DESIGN.md 6e), in the same way: VALU 88.94, SALU 59.67, "
-                                    "branch 14.91, LDS 10.83, wave cycles 495.6")
+    out["measured_pmc_per_step"] = ("this kernel and its parent (profiles/r13_l1_pipe_busy.json; tools/pmc_quick.sh, one counter pass per build, no tracing beside it): "
+                                    "VALU 85.92 (parent 89.91), SALU 60.33 (60.32), branch 14.91, LDS 10.83; wave cycles 483.1 (496.6; x4 clocks); vector pipe active "
+                                    "88.60 quad-cycles per step = 88 % of the kernel's cycles per SIMD (parent 92.59 = 89 %), scalar pipe 60.34 = 60 %.  "
+                                    "Before the scan lost its seeds (0d233da, profiles/r11_l1_pipe_busy_before.json): VALU 93.91, wave cycles 506.3, vector pipe 91 %")
     out["sum_static_all_paths_per_step"] = {k: round(v, 1) for k, v in sorted(tot.items())}
     out["sum_weighted_by_frequency_per_step"] = {k: round(v, 1) for k, v in sorted(wtot.items())}
     json.dump(out, sys.stdout, indent=1)
