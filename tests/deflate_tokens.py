@@ -6,7 +6,9 @@ position of each.  Stored blocks keep their length; an empty stored block that i
 point (the 00 00 ff ff marker of a full or sync flush), and `Stream.flushes` lists them.
 
 It shares nothing with the oracle (oracle/hd_inflate.c), the CPU twin or the kernels: it is the second reader the
-encode contracts (encode_contracts.py) stand on.
+encode contracts (encode_contracts.py) stand on.  Which codes it takes is restated from the oracle's build_code() (`_table`);
+the forms only libdeflate decodes -- its symbols, its one-symbol codes read from either bit -- are read with `wide=True` alone.  tests/test_index_models_vs_oracle.py holds the index
+models built on `_table` and `_dynamic_header` to the oracle's verdicts.
 """
 from deflate_gen import DIST_BASE, DIST_EXTRA, LEN_BASE, LEN_EXTRA, PRECODE_ORDER, STATIC_DIST, STATIC_LIT, rev
 
@@ -56,12 +58,14 @@ class Stream:
         return [m for b in self.blocks for m in b.matches()]
 
 
-def _table(lens):
-    """decode table of a code: index = the next `maxl` stream bits (LSB first) -> (symbol << 4) | length;
-    -1 where no codeword is assigned (an incomplete code)"""
+def _table(lens, either_bit=False):
+    """decode table of a code: index = the next `maxl` stream bits (LSB first) -> (symbol << 4) | length; -1 where no
+    codeword is assigned.  An over-subscribed code is refused; so is an incomplete one, but for the empty code and the code
+    of a single 1-bit codeword.  either_bit: those two as oracle/hd_inflate.c build_code() has them -- one symbol (0 for the
+    empty code) from either value of one bit; without it the unused value has no codeword, as RFC 1951 and zlib have it."""
     maxl = max(lens) if any(lens) else 0
     if maxl == 0:
-        return [], 0
+        return ([(0 << 4) | 1] * 2 if either_bit else [-1, -1]), 1
     t = [-1] * (1 << maxl)
     nxt, code, cnt = {}, 0, [0] * 16
     for l in lens:
@@ -70,6 +74,11 @@ def _table(lens):
     used = sum(c << (15 - l) for l, c in enumerate(cnt) if l)
     if used > 1 << 15:
         raise DeflateError("over-subscribed code")
+    if used < 1 << 15:
+        if used != 1 << 14 or cnt[1] != 1:
+            raise DeflateError("incomplete code")
+        e = (list(lens).index(1) << 4) | 1
+        return [e, e if either_bit else -1], 1
     for b in range(1, 16):
         code = (code + cnt[b - 1]) << 1
         nxt[b] = code
@@ -119,16 +128,18 @@ class _Bits:
         return e >> 4
 
 
-def _dynamic_header(bits, blk):
+def _dynamic_header(bits, blk, oracle=False):
+    """oracle: the oracle's rules alone -- none for a litlen code without an end-of-block codeword (such a block never ends:
+    its reader runs out of input), an empty precode is a code like the others, and the one-symbol codes decode from either bit"""
     hlit = bits.get(5) + 257
     hdist = bits.get(5) + 1
     hclen = bits.get(4) + 4
     pre = [0] * 19
     for k in range(hclen):
         pre[PRECODE_ORDER[k]] = bits.get(3)
-    pt, pm = _table(pre)
-    if not pm:
+    if not oracle and not any(pre):
         raise DeflateError("empty precode")
+    pt, pm = _table(pre, oracle)
     seq = []
     while len(seq) < hlit + hdist:
         s = bits.sym(pt, pm)
@@ -146,14 +157,19 @@ def _dynamic_header(bits, blk):
         raise DeflateError("code-length repeat runs past HLIT + HDIST")
     blk.hlit, blk.hdist, blk.hclen = hlit, hdist, hclen
     blk.pre_lens, blk.lit_lens, blk.dist_lens = pre, seq[:hlit], seq[hlit:]
-    if blk.lit_lens[256] == 0:
+    if not oracle and blk.lit_lens[256] == 0:
         raise DeflateError("no end-of-block code")
-    return _table(blk.lit_lens), _table(blk.dist_lens)
+    off = _table(blk.dist_lens, oracle)                # the offset code first, as the oracle builds them
+    return _table(blk.lit_lens, oracle), off
 
 
-def read(stream, expand=True, stop_at_final=True):
+def read(stream, expand=True, stop_at_final=True, wide=False):
     """-> Stream.  Decodes until a final block, or (stop_at_final False, or no final block) until the bytes run
-    out on a block end.  expand: also rebuild the output (Stream.out), byte by byte for overlapping copies."""
+    out on a block end.  expand: also rebuild the output (Stream.out), byte by byte for overlapping copies.
+    wide: also the forms only libdeflate (and so the oracle) decodes -- litlen symbols 286 / 287 as length 258, offset
+    symbols 30 / 31 as 24577 + 13 bits, a match through the empty offset code as offset symbol 0, the unused bit value of
+    a one-codeword code, a litlen code without end-of-block; without it they are refused, as RFC 1951 has them and as no
+    encoder may write them."""
     bits = _Bits(stream)
     out = bytearray()
     nout = 0
@@ -188,7 +204,7 @@ def read(stream, expand=True, stop_at_final=True):
             if btype == 1:
                 (lt, lm), (dt, dm) = _static_tables()
             else:
-                (lt, lm), (dt, dm) = _dynamic_header(bits, blk)
+                (lt, lm), (dt, dm) = _dynamic_header(bits, blk, oracle=wide)
             P, L, V = blk.pos, blk.length, blk.value
             sym = bits.sym
             while True:
@@ -203,14 +219,14 @@ def read(stream, expand=True, stop_at_final=True):
                     continue
                 if s == 256:
                     break
-                if s > 285:
+                if s > (287 if wide else 285):
                     raise DeflateError("litlen symbol %d" % s)
                 k = s - 257
                 length = LEN_BASE[k] + bits.get(LEN_EXTRA[k])
-                if not dm:
+                if not wide and blk.dist_lens is not None and not any(blk.dist_lens):
                     raise DeflateError("match in a block with no offset code")
                 ds = sym(dt, dm)
-                if ds > 29:
+                if ds > (31 if wide else 29):
                     raise DeflateError("offset symbol %d" % ds)
                 d = DIST_BASE[ds] + bits.get(DIST_EXTRA[ds])
                 if d > nout:

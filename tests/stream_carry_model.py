@@ -3,7 +3,8 @@ window"): stream_index_model with the window carried across the flush points.
   * piece(): stream_index_model.piece without its `d > nout` refusal, and with the furthest distance over the piece's first
     byte kept as its reach;
   * index_carry(): the chain, the five tables, the reach rule and its clause for a table that is too small;
-  * decode_carry(): the verdicts in the header's order; the bytes through ONE zlib.decompressobj over the stream;
+  * decode_carry(): the verdicts in the header's order; the bytes through ONE zlib.decompressobj over the stream (the
+    caller's own where zlib refuses the form);
   * two writers of such streams, and a composer for hand-built rows with chosen (length, distance) tokens.
 No GPU, no product code.  tests/test_stream_carry_model.py holds it to zlib."""
 import zlib
@@ -52,7 +53,7 @@ def piece(stream, p, n):
                     (lt, lm), (dt, dm) = _static_tables()
                 else:
                     try:
-                        (lt, lm), (dt, dm) = _dynamic_header(bits, blk)
+                        (lt, lm), (dt, dm) = _dynamic_header(bits, blk, oracle=True)
                     except DeflateError:
                         return fail(CUT if bits.over else BAD)
                     if bits.over:
@@ -66,15 +67,9 @@ def piece(stream, p, n):
                         continue
                     if s == 256:
                         break
-                    if s > 285:
-                        return fail(BAD)
-                    k = s - 257
+                    k = s - 257                              # (286, 287: length 258, as the oracle has them)
                     length = LEN_BASE[k] + bits.get(LEN_EXTRA[k])
-                    if not dm:
-                        return fail(CUT if bits.over else BAD)
-                    ds = bits.sym(dt, dm)
-                    if ds > 29:
-                        return fail(CUT if bits.over else BAD)
+                    ds = bits.sym(dt, dm)                    # (the empty code: symbol 0; 30, 31: 24577 + 13 bits)
                     d = DIST_BASE[ds] + bits.get(DIST_EXTRA[ds])
                     if bits.over:
                         return fail(CUT)
@@ -156,9 +151,11 @@ def row(stream, p, n):
             return nout, reach
 
 
-def decode_carry(stream, frame, in_off, in_len, out_size, out_off, reach, out_cap=None):
+def decode_carry(stream, frame, in_off, in_len, out_size, out_off, reach, out_cap=None, plain=None):
     """what hipdeflate_stream_inflate_carry_dev answers -> (summary as a dict, output or None).  summary["check"] is None
-    where the header leaves it unspecified (a bad row) or nothing was decoded."""
+    where the header leaves it unspecified (a bad row) or nothing was decoded.  plain: the bytes of the rows by the
+    caller's own reference (deflate_gen.expand of the token lists), taken where zlib refuses a row -- the forms only
+    libdeflate decodes -- and held to zlib's where it does not."""
     stream, n = bytes(stream), len(in_off)
     trl = TRAILER[frame]
 
@@ -189,8 +186,13 @@ def decode_carry(stream, frame, in_off, in_len, out_size, out_off, reach, out_ca
             return verdict(2, i, total, used), None
     # every row decodes to its size within its reach, and no reach goes over the start of the stream: the rows' bytes are
     # those of one inflate over them
-    d = zlib.decompressobj(-15)
-    out = b"".join(d.decompress(stream[in_off[i]:in_off[i] + in_len[i]]) for i in range(n))
+    try:
+        d = zlib.decompressobj(-15)
+        out = b"".join(d.decompress(stream[in_off[i]:in_off[i] + in_len[i]]) for i in range(n))
+        assert plain is None or out == bytes(plain[:total])
+    except zlib.error:
+        assert plain is not None, "rows zlib refuses: the caller states their bytes"
+        out = bytes(plain[:total])
     assert len(out) == total
     t = stream[used - trl:used]
     ok = True

@@ -89,7 +89,7 @@ def piece(stream, p, n):
                     (lt, lm), (dt, dm) = _static_tables()
                 else:
                     try:
-                        (lt, lm), (dt, dm) = _dynamic_header(bits, blk)
+                        (lt, lm), (dt, dm) = _dynamic_header(bits, blk, oracle=True)
                     except DeflateError:
                         return fail(CUT if bits.over else BAD)
                     if bits.over:
@@ -103,15 +103,9 @@ def piece(stream, p, n):
                         continue
                     if s == 256:
                         break
-                    if s > 285:
-                        return fail(BAD)
-                    k = s - 257
+                    k = s - 257                              # (286, 287: length 258, as the oracle has them)
                     length = LEN_BASE[k] + bits.get(LEN_EXTRA[k])
-                    if not dm:
-                        return fail(CUT if bits.over else BAD)
-                    ds = bits.sym(dt, dm)
-                    if ds > 29:
-                        return fail(CUT if bits.over else BAD)
+                    ds = bits.sym(dt, dm)                    # (the empty code: symbol 0; 30, 31: 24577 + 13 bits)
                     d = DIST_BASE[ds] + bits.get(DIST_EXTRA[ds])
                     if bits.over:
                         return fail(CUT)

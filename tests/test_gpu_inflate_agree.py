@@ -17,6 +17,8 @@ and tiny blocks, a header behind a 258-byte match; faults: every reject rule onc
 lengths and distances at every boundary, a distance of exactly the bytes out and one more; libdeflate_only: the symbols
 286 / 287 / 30 / 31).  Every decoder must give every stream the same status; where that is OK, the same output size --
 the generator's -- and, from the two that report it, the same bytes consumed: the whole stream.
+(The piece decoders of the stream indexes, k_inflate_piece and k_carry_piece, and the carry decoder k_carry_decode are held to
+the same streams in tests/test_gpu_carry_rows.py, through models that tests/test_index_models_vs_oracle.py pins to the oracle.)
 
 The size pass takes no room.  A stream that the others refuse for the room alone (cap_over_on_*: HD_INSUFFICIENT_SPACE one
 byte short) it must size as OK, at exactly one byte more than that room -- the same finding from the other side."""

@@ -24,16 +24,11 @@ import deflate_gen as dg
 import hdtest
 import stream_carry_model as cm
 import stream_index_model as m
+from carry_dev import FRAMES, GZIP, RAW, ZLIB, X_FIELDS, both, decode_check, fields, index_check, to_dev
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 64
-SENT = 0xa5
-RAW, ZLIB, GZIP = m.FRAME_RAW, m.FRAME_ZLIB, m.FRAME_GZIP
-FRAMES = (RAW, ZLIB, GZIP)
 WRITERS = (cm.sync_writer, cm.pigz_writer)
-X_FIELDS = ("nchunks", "out_bytes", "end_offset", "ncandidates", "hdr_bytes", "status")
-S_FIELDS = ("out_bytes", "in_bytes", "bad_chunk", "nchunks", "check", "status")
 W = cm.WINDOW
 
 
@@ -71,71 +66,6 @@ def text(n, seed=11):
         _text[seed] = cm.words(np.random.default_rng(seed), 320000)
     assert n <= len(_text[seed])
     return _text[seed][:n]
-
-
-def to_dev(torch, blob):
-    return torch.from_numpy(np.frombuffer(bytes(blob) + bytes(16), dtype=np.uint8).copy()).cuda()[:len(blob)]
-
-
-def u32(torch, values):
-    return torch.from_numpy(np.array([int(v) for v in values], dtype=np.uint32).view(np.int32).copy()).cuda()
-
-
-def u64(torch, values):
-    return torch.from_numpy(np.array([int(v) for v in values], dtype=np.uint64).view(np.int64).copy()).cuda()
-
-
-def fields(s, names):
-    return {f: getattr(s, f) for f in names}
-
-
-def index_check(torch, dev, stream, frame, max_chunks=None, max_chunk_in=0):
-    """one hipdeflate_stream_index_carry_dev held to the model: the summary, the rows of the five tables, and a sentinel row
-    either side of each -> the model's answer.  (Rows behind the one that ended the chain are not looked at.)"""
-    want = cm.index_carry(stream, frame, max_chunks, max_chunk_in)
-    rows = len(want[1])
-    cap = max(rows, want[0]["ncandidates"]) if max_chunks is None else max_chunks          # (a chain has at most a row per candidate)
-    tabs = [torch.full((cap + 2,), -2, dtype=t, device="cuda") for t in (torch.int64, torch.int32, torch.int32, torch.int64, torch.int32)]
-    s = dev.index_stream_carry_call(to_dev(torch, stream), frame, cap, max_chunk_in, *(t[1:] for t in tabs))
-    assert fields(s, X_FIELDS) == want[0]
-    for t, w, mask in zip(tabs, want[1:], (None, 0xffffffff, 0xffffffff, None, 0xffffffff)):
-        got = t.cpu().tolist()
-        assert got[0] == -2 and got[cap + 1] == -2
-        if want[0]["status"] != 1:
-            assert got[rows + 1:] == [-2] * (cap + 1 - rows)
-        assert [v & mask if mask else v for v in got[1:rows + 1]] == w
-    return want
-
-
-def decode_check(torch, dev, stream, frame, in_off, in_len, out_size, out_off, reach, cap=None):
-    """one hipdeflate_stream_inflate_carry_dev held to the model's verdict, 64 sentinel bytes either side of the output"""
-    want, out = cm.decode_carry(stream, frame, in_off, in_len, out_size, out_off, reach, cap)
-    room = (out_off[-1] + out_size[-1] if in_off else 0) if cap is None else cap
-    room = min(room, 1 << 24)
-    buf = torch.full((GUARD + room + GUARD,), SENT, dtype=torch.uint8, device="cuda")
-    s = dev.inflate_stream_carry_call(to_dev(torch, stream), frame, u64(torch, in_off), u32(torch, in_len), u32(torch, out_size),
-                                      u64(torch, out_off), u32(torch, reach), len(in_off), buf[GUARD:], room if cap is None else cap)
-    got = fields(s, S_FIELDS)
-    if want["check"] is None:
-        got["check"] = None
-    assert got == want
-    b = bytes(buf.cpu().numpy())
-    assert b[:GUARD] == bytes([SENT]) * GUARD and b[GUARD + room:] == bytes([SENT]) * GUARD
-    if want["status"] in (1, 3):                                               # nothing is decoded
-        assert b[GUARD:GUARD + room] == bytes([SENT]) * room
-    if want["status"] == 0:
-        assert b[GUARD:GUARD + room] == out
-    return want
-
-
-def both(torch, dev, stream, frame, plain, max_chunk_in=0):
-    """the index, then the decode on its table: the stream is one the method takes whole"""
-    assert zlib.decompress(stream, m.WBITS[frame]) == plain
-    x, *t = index_check(torch, dev, stream, frame, None, max_chunk_in)
-    assert x["status"] == 0 and x["out_bytes"] == len(plain) and x["end_offset"] == len(stream)
-    d = decode_check(torch, dev, stream, frame, *t)
-    assert d["status"] == 0
-    return x, t
 
 
 # ---- both writers -----------------------------------------------------------------------------------------------------------
