@@ -29,6 +29,7 @@
 #include "hd_carry.hpp"
 #include "hd_segment.hpp"
 #include "hd_tables.hpp"
+#include "hd_scratch.hpp"
 
 namespace {
 
@@ -992,22 +993,13 @@ int hipdeflate_batch_inflate_flush_dev(const void *in, const void *in_off, const
 
 static inline bool member_frame_ok(int frame) { return frame == HD_FRAME_RAW || frame == HD_FRAME_ZLIB || frame == HD_FRAME_GZIP; }
 
-// the payload table of one call in g.frame (the caller holds g.mu_dev and has entered): p_off u64 | p_len, verdict, used, chk u32
-struct FrameTable {
-	uint64_t *p_off;
-	uint32_t *p_len;
-	int32_t *verdict;
-	uint32_t *used, *chk;
-};
+// the payload table of one call in g.frame (the caller holds g.mu_dev and has entered)
+using hd::FrameTable;
 static int frame_table(Ctx &g, uint32_t n, hipStream_t st, FrameTable &t)
 {
-	if (g.frame.buf.grow_keep_old((size_t)n * 24))
+	if (g.frame.buf.grow_keep_old(FrameTable::bytes(n)))
 		return HD_E_NOMEM;
-	t.p_off = (uint64_t *)g.frame.buf.p;
-	t.p_len = (uint32_t *)(t.p_off + n);
-	t.verdict = (int32_t *)(t.p_len + n);
-	t.used = (uint32_t *)(t.verdict + n);
-	t.chk = t.used + n;
+	t = FrameTable(g.frame.buf.p, n);
 	return g.frame.enter(st);
 }
 
@@ -1155,6 +1147,97 @@ static void index_scan(const uint32_t *len, uint32_t n, uint64_t *tiles, uint64_
 	hipLaunchKernelGGL(hd::k_scan_tiles, dim3(1), dim3(256), 0, st, tiles, ntiles, base, total);
 	hipLaunchKernelGGL(hd::k_scan_finish, dim3(ntiles), dim3(256), 0, st, len, n, tiles, dst);
 }
+static_assert(hd::SCRATCH_SCAN_TILE == hd::SCAN_TILE, "hd_scratch.hpp counts the tiles index_scan uses");
+
+// what a call with a summary does first: the library is up, the summary is there and zeroed
+static int enter_call(void *summary, size_t bytes)
+{
+	const int r = ensure();
+	if (r || !summary)
+		return r ? r : HD_E_ARG;
+	memset(summary, 0, bytes);
+	return 0;
+}
+
+/* The chain index, which the member index and the stream indexes share: the sorted candidate list (chain_candidates), the
+   caller's links between candidates, the true chain out of the links and every link's rank on it (chain_rank), the caller's
+   rows and verdict, the summary read back (chain_read).  Scratch: hd::IndexBitmap in d_index (w: its words), hd::IndexCand in
+   d_cand (c). */
+
+// Pass 1 and 2 over src[0, n).  lo == nullptr: the member index's (k_index_flag, k_index_write); no candidate leaves d_cand
+// alone.  Else a stream index's: the markers from *lo on (k_stream_flag, k_stream_write) behind candidate 0, *lo itself.
+static int chain_candidates(Ctx &g, const uint8_t *src, uint64_t n, const uint32_t *lo, hd::IndexKind kind, uint32_t max_members,
+			    hd::IndexWords *&w, hd::IndexCand &c, uint32_t &ncand, hipStream_t st)
+{
+	const uint64_t nwords = (n + hd::IDX_WORD - 1) / hd::IDX_WORD, ntb64 = (nwords + hd::IDX_TILE_WORDS - 1) / hd::IDX_TILE_WORDS;
+	if (ntb64 > 0x7fffffffu)
+		return HD_E_ARG;
+	const uint32_t ntb = (uint32_t)ntb64;
+	if (g.d_index.reserve(hd::IndexBitmap::bytes(ntb, nwords, lo != nullptr)))
+		return HD_E_NOMEM;
+	const hd::IndexBitmap b(g.d_index.p, ntb, nwords, lo != nullptr);
+	w = b.w;
+	uint64_t found = 0;
+	HD_CHECK(hipMemsetAsync(b.w, 0, sizeof *b.w, st));
+	if (ntb) {
+		if (lo)
+			hipLaunchKernelGGL(hd::k_stream_flag, dim3(ntb), dim3(256), 0, st, src, n, (uint64_t)*lo, b.bitmap, b.tile_cnt);
+		else
+			hipLaunchKernelGGL(hd::k_index_flag, dim3(ntb), dim3(256), 0, st, src, n, b.bitmap, b.tile_cnt);
+		index_scan(b.tile_cnt, ntb, b.tiles, b.tile_off, &b.w->ncand, st);
+		HD_CHECK(hipGetLastError());
+		HD_CHECK(hipMemcpyAsync(&found, &b.w->ncand, 8, hipMemcpyDeviceToHost, st));
+		HD_CHECK(hipStreamSynchronize(st));
+	}
+	if (found + (lo ? 1 : 0) > 0x7fffffffu)                                  // candidate indices, and ncand + 255, stay well inside 32 bits
+		return HD_E_NOMEM;
+	ncand = (uint32_t)found + (lo ? 1 : 0);
+	if (ncand == 0)
+		return 0;
+	const size_t max_rows = lo ? ncand : max_members;
+	if (g.d_cand.reserve(hd::IndexCand::bytes(ncand, max_rows, kind)))
+		return HD_E_NOMEM;
+	c = hd::IndexCand(g.d_cand.p, ncand, max_rows, kind);
+	if (!lo) {
+		hipLaunchKernelGGL(hd::k_index_write, dim3(ntb), dim3(256), 0, st, src, n, (const uint64_t *)b.bitmap, nwords,
+				   (const uint64_t *)b.tile_off, c.pos);
+		return 0;
+	}
+	HD_CHECK(hipMemsetAsync(c.pos, 0, 8, st));
+	HD_CHECK(hipMemsetD32Async((hipDeviceptr_t)c.pos, (int)*lo, 1, st));
+	if (ncand > 1)
+		hipLaunchKernelGGL(hd::k_stream_write, dim3(ntb), dim3(256), 0, st, src, n, (uint64_t)*lo, (const uint64_t *)b.bitmap, nwords,
+				   (const uint64_t *)b.tile_off, c.pos + 1);
+	return 0;
+}
+
+// The true chain from the links in succ0 and mark: rounds until 2^rounds >= ncand (a chain has at most ncand rows), jump
+// the column k_index_jump reads; then every marked candidate's rank, over the successor tables, which are dead by then.
+// *nrows: the chain's length.
+static int chain_rank(const hd::IndexCand &c, uint32_t ncand, const uint32_t *jump, hd::IndexWords *w, uint64_t *nrows, hipStream_t st)
+{
+	uint32_t *succ0 = c.succ0, *succ1 = c.succ1;
+	for (uint64_t reach = 1; reach < ncand; reach *= 2) {
+		hipLaunchKernelGGL(hd::k_index_jump, dim3((ncand + 255) / 256), dim3(256), 0, st, (const uint32_t *)succ0, succ1, jump, c.mark, ncand);
+		std::swap(succ0, succ1);
+	}
+	index_scan(c.mark, ncand, c.tiles, c.rank, &w->rows, st);
+	HD_CHECK(hipGetLastError());
+	HD_CHECK(hipMemcpyAsync(nrows, &w->rows, 8, hipMemcpyDeviceToHost, st));
+	HD_CHECK(hipStreamSynchronize(st));
+	return 0;
+}
+
+// behind the caller's verdict kernel: the four words it leaves, into the four fields either summary has for them
+static int chain_read(const hd::IndexWords *w, uint64_t *rows, uint64_t *out_bytes, uint64_t *end_offset, uint32_t *status, hipStream_t st)
+{
+	hd::IndexWords h;
+	HD_CHECK(hipGetLastError());
+	HD_CHECK(hipMemcpyAsync(&h, w, offsetof(hd::IndexWords, ncand), hipMemcpyDeviceToHost, st));
+	HD_CHECK(hipStreamSynchronize(st));
+	*rows = h.rows, *out_bytes = h.out_bytes, *end_offset = h.end_offset, *status = (uint32_t)h.status;
+	return 0;
+}
 
 int hipdeflate_index_members_dev(const void *blob, uint64_t nbytes, uint32_t max_members, void *in_off, void *in_len,
 				 void *out_size, void *out_off, void *crc_want, hipdeflate_member_summary *summary, void *stream)
@@ -1171,72 +1254,29 @@ int hipdeflate_index_members_dev(const void *blob, uint64_t nbytes, uint32_t max
 	hipStream_t st = (hipStream_t)stream;
 	const uint8_t *src = (const uint8_t *)blob;
 	std::lock_guard<std::mutex> lk(g.mu_index);
-	// pass 1 and 2: the sorted candidate list
-	const uint64_t nwords = (nbytes + hd::IDX_WORD - 1) / hd::IDX_WORD;
-	const uint64_t ntb64 = (nwords + hd::IDX_TILE_WORDS - 1) / hd::IDX_TILE_WORDS;
-	if (ntb64 > 0x7fffffffu)
-		return HD_E_ARG;
-	const uint32_t ntb = (uint32_t)ntb64;
-	const size_t scan_tiles_a = (ntb + hd::SCAN_TILE - 1) / hd::SCAN_TILE;
-	// sum[4] | scan tiles | tile_off | bitmap | tile_cnt
-	if (g.d_index.reserve(64 + (scan_tiles_a + ntb + nwords) * 8 + (size_t)ntb * 4))
-		return HD_E_NOMEM;
-	uint64_t *sum = (uint64_t *)g.d_index.p, *tiles_a = sum + 8, *tile_off = tiles_a + scan_tiles_a;
-	uint64_t *bitmap = tile_off + ntb;
-	uint32_t *tile_cnt = (uint32_t *)(bitmap + nwords);
-	HD_CHECK(hipMemsetAsync(sum, 0, 64, st));
-	hipLaunchKernelGGL(hd::k_index_flag, dim3(ntb), dim3(256), 0, st, src, nbytes, bitmap, tile_cnt);
-	index_scan(tile_cnt, ntb, tiles_a, tile_off, sum + 4, st);
-	HD_CHECK(hipGetLastError());
-	uint64_t h[4] = { 0, 0, 0, 0 };
-	HD_CHECK(hipMemcpyAsync(h, sum + 4, 8, hipMemcpyDeviceToHost, st));
-	HD_CHECK(hipStreamSynchronize(st));
-	if (h[0] > 0x7fffffffu)                                                  // candidate indices, and ncand + 255, stay well inside 32 bits
-		return HD_E_NOMEM;
-	const uint32_t ncand = (uint32_t)h[0];
+	hd::IndexWords *w = nullptr;
+	hd::IndexCand c;
+	uint32_t ncand = 0;
+	if ((r = chain_candidates(g, src, nbytes, nullptr, hd::INDEX_MEMBERS, max_members, w, c, ncand, st)))
+		return r;
+	const uint32_t nwg = (ncand + 255) / 256;
 	uint64_t nrows = 0;
 	if (ncand) {
-		const size_t scan_tiles_b = ((size_t)ncand + hd::SCAN_TILE - 1) / hd::SCAN_TILE + ((size_t)max_members + hd::SCAN_TILE - 1) / hd::SCAN_TILE;
-		const size_t nc = ((size_t)ncand + 3) & ~(size_t)3;
-		// scan tiles | pos | succ[2] (later: rank) | mark | hdr | total
-		if (g.d_cand.reserve((scan_tiles_b + nc * 2) * 8 + nc * 12))
-			return HD_E_NOMEM;
-		uint64_t *tiles_b = (uint64_t *)g.d_cand.p, *pos = tiles_b + scan_tiles_b, *rank = pos + nc;
-		uint32_t *succ0 = (uint32_t *)rank, *succ1 = succ0 + nc, *mark = succ1 + nc, *hdr = mark + nc, *total = hdr + nc;
-		const uint32_t nwg = (ncand + 255) / 256;
-		hipLaunchKernelGGL(hd::k_index_write, dim3(ntb), dim3(256), 0, st, src, nbytes, (const uint64_t *)bitmap, nwords,
-				   (const uint64_t *)tile_off, pos);
-		hipLaunchKernelGGL(hd::k_index_links, dim3(nwg), dim3(256), 0, st, src, nbytes, (const uint64_t *)pos, ncand, succ0,
-				   hdr, total, mark);
-		// the true chain: rounds until 2^rounds >= ncand (a chain has at most ncand members)
-		for (uint64_t reach = 1; reach < ncand; reach *= 2) {
-			hipLaunchKernelGGL(hd::k_index_jump, dim3(nwg), dim3(256), 0, st, (const uint32_t *)succ0, succ1,
-					   (const uint32_t *)total, mark, ncand);
-			std::swap(succ0, succ1);
-		}
-		index_scan(mark, ncand, tiles_b, rank, sum + 0, st);                 // (the successor tables are dead: rank takes their place)
-		HD_CHECK(hipGetLastError());
-		HD_CHECK(hipMemcpyAsync(h, sum, 8, hipMemcpyDeviceToHost, st));
-		HD_CHECK(hipStreamSynchronize(st));
-		nrows = h[0];
+		hipLaunchKernelGGL(hd::k_index_links, dim3(nwg), dim3(256), 0, st, src, nbytes, (const uint64_t *)c.pos, ncand, c.succ0,
+				   c.hdr, c.total, c.mark);
+		if ((r = chain_rank(c, ncand, c.total, w, &nrows, st)))
+			return r;
 		if (nrows) {
 			const uint32_t ntab = (uint32_t)(nrows < max_members ? nrows : max_members);
-			hipLaunchKernelGGL(hd::k_members_tables, dim3(nwg), dim3(256), 0, st, src, (const uint64_t *)pos, (const uint32_t *)hdr,
-					   (const uint32_t *)total, (const uint32_t *)mark, (const uint64_t *)rank, ncand, nrows, max_members,
-					   (uint64_t *)in_off, (uint32_t *)in_len, (uint32_t *)out_size, (uint32_t *)crc_want, sum + 2);
+			hipLaunchKernelGGL(hd::k_members_tables, dim3(nwg), dim3(256), 0, st, src, (const uint64_t *)c.pos, (const uint32_t *)c.hdr,
+					   (const uint32_t *)c.total, (const uint32_t *)c.mark, (const uint64_t *)c.rank, ncand, nrows, max_members,
+					   (uint64_t *)in_off, (uint32_t *)in_len, (uint32_t *)out_size, (uint32_t *)crc_want, &w->end_offset);
 			if (ntab)
-				index_scan((const uint32_t *)out_size, ntab, tiles_b, (uint64_t *)out_off, sum + 1, st);
+				index_scan((const uint32_t *)out_size, ntab, c.tiles, (uint64_t *)out_off, &w->out_bytes, st);
 		}
 	}
-	hipLaunchKernelGGL(hd::k_index_verdict, dim3(1), dim3(1), 0, st, src, nbytes, nrows, max_members, sum);
-	HD_CHECK(hipGetLastError());
-	HD_CHECK(hipMemcpyAsync(h, sum, 32, hipMemcpyDeviceToHost, st));
-	HD_CHECK(hipStreamSynchronize(st));
-	summary->nmembers = h[0];
-	summary->out_bytes = h[1];
-	summary->end_offset = h[2];
-	summary->status = (uint32_t)h[3];
-	return 0;
+	hipLaunchKernelGGL(hd::k_index_verdict, dim3(1), dim3(1), 0, st, src, nbytes, nrows, max_members, &w->rows);
+	return chain_read(w, &summary->nmembers, &summary->out_bytes, &summary->end_offset, &summary->status, st);
 }
 
 int hipdeflate_verify_members_dev(const void *status, const void *out_len, const void *crc32, const void *out_size,
@@ -1255,9 +1295,9 @@ int hipdeflate_verify_members_dev(const void *status, const void *out_len, const
 		return HD_E_ARG;
 	hipStream_t st = (hipStream_t)stream;
 	std::lock_guard<std::mutex> lk(g.mu_index);
-	if (g.d_index.reserve(64))
+	if (g.d_index.reserve(hd::IndexBitmap::bytes()))
 		return HD_E_NOMEM;
-	uint32_t *d_bad = (uint32_t *)g.d_index.p, bad = hd::IDX_NIL;
+	uint32_t *d_bad = &hd::IndexBitmap(g.d_index.p).w->first, bad = hd::IDX_NIL;
 	HD_CHECK(hipMemsetAsync(d_bad, 0xff, 4, st));
 	hipLaunchKernelGGL(hd::k_members_verify, dim3((nmembers + 255) / 256), dim3(256), 0, st, (const int32_t *)status,
 			   (const uint32_t *)out_len, (const uint32_t *)crc32, (const uint32_t *)out_size, (const uint32_t *)crc_want,
@@ -1276,12 +1316,9 @@ int hipdeflate_read_ranges_dev(const void *blob, const void *in_off, const void 
 			       hipdeflate_range_summary *summary, void *stream)
 {
 	Ctx &g = cur();
-	int r = ensure();
+	int r = enter_call(summary, sizeof *summary);
 	if (r)
 		return r;
-	if (!summary)
-		return HD_E_ARG;
-	memset(summary, 0, sizeof *summary);
 	summary->bad_member = nmembers;
 	if (((uintptr_t)blob & 15) || (kind != HD_RANGE_BYTES && kind != HD_RANGE_VOFFSET) || (!dst && dst_cap) ||
 	    nmembers > 0x7fffffffu || nqueries > 0x7fffffffu ||                       // (n + 1 and n + 255 stay inside 32 bits)
@@ -1294,74 +1331,66 @@ int hipdeflate_read_ranges_dev(const void *blob, const void *in_off, const void 
 	const size_t n = nmembers, nq = nqueries;
 	const uint32_t wg_n = (nmembers + 255) / 256, wg_q = (nqueries + 255) / 256;
 	std::lock_guard<std::mutex> lk(g.mu_index);
-	// sum[8] | scan tiles | cover_scan[n + 1] | rank, scratch_off, c_in_off, c_out_off [n] | q_from, piece_off [nq] |
-	// cover[n + 1] | sel, sel_size, c_in_len, c_out_cap, c_crc_want, c_member, c_out_len, c_crc, c_status [n] | q_pieces, q_first [nq]
-	const size_t ntiles = ((n + 1 > nq ? n + 1 : nq) + hd::SCAN_TILE - 1) / hd::SCAN_TILE;
-	if (g.d_range.reserve((8 + ntiles + (n + 1) + 4 * n + 2 * nq) * 8 + ((n + 1) + 9 * n + 2 * nq) * 4))
+	if (g.d_range.reserve(hd::RangeTables::bytes(n, nq)))
 		return HD_E_NOMEM;
-	uint64_t *sum = (uint64_t *)g.d_range.p, *tiles = sum + 8, *cover_scan = tiles + ntiles, *rank = cover_scan + n + 1;
-	uint64_t *scratch_off = rank + n, *c_in_off = scratch_off + n, *c_out_off = c_in_off + n, *q_from = c_out_off + n;
-	uint64_t *piece_off = q_from + nq;
-	uint32_t *cover = (uint32_t *)(piece_off + nq), *sel = cover + n + 1, *sel_size = sel + n, *c_in_len = sel_size + n;
-	uint32_t *c_out_cap = c_in_len + n, *c_crc_want = c_out_cap + n, *c_member = c_crc_want + n, *c_out_len = c_member + n;
-	uint32_t *c_crc = c_out_len + n, *c_status = c_crc + n, *q_pieces = c_status + n, *q_first = q_pieces + nq;
-	// sum[]: 0 out_bytes | 1 pieces | 2 (the cover scan's total) | 3 nselected | 4 sel_bytes | 5 bad_member | 6 nrefused (u32) | 7 first bad row (u32)
-	uint32_t *d_refused = (uint32_t *)(sum + 6), *d_bad_row = (uint32_t *)(sum + 7);
-	HD_CHECK(hipMemsetAsync(sum, 0, 56, st));
-	HD_CHECK(hipMemsetAsync(d_bad_row, 0xff, 4, st));
-	HD_CHECK(hipMemsetAsync(cover, 0, (n + 1) * 4, st));
+	const hd::RangeTables t(g.d_range.p, n, nq);
+	hd::RangeWords *w = t.w;
+	HD_CHECK(hipMemsetAsync(w, 0, offsetof(hd::RangeWords, bad_row), st));
+	HD_CHECK(hipMemsetAsync(&w->bad_row, 0xff, 4, st));
+	HD_CHECK(hipMemsetAsync(t.cover, 0, (n + 1) * 4, st));
 	// queries -> lengths, first members, coverage; coverage -> selection, ranks, scratch layout
 	hipLaunchKernelGGL(hd::k_range_resolve, dim3(wg_q), dim3(256), 0, st, (const uint64_t *)in_off, (const uint32_t *)in_len,
 			   (const uint32_t *)out_size, (const uint64_t *)out_off, nmembers, kind, (const uint64_t *)q_begin,
-			   (const uint64_t *)q_end, nqueries, (uint32_t *)q_len, (int32_t *)q_status, q_pieces, q_first, q_from, cover,
-			   d_refused);
-	index_scan((const uint32_t *)q_len, nqueries, tiles, (uint64_t *)dst_off, sum + 0, st);
-	index_scan(q_pieces, nqueries, tiles, piece_off, sum + 1, st);
-	index_scan(cover, nmembers + 1, tiles, cover_scan, sum + 2, st);
-	hipLaunchKernelGGL(hd::k_range_select, dim3(wg_n), dim3(256), 0, st, (const uint64_t *)cover_scan, (const uint32_t *)out_size,
-			   nmembers, sel, sel_size);
-	index_scan(sel, nmembers, tiles, rank, sum + 3, st);
-	index_scan(sel_size, nmembers, tiles, scratch_off, sum + 4, st);
+			   (const uint64_t *)q_end, nqueries, (uint32_t *)q_len, (int32_t *)q_status, t.q_pieces, t.q_first, t.q_from, t.cover,
+			   &w->nrefused);
+	index_scan((const uint32_t *)q_len, nqueries, t.tiles, (uint64_t *)dst_off, &w->out_bytes, st);
+	index_scan(t.q_pieces, nqueries, t.tiles, t.piece_off, &w->pieces, st);
+	index_scan(t.cover, nmembers + 1, t.tiles, t.cover_scan, &w->cover_total, st);
+	hipLaunchKernelGGL(hd::k_range_select, dim3(wg_n), dim3(256), 0, st, (const uint64_t *)t.cover_scan, (const uint32_t *)out_size,
+			   nmembers, t.sel, t.sel_size);
+	index_scan(t.sel, nmembers, t.tiles, t.rank, &w->nselected, st);
+	index_scan(t.sel_size, nmembers, t.tiles, t.scratch_off, &w->sel_bytes, st);
 	HD_CHECK(hipGetLastError());
-	uint64_t h[8];
-	HD_CHECK(hipMemcpyAsync(h, sum, 64, hipMemcpyDeviceToHost, st));
+	hd::RangeWords h;
+	HD_CHECK(hipMemcpyAsync(&h, w, sizeof h, hipMemcpyDeviceToHost, st));
 	HD_CHECK(hipStreamSynchronize(st));
-	summary->out_bytes = h[0];
-	summary->nselected = h[3];
-	summary->sel_bytes = h[4];
-	summary->nrefused = (uint32_t)h[6];
-	if (h[0] > dst_cap) {
+	summary->out_bytes = h.out_bytes;
+	summary->nselected = h.nselected;
+	summary->sel_bytes = h.sel_bytes;
+	summary->nrefused = h.nrefused;
+	if (h.out_bytes > dst_cap) {
 		summary->status = 3;
 		return 0;
 	}
-	if (h[3] == 0)                                                           // no query took a byte
+	if (h.nselected == 0)                                                    // no query took a byte
 		return 0;
 	// the selected members, inflated back to back into the scratch and held to their trailers
-	const uint32_t nsel = (uint32_t)h[3];
-	if (g.d_range_out.reserve(h[4] + 16))
+	const uint32_t nsel = (uint32_t)h.nselected;
+	if (g.d_range_out.reserve(h.sel_bytes + 16))
 		return HD_E_NOMEM;
 	uint8_t *scratch = (uint8_t *)g.d_range_out.p;
 	hipLaunchKernelGGL(hd::k_range_tables, dim3(wg_n), dim3(256), 0, st, (const uint64_t *)in_off, (const uint32_t *)in_len,
-			   (const uint32_t *)out_size, (const uint32_t *)crc_want, (const uint32_t *)sel, (const uint64_t *)rank,
-			   (const uint64_t *)scratch_off, nmembers, c_in_off, c_in_len, c_out_off, c_out_cap, c_crc_want, c_member);
-	if ((r = batch_inflate_dev(blob, c_in_off, c_in_len, nsel, scratch, c_out_off, c_out_cap, c_out_len, c_crc, c_status, stream, 0)))
+			   (const uint32_t *)out_size, (const uint32_t *)crc_want, (const uint32_t *)t.sel, (const uint64_t *)t.rank,
+			   (const uint64_t *)t.scratch_off, nmembers, t.c_in_off, t.c_in_len, t.c_out_off, t.c_out_cap, t.c_crc_want, t.c_member);
+	if ((r = batch_inflate_dev(blob, t.c_in_off, t.c_in_len, nsel, scratch, t.c_out_off, t.c_out_cap, t.c_out_len, t.c_crc, t.c_status,
+				   stream, 0)))
 		return r;
-	hipLaunchKernelGGL(hd::k_members_verify, dim3((nsel + 255) / 256), dim3(256), 0, st, (const int32_t *)c_status,
-			   (const uint32_t *)c_out_len, (const uint32_t *)c_crc, (const uint32_t *)c_out_cap, (const uint32_t *)c_crc_want,
-			   nsel, d_bad_row);
-	hipLaunchKernelGGL(hd::k_range_verdict, dim3(1), dim3(1), 0, st, (const uint32_t *)d_bad_row, (const uint32_t *)c_member,
-			   nmembers, sum + 5);
+	hipLaunchKernelGGL(hd::k_members_verify, dim3((nsel + 255) / 256), dim3(256), 0, st, (const int32_t *)t.c_status,
+			   (const uint32_t *)t.c_out_len, (const uint32_t *)t.c_crc, (const uint32_t *)t.c_out_cap,
+			   (const uint32_t *)t.c_crc_want, nsel, &w->bad_row);
+	hipLaunchKernelGGL(hd::k_range_verdict, dim3(1), dim3(1), 0, st, (const uint32_t *)&w->bad_row, (const uint32_t *)t.c_member,
+			   nmembers, &w->bad_member);
 	// every query's run of the scratch -> dst + dst_off[q], in pieces over a persistent grid
 	const uint64_t grid_cap = (uint64_t)hd::compact_device_cus() * hd::COMPACT_WAVES_PER_CU;
-	hipLaunchKernelGGL(hd::k_range_gather, dim3((uint32_t)(h[1] < grid_cap ? h[1] : grid_cap)), dim3(64), 0, st,
-			   (const uint8_t *)scratch, (const uint64_t *)scratch_off, (const uint64_t *)out_off, (const uint32_t *)q_first,
-			   (const uint64_t *)q_from, (const uint32_t *)q_len, (const uint64_t *)dst_off, (const uint64_t *)piece_off,
-			   nqueries, h[1], (uint8_t *)dst);
+	hipLaunchKernelGGL(hd::k_range_gather, dim3((uint32_t)(h.pieces < grid_cap ? h.pieces : grid_cap)), dim3(64), 0, st,
+			   (const uint8_t *)scratch, (const uint64_t *)t.scratch_off, (const uint64_t *)out_off, (const uint32_t *)t.q_first,
+			   (const uint64_t *)t.q_from, (const uint32_t *)q_len, (const uint64_t *)dst_off, (const uint64_t *)t.piece_off,
+			   nqueries, h.pieces, (uint8_t *)dst);
 	HD_CHECK(hipGetLastError());
-	HD_CHECK(hipMemcpyAsync(h, sum + 5, 8, hipMemcpyDeviceToHost, st));
+	HD_CHECK(hipMemcpyAsync(&h.bad_member, &w->bad_member, 8, hipMemcpyDeviceToHost, st));
 	HD_CHECK(hipStreamSynchronize(st));
-	summary->bad_member = h[0];
-	if (h[0] != nmembers)
+	summary->bad_member = h.bad_member;
+	if (h.bad_member != nmembers)
 		summary->status = 2;
 	return 0;
 }
@@ -1413,14 +1442,13 @@ int hipdeflate_check_combine_dev(const void *check, const void *len, uint32_t n,
 	if (!result || (kind != (int)hd::CHECK_CRC32 && kind != (int)hd::CHECK_ADLER32) || n > STREAM_MAX_PARTS || (n && (!check || !len)))
 		return HD_E_ARG;
 	hipStream_t st = (hipStream_t)stream;
-	const size_t ntiles = ((size_t)n + hd::SCAN_TILE - 1) / hd::SCAN_TILE;
 	std::lock_guard<std::mutex> lk(g.mu_index);
-	if (g.d_stream.reserve((8 + ntiles + (size_t)n) * 8))
+	if (g.d_stream.reserve(hd::FoldScratch::bytes(n)))
 		return HD_E_NOMEM;
-	uint64_t *sum = (uint64_t *)g.d_stream.p, *tiles = sum + 8, *prefix = tiles + ntiles;
-	uint32_t *carry = (uint32_t *)(sum + 4);
+	const hd::FoldScratch t(g.d_stream.p, n);
+	uint32_t *carry = &t.w->v.check;
 	HD_CHECK(hipMemsetD32Async((hipDeviceptr_t)carry, kind == (int)hd::CHECK_ADLER32 ? 1 : 0, 1, st));
-	if ((r = fold_launch((const uint32_t *)check, (const uint32_t *)len, n, (uint32_t)kind, tiles, prefix, sum, carry, st)))
+	if ((r = fold_launch((const uint32_t *)check, (const uint32_t *)len, n, (uint32_t)kind, t.tiles, t.prefix, t.w->fold, carry, st)))
 		return r;
 	HD_CHECK(hipMemcpyAsync(result, carry, 4, hipMemcpyDeviceToHost, st));
 	HD_CHECK(hipStreamSynchronize(st));
@@ -1431,12 +1459,9 @@ int hipdeflate_stream_deflate_dev(const void *in, uint64_t nbytes, uint32_t chun
 				  uint64_t dst_cap, void *chunk_off, hipdeflate_stream_summary *summary, void *stream)
 {
 	Ctx &g = cur();
-	int r = ensure();
+	int r = enter_call(summary, sizeof *summary);
 	if (r)
 		return r;
-	if (!summary)
-		return HD_E_ARG;
-	memset(summary, 0, sizeof *summary);
 	if (!stream_frame_ok(frame) || !stream_chunk_ok(chunk_bytes) || ((uintptr_t)in & 15) || ((uintptr_t)dst & 15) || (nbytes && !in) ||
 	    (dst_cap && !dst) || (nbytes + chunk_bytes - 1) / chunk_bytes > STREAM_MAX_PARTS)
 		return HD_E_ARG;
@@ -1450,50 +1475,44 @@ int hipdeflate_stream_deflate_dev(const void *in, uint64_t nbytes, uint32_t chun
 	if (!g_test_stream_window && nchunks)                          // windows of one size: no short one left over at the end
 		W = (nchunks + (nchunks + W - 1) / W - 1) / ((nchunks + W - 1) / W);
 	hipStream_t st = (hipStream_t)stream;
-	const size_t ntiles = (W + hd::SCAN_TILE - 1) / hd::SCAN_TILE;
 	std::lock_guard<std::mutex> lk(g.mu_index);
-	// sum[8] | scan tiles | in_off, own_off, prefix [W] | in_len, out_len, crc, adler, status [W]
-	if (g.d_stream.reserve((8 + ntiles + 3 * W) * 8 + 5 * W * 4) || (nchunks && g.d_stream_slots.reserve(W * slot + 16)))
+	if (g.d_stream.reserve(hd::EncodeWindow::bytes(W)) || (nchunks && g.d_stream_slots.reserve(W * slot + 16)))
 		return HD_E_NOMEM;
-	uint64_t *sum = (uint64_t *)g.d_stream.p, *tiles = sum + 8, *in_off = tiles + ntiles, *own_off = in_off + W, *prefix = own_off + W;
-	uint32_t *in_len = (uint32_t *)(prefix + W), *out_len = in_len + W, *crc = out_len + W, *adler = crc + W;
-	int32_t *status = (int32_t *)(adler + W);
+	const hd::EncodeWindow t(g.d_stream.p, W);
 	uint8_t *slots = (uint8_t *)g.d_stream_slots.p;
-	// sum[]: 0 the window's bytes out | 1 its bytes in, 2..3 the fold's accumulators | 4 the running check (u32), the window's first bad chunk (u32)
-	uint32_t *carry = (uint32_t *)(sum + 4), *d_bad = carry + 1;
+	uint32_t *carry = &t.w->v.check, *d_bad = &t.w->v.fault;     // the running check, the window's first bad chunk
 	HD_CHECK(hipMemsetD32Async((hipDeviceptr_t)carry, kind == hd::CHECK_ADLER32 ? 1 : 0, 1, st));
 	uint64_t pos = hdr, bad_chunk = nchunks;
 	bool fits = true;
 	for (uint32_t c0 = 0; c0 < nchunks; c0 += (uint32_t)W) {
 		const uint32_t w = nchunks - c0 < W ? nchunks - c0 : (uint32_t)W, wgs = (w + 255) / 256;
-		hipLaunchKernelGGL(hd::k_stream_table, dim3(wgs), dim3(256), 0, st, c0, w, chunk_bytes, nbytes, in_off, in_len);
-		if ((r = batch_deflate_dev_impl(in, in_off, in_len, w, level, HD_FRAME_RAW_FLUSH, slots, slot, (uint32_t)slot, out_len, crc,
-						status, stream, 0)))
+		hipLaunchKernelGGL(hd::k_stream_table, dim3(wgs), dim3(256), 0, st, c0, w, chunk_bytes, nbytes, t.in_off, t.in_len);
+		if ((r = batch_deflate_dev_impl(in, t.in_off, t.in_len, w, level, HD_FRAME_RAW_FLUSH, slots, slot, (uint32_t)slot, t.out_len, t.crc,
+						t.status, stream, 0)))
 			return r;
 		// every chunk's place in the stream, straight into the caller's table where there is one: the running total goes
 		// from window to window as the scan's base
-		uint64_t *dst_off = chunk_off ? (uint64_t *)chunk_off + c0 : own_off;
-		index_scan(out_len, w, tiles, dst_off, sum + 0, st, pos);
+		uint64_t *dst_off = chunk_off ? (uint64_t *)chunk_off + c0 : t.own_off;
+		index_scan(t.out_len, w, t.tiles, dst_off, &t.w->total, st, pos);
 		HD_CHECK(hipMemsetAsync(d_bad, 0xff, 4, st));
-		hipLaunchKernelGGL(hd::k_members_verify, dim3(wgs), dim3(256), 0, st, (const int32_t *)status, (const uint32_t *)out_len,
-				   (const uint32_t *)crc, (const uint32_t *)out_len, (const uint32_t *)crc, w, d_bad);     // (the status alone)
+		hipLaunchKernelGGL(hd::k_members_verify, dim3(wgs), dim3(256), 0, st, (const int32_t *)t.status, (const uint32_t *)t.out_len,
+				   (const uint32_t *)t.crc, (const uint32_t *)t.out_len, (const uint32_t *)t.crc, w, d_bad);     // (the status alone)
 		if (kind == hd::CHECK_ADLER32)
-			hipLaunchKernelGGL(hd::k_chunk_adler, dim3(w), dim3(64), 0, st, (const uint8_t *)in, (const uint64_t *)in_off,
-					   (const uint32_t *)in_len, (const uint32_t *)nullptr, w, adler);
-		if ((r = fold_launch(kind == hd::CHECK_ADLER32 ? adler : crc, in_len, w, kind, tiles, prefix, sum + 1, carry, st)))
+			hipLaunchKernelGGL(hd::k_chunk_adler, dim3(w), dim3(64), 0, st, (const uint8_t *)in, (const uint64_t *)t.in_off,
+					   (const uint32_t *)t.in_len, (const uint32_t *)nullptr, w, t.adler);
+		if ((r = fold_launch(kind == hd::CHECK_ADLER32 ? t.adler : t.crc, t.in_len, w, kind, t.tiles, t.prefix, t.w->fold, carry, st)))
 			return r;
-		uint64_t h[5];
-		HD_CHECK(hipMemcpyAsync(h, sum, 40, hipMemcpyDeviceToHost, st));
+		hd::StreamWords h;
+		HD_CHECK(hipMemcpyAsync(&h, t.w, offsetof(hd::StreamWords, v.mismatch), hipMemcpyDeviceToHost, st));
 		HD_CHECK(hipStreamSynchronize(st));
-		const uint32_t bad = (uint32_t)(h[4] >> 32);
-		if (bad != hd::IDX_NIL && bad_chunk == nchunks)
-			bad_chunk = (uint64_t)c0 + bad;
+		if (h.v.fault != hd::IDX_NIL && bad_chunk == nchunks)
+			bad_chunk = (uint64_t)c0 + h.v.fault;
 		// the gather, the scan's base as the header and the windows in front: only while every byte of it has room
-		if (fits && pos + h[0] <= dst_cap)
-			hd::launch_compact(slots, slot, out_len, dst_off, w, (uint8_t *)dst, st);
+		if (fits && pos + h.total <= dst_cap)
+			hd::launch_compact(slots, slot, t.out_len, dst_off, w, (uint8_t *)dst, st);
 		else
 			fits = false;
-		pos += h[0];
+		pos += h.total;
 	}
 	const uint64_t need = pos + 2 + trl;
 	fits = fits && need <= dst_cap;
@@ -1515,111 +1534,63 @@ int hipdeflate_stream_deflate_dev(const void *in, uint64_t nbytes, uint32_t chun
 	return 0;
 }
 
-// The decode behind the table check, for hipdeflate_stream_inflate_dev and hipdeflate_stream_inflate_table_dev: row i by the
-// flush-rule inflate into out + out_off[i] with out_size[i] as room, every row held to its size, the rows' checks folded and
-// held to the trailer that ends at nbytes.  sum[4..5] as u32: the folded check (0 / 1 before the call) | - | the trailer
-// disagrees | the lowest bad row (0xffffffff before the call).  The caller has set summary->nchunks and bad_chunk.
+// a row table as a decoder takes it: the caller's columns, or (the decode by chunk table) the scratch's own
 struct StreamRows {
 	const uint64_t *in_off;
 	const uint32_t *in_len;
 	const uint64_t *out_off;
-	const uint32_t *out_size;
-	uint32_t *out_len, *chk;
-	int32_t *status;
-	uint64_t *tiles, *prefix, *sum;
+	const uint32_t *out_size, *reach;        // reach: the carry decode's
 };
-static int stream_decode_rows(Ctx &g, const void *strm, uint64_t nbytes, int frame, const StreamRows &t, uint32_t nchunks,
-			      uint64_t out_bytes, void *out, hipdeflate_stream_summary *summary, hipStream_t st)
+
+// the verdict words before a decode: the check's start value, no fault, no bad row
+static int stream_words_reset(hd::StreamWords *w, uint32_t kind, hipStream_t st)
 {
-	int r;
-	const uint32_t kind = frame == HD_FRAME_ZLIB ? hd::CHECK_ADLER32 : hd::CHECK_CRC32;
-	uint32_t *carry = (uint32_t *)(t.sum + 4), *d_mismatch = carry + 2, *d_bad = carry + 3;
-	uint32_t h[4] = { 0, 0, 0, 0 };
-	if (nchunks) {
-		if ((r = launch_inflate({ (const uint8_t *)strm, t.in_off, t.in_len, nchunks, (uint8_t *)out, t.out_off, t.out_size, t.out_len,
-					  kind == hd::CHECK_ADLER32 ? nullptr : t.chk, t.status, g.d_ct, hd::INF_FLUSHED }, st)))
-			return r;
-		if (kind == hd::CHECK_ADLER32)
-			hipLaunchKernelGGL(hd::k_chunk_adler, dim3(nchunks), dim3(64), 0, st, (const uint8_t *)out, t.out_off,
-					   (const uint32_t *)t.out_len, t.out_size, nchunks, t.chk);
-		hipLaunchKernelGGL(hd::k_members_verify, dim3((nchunks + 255) / 256), dim3(256), 0, st, (const int32_t *)t.status,
-				   (const uint32_t *)t.out_len, (const uint32_t *)t.chk, t.out_size, (const uint32_t *)t.chk, nchunks,
-				   d_bad);                                                   // (status and length: the check is the fold's)
-	}
-	if ((r = fold_launch(t.chk, t.out_size, nchunks, kind, t.tiles, t.prefix, t.sum + 1, carry, st)))
-		return r;
-	hipLaunchKernelGGL(hd::k_stream_trailer, dim3(1), dim3(64), 0, st, (const uint8_t *)strm, nbytes, frame, out_bytes,
-			   (const uint32_t *)carry, d_mismatch);
-	HD_CHECK(hipGetLastError());
-	HD_CHECK(hipMemcpyAsync(h, carry, 16, hipMemcpyDeviceToHost, st));
-	HD_CHECK(hipStreamSynchronize(st));
-	summary->out_bytes = out_bytes;
-	summary->in_bytes = nbytes;
-	summary->check = h[0];
-	if (h[3] != hd::IDX_NIL) {
-		summary->status = 2;
-		summary->bad_chunk = h[3];
-	} else if (h[2]) {
-		summary->status = 2;
-	}
+	HD_CHECK(hipMemsetAsync(w, 0, sizeof *w, st));
+	HD_CHECK(hipMemsetD32Async((hipDeviceptr_t)&w->v.check, kind == hd::CHECK_ADLER32 ? 1 : 0, 1, st));
+	HD_CHECK(hipMemsetD32Async((hipDeviceptr_t)&w->v.fault, (int)hd::IDX_NIL, 1, st));
+	HD_CHECK(hipMemsetD32Async((hipDeviceptr_t)&w->v.bad, (int)hd::IDX_NIL, 1, st));
 	return 0;
 }
 
-int hipdeflate_stream_inflate_dev(const void *strm, uint64_t nbytes, int frame, const void *chunk_off, uint32_t nchunks,
-				  uint32_t chunk_bytes, uint64_t out_bytes, void *out, uint64_t out_cap,
-				  hipdeflate_stream_summary *summary, void *stream)
+// Rows [r0, r0 + nr) by the flush rule: row i inflated into out + out_off[i] with out_size[i] as room and held to its size
+// (status and length; the lowest row that fails -> v.bad), the rows' checks folded onto v.check
+static int stream_rows_flushed(Ctx &g, const void *strm, uint32_t kind, const StreamRows &t, const hd::DecodeScratch &d, uint32_t r0,
+			       uint32_t nr, void *out, hipStream_t st)
 {
-	Ctx &g = cur();
-	int r = ensure();
-	if (r)
-		return r;
-	if (!summary)
-		return HD_E_ARG;
-	memset(summary, 0, sizeof *summary);
-	summary->nchunks = nchunks;
-	summary->bad_chunk = nchunks;
-	if (!stream_frame_ok(frame) || !stream_chunk_ok(chunk_bytes) || ((uintptr_t)strm & 15) || (nbytes && !strm) || !chunk_off ||
-	    nchunks >= STREAM_MAX_PARTS || (out_cap && !out))
-		return HD_E_ARG;
-	const uint32_t hdr = stream_hdr(frame), trl = stream_trl(frame);
-	const uint32_t kind = frame == HD_FRAME_ZLIB ? hd::CHECK_ADLER32 : hd::CHECK_CRC32;
-	// what nchunks and chunk_bytes allow, a stream long enough for its two ends: before any byte is looked at
-	if ((out_bytes + chunk_bytes - 1) / chunk_bytes != nchunks || nbytes < (uint64_t)hdr + 2 + trl) {
-		summary->status = 1;
-		return 0;
+	int r;
+	if (nr) {
+		if ((r = launch_inflate({ (const uint8_t *)strm, t.in_off + r0, t.in_len + r0, nr, (uint8_t *)out, t.out_off + r0, t.out_size + r0,
+					  d.out_len + r0, kind == hd::CHECK_ADLER32 ? nullptr : d.chk + r0, d.status + r0, g.d_ct, hd::INF_FLUSHED },
+					st)))
+			return r;
+		if (kind == hd::CHECK_ADLER32)
+			hipLaunchKernelGGL(hd::k_chunk_adler, dim3(nr), dim3(64), 0, st, (const uint8_t *)out, t.out_off + r0,
+					   (const uint32_t *)(d.out_len + r0), t.out_size + r0, nr, d.chk + r0);
+		hipLaunchKernelGGL(hd::k_carry_verify, dim3((nr + 255) / 256), dim3(256), 0, st, (const int32_t *)d.status,
+				   (const uint32_t *)d.out_len, t.out_size, r0, nr, &d.w->v.bad);
 	}
-	hipStream_t st = (hipStream_t)stream;
-	const size_t n = nchunks, ntiles = (n + hd::SCAN_TILE - 1) / hd::SCAN_TILE;
-	std::lock_guard<std::mutex> lk(g.mu_index);
-	// sum[8] | scan tiles | in_off, out_off, prefix [n] | in_len, out_size, out_len, check, status [n]
-	if (g.d_stream.reserve((8 + ntiles + 3 * n) * 8 + 5 * n * 4))
-		return HD_E_NOMEM;
-	uint64_t *sum = (uint64_t *)g.d_stream.p, *tiles = sum + 8, *in_off = tiles + ntiles, *out_off = in_off + n, *prefix = out_off + n;
-	uint32_t *in_len = (uint32_t *)(prefix + n), *out_size = in_len + n, *out_len = out_size + n, *chk = out_len + n;
-	int32_t *status = (int32_t *)(chk + n);
-	// sum[4..5] as u32: the folded check | the lowest table entry at fault | the trailer disagrees | the lowest bad chunk
-	uint32_t *carry = (uint32_t *)(sum + 4), *d_fault = carry + 1, *d_bad = carry + 3;
-	uint32_t h[4] = { 0, 0, 0, 0 };
-	HD_CHECK(hipMemsetAsync(sum, 0, 64, st));
-	HD_CHECK(hipMemsetD32Async((hipDeviceptr_t)carry, kind == hd::CHECK_ADLER32 ? 1 : 0, 1, st));
-	HD_CHECK(hipMemsetD32Async((hipDeviceptr_t)d_fault, (int)hd::IDX_NIL, 1, st));
-	HD_CHECK(hipMemsetD32Async((hipDeviceptr_t)d_bad, (int)hd::IDX_NIL, 1, st));
-	hipLaunchKernelGGL(hd::k_stream_check_table, dim3((nchunks + 1 + 255) / 256), dim3(256), 0, st, (const uint8_t *)strm, nbytes,
-			   (const uint64_t *)chunk_off, nchunks, chunk_bytes, out_bytes, frame, in_off, in_len, out_off, out_size, d_fault);
+	return fold_launch(d.chk + r0, t.out_size + r0, nr, kind, d.tiles, d.prefix, d.w->fold, &d.w->v.check, st);
+}
+
+// The end of a decode: the folded check held to the trailer that ends at in_bytes, the verdict read, the summary filled
+// (the caller has set summary->nchunks and bad_chunk)
+static int stream_decode_end(const void *strm, uint64_t in_bytes, int frame, uint64_t out_bytes, hd::StreamWords *w,
+			     hipdeflate_stream_summary *summary, hipStream_t st)
+{
+	hipLaunchKernelGGL(hd::k_stream_trailer, dim3(1), dim3(64), 0, st, (const uint8_t *)strm, in_bytes, frame, out_bytes,
+			   (const uint32_t *)&w->v.check, &w->v.mismatch);
 	HD_CHECK(hipGetLastError());
-	HD_CHECK(hipMemcpyAsync(h, carry, 16, hipMemcpyDeviceToHost, st));
+	hd::StreamVerdict h;
+	HD_CHECK(hipMemcpyAsync(&h, &w->v, sizeof h, hipMemcpyDeviceToHost, st));
 	HD_CHECK(hipStreamSynchronize(st));
-	if (h[1] != hd::IDX_NIL) {
-		summary->status = 1;
-		summary->bad_chunk = h[1];
-		return 0;
-	}
-	if (out_cap < out_bytes) {
-		summary->status = 3;
-		return 0;
-	}
-	return stream_decode_rows(g, strm, nbytes, frame, { in_off, in_len, out_off, out_size, out_len, chk, status, tiles, prefix, sum },
-				  nchunks, out_bytes, out, summary, st);
+	summary->out_bytes = out_bytes;
+	summary->in_bytes = in_bytes;
+	summary->check = h.check;
+	if (h.bad != hd::IDX_NIL || h.mismatch)
+		summary->status = 2;
+	if (h.bad != hd::IDX_NIL)
+		summary->bad_chunk = h.bad;
+	return 0;
 }
 
 /* ---- ... and a stream nobody kept a table for: the index of its flush points (hd_stream.hpp) ---- */
@@ -1654,24 +1625,28 @@ static int stream_open(const void *strm, uint64_t nbytes, int frame, uint64_t *w
 	return 0;
 }
 
-// own: the tables are the library's, made as large as the stream needs once that is known -- in_off, out_off u64[n] |
-// in_len, out_size u32[n] (carry: | reach u32[n]) in *own, n = the chain's rows (summary->nchunks where the status is 0) --
-// and the table arguments are not looked at.  carry: the index of hd_carry.hpp -- k_carry_piece in the place of
-// k_inflate_piece, the reach column, and the reach rule behind the verdict.
+// own: the tables are the library's, made as large as the stream needs once that is known -- a hd::RowTable of the chain's
+// rows (summary->nchunks where the status is 0) in *own -- and the table arguments are not looked at.  carry: the index
+// of hd_carry.hpp -- k_carry_piece in the place of k_inflate_piece, the reach column, and the reach rule behind the verdict.
 static int stream_index(Ctx &g, const void *strm, uint64_t nbytes, int frame, uint32_t max_chunks, uint32_t max_chunk_in, void *in_off,
 			void *in_len, void *out_size, void *out_off, hipdeflate_stream_index_summary *summary, hipStream_t st, Buf *own,
 			bool carry = false, void *reach = nullptr)
 {
-	int r;
+	int r = enter_call(summary, sizeof *summary);
+	if (r)
+		return r;
+	if (!stream_frame_ok(frame) || ((uintptr_t)strm & 15) || (nbytes && !strm) || max_chunk_in >= HD_INFLATE_MAX_IN ||
+	    (max_chunks && (!in_off || !in_len || !out_size || !out_off || (carry && !reach))))
+		return HD_E_ARG;
 	const uint8_t *src = (const uint8_t *)strm;
 	const uint32_t trl = stream_trl(frame);
 	if (max_chunk_in == 0)
 		max_chunk_in = HD_INFLATE_MAX_IN - 1;
 	std::lock_guard<std::mutex> lk(g.mu_index);
-	if (g.d_index.reserve(128))
+	if (g.d_index.reserve(hd::IndexBitmap::bytes(0, 0, true)))
 		return HD_E_NOMEM;
 	uint32_t hdr = 0, refused = 0;
-	if ((r = stream_open(strm, nbytes, frame, (uint64_t *)g.d_index.p + 8, st, &hdr, &refused)))
+	if ((r = stream_open(strm, nbytes, frame, hd::IndexBitmap(g.d_index.p, 0, 0, true).header, st, &hdr, &refused)))
 		return r;
 	summary->hdr_bytes = hdr;
 	summary->end_offset = hdr;
@@ -1685,196 +1660,65 @@ static int stream_index(Ctx &g, const void *strm, uint64_t nbytes, int frame, ui
 		summary->status = 2;
 		return 0;
 	}
-	// pass 1 and 2: the sorted candidate list.  The passes' nbytes is the last payload byte: a marker there makes no candidate
-	const uint64_t scan_n = payload_end - 1;
-	const uint64_t nwords = (scan_n + hd::IDX_WORD - 1) / hd::IDX_WORD;
-	const uint64_t ntb64 = (nwords + hd::IDX_TILE_WORDS - 1) / hd::IDX_TILE_WORDS;
-	if (ntb64 > 0x7fffffffu)
-		return HD_E_ARG;
-	const uint32_t ntb = (uint32_t)ntb64;
-	const size_t scan_tiles_a = (ntb + hd::SCAN_TILE - 1) / hd::SCAN_TILE;
-	// sum[8] | the header's [8] | scan tiles | tile_off | bitmap | tile_cnt
-	if (g.d_index.reserve(128 + (scan_tiles_a + ntb + nwords) * 8 + (size_t)ntb * 4))
-		return HD_E_NOMEM;
-	uint64_t *sum = (uint64_t *)g.d_index.p, *tiles_a = sum + 16, *tile_off = tiles_a + scan_tiles_a;
-	uint64_t *bitmap = tile_off + ntb;
-	uint32_t *tile_cnt = (uint32_t *)(bitmap + nwords);
-	uint64_t h[4] = { 0, 0, 0, 0 };
-	HD_CHECK(hipMemsetAsync(sum, 0, 64, st));
-	if (ntb) {
-		hipLaunchKernelGGL(hd::k_stream_flag, dim3(ntb), dim3(256), 0, st, src, scan_n, (uint64_t)hdr, bitmap, tile_cnt);
-		index_scan(tile_cnt, ntb, tiles_a, tile_off, sum + 4, st);
-		HD_CHECK(hipGetLastError());
-		HD_CHECK(hipMemcpyAsync(h, sum + 4, 8, hipMemcpyDeviceToHost, st));
-		HD_CHECK(hipStreamSynchronize(st));
-	}
-	if (h[0] >= 0x7fffffffu)                                                 // candidate indices, and ncand + 255, stay well inside 32 bits
-		return HD_E_NOMEM;
-	const uint32_t ncand = (uint32_t)h[0] + 1;
-	summary->ncandidates = ncand;
-	const size_t scan_tiles_b = ((size_t)ncand + hd::SCAN_TILE - 1) / hd::SCAN_TILE + ((size_t)ncand + hd::SCAN_TILE - 1) / hd::SCAN_TILE;
-	const size_t nc = ((size_t)ncand + 3) & ~(size_t)3;
-	// scan tiles | pos | succ[2] (later: rank) | mark | in_used | out_size | status | stop
-	if (g.d_cand.reserve((scan_tiles_b + nc * 2) * 8 + nc * (carry ? 24 : 20)))
-		return HD_E_NOMEM;
-	uint64_t *tiles_b = (uint64_t *)g.d_cand.p, *pos = tiles_b + scan_tiles_b, *rank = pos + nc;
-	uint32_t *succ0 = (uint32_t *)rank, *succ1 = succ0 + nc, *mark = succ1 + nc, *used = mark + nc, *osize = used + nc;
-	int32_t *pstat = (int32_t *)(osize + nc);
-	uint32_t *stop = (uint32_t *)(pstat + nc);
-	uint32_t *preach = stop + nc;                                            // (carry) every candidate's reach
+	// the passes' nbytes is the last payload byte: a marker there makes no candidate
+	hd::IndexWords *w = nullptr;
+	hd::IndexCand c;
+	uint32_t ncand = 0;
+	r = chain_candidates(g, src, payload_end - 1, &hdr, carry ? hd::INDEX_CARRY : hd::INDEX_STREAM, 0, w, c, ncand, st);
+	if (ncand)
+		summary->ncandidates = ncand;
+	if (r)
+		return r;
 	const uint32_t nwg = (ncand + 255) / 256;
-	HD_CHECK(hipMemsetAsync(pos, 0, 8, st));
-	HD_CHECK(hipMemsetD32Async((hipDeviceptr_t)pos, (int)hdr, 1, st));
-	if (ncand > 1)
-		hipLaunchKernelGGL(hd::k_stream_write, dim3(ntb), dim3(256), 0, st, src, scan_n, (uint64_t)hdr, (const uint64_t *)bitmap, nwords,
-				   (const uint64_t *)tile_off, pos + 1);
 	// one bounded decode per candidate
 	if (carry)
 		hipLaunchKernelGGL(hd::k_carry_piece, dim3(ncand), dim3(64), 0, st,
-				   hd::CarryPieceArgs{ { src, (const uint64_t *)pos, ncand, max_chunk_in, payload_end, osize, used, pstat, stop }, preach });
+				   hd::CarryPieceArgs{ { src, (const uint64_t *)c.pos, ncand, max_chunk_in, payload_end, c.osize, c.used, c.pstat, c.stop },
+						       c.reach });
 	else
 		hipLaunchKernelGGL(hd::k_inflate_piece, dim3(ncand), dim3(64), 0, st,
-				   hd::PieceArgs{ src, (const uint64_t *)pos, ncand, max_chunk_in, payload_end, osize, used, pstat, stop });
-	hipLaunchKernelGGL(hd::k_stream_links, dim3(nwg), dim3(256), 0, st, (const uint64_t *)pos, (const uint32_t *)used,
-			   (const uint32_t *)stop, ncand, succ0, mark);
-	// the true chain: rounds until 2^rounds >= ncand (a chain has at most ncand rows)
-	for (uint64_t reach = 1; reach < ncand; reach *= 2) {
-		hipLaunchKernelGGL(hd::k_index_jump, dim3(nwg), dim3(256), 0, st, (const uint32_t *)succ0, succ1, (const uint32_t *)used, mark,
-				   ncand);
-		std::swap(succ0, succ1);
-	}
-	index_scan(mark, ncand, tiles_b, rank, sum + 0, st);                     // (the successor tables are dead: rank takes their place)
-	HD_CHECK(hipGetLastError());
-	HD_CHECK(hipMemcpyAsync(h, sum, 8, hipMemcpyDeviceToHost, st));
-	HD_CHECK(hipStreamSynchronize(st));
-	const uint64_t nrows = h[0];
+				   hd::PieceArgs{ src, (const uint64_t *)c.pos, ncand, max_chunk_in, payload_end, c.osize, c.used, c.pstat, c.stop });
+	hipLaunchKernelGGL(hd::k_stream_links, dim3(nwg), dim3(256), 0, st, (const uint64_t *)c.pos, (const uint32_t *)c.used,
+			   (const uint32_t *)c.stop, ncand, c.succ0, c.mark);
+	uint64_t nrows = 0;
+	if ((r = chain_rank(c, ncand, c.used, w, &nrows, st)))
+		return r;
 	if (own) {
-		if (own->reserve((size_t)nrows * (carry ? 28 : 24) + 64))
+		if (own->reserve(hd::RowTable::bytes(nrows, carry)))
 			return HD_E_NOMEM;
+		const hd::RowTable t(own->p, nrows, carry);
 		max_chunks = (uint32_t)nrows;
-		in_off = own->p;
-		out_off = (uint64_t *)in_off + nrows;
-		in_len = (uint64_t *)out_off + nrows;
-		out_size = (uint32_t *)in_len + nrows;
-		reach = (uint32_t *)out_size + nrows;
+		in_off = t.in_off, out_off = t.out_off, in_len = t.in_len, out_size = t.out_size, reach = t.reach;
 	}
 	const uint32_t ntab = (uint32_t)(nrows < max_chunks ? nrows : max_chunks);
 	if (nrows) {
-		hipLaunchKernelGGL(hd::k_stream_rows, dim3(nwg), dim3(256), 0, st, (const uint64_t *)pos, (const uint32_t *)used,
-				   (const uint32_t *)osize, (const uint32_t *)mark, (const uint64_t *)rank, ncand, nrows, max_chunks,
-				   (uint64_t *)in_off, (uint32_t *)in_len, (uint32_t *)out_size, sum + 5);
+		hipLaunchKernelGGL(hd::k_stream_rows, dim3(nwg), dim3(256), 0, st, (const uint64_t *)c.pos, (const uint32_t *)c.used,
+				   (const uint32_t *)c.osize, (const uint32_t *)c.mark, (const uint64_t *)c.rank, ncand, nrows, max_chunks,
+				   (uint64_t *)in_off, (uint32_t *)in_len, (uint32_t *)out_size, &w->last);
 		if (ntab)
-			index_scan((const uint32_t *)out_size, ntab, tiles_b, (uint64_t *)out_off, sum + 1, st);
+			index_scan((const uint32_t *)out_size, ntab, c.tiles, (uint64_t *)out_off, &w->out_bytes, st);
 		if (carry && ntab)
-			hipLaunchKernelGGL(hd::k_carry_reach_rows, dim3(nwg), dim3(256), 0, st, (const uint32_t *)preach, (const uint32_t *)mark,
-					   (const uint64_t *)rank, ncand, max_chunks, (uint32_t *)reach);
+			hipLaunchKernelGGL(hd::k_carry_reach_rows, dim3(nwg), dim3(256), 0, st, (const uint32_t *)c.reach, (const uint32_t *)c.mark,
+					   (const uint64_t *)c.rank, ncand, max_chunks, (uint32_t *)reach);
 	}
-	hipLaunchKernelGGL(hd::k_stream_verdict, dim3(1), dim3(1), 0, st, (const uint64_t *)pos, (const uint32_t *)used, (const int32_t *)pstat,
-			   (const uint32_t *)stop, ncand, nrows, max_chunks, max_chunk_in, payload_end, trl, sum);
+	hipLaunchKernelGGL(hd::k_stream_verdict, dim3(1), dim3(1), 0, st, (const uint64_t *)c.pos, (const uint32_t *)c.used,
+			   (const int32_t *)c.pstat, (const uint32_t *)c.stop, ncand, nrows, max_chunks, max_chunk_in, payload_end, trl, &w->rows);
 	if (carry && ntab) {
-		// the reach rule, on the rows in the table: sum[6] as u32 = the first row that reaches back over the stream's start
-		uint32_t *first = (uint32_t *)(sum + 6);
-		HD_CHECK(hipMemsetD32Async((hipDeviceptr_t)first, (int)hd::IDX_NIL, 1, st));
+		// the reach rule, on the rows in the table: w->first = the first row that reaches back over the stream's start
+		HD_CHECK(hipMemsetD32Async((hipDeviceptr_t)&w->first, (int)hd::IDX_NIL, 1, st));
 		hipLaunchKernelGGL(hd::k_carry_check_reach, dim3((ntab + 255) / 256), dim3(256), 0, st, (const uint32_t *)reach,
-				   (const uint64_t *)out_off, ntab, 0xffffffffu, first);
-		hipLaunchKernelGGL(hd::k_carry_cut, dim3(1), dim3(64), 0, st, (const uint32_t *)first, (const uint64_t *)in_off,
-				   (const uint64_t *)out_off, sum);
+				   (const uint64_t *)out_off, ntab, 0xffffffffu, &w->first);
+		hipLaunchKernelGGL(hd::k_carry_cut, dim3(1), dim3(64), 0, st, (const uint32_t *)&w->first, (const uint64_t *)in_off,
+				   (const uint64_t *)out_off, &w->rows);
 	}
-	HD_CHECK(hipGetLastError());
-	HD_CHECK(hipMemcpyAsync(h, sum, 32, hipMemcpyDeviceToHost, st));
-	HD_CHECK(hipStreamSynchronize(st));
-	summary->nchunks = h[0];
-	summary->out_bytes = h[1];
-	summary->end_offset = h[2];
-	summary->status = (uint32_t)h[3];
-	return 0;
+	return chain_read(w, &summary->nchunks, &summary->out_bytes, &summary->end_offset, &summary->status, st);
 }
 
 int hipdeflate_stream_index_dev(const void *strm, uint64_t nbytes, int frame, uint32_t max_chunks, uint32_t max_chunk_in, void *in_off,
 				void *in_len, void *out_size, void *out_off, hipdeflate_stream_index_summary *summary, void *stream)
 {
-	Ctx &g = cur();
-	int r = ensure();
-	if (r)
-		return r;
-	if (!summary)
-		return HD_E_ARG;
-	memset(summary, 0, sizeof *summary);
-	if (!stream_frame_ok(frame) || ((uintptr_t)strm & 15) || (nbytes && !strm) || max_chunk_in >= HD_INFLATE_MAX_IN ||
-	    (max_chunks && (!in_off || !in_len || !out_size || !out_off)))
-		return HD_E_ARG;
-	return stream_index(g, strm, nbytes, frame, max_chunks, max_chunk_in, in_off, in_len, out_size, out_off, summary, (hipStream_t)stream,
-			    nullptr);
-}
-
-int hipdeflate_stream_inflate_table_dev(const void *strm, uint64_t nbytes, int frame, const void *in_off, const void *in_len,
-					const void *out_size, const void *out_off, uint32_t nchunks, void *out, uint64_t out_cap,
-					hipdeflate_stream_summary *summary, void *stream)
-{
-	Ctx &g = cur();
-	int r = ensure();
-	if (r)
-		return r;
-	if (!summary)
-		return HD_E_ARG;
-	memset(summary, 0, sizeof *summary);
-	summary->nchunks = nchunks;
-	summary->bad_chunk = nchunks;
-	if (!stream_frame_ok(frame) || ((uintptr_t)strm & 15) || (nbytes && !strm) || nchunks >= STREAM_MAX_PARTS || (out_cap && !out) ||
-	    (nchunks && (!in_off || !in_len || !out_size || !out_off)))
-		return HD_E_ARG;
-	if (nchunks == 0) {                                           // a stream has its final block, and that is a row
-		summary->status = 1;
-		return 0;
-	}
-	hipStream_t st = (hipStream_t)stream;
-	const uint32_t trl = stream_trl(frame);
-	const uint32_t kind = frame == HD_FRAME_ZLIB ? hd::CHECK_ADLER32 : hd::CHECK_CRC32;
-	const size_t n = nchunks, ntiles = (n + hd::SCAN_TILE - 1) / hd::SCAN_TILE;
-	std::lock_guard<std::mutex> lk(g.mu_index);
-	// sum[8] | the header's [8], then where the rows end [2] | scan tiles | prefix [n] | out_len, check, status [n]
-	if (g.d_stream.reserve((18 + ntiles + n) * 8 + 3 * n * 4))
-		return HD_E_NOMEM;
-	uint64_t *sum = (uint64_t *)g.d_stream.p, *ends = sum + 16, *tiles = ends + 2, *prefix = tiles + ntiles;
-	uint32_t *out_len = (uint32_t *)(prefix + n), *chk = out_len + n;
-	int32_t *status = (int32_t *)(chk + n);
-	uint32_t hdr = 0, refused = 0;
-	if ((r = stream_open(strm, nbytes, frame, sum + 8, st, &hdr, &refused)))
-		return r;
-	if (refused) {
-		summary->status = 1;
-		return 0;
-	}
-	uint32_t *carry = (uint32_t *)(sum + 4), *d_fault = carry + 1, *d_bad = carry + 3;
-	HD_CHECK(hipMemsetAsync(sum, 0, 64, st));
-	HD_CHECK(hipMemsetAsync(ends, 0, 16, st));
-	HD_CHECK(hipMemsetD32Async((hipDeviceptr_t)carry, kind == hd::CHECK_ADLER32 ? 1 : 0, 1, st));
-	HD_CHECK(hipMemsetD32Async((hipDeviceptr_t)d_fault, (int)hd::IDX_NIL, 1, st));
-	HD_CHECK(hipMemsetD32Async((hipDeviceptr_t)d_bad, (int)hd::IDX_NIL, 1, st));
-	hipLaunchKernelGGL(hd::k_stream_check_rows, dim3((nchunks + 255) / 256), dim3(256), 0, st, (const uint64_t *)in_off,
-			   (const uint32_t *)in_len, (const uint32_t *)out_size, (const uint64_t *)out_off, nchunks, (uint64_t)hdr, nbytes - trl,
-			   d_fault, ends);
-	HD_CHECK(hipGetLastError());
-	uint32_t h[4] = { 0, 0, 0, 0 };
-	uint64_t e[2] = { 0, 0 };
-	HD_CHECK(hipMemcpyAsync(h, carry, 16, hipMemcpyDeviceToHost, st));
-	HD_CHECK(hipMemcpyAsync(e, ends, 16, hipMemcpyDeviceToHost, st));
-	HD_CHECK(hipStreamSynchronize(st));
-	if (h[1] != hd::IDX_NIL) {
-		summary->status = 1;
-		summary->bad_chunk = h[1];
-		return 0;
-	}
-	if (out_cap < e[1]) {
-		summary->status = 3;
-		summary->out_bytes = e[1];
-		return 0;
-	}
-	// the trailer lies behind the last row, wherever the caller's buffer ends
-	return stream_decode_rows(g, strm, e[0] + trl, frame,
-				  { (const uint64_t *)in_off, (const uint32_t *)in_len, (const uint64_t *)out_off, (const uint32_t *)out_size, out_len,
-				    chk, status, tiles, prefix, sum },
-				  nchunks, e[1], out, summary, st);
+	return stream_index(cur(), strm, nbytes, frame, max_chunks, max_chunk_in, in_off, in_len, out_size, out_off, summary,
+			    (hipStream_t)stream, nullptr);
 }
 
 /* ---- ... and a stream cut by sync flushes, which carry the window across the cut (hd_carry.hpp) ---- */
@@ -1931,147 +1775,62 @@ int hipdeflate_stream_index_carry_dev(const void *strm, uint64_t nbytes, int fra
 				      void *in_len, void *out_size, void *out_off, void *reach, hipdeflate_stream_index_summary *summary,
 				      void *stream)
 {
-	Ctx &g = cur();
-	int r = ensure();
-	if (r)
-		return r;
-	if (!summary)
-		return HD_E_ARG;
-	memset(summary, 0, sizeof *summary);
-	if (!stream_frame_ok(frame) || ((uintptr_t)strm & 15) || (nbytes && !strm) || max_chunk_in >= HD_INFLATE_MAX_IN ||
-	    (max_chunks && (!in_off || !in_len || !out_size || !out_off || !reach)))
-		return HD_E_ARG;
-	return stream_index(g, strm, nbytes, frame, max_chunks, max_chunk_in, in_off, in_len, out_size, out_off, summary, (hipStream_t)stream,
-			    nullptr, true, reach);
+	return stream_index(cur(), strm, nbytes, frame, max_chunks, max_chunk_in, in_off, in_len, out_size, out_off, summary,
+			    (hipStream_t)stream, nullptr, true, reach);
 }
 
-int hipdeflate_stream_inflate_carry_dev(const void *strm, uint64_t nbytes, int frame, const void *in_off, const void *in_len,
-					const void *out_size, const void *out_off, const void *reach, uint32_t nchunks, void *out,
-					uint64_t out_cap, hipdeflate_stream_summary *summary, void *stream)
+// The carry decode's rows, group by group in stream order: the check runs on in d.w->v.check, the lowest bad row in v.bad
+static int carry_decode_groups(Ctx &g, const void *strm, uint32_t kind, const StreamRows &t, const hd::DecodeScratch &d, uint32_t nchunks,
+			       void *out, hipStream_t st)
 {
-	Ctx &g = cur();
-	int r = ensure();
-	if (r)
-		return r;
-	if (!summary)
-		return HD_E_ARG;
-	memset(summary, 0, sizeof *summary);
-	summary->nchunks = nchunks;
-	summary->bad_chunk = nchunks;
-	if (!stream_frame_ok(frame) || ((uintptr_t)strm & 15) || (nbytes && !strm) || nchunks >= STREAM_MAX_PARTS || (out_cap && !out) ||
-	    (nchunks && (!in_off || !in_len || !out_size || !out_off || !reach)))
-		return HD_E_ARG;
-	if (nchunks == 0) {                                           // a stream has its final block, and that is a row
-		summary->status = 1;
-		return 0;
-	}
-	hipStream_t st = (hipStream_t)stream;
-	const uint32_t trl = stream_trl(frame);
-	const uint32_t kind = frame == HD_FRAME_ZLIB ? hd::CHECK_ADLER32 : hd::CHECK_CRC32;
-	const size_t n = nchunks, ntiles = (n + hd::SCAN_TILE - 1) / hd::SCAN_TILE;
-	const uint64_t *t_in_off = (const uint64_t *)in_off, *t_out_off = (const uint64_t *)out_off;
-	const uint32_t *t_in_len = (const uint32_t *)in_len, *t_out_size = (const uint32_t *)out_size, *t_reach = (const uint32_t *)reach;
-	std::lock_guard<std::mutex> lk(g.mu_index);
-	// sum[8] | the header's [8], then where the rows end [2], the group's record [4] | scan tiles | prefix [n] | out_len, check, status [n]
-	if (g.d_stream.reserve((22 + ntiles + n) * 8 + 3 * n * 4))
-		return HD_E_NOMEM;
-	uint64_t *sum = (uint64_t *)g.d_stream.p, *ends = sum + 16, *rec = ends + 2, *tiles = rec + 4, *prefix = tiles + ntiles;
-	uint32_t *out_len = (uint32_t *)(prefix + n), *chk = out_len + n;
-	int32_t *status = (int32_t *)(chk + n);
-	uint32_t hdr = 0, refused = 0;
-	if ((r = stream_open(strm, nbytes, frame, sum + 8, st, &hdr, &refused)))
-		return r;
-	if (refused) {
-		summary->status = 1;
-		return 0;
-	}
-	// sum[4..5] as u32: the folded check | the lowest row of the table at fault | the trailer disagrees | the lowest bad row
-	uint32_t *carry = (uint32_t *)(sum + 4), *d_fault = carry + 1, *d_mismatch = carry + 2, *d_bad = carry + 3;
-	HD_CHECK(hipMemsetAsync(sum, 0, 64, st));
-	HD_CHECK(hipMemsetAsync(ends, 0, 16, st));
-	HD_CHECK(hipMemsetD32Async((hipDeviceptr_t)carry, kind == hd::CHECK_ADLER32 ? 1 : 0, 1, st));
-	HD_CHECK(hipMemsetD32Async((hipDeviceptr_t)d_fault, (int)hd::IDX_NIL, 1, st));
-	HD_CHECK(hipMemsetD32Async((hipDeviceptr_t)d_bad, (int)hd::IDX_NIL, 1, st));
-	hipLaunchKernelGGL(hd::k_stream_check_rows, dim3((nchunks + 255) / 256), dim3(256), 0, st, t_in_off, t_in_len, t_out_size, t_out_off,
-			   nchunks, (uint64_t)hdr, nbytes - trl, d_fault, ends);
-	hipLaunchKernelGGL(hd::k_carry_check_reach, dim3((nchunks + 255) / 256), dim3(256), 0, st, t_reach, t_out_off, nchunks,
-			   hd::CARRY_WINDOW, d_fault);
-	HD_CHECK(hipGetLastError());
-	uint32_t h[4] = { 0, 0, 0, 0 };
-	uint64_t e[2] = { 0, 0 };
-	HD_CHECK(hipMemcpyAsync(h, carry, 16, hipMemcpyDeviceToHost, st));
-	HD_CHECK(hipMemcpyAsync(e, ends, 16, hipMemcpyDeviceToHost, st));
-	HD_CHECK(hipStreamSynchronize(st));
-	if (h[1] != hd::IDX_NIL) {
-		summary->status = 1;
-		summary->bad_chunk = h[1];
-		return 0;
-	}
-	if (out_cap < e[1]) {
-		summary->status = 3;
-		summary->out_bytes = e[1];
-		return 0;
-	}
-	// group by group, in stream order: the check runs on in *carry, the lowest bad row in *d_bad
+	int r;
+	uint32_t *carry = &d.w->v.check, *d_bad = &d.w->v.bad;
 	const uint64_t group_bytes = g_test_carry_group ? g_test_carry_group : HD_CARRY_GROUP_BYTES;
 	for (uint32_t r0 = 0; r0 < nchunks;) {
 		uint64_t gr[4];
-		hipLaunchKernelGGL(hd::k_carry_group, dim3(1), dim3(256), 0, st, t_out_off, t_out_size, t_reach, r0, nchunks, group_bytes, rec);
+		hd::StreamVerdict h;
+		hipLaunchKernelGGL(hd::k_carry_group, dim3(1), dim3(256), 0, st, t.out_off, t.out_size, t.reach, r0, nchunks, group_bytes, d.group);
 		HD_CHECK(hipGetLastError());
-		HD_CHECK(hipMemcpyAsync(gr, rec, 32, hipMemcpyDeviceToHost, st));
-		HD_CHECK(hipMemcpyAsync(h, carry, 16, hipMemcpyDeviceToHost, st));
+		HD_CHECK(hipMemcpyAsync(gr, d.group, 32, hipMemcpyDeviceToHost, st));
+		HD_CHECK(hipMemcpyAsync(&h, &d.w->v, sizeof h, hipMemcpyDeviceToHost, st));
 		HD_CHECK(hipStreamSynchronize(st));
-		if (h[3] != hd::IDX_NIL)
+		if (h.bad != hd::IDX_NIL)
 			break;                                                    // a row of an earlier group is bad: the verdict is in
 		const uint32_t r1 = (uint32_t)gr[0], nr = r1 - r0;
 		const uint64_t begin = gr[2], gbytes = gr[3] - gr[2];
-		if (gr[1] == 0) {
-			// no row of the group reaches back: the flush-rule batch inflate into place, as stream_decode_rows does it
-			if ((r = launch_inflate({ (const uint8_t *)strm, t_in_off + r0, t_in_len + r0, nr, (uint8_t *)out, t_out_off + r0,
-						  t_out_size + r0, out_len + r0, kind == hd::CHECK_ADLER32 ? nullptr : chk + r0, status + r0,
-						  g.d_ct, hd::INF_FLUSHED }, st)))
-				return r;
-			if (kind == hd::CHECK_ADLER32)
-				hipLaunchKernelGGL(hd::k_chunk_adler, dim3(nr), dim3(64), 0, st, (const uint8_t *)out, t_out_off + r0,
-						   (const uint32_t *)(out_len + r0), t_out_size + r0, nr, chk + r0);
-			hipLaunchKernelGGL(hd::k_carry_verify, dim3((nr + 255) / 256), dim3(256), 0, st, (const int32_t *)status,
-					   (const uint32_t *)out_len, t_out_size, r0, nr, d_bad);
-			if ((r = fold_launch(chk + r0, t_out_size + r0, nr, kind, tiles, prefix, sum + 1, carry, st)))
+		if (gr[1] == 0) {                                                 // no row of the group reaches back
+			if ((r = stream_rows_flushed(g, strm, kind, t, d, r0, nr, out, st)))
 				return r;
 		} else {
-			// the marker path: symbols | the check's pieces: off, prefix u64[np], scan tiles | len, check u32[np]
+			// the marker path: the group as symbols, and its check in pieces
 			const uint64_t np64 = (gbytes + HD_CARRY_CHECK_PIECE - 1) / HD_CARRY_CHECK_PIECE;
-			if (np64 >= STREAM_MAX_PARTS)
+			if (np64 >= STREAM_MAX_PARTS || gbytes > (uint64_t)1 << 40 ||
+			    g.d_stream_slots.reserve(hd::MarkerScratch::bytes(gbytes, np64)))
 				return HD_E_NOMEM;
 			const uint32_t np = (uint32_t)np64;
-			const size_t sym_bytes = (size_t)((2 * gbytes + 15) & ~(uint64_t)15), ptiles_n = ((size_t)np + hd::SCAN_TILE - 1) / hd::SCAN_TILE;
-			if (gbytes > (uint64_t)1 << 40 || g.d_stream_slots.reserve(sym_bytes + ((size_t)np * 2 + ptiles_n) * 8 + (size_t)np * 8 + 16))
-				return HD_E_NOMEM;
-			uint16_t *sym = (uint16_t *)g.d_stream_slots.p;
-			uint64_t *poff = (uint64_t *)((uint8_t *)g.d_stream_slots.p + sym_bytes), *pprefix = poff + np, *ptiles = pprefix + np;
-			uint32_t *plen = (uint32_t *)(ptiles + ptiles_n), *pchk = plen + np;
+			const hd::MarkerScratch m(g.d_stream_slots.p, gbytes, np);
 			CarryTimer tm(g_carry_timed);
 			tm.mark(0, st);
 			hipLaunchKernelGGL(hd::k_carry_decode, dim3(nr), dim3(64), 0, st,
-					   hd::CarryDecodeArgs{ (const uint8_t *)strm, t_in_off, t_in_len, t_out_size, t_out_off, t_reach, r0, nr, begin,
-								sym, out_len, status });
-			const hd::CarryRowsArgs ra{ sym, begin, t_out_off, t_out_size, out_len, status, r0, nr, (uint8_t *)out };
+					   hd::CarryDecodeArgs{ (const uint8_t *)strm, t.in_off, t.in_len, t.out_size, t.out_off, t.reach, r0, nr, begin,
+								m.sym, d.out_len, d.status });
+			const hd::CarryRowsArgs ra{ m.sym, begin, t.out_off, t.out_size, d.out_len, d.status, r0, nr, (uint8_t *)out };
 			tm.mark(1, st);
 			hipLaunchKernelGGL(hd::k_carry_tails, dim3(1), dim3(hd::CARRY_TAIL_THREADS), 0, st, ra);
 			tm.mark(2, st);
 			hipLaunchKernelGGL(hd::k_carry_resolve, dim3(nr), dim3(256), 0, st, ra);
 			tm.mark(3, st);
-			hipLaunchKernelGGL(hd::k_carry_verify, dim3((nr + 255) / 256), dim3(256), 0, st, (const int32_t *)status,
-					   (const uint32_t *)out_len, t_out_size, r0, nr, d_bad);
+			hipLaunchKernelGGL(hd::k_carry_verify, dim3((nr + 255) / 256), dim3(256), 0, st, (const int32_t *)d.status,
+					   (const uint32_t *)d.out_len, t.out_size, r0, nr, d_bad);
 			if (np) {
-				hipLaunchKernelGGL(hd::k_carry_parts, dim3((np + 255) / 256), dim3(256), 0, st, begin, gr[3], np, poff, plen);
+				hipLaunchKernelGGL(hd::k_carry_parts, dim3((np + 255) / 256), dim3(256), 0, st, begin, gr[3], np, m.off, m.len);
 				if (kind == hd::CHECK_ADLER32)
-					hipLaunchKernelGGL(hd::k_chunk_adler, dim3(np), dim3(64), 0, st, (const uint8_t *)out, (const uint64_t *)poff,
-							   (const uint32_t *)plen, (const uint32_t *)nullptr, np, pchk);
+					hipLaunchKernelGGL(hd::k_chunk_adler, dim3(np), dim3(64), 0, st, (const uint8_t *)out, (const uint64_t *)m.off,
+							   (const uint32_t *)m.len, (const uint32_t *)nullptr, np, m.chk);
 				else
 					hipLaunchKernelGGL(hd::k_carry_crc, dim3(np), dim3(64), 0, st, (const CrcTables *)g.d_ct, (const uint8_t *)out,
-							   (const uint64_t *)poff, (const uint32_t *)plen, np, pchk);
-				if ((r = fold_launch(pchk, plen, np, kind, ptiles, pprefix, sum + 1, carry, st)))
+							   (const uint64_t *)m.off, (const uint32_t *)m.len, np, m.chk);
+				if ((r = fold_launch(m.chk, m.len, np, kind, m.tiles, m.prefix, d.w->fold, carry, st)))
 					return r;
 			}
 			tm.mark(4, st);
@@ -2079,22 +1838,107 @@ int hipdeflate_stream_inflate_carry_dev(const void *strm, uint64_t nbytes, int f
 		}
 		r0 = r1;
 	}
-	// the trailer lies behind the last row, wherever the caller's buffer ends
-	hipLaunchKernelGGL(hd::k_stream_trailer, dim3(1), dim3(64), 0, st, (const uint8_t *)strm, e[0] + trl, frame, e[1], (const uint32_t *)carry,
-			   d_mismatch);
-	HD_CHECK(hipGetLastError());
-	HD_CHECK(hipMemcpyAsync(h, carry, 16, hipMemcpyDeviceToHost, st));
-	HD_CHECK(hipStreamSynchronize(st));
-	summary->out_bytes = e[1];
-	summary->in_bytes = e[0] + trl;
-	summary->check = h[0];
-	if (h[3] != hd::IDX_NIL) {
-		summary->status = 2;
-		summary->bad_chunk = h[3];
-	} else if (h[2]) {
-		summary->status = 2;
-	}
 	return 0;
+}
+
+// The three decoders behind their entry points.  By rows: the caller's table t held to the stream's rules (carry: and its
+// reach column), the trailer behind the last row wherever the caller's buffer ends.  By chunks (ct): the rows made from the
+// chunk table by k_stream_check_table, the trailer at the buffer's end.  Then the rows decoded -- side by side by the flush
+// rule, or group by group -- and the folded check held to the trailer.
+struct StreamChunks {
+	const uint64_t *off;
+	uint32_t bytes;
+	uint64_t out_bytes;
+};
+static int stream_inflate_rows(Ctx &g, const void *strm, uint64_t nbytes, int frame, StreamRows t, const StreamChunks *ct, bool carry,
+			       uint32_t nchunks, void *out, uint64_t out_cap, hipdeflate_stream_summary *summary, hipStream_t st)
+{
+	int r = enter_call(summary, sizeof *summary);
+	if (r)
+		return r;
+	summary->bad_chunk = summary->nchunks = nchunks;
+	if (!stream_frame_ok(frame) || ((uintptr_t)strm & 15) || (nbytes && !strm) || nchunks >= STREAM_MAX_PARTS || (out_cap && !out) ||
+	    (ct ? !stream_chunk_ok(ct->bytes) || !ct->off
+		: nchunks && (!t.in_off || !t.in_len || !t.out_size || !t.out_off || (carry && !t.reach))))
+		return HD_E_ARG;
+	const uint32_t trl = stream_trl(frame), kind = frame == HD_FRAME_ZLIB ? hd::CHECK_ADLER32 : hd::CHECK_CRC32;
+	// before any byte is looked at, and before the lock.  By chunks: what nchunks and the chunk size allow, a stream long
+	// enough for its two ends.  By rows: a stream has its final block, and that is a row
+	if (ct ? (ct->out_bytes + ct->bytes - 1) / ct->bytes != nchunks || nbytes < (uint64_t)stream_hdr(frame) + 2 + trl : nchunks == 0) {
+		summary->status = 1;
+		return 0;
+	}
+	std::lock_guard<std::mutex> lk(g.mu_index);
+	if (g.d_stream.reserve(hd::DecodeScratch::bytes(nchunks, ct != nullptr)))
+		return HD_E_NOMEM;
+	const hd::DecodeScratch d(g.d_stream.p, nchunks, ct != nullptr);
+	uint32_t hdr = 0, refused = 0;
+	if (!ct && (r = stream_open(strm, nbytes, frame, d.header, st, &hdr, &refused)))
+		return r;
+	if (refused) {
+		summary->status = 1;
+		return 0;
+	}
+	if ((r = stream_words_reset(d.w, kind, st)))
+		return r;
+	uint64_t e[2] = { nbytes - trl, ct ? ct->out_bytes : 0 };     // where the rows end: in the stream, in the output
+	if (ct) {
+		hipLaunchKernelGGL(hd::k_stream_check_table, dim3((nchunks + 1 + 255) / 256), dim3(256), 0, st, (const uint8_t *)strm, nbytes,
+				   ct->off, nchunks, ct->bytes, ct->out_bytes, frame, d.in_off, d.in_len, d.out_off, d.out_size, &d.w->v.fault);
+		t = { d.in_off, d.in_len, d.out_off, d.out_size, nullptr };
+	} else {
+		HD_CHECK(hipMemsetAsync(d.ends, 0, 16, st));
+		hipLaunchKernelGGL(hd::k_stream_check_rows, dim3((nchunks + 255) / 256), dim3(256), 0, st, t.in_off, t.in_len, t.out_size,
+				   t.out_off, nchunks, (uint64_t)hdr, nbytes - trl, &d.w->v.fault, d.ends);
+		if (carry)
+			hipLaunchKernelGGL(hd::k_carry_check_reach, dim3((nchunks + 255) / 256), dim3(256), 0, st, t.reach, t.out_off, nchunks,
+					   hd::CARRY_WINDOW, &d.w->v.fault);
+	}
+	HD_CHECK(hipGetLastError());
+	hd::StreamVerdict h;
+	HD_CHECK(hipMemcpyAsync(&h, &d.w->v, sizeof h, hipMemcpyDeviceToHost, st));
+	if (!ct)
+		HD_CHECK(hipMemcpyAsync(e, d.ends, 16, hipMemcpyDeviceToHost, st));
+	HD_CHECK(hipStreamSynchronize(st));
+	if (h.fault != hd::IDX_NIL) {
+		summary->status = 1;
+		summary->bad_chunk = h.fault;
+		return 0;
+	}
+	if (out_cap < e[1]) {
+		summary->status = 3;
+		summary->out_bytes = ct ? 0 : e[1];
+		return 0;
+	}
+	if ((r = carry ? carry_decode_groups(g, strm, kind, t, d, nchunks, out, st) : stream_rows_flushed(g, strm, kind, t, d, 0, nchunks, out, st)))
+		return r;
+	return stream_decode_end(strm, e[0] + trl, frame, e[1], d.w, summary, st);
+}
+
+int hipdeflate_stream_inflate_dev(const void *strm, uint64_t nbytes, int frame, const void *chunk_off, uint32_t nchunks,
+				  uint32_t chunk_bytes, uint64_t out_bytes, void *out, uint64_t out_cap,
+				  hipdeflate_stream_summary *summary, void *stream)
+{
+	const StreamChunks ct = { (const uint64_t *)chunk_off, chunk_bytes, out_bytes };
+	return stream_inflate_rows(cur(), strm, nbytes, frame, {}, &ct, false, nchunks, out, out_cap, summary, (hipStream_t)stream);
+}
+
+int hipdeflate_stream_inflate_table_dev(const void *strm, uint64_t nbytes, int frame, const void *in_off, const void *in_len,
+					const void *out_size, const void *out_off, uint32_t nchunks, void *out, uint64_t out_cap,
+					hipdeflate_stream_summary *summary, void *stream)
+{
+	return stream_inflate_rows(cur(), strm, nbytes, frame,
+				   { (const uint64_t *)in_off, (const uint32_t *)in_len, (const uint64_t *)out_off, (const uint32_t *)out_size, nullptr },
+				   nullptr, false, nchunks, out, out_cap, summary, (hipStream_t)stream);
+}
+
+int hipdeflate_stream_inflate_carry_dev(const void *strm, uint64_t nbytes, int frame, const void *in_off, const void *in_len,
+					const void *out_size, const void *out_off, const void *reach, uint32_t nchunks, void *out,
+					uint64_t out_cap, hipdeflate_stream_summary *summary, void *stream)
+{
+	const StreamRows t = { (const uint64_t *)in_off, (const uint32_t *)in_len, (const uint64_t *)out_off, (const uint32_t *)out_size,
+			       (const uint32_t *)reach };
+	return stream_inflate_rows(cur(), strm, nbytes, frame, t, nullptr, true, nchunks, out, out_cap, summary, (hipStream_t)stream);
 }
 
 /* ---- host-pointer API ------------------------------------------------------ */
@@ -3251,7 +3095,10 @@ int hip_deflate_stream(unsigned char *dest, size_t *destLen, const unsigned char
 	return 0;
 }
 
-int hip_inflate_stream(unsigned char *dest, size_t *destLen, const unsigned char *source, size_t sourceLen, int frame, size_t *in_used)
+// hip_inflate_stream and, for a stream whose flushes carry the window (carry), hip_inflate_stream_carry: stage, index,
+// decode.  The row table stays on the device, in d_meta, as large as the stream needs
+static int inflate_stream_host(unsigned char *dest, size_t *destLen, const unsigned char *source, size_t sourceLen, int frame,
+			       size_t *in_used, bool carry)
 {
 	Ctx &g = cur();
 	int r = ensure();
@@ -3266,10 +3113,8 @@ int hip_inflate_stream(unsigned char *dest, size_t *destLen, const unsigned char
 		return HD_E_NOMEM;
 	if (sourceLen)
 		HD_CHECK(hipMemcpyAsync(g.d_in.p, source, sourceLen, hipMemcpyHostToDevice, g.stream));
-	// stage, index, decode: the table stays on the device, in d_meta, as large as the stream needs
 	hipdeflate_stream_index_summary xs;
-	memset(&xs, 0, sizeof xs);
-	if ((r = stream_index(g, g.d_in.p, sourceLen, frame, 0, 0, nullptr, nullptr, nullptr, nullptr, &xs, g.stream, &g.d_meta)))
+	if ((r = stream_index(g, g.d_in.p, sourceLen, frame, 0, 0, nullptr, nullptr, nullptr, nullptr, &xs, g.stream, &g.d_meta, carry)))
 		return r;
 	g.stream_drained(g.stream);
 	if (in_used)
@@ -3282,12 +3127,10 @@ int hip_inflate_stream(unsigned char *dest, size_t *destLen, const unsigned char
 	}
 	if (g.d_packed.reserve(up16(xs.out_bytes) + 16))
 		return HD_E_NOMEM;
-	const uint64_t n = xs.nchunks;
-	const uint64_t *in_off = (const uint64_t *)g.d_meta.p, *out_off = in_off + n;
-	const uint32_t *in_len = (const uint32_t *)(out_off + n), *out_size = in_len + n;
+	const hd::RowTable t(g.d_meta.p, xs.nchunks, carry);         // (status 0: the chain's rows, which the table's layout goes by)
 	hipdeflate_stream_summary s;
-	if ((r = hipdeflate_stream_inflate_table_dev(g.d_in.p, xs.end_offset, frame, in_off, in_len, out_size, out_off, (uint32_t)n,
-						     g.d_packed.p, xs.out_bytes, &s, g.stream)))
+	if ((r = stream_inflate_rows(g, g.d_in.p, xs.end_offset, frame, { t.in_off, t.in_len, t.out_off, t.out_size, t.reach }, nullptr, carry,
+				     (uint32_t)xs.nchunks, g.d_packed.p, xs.out_bytes, &s, g.stream)))
 		return r;
 	if (s.status)
 		return 1;
@@ -3297,50 +3140,14 @@ int hip_inflate_stream(unsigned char *dest, size_t *destLen, const unsigned char
 	return 0;
 }
 
-// hip_inflate_stream for a stream whose flushes carry the window: the carry index and the carry decode behind the staging
+int hip_inflate_stream(unsigned char *dest, size_t *destLen, const unsigned char *source, size_t sourceLen, int frame, size_t *in_used)
+{
+	return inflate_stream_host(dest, destLen, source, sourceLen, frame, in_used, false);
+}
+
 int hip_inflate_stream_carry(unsigned char *dest, size_t *destLen, const unsigned char *source, size_t sourceLen, int frame, size_t *in_used)
 {
-	Ctx &g = cur();
-	int r = ensure();
-	if (r)
-		return r;
-	if (!destLen || (*destLen && !dest) || (sourceLen && !source) || !stream_frame_ok(frame))
-		return HD_E_ARG;
-	std::lock_guard<std::mutex> lk(g.mu);
-	if ((r = bind_device(g)))
-		return r;
-	if (g.d_in.reserve(up16(sourceLen) + 16))
-		return HD_E_NOMEM;
-	if (sourceLen)
-		HD_CHECK(hipMemcpyAsync(g.d_in.p, source, sourceLen, hipMemcpyHostToDevice, g.stream));
-	hipdeflate_stream_index_summary xs;
-	memset(&xs, 0, sizeof xs);
-	if ((r = stream_index(g, g.d_in.p, sourceLen, frame, 0, 0, nullptr, nullptr, nullptr, nullptr, &xs, g.stream, &g.d_meta, true)))
-		return r;
-	g.stream_drained(g.stream);
-	if (in_used)
-		*in_used = xs.end_offset;
-	if (xs.status)
-		return 1;
-	if (xs.out_bytes > *destLen) {
-		*destLen = xs.out_bytes;
-		return 3;
-	}
-	if (g.d_packed.reserve(up16(xs.out_bytes) + 16))
-		return HD_E_NOMEM;
-	const uint64_t n = xs.nchunks;                               // (status 0: the chain's rows, which the table's layout goes by)
-	const uint64_t *in_off = (const uint64_t *)g.d_meta.p, *out_off = in_off + n;
-	const uint32_t *in_len = (const uint32_t *)(out_off + n), *out_size = in_len + n, *reach = out_size + n;
-	hipdeflate_stream_summary s;
-	if ((r = hipdeflate_stream_inflate_carry_dev(g.d_in.p, xs.end_offset, frame, in_off, in_len, out_size, out_off, reach, (uint32_t)n,
-						     g.d_packed.p, xs.out_bytes, &s, g.stream)))
-		return r;
-	if (s.status)
-		return 1;
-	if (xs.out_bytes)
-		HD_CHECK(hipMemcpy(dest, g.d_packed.p, xs.out_bytes, hipMemcpyDeviceToHost));
-	*destLen = xs.out_bytes;
-	return 0;
+	return inflate_stream_host(dest, destLen, source, sourceLen, frame, in_used, true);
 }
 
 } // extern "C"
