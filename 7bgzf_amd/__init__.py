@@ -63,6 +63,15 @@ class StreamIndexSummary(ctypes.Structure):
                 ("ncandidates", ctypes.c_uint64), ("hdr_bytes", ctypes.c_uint32), ("status", ctypes.c_uint32)]
 
 
+class BlockIndexSummary(ctypes.Structure):
+    """hipdeflate_block_index_summary (include/hipdeflate.h)"""
+    _fields_ = [("nrows", ctypes.c_uint64), ("npieces", ctypes.c_uint64), ("out_bytes", ctypes.c_uint64),
+                ("end_offset", ctypes.c_uint64), ("end_bit", ctypes.c_uint64), ("ncandidates", ctypes.c_uint64),
+                ("hdr_bytes", ctypes.c_uint32), ("status", ctypes.c_uint32)]
+
+
+BLOCK_PIECE_IN = 1 << 20             # include/hipdeflate_params.h HD_BLOCK_PIECE_IN: max_chunk_in of the convenience calls' first index
+BLOCK_ROW_BYTES = 128 << 10          # include/hipdeflate_params.h HD_BLOCK_ROW_BYTES: output bytes the block index merges a row to
 STREAM_WINDOW_BYTES = 1 << 30        # include/hipdeflate_params.h HD_STREAM_WINDOW_BYTES: slots of one window of the stream encoder
 CHECK_CRC32, CHECK_ADLER32 = 0, 1    # `kind` of hipdeflate_check_combine_dev
 RANGE_BYTES, RANGE_VOFFSET = 0, 1    # HD_RANGE_*: what the begin / end of a ranged read are
@@ -91,6 +100,9 @@ EXPORTS = [
     "hipdeflate_stream_index_dev", "hipdeflate_stream_inflate_table_dev", "hip_inflate_stream",
     "hipdeflate_stream_index_carry_dev", "hipdeflate_stream_inflate_carry_dev", "hip_inflate_stream_carry",
     "hipdeflate_test_carry_group", "hipdeflate_test_carry_times",
+    "hipdeflate_stream_index_blocks_dev", "hipdeflate_stream_inflate_blocks_dev", "hip_inflate_stream_blocks",
+    "hipdeflate_test_block_headers_dev", "hipdeflate_test_blocks_times", "hipdeflate_test_blocks_counts",
+    "hipdeflate_test_block_candidates_dev",
     "hipdeflate_init_devices", "hipdeflate_device_count", "hipdeflate_use_device",
     "hipdeflate_pipe_open_on", "hipdeflate_unpipe_open_on", "hipdeflate_lat_open_on",
     "hipdeflate_batch_inflate_size_dev", "hipdeflate_batch_inflate_framed_dev", "hipdeflate_batch_inflate_size",
@@ -203,6 +215,18 @@ def lib():
     L.hipdeflate_test_carry_group.restype = None
     L.hipdeflate_test_carry_times.argtypes = [ctypes.POINTER(ctypes.c_double)]
     L.hipdeflate_test_carry_times.restype = None
+    L.hipdeflate_stream_index_blocks_dev.argtypes = [_vp, ctypes.c_uint64, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                                     _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(BlockIndexSummary), _vp]
+    L.hipdeflate_stream_inflate_blocks_dev.argtypes = [_vp, ctypes.c_uint64, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint32, _vp,
+                                                       ctypes.c_uint64, ctypes.POINTER(StreamSummary), _vp]
+    L.hip_inflate_stream_blocks.argtypes = [_vp, sz_p, _vp, ctypes.c_size_t, ctypes.c_int, sz_p]
+    L.hipdeflate_test_block_headers_dev.argtypes = [_vp, ctypes.c_uint64, _vp, ctypes.c_uint32, _vp, _vp]
+    L.hipdeflate_test_blocks_times.argtypes = [ctypes.POINTER(ctypes.c_double)]
+    L.hipdeflate_test_blocks_times.restype = None
+    L.hipdeflate_test_blocks_counts.argtypes = [ctypes.POINTER(ctypes.c_uint64)]
+    L.hipdeflate_test_blocks_counts.restype = None
+    L.hipdeflate_test_block_candidates_dev.argtypes = [_vp, ctypes.c_uint64, ctypes.c_uint64, _vp, ctypes.c_uint32,
+                                                       ctypes.POINTER(ctypes.c_uint64), _vp]
     L.hipdeflate_pipe_open.restype = _vp
     L.hipdeflate_pipe_open.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int]
     L.hipdeflate_pipe_input.restype = _vp
@@ -321,6 +345,16 @@ def hip_inflate_stream_carry(data, cap, frame=FRAME_GZIP):
     dst = np.zeros(max(cap, 1), dtype=np.uint8)
     n, used = ctypes.c_size_t(cap), ctypes.c_size_t(0)
     r = lib().hip_inflate_stream_carry(_p(dst), ctypes.byref(n), _p(src), len(src), frame, ctypes.byref(used))
+    return r, bytes(dst[: n.value]) if r == 0 else b"", n.value, used.value
+
+
+def hip_inflate_stream_blocks(data, cap, frame=FRAME_GZIP):
+    """hip_inflate_stream for a plain stream, which has no flush point (gzip, zlib.compress, an IDAT): the block index and the
+    block decode behind host buffers -> (ret, bytes, need, in_used), as hip_inflate_stream gives them"""
+    src = as_u8(data)
+    dst = np.zeros(max(cap, 1), dtype=np.uint8)
+    n, used = ctypes.c_size_t(cap), ctypes.c_size_t(0)
+    r = lib().hip_inflate_stream_blocks(_p(dst), ctypes.byref(n), _p(src), len(src), frame, ctypes.byref(used))
     return r, bytes(dst[: n.value]) if r == 0 else b"", n.value, used.value
 
 

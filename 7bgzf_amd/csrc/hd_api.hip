@@ -27,6 +27,7 @@
 #include "hd_range.hpp"
 #include "hd_stream.hpp"
 #include "hd_carry.hpp"
+#include "hd_blocks.hpp"
 #include "hd_segment.hpp"
 #include "hd_tables.hpp"
 #include "hd_scratch.hpp"
@@ -196,6 +197,8 @@ struct Ctx {
 	Buf d_range, d_range_out;
 	// one stream from a resident buffer (hd_stream.hpp), behind mu_index too: the tables of a window of chunks, and its slots
 	Buf d_stream, d_stream_slots;
+	// the block index's merge (hd_blocks.hpp), behind mu_index too: the chain's pieces and the rows they become
+	Buf d_blocks;
 };
 
 // One context per entry of the device list (hipdeflate_init(devices...)).  An entry is a HIP device ordinal;
@@ -706,7 +709,7 @@ void hipdeflate_shutdown(void)
 		(void)hipSetDevice(g.device);
 		(void)hipDeviceSynchronize();                        // launches on callers' streams may still use our scratch
 		for (Buf *b : { &g.d_in, &g.d_meta, &g.d_slots, &g.d_packed, &g.d_scratch, &g.h_in, &g.h_meta, &g.h_out, &g.d_index,
-				&g.d_cand, &g.d_range, &g.d_range_out, &g.d_stream, &g.d_stream_slots })
+				&g.d_cand, &g.d_range, &g.d_range_out, &g.d_stream, &g.d_stream_slots, &g.d_blocks })
 			b->release();
 		(void)hipFree(g.d_ct);
 		(void)hipFree(g.d_stalls);
@@ -1779,9 +1782,10 @@ int hipdeflate_stream_index_carry_dev(const void *strm, uint64_t nbytes, int fra
 			    (hipStream_t)stream, nullptr, true, reach);
 }
 
-// The carry decode's rows, group by group in stream order: the check runs on in d.w->v.check, the lowest bad row in v.bad
+// The carry decode's rows, group by group in stream order: the check runs on in d.w->v.check, the lowest bad row in v.bad.
+// bits: the rows of the block index (hd_blocks.hpp), which start and end on a bit -- every group takes the marker path
 static int carry_decode_groups(Ctx &g, const void *strm, uint32_t kind, const StreamRows &t, const hd::DecodeScratch &d, uint32_t nchunks,
-			       void *out, hipStream_t st)
+			       void *out, hipStream_t st, bool bits = false)
 {
 	int r;
 	uint32_t *carry = &d.w->v.check, *d_bad = &d.w->v.bad;
@@ -1798,7 +1802,7 @@ static int carry_decode_groups(Ctx &g, const void *strm, uint32_t kind, const St
 			break;                                                    // a row of an earlier group is bad: the verdict is in
 		const uint32_t r1 = (uint32_t)gr[0], nr = r1 - r0;
 		const uint64_t begin = gr[2], gbytes = gr[3] - gr[2];
-		if (gr[1] == 0) {                                                 // no row of the group reaches back
+		if (gr[1] == 0 && !bits) {                                        // no row of the group reaches back
 			if ((r = stream_rows_flushed(g, strm, kind, t, d, r0, nr, out, st)))
 				return r;
 		} else {
@@ -1811,9 +1815,12 @@ static int carry_decode_groups(Ctx &g, const void *strm, uint32_t kind, const St
 			const hd::MarkerScratch m(g.d_stream_slots.p, gbytes, np);
 			CarryTimer tm(g_carry_timed);
 			tm.mark(0, st);
-			hipLaunchKernelGGL(hd::k_carry_decode, dim3(nr), dim3(64), 0, st,
-					   hd::CarryDecodeArgs{ (const uint8_t *)strm, t.in_off, t.in_len, t.out_size, t.out_off, t.reach, r0, nr, begin,
-								m.sym, d.out_len, d.status });
+			const hd::CarryDecodeArgs da{ (const uint8_t *)strm, t.in_off, t.in_len, t.out_size, t.out_off, t.reach, r0, nr, begin,
+						      m.sym, d.out_len, d.status };
+			if (bits)
+				hipLaunchKernelGGL(hd::k_blocks_decode, dim3(nr), dim3(64), 0, st, hd::BlocksDecodeArgs{ da });
+			else
+				hipLaunchKernelGGL(hd::k_carry_decode, dim3(nr), dim3(64), 0, st, da);
 			const hd::CarryRowsArgs ra{ m.sym, begin, t.out_off, t.out_size, d.out_len, d.status, r0, nr, (uint8_t *)out };
 			tm.mark(1, st);
 			hipLaunchKernelGGL(hd::k_carry_tails, dim3(1), dim3(hd::CARRY_TAIL_THREADS), 0, st, ra);
@@ -1850,8 +1857,10 @@ struct StreamChunks {
 	uint32_t bytes;
 	uint64_t out_bytes;
 };
+// bits (with carry): the block index's table, in_off and in_len in bits (k_blocks_check_rows, k_blocks_decode).
 static int stream_inflate_rows(Ctx &g, const void *strm, uint64_t nbytes, int frame, StreamRows t, const StreamChunks *ct, bool carry,
-			       uint32_t nchunks, void *out, uint64_t out_cap, hipdeflate_stream_summary *summary, hipStream_t st)
+			       uint32_t nchunks, void *out, uint64_t out_cap, hipdeflate_stream_summary *summary, hipStream_t st,
+			       bool bits = false)
 {
 	int r = enter_call(summary, sizeof *summary);
 	if (r)
@@ -1888,8 +1897,12 @@ static int stream_inflate_rows(Ctx &g, const void *strm, uint64_t nbytes, int fr
 		t = { d.in_off, d.in_len, d.out_off, d.out_size, nullptr };
 	} else {
 		HD_CHECK(hipMemsetAsync(d.ends, 0, 16, st));
-		hipLaunchKernelGGL(hd::k_stream_check_rows, dim3((nchunks + 255) / 256), dim3(256), 0, st, t.in_off, t.in_len, t.out_size,
-				   t.out_off, nchunks, (uint64_t)hdr, nbytes - trl, &d.w->v.fault, d.ends);
+		if (bits)
+			hipLaunchKernelGGL(hd::k_blocks_check_rows, dim3((nchunks + 255) / 256), dim3(256), 0, st, t.in_off, t.in_len, t.out_size,
+					   t.out_off, nchunks, (uint64_t)hdr, nbytes - trl, &d.w->v.fault, d.ends);
+		else
+			hipLaunchKernelGGL(hd::k_stream_check_rows, dim3((nchunks + 255) / 256), dim3(256), 0, st, t.in_off, t.in_len, t.out_size,
+					   t.out_off, nchunks, (uint64_t)hdr, nbytes - trl, &d.w->v.fault, d.ends);
 		if (carry)
 			hipLaunchKernelGGL(hd::k_carry_check_reach, dim3((nchunks + 255) / 256), dim3(256), 0, st, t.reach, t.out_off, nchunks,
 					   hd::CARRY_WINDOW, &d.w->v.fault);
@@ -1910,9 +1923,9 @@ static int stream_inflate_rows(Ctx &g, const void *strm, uint64_t nbytes, int fr
 		summary->out_bytes = ct ? 0 : e[1];
 		return 0;
 	}
-	if ((r = carry ? carry_decode_groups(g, strm, kind, t, d, nchunks, out, st) : stream_rows_flushed(g, strm, kind, t, d, 0, nchunks, out, st)))
+	if ((r = carry ? carry_decode_groups(g, strm, kind, t, d, nchunks, out, st, bits) : stream_rows_flushed(g, strm, kind, t, d, 0, nchunks, out, st)))
 		return r;
-	return stream_decode_end(strm, e[0] + trl, frame, e[1], d.w, summary, st);
+	return stream_decode_end(strm, (bits ? (e[0] + 7) >> 3 : e[0]) + trl, frame, e[1], d.w, summary, st);
 }
 
 int hipdeflate_stream_inflate_dev(const void *strm, uint64_t nbytes, int frame, const void *chunk_off, uint32_t nchunks,
@@ -1939,6 +1952,243 @@ int hipdeflate_stream_inflate_carry_dev(const void *strm, uint64_t nbytes, int f
 	const StreamRows t = { (const uint64_t *)in_off, (const uint32_t *)in_len, (const uint64_t *)out_off, (const uint32_t *)out_size,
 			       (const uint32_t *)reach };
 	return stream_inflate_rows(cur(), strm, nbytes, frame, t, nullptr, true, nchunks, out, out_cap, summary, (hipStream_t)stream);
+}
+
+/* ---- ... and a stream without a flush point: the index of its blocks, rows that start and end on a bit (hd_blocks.hpp) ---- */
+
+// hipdeflate_test_blocks_times: milliseconds of the index's passes -- candidates, pieces, chain, merge (tools/stream_blocks_bench.py)
+static bool g_blocks_timed = false;
+static double g_blocks_ms[4] = { 0, 0, 0, 0 };
+void hipdeflate_test_blocks_times(double *ms4)
+{
+	for (int k = 0; k < 4; k++) {
+		if (ms4)
+			ms4[k] = g_blocks_ms[k];
+		g_blocks_ms[k] = 0;
+	}
+	g_blocks_timed = ms4 != nullptr;
+}
+
+// hipdeflate_test_blocks_counts: of the last index call made while the timing was on, the candidates whose piece got past its
+// own first block header, and those whose piece decodes to its stop
+static uint64_t g_blocks_counts[2] = { 0, 0 };
+void hipdeflate_test_blocks_counts(uint64_t *out2)
+{
+	out2[0] = g_blocks_counts[0];
+	out2[1] = g_blocks_counts[1];
+}
+
+// The candidate list of src[0, end): `first`, a bit position, whatever stands there, then every position behind it that passes
+// the header rule (k_blocks_flag, k_blocks_write), ascending, in c.pos.  header8: eight dead u64 of d_index.  (Synchronises.)
+static int blocks_candidates(Ctx &g, const uint8_t *src, uint64_t end, uint64_t first, hd::IndexWords *&w, hd::IndexCand &c,
+			     uint32_t &ncand, uint64_t *&header8, hipStream_t st)
+{
+	const uint64_t nwords = (end + hd::IDX_WORD - 1) / hd::IDX_WORD, ntb64 = (nwords + hd::BLOCK_TILE_WORDS - 1) / hd::BLOCK_TILE_WORDS;
+	if (ntb64 > 0x7fffffffu)
+		return HD_E_ARG;
+	const uint32_t ntb = (uint32_t)ntb64;
+	if (g.d_index.reserve(hd::IndexBitmap::bytes(ntb, nwords, true)))
+		return HD_E_NOMEM;
+	const hd::IndexBitmap b(g.d_index.p, ntb, nwords, true);
+	w = b.w;
+	header8 = b.header;
+	uint64_t found = 0;
+	HD_CHECK(hipMemsetAsync(w, 0, sizeof *w, st));
+	HD_CHECK(hipMemsetD32Async((hipDeviceptr_t)&w->first, (int)hd::IDX_NIL, 1, st));
+	hipLaunchKernelGGL(hd::k_blocks_flag, dim3(ntb), dim3(64), 0, st, src, end, first + 1, b.bitmap, b.tile_cnt);
+	index_scan(b.tile_cnt, ntb, b.tiles, b.tile_off, &w->ncand, st);
+	HD_CHECK(hipGetLastError());
+	HD_CHECK(hipMemcpyAsync(&found, &w->ncand, 8, hipMemcpyDeviceToHost, st));
+	HD_CHECK(hipStreamSynchronize(st));
+	if (found + 1 > 0x7fffffffu)
+		return HD_E_NOMEM;
+	ncand = (uint32_t)found + 1;
+	if (g.d_cand.reserve(hd::IndexCand::bytes(ncand, 0, hd::INDEX_BLOCKS)))
+		return HD_E_NOMEM;
+	c = hd::IndexCand(g.d_cand.p, ncand, 0, hd::INDEX_BLOCKS);
+	HD_CHECK(hipMemcpyAsync(c.pos, &first, 8, hipMemcpyHostToDevice, st));
+	HD_CHECK(hipStreamSynchronize(st));                                      // (`first` is the caller's)
+	if (ncand > 1)
+		hipLaunchKernelGGL(hd::k_blocks_write, dim3(ntb), dim3(64), 0, st, src, end, first + 1, (const uint64_t *)b.bitmap, nwords,
+				   (const uint64_t *)b.tile_off, c.pos + 1);
+	return 0;
+}
+
+int hipdeflate_test_block_candidates_dev(const void *strm, uint64_t nbytes, uint64_t first, void *pos, uint32_t max_pos, uint64_t *count,
+					 void *stream)
+{
+	Ctx &g = cur();
+	const int e = ensure();
+	if (e)
+		return e;
+	if (!strm || !nbytes || ((uintptr_t)strm & 15) || nbytes > ((uint64_t)1 << 60) || first >= 8 * nbytes || !count || (max_pos && !pos))
+		return HD_E_ARG;
+	hipStream_t st = (hipStream_t)stream;
+	std::lock_guard<std::mutex> lk(g.mu_index);
+	hd::IndexWords *w = nullptr;
+	hd::IndexCand c;
+	uint32_t ncand = 0;
+	uint64_t *unused = nullptr;
+	int r = blocks_candidates(g, (const uint8_t *)strm, nbytes, first, w, c, ncand, unused, st);
+	if (r)
+		return r;
+	*count = ncand;
+	const uint32_t n = ncand < max_pos ? ncand : max_pos;
+	if (n)
+		HD_CHECK(hipMemcpyAsync(pos, c.pos, 8 * (size_t)n, hipMemcpyDeviceToDevice, st));
+	HD_CHECK(hipStreamSynchronize(st));
+	return 0;
+}
+
+int hipdeflate_test_block_headers_dev(const void *strm, uint64_t nbytes, const void *pos, uint32_t n, void *verdict, void *stream)
+{
+	const int r = ensure();
+	if (r)
+		return r;
+	if ((nbytes && !strm) || nbytes > ((uint64_t)1 << 60) || (n && (!pos || !verdict)))
+		return HD_E_ARG;
+	if (n)
+		hipLaunchKernelGGL(hd::k_blocks_rule, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const uint8_t *)strm, nbytes,
+				   (const uint64_t *)pos, n, (uint32_t *)verdict);
+	HD_CHECK(hipGetLastError());
+	return 0;
+}
+
+// own: as stream_index has it -- a hd::RowTable with the reach column in *own, as large as the chain needs
+static int blocks_index(Ctx &g, const void *strm, uint64_t nbytes, int frame, uint32_t max_rows, uint32_t max_chunk_in, uint32_t row_bytes,
+			void *in_off, void *in_len, void *out_size, void *out_off, void *reach, hipdeflate_block_index_summary *summary,
+			hipStream_t st, Buf *own)
+{
+	int r = enter_call(summary, sizeof *summary);
+	if (r)
+		return r;
+	if (!stream_frame_ok(frame) || ((uintptr_t)strm & 15) || (nbytes && !strm) || max_chunk_in >= HD_INFLATE_MAX_IN ||
+	    (max_rows && (!in_off || !in_len || !out_size || !out_off || !reach)))
+		return HD_E_ARG;
+	const uint8_t *src = (const uint8_t *)strm;
+	const uint32_t trl = stream_trl(frame);
+	if (max_chunk_in == 0)
+		max_chunk_in = HD_INFLATE_MAX_IN - 1;
+	if (row_bytes == 0)
+		row_bytes = HD_BLOCK_ROW_BYTES;
+	std::lock_guard<std::mutex> lk(g.mu_index);
+	if (g.d_index.reserve(hd::IndexBitmap::bytes(0, 0, true)))
+		return HD_E_NOMEM;
+	uint32_t hdr = 0, refused = 0;
+	if ((r = stream_open(strm, nbytes, frame, hd::IndexBitmap(g.d_index.p, 0, 0, true).header, st, &hdr, &refused)))
+		return r;
+	summary->hdr_bytes = hdr;
+	summary->end_offset = hdr;
+	summary->end_bit = 8 * (uint64_t)hdr;
+	if (refused) {
+		summary->status = refused;
+		return 0;
+	}
+	summary->ncandidates = 1;                                                // the first payload bit, whatever stands there
+	const uint64_t payload_end = nbytes - trl;                               // (k_frame_open: hdr + trl <= nbytes)
+	if (payload_end == hdr) {
+		summary->status = 2;
+		return 0;
+	}
+	hd::IndexWords *w = nullptr;
+	hd::IndexCand c;
+	uint32_t ncand = 0;
+	uint64_t *counts = nullptr;
+	CarryTimer tm(g_blocks_timed);
+	tm.mark(0, st);
+	if ((r = blocks_candidates(g, src, payload_end, 8 * (uint64_t)hdr, w, c, ncand, counts, st)))
+		return r;
+	const uint32_t nwg = (ncand + 255) / 256;
+	summary->ncandidates = ncand;
+	tm.mark(1, st);
+	// one bounded decode per candidate, from its bit
+	hipLaunchKernelGGL(hd::k_blocks_piece, dim3(ncand), dim3(64), 0, st,
+			   hd::BlocksPieceArgs{ { { src, (const uint64_t *)c.pos, ncand, max_chunk_in, payload_end, c.osize, c.used, c.pstat, c.stop },
+						c.reach } });
+	tm.mark(2, st);
+	if (g_blocks_timed) {                                                    // (the bench's two counts, in the header's dead words)
+		HD_CHECK(hipMemsetAsync(counts, 0, 16, st));
+		hipLaunchKernelGGL(hd::k_blocks_count, dim3(nwg), dim3(256), 0, st, (const uint32_t *)c.stop, (const uint32_t *)c.used, ncand,
+				   (unsigned long long *)counts);
+		HD_CHECK(hipMemcpyAsync(g_blocks_counts, counts, 16, hipMemcpyDeviceToHost, st));
+	}
+	hipLaunchKernelGGL(hd::k_blocks_links, dim3(nwg), dim3(256), 0, st, (const uint64_t *)c.pos, (const uint32_t *)c.used,
+			   (const uint32_t *)c.stop, ncand, c.succ0, c.mark);
+	uint64_t npieces = 0, nrows = 0;
+	if ((r = chain_rank(c, ncand, c.used, w, &npieces, st)))
+		return r;
+	tm.mark(3, st);
+	// the merge: the chain's pieces in rank order, the rows they begin, the rows' columns
+	const uint64_t *h_pos = nullptr, *h_out = nullptr;
+	if (npieces) {
+		const uint32_t np = (uint32_t)npieces, npg = (np + 255) / 256;
+		if (g.d_blocks.reserve(hd::BlockPieces::bytes(np)))
+			return HD_E_NOMEM;
+		const hd::BlockPieces m(g.d_blocks.p, np);
+		h_pos = m.h_pos, h_out = m.h_out;
+		hipLaunchKernelGGL(hd::k_blocks_sizes, dim3(nwg), dim3(256), 0, st, (const uint32_t *)c.osize, (const uint32_t *)c.mark,
+				   (const uint64_t *)c.rank, ncand, npieces, m.p_size, &w->last);
+		index_scan(m.p_size, np, m.tiles, m.p_out, &w->out_bytes, st);
+		hipLaunchKernelGGL(hd::k_blocks_starts, dim3(npg), dim3(256), 0, st, (const uint64_t *)m.p_out, np, (uint64_t)row_bytes, m.start);
+		index_scan(m.start, np, m.tiles, m.before, &w->rows, st);
+		HD_CHECK(hipGetLastError());
+		HD_CHECK(hipMemcpyAsync(&nrows, &w->rows, 8, hipMemcpyDeviceToHost, st));
+		HD_CHECK(hipStreamSynchronize(st));
+		if (own) {
+			if (own->reserve(hd::RowTable::bytes(nrows, true)))
+				return HD_E_NOMEM;
+			const hd::RowTable t(own->p, nrows, true);
+			max_rows = (uint32_t)nrows;
+			in_off = t.in_off, out_off = t.out_off, in_len = t.in_len, out_size = t.out_size, reach = t.reach;
+		}
+		const uint32_t ntab = (uint32_t)(nrows < max_rows ? nrows : max_rows);
+		hipLaunchKernelGGL(hd::k_blocks_heads, dim3(nwg), dim3(256), 0, st, (const uint64_t *)c.pos, (const uint32_t *)c.used,
+				   (const uint32_t *)c.osize, (const uint32_t *)c.mark, (const uint64_t *)c.rank, ncand, npieces,
+				   (const uint64_t *)m.p_out, (const uint32_t *)m.start, (const uint64_t *)m.before, nrows, m.h_pos, m.h_out);
+		if (ntab) {
+			hipLaunchKernelGGL(hd::k_blocks_rows, dim3((ntab + 255) / 256), dim3(256), 0, st, h_pos, h_out, ntab, max_chunk_in,
+					   (uint64_t *)in_off, (uint32_t *)in_len, (uint32_t *)out_size, (uint64_t *)out_off, (uint32_t *)reach, &w->first);
+			hipLaunchKernelGGL(hd::k_blocks_reach, dim3(nwg), dim3(256), 0, st, (const uint32_t *)c.reach, (const uint32_t *)c.mark,
+					   (const uint64_t *)c.rank, ncand, (const uint64_t *)m.p_out, (const uint32_t *)m.start,
+					   (const uint64_t *)m.before, h_out, ntab, (uint32_t *)reach);
+			// the reach rule, on the rows in the table: the lowest row at fault by either rule in w->first
+			hipLaunchKernelGGL(hd::k_carry_check_reach, dim3((ntab + 255) / 256), dim3(256), 0, st, (const uint32_t *)reach,
+					   (const uint64_t *)out_off, ntab, 0xffffffffu, &w->first);
+		}
+	}
+	tm.mark(4, st);
+	hipLaunchKernelGGL(hd::k_blocks_verdict, dim3(1), dim3(1), 0, st, src, (const uint64_t *)c.pos, (const uint32_t *)c.used,
+			   (const int32_t *)c.pstat, (const uint32_t *)c.stop, ncand, npieces, nrows, max_rows, max_chunk_in, payload_end, trl, h_pos,
+			   h_out, &w->rows);
+	HD_CHECK(hipGetLastError());
+	hd::IndexWords h;
+	HD_CHECK(hipMemcpyAsync(&h, w, sizeof h, hipMemcpyDeviceToHost, st));
+	HD_CHECK(hipStreamSynchronize(st));
+	tm.add(g_blocks_ms);
+	summary->nrows = h.rows;
+	summary->npieces = npieces;
+	summary->out_bytes = h.out_bytes;
+	summary->end_offset = h.end_offset;
+	summary->end_bit = h.spare;
+	summary->status = (uint32_t)h.status;
+	return 0;
+}
+
+int hipdeflate_stream_index_blocks_dev(const void *strm, uint64_t nbytes, int frame, uint32_t max_rows, uint32_t max_chunk_in,
+				       uint32_t row_bytes, void *in_off, void *in_len, void *out_size, void *out_off, void *reach,
+				       hipdeflate_block_index_summary *summary, void *stream)
+{
+	return blocks_index(cur(), strm, nbytes, frame, max_rows, max_chunk_in, row_bytes, in_off, in_len, out_size, out_off, reach, summary,
+			    (hipStream_t)stream, nullptr);
+}
+
+int hipdeflate_stream_inflate_blocks_dev(const void *strm, uint64_t nbytes, int frame, const void *in_off, const void *in_len,
+					 const void *out_size, const void *out_off, const void *reach, uint32_t nrows, void *out,
+					 uint64_t out_cap, hipdeflate_stream_summary *summary, void *stream)
+{
+	const StreamRows t = { (const uint64_t *)in_off, (const uint32_t *)in_len, (const uint64_t *)out_off, (const uint32_t *)out_size,
+			       (const uint32_t *)reach };
+	return stream_inflate_rows(cur(), strm, nbytes, frame, t, nullptr, true, nrows, out, out_cap, summary, (hipStream_t)stream, true);
 }
 
 /* ---- host-pointer API ------------------------------------------------------ */
@@ -3097,8 +3347,9 @@ int hip_deflate_stream(unsigned char *dest, size_t *destLen, const unsigned char
 
 // hip_inflate_stream and, for a stream whose flushes carry the window (carry), hip_inflate_stream_carry: stage, index,
 // decode.  The row table stays on the device, in d_meta, as large as the stream needs
+// blocks: hip_inflate_stream_blocks -- the block index and its bit rows (hd_blocks.hpp), with the carry decode's table
 static int inflate_stream_host(unsigned char *dest, size_t *destLen, const unsigned char *source, size_t sourceLen, int frame,
-			       size_t *in_used, bool carry)
+			       size_t *in_used, bool carry, bool blocks = false)
 {
 	Ctx &g = cur();
 	int r = ensure();
@@ -3114,8 +3365,20 @@ static int inflate_stream_host(unsigned char *dest, size_t *destLen, const unsig
 	if (sourceLen)
 		HD_CHECK(hipMemcpyAsync(g.d_in.p, source, sourceLen, hipMemcpyHostToDevice, g.stream));
 	hipdeflate_stream_index_summary xs;
-	if ((r = stream_index(g, g.d_in.p, sourceLen, frame, 0, 0, nullptr, nullptr, nullptr, nullptr, &xs, g.stream, &g.d_meta, carry)))
+	if (blocks) {
+		hipdeflate_block_index_summary bs;
+		// a piece of HD_BLOCK_PIECE_IN bytes at the most first: that bounds what a false candidate can cost.  Status 1 may then
+		// be the bound's doing (a long stored span, a writer of larger blocks): only then the unbounded index decides
+		if ((r = blocks_index(g, g.d_in.p, sourceLen, frame, 0, HD_BLOCK_PIECE_IN, 0, nullptr, nullptr, nullptr, nullptr, nullptr, &bs, g.stream,
+				      &g.d_meta)))
+			return r;
+		if (bs.status == 1 && sourceLen > HD_BLOCK_PIECE_IN &&
+		    (r = blocks_index(g, g.d_in.p, sourceLen, frame, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, &bs, g.stream, &g.d_meta)))
+			return r;
+		xs = { bs.nrows, bs.out_bytes, bs.end_offset, bs.ncandidates, bs.hdr_bytes, bs.status };
+	} else if ((r = stream_index(g, g.d_in.p, sourceLen, frame, 0, 0, nullptr, nullptr, nullptr, nullptr, &xs, g.stream, &g.d_meta, carry))) {
 		return r;
+	}
 	g.stream_drained(g.stream);
 	if (in_used)
 		*in_used = xs.end_offset;
@@ -3130,7 +3393,7 @@ static int inflate_stream_host(unsigned char *dest, size_t *destLen, const unsig
 	const hd::RowTable t(g.d_meta.p, xs.nchunks, carry);         // (status 0: the chain's rows, which the table's layout goes by)
 	hipdeflate_stream_summary s;
 	if ((r = stream_inflate_rows(g, g.d_in.p, xs.end_offset, frame, { t.in_off, t.in_len, t.out_off, t.out_size, t.reach }, nullptr, carry,
-				     (uint32_t)xs.nchunks, g.d_packed.p, xs.out_bytes, &s, g.stream)))
+				     (uint32_t)xs.nchunks, g.d_packed.p, xs.out_bytes, &s, g.stream, blocks)))
 		return r;
 	if (s.status)
 		return 1;
@@ -3148,6 +3411,11 @@ int hip_inflate_stream(unsigned char *dest, size_t *destLen, const unsigned char
 int hip_inflate_stream_carry(unsigned char *dest, size_t *destLen, const unsigned char *source, size_t sourceLen, int frame, size_t *in_used)
 {
 	return inflate_stream_host(dest, destLen, source, sourceLen, frame, in_used, true);
+}
+
+int hip_inflate_stream_blocks(unsigned char *dest, size_t *destLen, const unsigned char *source, size_t sourceLen, int frame, size_t *in_used)
+{
+	return inflate_stream_host(dest, destLen, source, sourceLen, frame, in_used, true, true);
 }
 
 } // extern "C"

@@ -70,25 +70,36 @@ struct PieceArgs {
 	uint32_t *stop;                  // PIECE_FLUSH | PIECE_FINAL, 0 where the piece does not decode
 };
 constexpr int32_t PIECE_CUT = 4;
-constexpr uint32_t PIECE_FLUSH = 1, PIECE_FINAL = 2;
+constexpr uint32_t PIECE_FLUSH = 1, PIECE_FINAL = 2, PIECE_NEXT = 3, PIECE_PAST_HEADER = 4;
 // The carried form (k_carry_piece, hd_carry.hpp): a piece of a stream whose writer kept the window across the flush.  A
 // distance past the bytes the piece has put out is no fault then -- 32768 is DEFLATE's most, and the bytes in front of the
 // piece are another row's -- and reach[] takes the furthest one: 0 where the piece stands alone.
 struct CarryPieceArgs : PieceArgs {
 	uint32_t *reach;
 };
+// The block form (k_blocks_piece, hd_blocks.hpp): a carried piece of a stream without flush points.  pos[] holds BIT
+// positions and the piece starts on its bit; it stops behind a final block, or behind a non-final block with BFINAL 0 /
+// BTYPE 2 in the three bits behind it (PIECE_NEXT: the next non-final dynamic header) -- a flush point is no stop -- and
+// in_used[] is in BITS from the candidate's bit.  A piece that does not decode but got past its own first block header -- the
+// tables of a dynamic block built, LEN / NLEN of a stored one agreeing -- says so in stop[] (PIECE_PAST_HEADER: a count for
+// the bench, no link and no verdict looks at it).
 
-template <bool PIECE, class Args, bool CARRY = false> __device__ __forceinline__ void inflate_size_body(const Args &a)
+template <bool PIECE, class Args, bool CARRY = false, bool BITS = false> __device__ __forceinline__ void inflate_size_body(const Args &a)
 {
 	__shared__ InfSizeLds L;
 	const uint32_t lane = threadIdx.x;
 	const uint32_t b = blockIdx.x;
 	uint64_t p_off;
 	uint32_t n;
+	[[maybe_unused]] uint32_t sh = 0;              // (block form) the candidate's bit in its byte
 	if constexpr (PIECE) {
 		if (b >= a.ncand)
 			return;
 		p_off = a.pos[b];
+		if constexpr (BITS) {
+			sh = (uint32_t)p_off & 7;
+			p_off >>= 3;
+		}
 		const uint64_t left = a.payload_end - p_off;
 		n = left < a.max_in ? (uint32_t)left : a.max_in;
 	} else {
@@ -111,6 +122,8 @@ template <bool PIECE, class Args, bool CARRY = false> __device__ __forceinline__
 	}
 
 	InfReader R(src, n, lane);
+	if constexpr (BITS)
+		R.drop(sh);
 	uint64_t pos = 0;                              // bytes the stream has decoded to so far (uniform)
 	[[maybe_unused]] uint32_t reach = 0;           // (carried form) the furthest a match went back over the piece's first byte
 	constexpr uint64_t POS_LIMIT = 0xffffffffull;  // the largest room a u32 table states: past it the answer is "does not fit"
@@ -190,6 +203,7 @@ template <bool PIECE, class Args, bool CARRY = false> __device__ __forceinline__
 	int32_t st = HD_OK;
 	bool static_loaded = false;
 	uint32_t stop = 0;                            // (piece form) the stop it hit
+	[[maybe_unused]] bool past = false;           // (block form) the first block's header is behind the decoder
 	bool cut = false;                             // (piece form) a stored block's LEN / NLEN or payload reaches past the input
 	for (;;) {
 		R.refill();
@@ -209,11 +223,13 @@ template <bool PIECE, class Args, bool CARRY = false> __device__ __forceinline__
 			const uint32_t len = (uint32_t)R.bb & 0xffff, nlen = ((uint32_t)R.bb >> 16) & 0xffff;
 			ip += 4;
 			if (len != (~nlen & 0xffff)) { st = HD_BAD_DATA; break; }
+			if constexpr (BITS)
+				past = true;
 			if (pos + len > POS_LIMIT) { st = HD_INSUFFICIENT_SPACE; break; }
 			if (len > n - ip) { st = HD_BAD_DATA; cut = true; break; }
 			pos += len;
 			R.seek_byte(ip + len);
-			if constexpr (PIECE) {
+			if constexpr (PIECE && !BITS) {
 				if (!bfinal && len == 0) {
 					stop = PIECE_FLUSH;
 					break;
@@ -231,6 +247,8 @@ template <bool PIECE, class Args, bool CARRY = false> __device__ __forceinline__
 				static_loaded = true;
 			}
 
+			if constexpr (BITS)
+				past = true;
 			// ---- symbol loop ----------------------------------------------
 			for (;;) {
 				if (uniform(run_windows(st)))
@@ -287,6 +305,13 @@ template <bool PIECE, class Args, bool CARRY = false> __device__ __forceinline__
 			break;
 		}
 		if (R.consumed_bits() > 8 * (int64_t)n + 64) { st = HD_BAD_DATA; break; }
+		if constexpr (BITS) {
+			R.refill();
+			if (((uint32_t)R.bb & 7) == 4) {             // BFINAL 0, BTYPE 2: with bit 2 set, all three are the stream's own
+				stop = PIECE_NEXT;
+				break;
+			}
+		}
 	}
 	if constexpr (PIECE) {
 		// with the decoder's position past the input -- at a stop it reached through the zero bits, or at the failure they
@@ -295,9 +320,12 @@ template <bool PIECE, class Args, bool CARRY = false> __device__ __forceinline__
 			st = PIECE_CUT;
 		if (lane == 0) {
 			a.out_size[b] = st == HD_OK ? (uint32_t)pos : 0u;
-			a.in_used[b] = st == HD_OK ? (uint32_t)((R.consumed_bits() + 7) >> 3) : 0u;
+			if constexpr (BITS)
+				a.in_used[b] = st == HD_OK ? (uint32_t)(R.consumed_bits() - sh) : 0u;
+			else
+				a.in_used[b] = st == HD_OK ? (uint32_t)((R.consumed_bits() + 7) >> 3) : 0u;
 			a.status[b] = st;
-			a.stop[b] = st == HD_OK ? stop : 0u;
+			a.stop[b] = st == HD_OK ? stop : BITS && past ? PIECE_PAST_HEADER : 0u;
 			if constexpr (CARRY)
 				a.reach[b] = st == HD_OK ? reach : 0u;
 		}

@@ -103,11 +103,11 @@ struct IndexBitmap : Layout<IndexBitmap> {
 
 // d_cand: ncand candidates in columns of nc, and the tiles of two scans, of ncand and of max_rows elements.  The successor
 // tables are dead when the rank scan runs: rank lies over them.
-enum IndexKind { INDEX_MEMBERS, INDEX_STREAM, INDEX_CARRY };
+enum IndexKind { INDEX_MEMBERS, INDEX_STREAM, INDEX_CARRY, INDEX_BLOCKS };
 struct IndexCand : Layout<IndexCand> {
 	IndexCand(void *base = nullptr, size_t ncand = 0, size_t max_rows = 0, IndexKind kind = INDEX_MEMBERS)
 		: Layout(base), nc((ncand + 3) & ~(size_t)3), ntiles(scan_tiles(ncand) + scan_tiles(max_rows)), nm(kind == INDEX_MEMBERS ? nc : 0),
-		  ns(kind == INDEX_MEMBERS ? 0 : nc), nr(kind == INDEX_CARRY ? nc : 0) {}
+		  ns(kind == INDEX_MEMBERS ? 0 : nc), nr(kind == INDEX_CARRY || kind == INDEX_BLOCKS ? nc : 0) {}
 	size_t nc, ntiles, nm, ns, nr;
 	uint64_t *tiles = c.take<uint64_t>(ntiles), *pos = c.take<uint64_t>(nc);
 	size_t succ_at = c.bytes();
@@ -117,7 +117,17 @@ struct IndexCand : Layout<IndexCand> {
 	uint32_t *hdr = c.take<uint32_t>(nm), *total = c.take<uint32_t>(nm);                                         // INDEX_MEMBERS
 	uint32_t *used = c.take<uint32_t>(ns), *osize = c.take<uint32_t>(ns), *stop = c.take<uint32_t>(ns);          // both stream indexes
 	int32_t *pstat = c.take<int32_t>(ns);
-	uint32_t *reach = c.take<uint32_t>(nr);                                                                      // INDEX_CARRY
+	uint32_t *reach = c.take<uint32_t>(nr);                                                                      // INDEX_CARRY, INDEX_BLOCKS
+};
+
+// d_blocks, the block index's merge (hd_blocks.hpp): the np pieces of the chain in rank order, and the rows they merge into
+// (np at the most, and one entry behind the last row: the chain's end)
+struct BlockPieces : Layout<BlockPieces> {
+	BlockPieces(void *base, size_t np_) : Layout(base), np(np_) {}
+	size_t np;
+	uint64_t *tiles = c.take<uint64_t>(scan_tiles(np)), *p_out = c.take<uint64_t>(np), *before = c.take<uint64_t>(np);
+	uint64_t *h_pos = c.take<uint64_t>(np + 1), *h_out = c.take<uint64_t>(np + 1);
+	uint32_t *p_size = c.take<uint32_t>(np), *start = c.take<uint32_t>(np);
 };
 
 // d_range: n members, nq queries

@@ -327,6 +327,67 @@ def inflate_stream_carry(stream, frame=_pkg.FRAME_GZIP):
     return out, x
 
 
+def index_stream_blocks_call(stream, frame, max_rows, max_chunk_in, row_bytes, in_off, in_len, out_size, out_off, reach):
+    """one hipdeflate_stream_index_blocks_dev: stream a 16-byte aligned uint8 tensor, the five tables int64 / int32 tensors of
+    max_rows entries (None with max_rows == 0: the sizing call), in_off and in_len in BITS -> BlockIndexSummary"""
+    summary = _pkg.BlockIndexSummary()
+    rc = _pkg.lib().hipdeflate_stream_index_blocks_dev(_ptr(stream), stream.numel(), frame, max_rows, max_chunk_in, row_bytes,
+                                                       _ptr(in_off), _ptr(in_len), _ptr(out_size), _ptr(out_off), _ptr(reach),
+                                                       ctypes.byref(summary), _stream())
+    _pkg._check(rc, "hipdeflate_stream_index_blocks_dev")
+    return summary
+
+
+def index_stream_blocks(stream, frame=_pkg.FRAME_GZIP, max_rows=None, max_chunk_in=0, row_bytes=0):
+    """the row table of a plain stream, which has no flush point: its blocks found at their bits and merged into rows of
+    about row_bytes of output (0: BLOCK_ROW_BYTES) -> (in_off, in_len, out_size, out_off, reach, BlockIndexSummary), in_off
+    and in_len in BITS.  Without max_rows the tables get one row per 64 stream bytes, and where a chain has more (status 3
+    names the number) the stream is indexed again on tables of that size."""
+    dev = stream.device
+
+    def run(n):
+        t = (torch.zeros(n, dtype=torch.int64, device=dev), torch.zeros(n, dtype=torch.int32, device=dev),
+             torch.zeros(n, dtype=torch.int32, device=dev), torch.zeros(n, dtype=torch.int64, device=dev),
+             torch.zeros(n, dtype=torch.int32, device=dev))
+        return t + (index_stream_blocks_call(stream, frame, n, max_chunk_in, row_bytes, *t),)
+
+    if max_rows is not None:
+        return run(max_rows)
+    r = run(stream.numel() // 64 + 16)
+    return run(r[5].nrows) if r[5].status == 3 else r
+
+
+def inflate_stream_blocks_call(stream, frame, in_off, in_len, out_size, out_off, reach, nrows, out, out_cap):
+    """one hipdeflate_stream_inflate_blocks_dev -> StreamSummary"""
+    summary = _pkg.StreamSummary()
+    rc = _pkg.lib().hipdeflate_stream_inflate_blocks_dev(_ptr(stream), stream.numel(), frame, _ptr(in_off), _ptr(in_len),
+                                                         _ptr(out_size), _ptr(out_off), _ptr(reach), nrows, _ptr(out), out_cap,
+                                                         ctypes.byref(summary), _stream())
+    _pkg._check(rc, "hipdeflate_stream_inflate_blocks_dev")
+    return summary
+
+
+def inflate_stream_blocks(stream, frame=_pkg.FRAME_GZIP):
+    """inflate_stream_auto for a plain stream, which has no flush point (gzip, zlib.compress, an IDAT) -> (uint8 tensor of
+    its contents, BlockIndexSummary): the block index, one allocation, the rows decoded side by side and held to the trailer.
+    The index runs with max_chunk_in = BLOCK_PIECE_IN first, which bounds what a false candidate costs, and unbounded only
+    where that answers status 1."""
+    in_off, in_len, out_size, out_off, reach, x = index_stream_blocks(stream, frame, max_chunk_in=_pkg.BLOCK_PIECE_IN)
+    if x.status == 1 and stream.numel() > _pkg.BLOCK_PIECE_IN:
+        in_off, in_len, out_size, out_off, reach, x = index_stream_blocks(stream, frame)
+    if x.status:
+        why = {1: "a piece does not decode, or the header is refused", 2: "the stream is cut"}
+        raise _pkg.HipDeflateError("block index: %s at bit %d (status %d, %d rows)" % (why.get(x.status, "?"), x.end_bit, x.status,
+                                                                                       x.nrows))
+    out = torch.empty(x.out_bytes, dtype=torch.uint8, device=stream.device)
+    s = inflate_stream_blocks_call(stream, frame, in_off, in_len, out_size, out_off, reach, x.nrows, out, x.out_bytes)
+    if s.status:
+        why = {1: "a bad table", 2: "a row or the check disagrees", 3: "room too small"}
+        raise _pkg.HipDeflateError("stream decode: %s (status %d, bad_chunk %d of %d)" % (why.get(s.status, "?"), s.status,
+                                                                                         s.bad_chunk, s.nchunks))
+    return out, x
+
+
 def check_combine(check, lens, kind=_pkg.CHECK_CRC32):
     """the CRC-32 (kind 0) / Adler-32 (kind 1) of a concatenation from the checks and lengths of its parts: int32 device
     tensors holding the bits of the u32 values -> int"""

@@ -572,6 +572,102 @@ void hipdeflate_test_carry_group(uint64_t bytes);
  * the last call, by events around their launches (one more wait per group while it is on); the call turns the timing on,
  * NULL turns it off */
 void hipdeflate_test_carry_times(double *ms4);
+/* ---- ... and a PLAIN stream, which has no flush point at all: gzip, zlib.compress, a PNG's IDAT ----------------------
+ * Role: the reader of applet/7gzip.c:8-116 and of zlibrawstdio, one serial inflate there.  Most .gz files, zlib buffers and
+ * IDATs hold one stream that nobody flushed; for such a stream both indexes above answer "one row", and one wavefront decodes
+ * the file.  What such a stream does have is BLOCKS, which start at any BIT.  The two calls below are the carry index and
+ * the carry decode for rows that start and end on a bit.
+ *
+ * hipdeflate_stream_index_blocks_dev follows the method of hipdeflate_stream_index_dev with a header rule in the place of the
+ * 00 00 ff ff marker.  Candidate 0 is the first payload bit, 8 * hdr_bytes, whatever stands there.  Every other candidate
+ * is a bit position p behind it at which a NON-FINAL DYNAMIC block header could start: the bits read BFINAL 0, BTYPE 2, HLIT
+ * (5 bits), HDIST (5), HCLEN (4), then HCLEN + 4 precode lengths of 3 bits, all 17 + 3 (HCLEN + 4) of them in front of
+ * nbytes - trailer, and the precode is one the decoder takes: with K = the sum of 2^(7 - len) over the non-zero lengths,
+ * K == 128, K == 0, or one non-zero length that is 1.  Nothing else is examined, so the rule drops no header the decoder
+ * would take; random bits pass it at 5.13e-4 of the positions, one candidate per 244 bytes of stream.  One wavefront per
+ * candidate then decodes from that bit, block after block, without output (a PIECE): to the end of a final block, or to
+ * the end of a non-final block with BFINAL 0 / BTYPE 2 in the three bits behind it.  So a piece never runs through a
+ * non-final dynamic header except its own first one; static and stored blocks, and the final block, ride with the piece
+ * in front of them, and a flush point is no stop.  A piece that ends in front of such a header links to the candidate at
+ * that bit, and only the chain from candidate 0 decides: bits in a stored payload or inside a token that look like a header
+ * are candidates that nothing links to.  max_chunk_in bounds one piece's input in bytes (0: HD_INFLATE_MAX_IN - 1, also the
+ * most) -- a false candidate costs one bounded decode, and most end inside their header.
+ *   Behind the chain its pieces are MERGED, on the device: a row is the run of consecutive pieces whose out_off lies in the
+ * same multiple of row_bytes (0: HD_BLOCK_ROW_BYTES; a piece is never split, so row_bytes 1 gives a row per piece), and its
+ * reach is the largest of reach_j - (out_off_j - out_off_row) over its pieces, 0 at the least.  The table, device arrays of
+ * max_rows entries: in_off (u64) = the BIT offset of the row's first block header in the stream; in_len (u32) = its length
+ * in BITS, below 2^31; out_size, out_off, reach as the carry index has them.  The rows tile the payload bit for bit.
+ *   status 0  the chain's last piece ended in a final block and the trailer's bytes lie behind it: end_offset = the first
+ *             byte behind the trailer, end_bit = the bit behind the final block.  The trailer's contents are not examined.
+ *   status 1  the piece at end_bit does not decode, or the header rule refuses the bits there although they are all present,
+ *             or the stream's own header is refused (all fields 0); or, as in the carry index, the first row of the table
+ *             with reach[i] > out_off[i], or with more than max_chunk_in bytes of stream (a run of empty blocks makes such
+ *             a row; so does a long span without a dynamic header, which is one piece), ends the chain: nrows = i,
+ *             out_bytes = out_off[i], end_bit = in_off[i], and the rows in front stay usable.
+ *   status 2  the piece at end_bit needed a bit at or behind nbytes - trailer, or the header there does not fit in front of
+ *             it, or there is no payload.
+ *   status 3  the chain has more rows than max_rows: nrows = that number, the table holds the first max_rows, out_bytes is
+ *             their sum; the two row rules are applied to the rows in the table only, as in the carry index.  max_rows == 0
+ *             with NULL tables is the sizing call.
+ * In every status but 0, end_offset = end_bit / 8.  npieces = the pieces of the whole chain, ncandidates = the list's length.
+ * Stated limits.  Only non-final dynamic headers are found: a stream of static or stored blocks only (this library's level 1,
+ * incompressible data) is one piece and one row, decoded by one wavefront, and status 1 where it is longer than
+ * max_chunk_in.  Scratch, the library's, grow-only: 40 bytes per candidate -- at one per 244 bytes of stream, 4.4 M
+ * candidates and 180 MB for 1 GiB -- one bit per 16 stream bytes, and 40 bytes per piece of the chain.
+ * strm 16-byte aligned; no byte at or behind strm + nbytes is read.  Returns 0 whenever the call ran.  (Synchronises the
+ * stream; takes turns as the other indexes do.) */
+typedef struct hipdeflate_block_index_summary {
+	uint64_t nrows;        /* rows in the table (status 3: rows the chain has) */
+	uint64_t npieces;      /* pieces of the chain, before the merge */
+	uint64_t out_bytes;    /* sum of out_size over the table */
+	uint64_t end_offset;   /* bytes.  status 0: the first byte behind the trailer; else end_bit / 8 */
+	uint64_t end_bit;      /* the exact bit where the chain stopped */
+	uint64_t ncandidates;
+	uint32_t hdr_bytes;
+	uint32_t status;
+} hipdeflate_block_index_summary;
+int hipdeflate_stream_index_blocks_dev(const void *strm, uint64_t nbytes, int frame, uint32_t max_rows, uint32_t max_chunk_in,
+				       uint32_t row_bytes, void *in_off /* u64, bits */, void *in_len /* u32, bits */,
+				       void *out_size /* u32 */, void *out_off /* u64 */, void *reach /* u32 */,
+				       hipdeflate_block_index_summary *summary /* HOST */, void *stream);
+/* The decode on such a table: hipdeflate_stream_inflate_carry_dev for bit rows, with the same summary and the same order of
+ * statuses.  The table is checked, never trusted:
+ *   status 1  nrows is 0, or the header is refused; a row starts in front of bit 8 * hdr_bytes, ends behind bit
+ *             8 * (nbytes - trailer), overlaps its successor or comes after it, or has in_len >= 2^31; out_off is not the
+ *             exclusive prefix sum of out_size; reach[i] > 32768 or reach[i] > out_off[i].  bad_chunk = the lowest row at
+ *             fault.  Nothing is decoded.
+ *   status 3  out_cap < out_off[n-1] + out_size[n-1]; out_bytes is that need.  Nothing is decoded.
+ *   status 2  bad_chunk = i: row i, decoded from bit in_off[i] & 7 of byte in_off[i] / 8, does not end behind a final block or
+ *             behind a block that ends on bit in_len[i] exactly (a block end past in_len[i] is this), is not out_size[i]
+ *             long, or reaches further back than reach[i]; bad_chunk = nrows: the folded check, or the gzip ISIZE, disagrees
+ *             with the trailer, which is read at the byte behind the last row's last bit.
+ * A row writes at most out_size[i] bytes at out_off[i].  The groups of the carry decode run as they stand, but there is no
+ * fast path -- the flush-rule batch inflate starts on a byte -- so every group takes the marker path: scratch 2 bytes per
+ * output byte of the largest group.  hipdeflate_test_carry_group sizes the groups here too. */
+int hipdeflate_stream_inflate_blocks_dev(const void *strm, uint64_t nbytes, int frame,
+					 const void *in_off, const void *in_len, const void *out_size, const void *out_off,
+					 const void *reach, uint32_t nrows, void *out, uint64_t out_cap,
+					 hipdeflate_stream_summary *summary /* HOST */, void *stream);
+/* host-buffer form: hip_inflate_stream with the block index and the block decode; the same arguments and return values.  The
+ * index runs with max_chunk_in = HD_BLOCK_PIECE_IN (hipdeflate_params.h) first and with 0 only where that answers status 1, so
+ * a stream whose pieces are longer than that, or that is bad, is indexed twice. */
+int hip_inflate_stream_blocks(unsigned char *dest, size_t *destLen, const unsigned char *source, size_t sourceLen, int frame,
+			      size_t *in_used);
+/* test entry: the header rule alone.  pos[] (u64, device) holds n bit positions of the stream strm[0, nbytes), whose bits at
+ * and behind 8 * nbytes do not exist; verdict[] (u32, device) gets 0 = the rule refuses the position, 1 = it accepts it,
+ * 2 = the header does not fit in front of the end.  (Does not synchronise.) */
+int hipdeflate_test_block_headers_dev(const void *strm, uint64_t nbytes, const void *pos, uint32_t n, void *verdict, void *stream);
+/* test entry: ms4[0..3] = the milliseconds the block index's passes -- candidates, pieces, chain, merge -- took since the
+ * last call, by events around their launches; the call turns the timing on, NULL turns it off */
+void hipdeflate_test_blocks_times(double *ms4);
+/* test entry: out2[0] = the candidates of the last index call made while that timing was on whose piece got past its own first
+ * block header, out2[1] = those whose piece decodes to its stop */
+void hipdeflate_test_blocks_counts(uint64_t *out2);
+/* test entry: the candidate list alone, by the two passes the index uses.  strm[0, nbytes) 16-byte aligned; the list is `first`
+ * (a bit position below 8 * nbytes, whatever stands there) and every position behind it that the header rule accepts,
+ * ascending; *count HOST = its length, pos[] (u64, device) gets the first min(*count, max_pos).  (Synchronises the stream.) */
+int hipdeflate_test_block_candidates_dev(const void *strm, uint64_t nbytes, uint64_t first, void *pos, uint32_t max_pos,
+					 uint64_t *count /* HOST */, void *stream);
 /* the fold on its own: check[] / len[] device arrays of n parts (u32 each, n < 2^31), kind 0 = CRC-32, 1 = Adler-32; *result HOST.
  * The check of the concatenation of the parts from the parts' own: the role of crc_append (the hosts' serial fold, after
  * zlib's crc32_combine) with one lane per part -- part i contributes check[i] moved over the S_i bytes behind it, S_i a

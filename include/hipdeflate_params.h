@@ -217,6 +217,15 @@
 #define HD_CARRY_GROUP_BYTES   (256u << 20)
 #define HD_CARRY_CHECK_PIECE   (64u << 10)
 
+/* hipdeflate_stream_index_blocks_dev: the blocks of the chain are merged into ROWS, the consecutive pieces whose out_off lies
+ * in the same multiple of this many bytes (a piece is never split), so that the one workgroup that walks the rows of the
+ * decode in order has a row of useful size to take at a time; row_bytes == 0 means this */
+#define HD_BLOCK_ROW_BYTES     (128u << 10)
+/* hip_inflate_stream_blocks and device.inflate_stream_blocks index with this max_chunk_in first, so that a false candidate
+ * whose random tables decode on and on costs at most this many bytes of input, and with 0 only where that answers status 1:
+ * zlib's and libdeflate's blocks, and rows of HD_BLOCK_ROW_BYTES made of them, stay well below it */
+#define HD_BLOCK_PIECE_IN      (1u << 20)
+
 /* result codes of the inflate path = enum libdeflate_result
  * (lib/libdeflate/libdeflate.h:193-208), which libdeflate_inflate
  * (lib/zlibutil.c:194-204) hands straight back to the applet */
