@@ -63,6 +63,11 @@ class StreamIndexSummary(ctypes.Structure):
                 ("ncandidates", ctypes.c_uint64), ("hdr_bytes", ctypes.c_uint32), ("status", ctypes.c_uint32)]
 
 
+class WindowSummary(ctypes.Structure):
+    """hipdeflate_window_summary (include/hipdeflate.h)"""
+    _fields_ = [("win_bytes", ctypes.c_uint64), ("bad_row", ctypes.c_uint64), ("status", ctypes.c_uint32)]
+
+
 class BlockIndexSummary(ctypes.Structure):
     """hipdeflate_block_index_summary (include/hipdeflate.h)"""
     _fields_ = [("nrows", ctypes.c_uint64), ("npieces", ctypes.c_uint64), ("out_bytes", ctypes.c_uint64),
@@ -75,6 +80,7 @@ BLOCK_ROW_BYTES = 128 << 10          # include/hipdeflate_params.h HD_BLOCK_ROW_
 STREAM_WINDOW_BYTES = 1 << 30        # include/hipdeflate_params.h HD_STREAM_WINDOW_BYTES: slots of one window of the stream encoder
 CHECK_CRC32, CHECK_ADLER32 = 0, 1    # `kind` of hipdeflate_check_combine_dev
 RANGE_BYTES, RANGE_VOFFSET = 0, 1    # HD_RANGE_*: what the begin / end of a ranged read are
+ROWS_BYTES, ROWS_BITS = 0, 1          # HD_ROWS_*: what in_off / in_len of a row table count (hipdeflate_stream_read_ranges_dev)
 RANGE_PIECE = 256 << 10              # include/hipdeflate_params.h HD_RANGE_PIECE: bytes a wavefront of the slice copy takes at a time
 
 
@@ -103,6 +109,7 @@ EXPORTS = [
     "hipdeflate_stream_index_blocks_dev", "hipdeflate_stream_inflate_blocks_dev", "hip_inflate_stream_blocks",
     "hipdeflate_test_block_headers_dev", "hipdeflate_test_blocks_times", "hipdeflate_test_blocks_counts",
     "hipdeflate_test_block_candidates_dev",
+    "hipdeflate_stream_windows_dev", "hipdeflate_stream_read_ranges_dev",
     "hipdeflate_init_devices", "hipdeflate_device_count", "hipdeflate_use_device",
     "hipdeflate_pipe_open_on", "hipdeflate_unpipe_open_on", "hipdeflate_lat_open_on",
     "hipdeflate_batch_inflate_size_dev", "hipdeflate_batch_inflate_framed_dev", "hipdeflate_batch_inflate_size",
@@ -227,6 +234,11 @@ def lib():
     L.hipdeflate_test_blocks_counts.restype = None
     L.hipdeflate_test_block_candidates_dev.argtypes = [_vp, ctypes.c_uint64, ctypes.c_uint64, _vp, ctypes.c_uint32,
                                                        ctypes.POINTER(ctypes.c_uint64), _vp]
+    L.hipdeflate_stream_windows_dev.argtypes = [_vp, ctypes.c_uint64, _vp, _vp, _vp, ctypes.c_uint32, _vp, _vp, ctypes.c_uint64, _vp,
+                                                ctypes.POINTER(WindowSummary), _vp]
+    L.hipdeflate_stream_read_ranges_dev.argtypes = [_vp, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                    ctypes.c_uint64, _vp, ctypes.c_uint32, _vp, _vp, ctypes.c_uint32, _vp, ctypes.c_uint64,
+                                                    _vp, _vp, _vp, ctypes.POINTER(RangeSummary), _vp]
     L.hipdeflate_pipe_open.restype = _vp
     L.hipdeflate_pipe_open.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int]
     L.hipdeflate_pipe_input.restype = _vp

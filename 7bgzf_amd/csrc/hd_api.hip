@@ -28,6 +28,7 @@
 #include "hd_stream.hpp"
 #include "hd_carry.hpp"
 #include "hd_blocks.hpp"
+#include "hd_seek.hpp"
 #include "hd_segment.hpp"
 #include "hd_tables.hpp"
 #include "hd_scratch.hpp"
@@ -1313,6 +1314,39 @@ int hipdeflate_verify_members_dev(const void *status, const void *out_len, const
 	return 0;
 }
 
+// The queries of a ranged read on a table of n rows -- a container's members, or one stream's rows (hd_seek.hpp): lengths,
+// first rows and coverage; coverage -> selection, ranks, the layout in the scratch.  *h: the words read back, of which the
+// summary gets its four counts.  (Synchronises the stream.)
+static int range_plan(const hd::RangeTables &t, const void *in_off, const void *in_len, const void *out_size, const void *out_off, uint32_t n,
+		      int kind, const void *q_begin, const void *q_end, uint32_t nqueries, void *dst_off, void *q_len, void *q_status,
+		      hd::RangeWords *h, hipdeflate_range_summary *summary, hipStream_t st)
+{
+	const uint32_t wg_n = (n + 255) / 256, wg_q = (nqueries + 255) / 256;
+	hd::RangeWords *w = t.w;
+	HD_CHECK(hipMemsetAsync(w, 0, offsetof(hd::RangeWords, bad_row), st));
+	HD_CHECK(hipMemsetAsync(&w->bad_row, 0xff, 4, st));
+	HD_CHECK(hipMemsetAsync(t.cover, 0, ((size_t)n + 1) * 4, st));
+	hipLaunchKernelGGL(hd::k_range_resolve, dim3(wg_q), dim3(256), 0, st, (const uint64_t *)in_off, (const uint32_t *)in_len,
+			   (const uint32_t *)out_size, (const uint64_t *)out_off, n, kind, (const uint64_t *)q_begin,
+			   (const uint64_t *)q_end, nqueries, (uint32_t *)q_len, (int32_t *)q_status, t.q_pieces, t.q_first, t.q_from, t.cover,
+			   &w->nrefused);
+	index_scan((const uint32_t *)q_len, nqueries, t.tiles, (uint64_t *)dst_off, &w->out_bytes, st);
+	index_scan(t.q_pieces, nqueries, t.tiles, t.piece_off, &w->pieces, st);
+	index_scan(t.cover, n + 1, t.tiles, t.cover_scan, &w->cover_total, st);
+	hipLaunchKernelGGL(hd::k_range_select, dim3(wg_n), dim3(256), 0, st, (const uint64_t *)t.cover_scan, (const uint32_t *)out_size, n,
+			   t.sel, t.sel_size);
+	index_scan(t.sel, n, t.tiles, t.rank, &w->nselected, st);
+	index_scan(t.sel_size, n, t.tiles, t.scratch_off, &w->sel_bytes, st);
+	HD_CHECK(hipGetLastError());
+	HD_CHECK(hipMemcpyAsync(h, w, sizeof *h, hipMemcpyDeviceToHost, st));
+	HD_CHECK(hipStreamSynchronize(st));
+	summary->out_bytes = h->out_bytes;
+	summary->nselected = h->nselected;
+	summary->sel_bytes = h->sel_bytes;
+	summary->nrefused = h->nrefused;
+	return 0;
+}
+
 int hipdeflate_read_ranges_dev(const void *blob, const void *in_off, const void *in_len, const void *out_size, const void *out_off,
 			       const void *crc_want, uint32_t nmembers, int kind, const void *q_begin, const void *q_end,
 			       uint32_t nqueries, void *dst, uint64_t dst_cap, void *dst_off, void *q_len, void *q_status,
@@ -1332,35 +1366,14 @@ int hipdeflate_read_ranges_dev(const void *blob, const void *in_off, const void 
 		return 0;
 	hipStream_t st = (hipStream_t)stream;
 	const size_t n = nmembers, nq = nqueries;
-	const uint32_t wg_n = (nmembers + 255) / 256, wg_q = (nqueries + 255) / 256;
+	const uint32_t wg_n = (nmembers + 255) / 256;
 	std::lock_guard<std::mutex> lk(g.mu_index);
 	if (g.d_range.reserve(hd::RangeTables::bytes(n, nq)))
 		return HD_E_NOMEM;
 	const hd::RangeTables t(g.d_range.p, n, nq);
-	hd::RangeWords *w = t.w;
-	HD_CHECK(hipMemsetAsync(w, 0, offsetof(hd::RangeWords, bad_row), st));
-	HD_CHECK(hipMemsetAsync(&w->bad_row, 0xff, 4, st));
-	HD_CHECK(hipMemsetAsync(t.cover, 0, (n + 1) * 4, st));
-	// queries -> lengths, first members, coverage; coverage -> selection, ranks, scratch layout
-	hipLaunchKernelGGL(hd::k_range_resolve, dim3(wg_q), dim3(256), 0, st, (const uint64_t *)in_off, (const uint32_t *)in_len,
-			   (const uint32_t *)out_size, (const uint64_t *)out_off, nmembers, kind, (const uint64_t *)q_begin,
-			   (const uint64_t *)q_end, nqueries, (uint32_t *)q_len, (int32_t *)q_status, t.q_pieces, t.q_first, t.q_from, t.cover,
-			   &w->nrefused);
-	index_scan((const uint32_t *)q_len, nqueries, t.tiles, (uint64_t *)dst_off, &w->out_bytes, st);
-	index_scan(t.q_pieces, nqueries, t.tiles, t.piece_off, &w->pieces, st);
-	index_scan(t.cover, nmembers + 1, t.tiles, t.cover_scan, &w->cover_total, st);
-	hipLaunchKernelGGL(hd::k_range_select, dim3(wg_n), dim3(256), 0, st, (const uint64_t *)t.cover_scan, (const uint32_t *)out_size,
-			   nmembers, t.sel, t.sel_size);
-	index_scan(t.sel, nmembers, t.tiles, t.rank, &w->nselected, st);
-	index_scan(t.sel_size, nmembers, t.tiles, t.scratch_off, &w->sel_bytes, st);
-	HD_CHECK(hipGetLastError());
-	hd::RangeWords h;
-	HD_CHECK(hipMemcpyAsync(&h, w, sizeof h, hipMemcpyDeviceToHost, st));
-	HD_CHECK(hipStreamSynchronize(st));
-	summary->out_bytes = h.out_bytes;
-	summary->nselected = h.nselected;
-	summary->sel_bytes = h.sel_bytes;
-	summary->nrefused = h.nrefused;
+	hd::RangeWords *w = t.w, h;
+	if ((r = range_plan(t, in_off, in_len, out_size, out_off, nmembers, kind, q_begin, q_end, nqueries, dst_off, q_len, q_status, &h, summary, st)))
+		return r;
 	if (h.out_bytes > dst_cap) {
 		summary->status = 3;
 		return 0;
@@ -2189,6 +2202,197 @@ int hipdeflate_stream_inflate_blocks_dev(const void *strm, uint64_t nbytes, int 
 	const StreamRows t = { (const uint64_t *)in_off, (const uint32_t *)in_len, (const uint64_t *)out_off, (const uint32_t *)out_size,
 			       (const uint32_t *)reach };
 	return stream_inflate_rows(cur(), strm, nbytes, frame, t, nullptr, true, nrows, out, out_cap, summary, (hipStream_t)stream, true);
+}
+
+/* ---- ... and a seek index on either table: the window in front of every row, and ranged reads on it (hd_seek.hpp) ---- */
+
+int hipdeflate_stream_windows_dev(const void *out, uint64_t out_bytes, const void *out_size, const void *out_off, const void *reach,
+				  uint32_t nrows, void *win_off, void *win, uint64_t win_cap, void *row_check,
+				  hipdeflate_window_summary *summary, void *stream)
+{
+	Ctx &g = cur();
+	int r = enter_call(summary, sizeof *summary);
+	if (r)
+		return r;
+	summary->bad_row = nrows;
+	if (nrows >= STREAM_MAX_PARTS || (out_bytes && !out) || (win_cap && !win) ||
+	    (nrows && (!out_size || !out_off || !reach || !win_off)))
+		return HD_E_ARG;
+	if (nrows == 0) {                                                            // a stream has its final row
+		summary->status = 1;
+		summary->bad_row = 0;
+		return 0;
+	}
+	hipStream_t st = (hipStream_t)stream;
+	const uint32_t wg = (nrows + 255) / 256;
+	std::lock_guard<std::mutex> lk(g.mu_index);
+	if (g.d_stream.reserve(hd::WindowScratch::bytes(nrows)))
+		return HD_E_NOMEM;
+	const hd::WindowScratch d(g.d_stream.p, nrows);
+	HD_CHECK(hipMemsetD32Async((hipDeviceptr_t)&d.w->v.fault, (int)hd::IDX_NIL, 1, st));
+	hipLaunchKernelGGL(hd::k_seek_check_out, dim3(wg), dim3(256), 0, st, (const uint32_t *)out_size, (const uint64_t *)out_off, nrows,
+			   out_bytes, &d.w->v.fault);
+	hipLaunchKernelGGL(hd::k_carry_check_reach, dim3(wg), dim3(256), 0, st, (const uint32_t *)reach, (const uint64_t *)out_off, nrows,
+			   hd::CARRY_WINDOW, &d.w->v.fault);
+	HD_CHECK(hipGetLastError());
+	uint32_t fault = hd::IDX_NIL;
+	HD_CHECK(hipMemcpyAsync(&fault, &d.w->v.fault, 4, hipMemcpyDeviceToHost, st));
+	HD_CHECK(hipStreamSynchronize(st));
+	if (fault != hd::IDX_NIL) {
+		summary->status = 1;
+		summary->bad_row = fault;
+		return 0;
+	}
+	uint64_t *woff = (uint64_t *)win_off;
+	index_scan((const uint32_t *)reach, nrows, d.tiles, woff, woff + nrows, st);
+	HD_CHECK(hipGetLastError());
+	HD_CHECK(hipMemcpyAsync(&summary->win_bytes, woff + nrows, 8, hipMemcpyDeviceToHost, st));
+	HD_CHECK(hipStreamSynchronize(st));
+	if (summary->win_bytes > win_cap) {
+		summary->status = 3;
+		return 0;
+	}
+	if (summary->win_bytes) {
+		const uint64_t cap = (uint64_t)hd::compact_device_cus() * hd::COMPACT_WAVES_PER_CU;
+		hipLaunchKernelGGL(hd::k_seek_windows, dim3((uint32_t)(nrows < cap ? nrows : cap)), dim3(64), 0, st, (const uint8_t *)out,
+				   (const uint64_t *)out_off, (const uint32_t *)reach, (const uint64_t *)woff, nrows, (uint8_t *)win);
+	}
+	if (row_check)
+		hipLaunchKernelGGL(hd::k_carry_crc, dim3(nrows), dim3(64), 0, st, (const CrcTables *)g.d_ct, (const uint8_t *)out,
+				   (const uint64_t *)out_off, (const uint32_t *)out_size, nrows, (uint32_t *)row_check);
+	HD_CHECK(hipGetLastError());
+	HD_CHECK(hipStreamSynchronize(st));
+	return 0;
+}
+
+int hipdeflate_stream_read_ranges_dev(const void *strm, uint64_t nbytes, int frame, int unit, const void *in_off, const void *in_len,
+				      const void *out_size, const void *out_off, const void *reach, const void *win_off, const void *win,
+				      uint64_t win_bytes, const void *row_check, uint32_t nrows, const void *q_begin, const void *q_end,
+				      uint32_t nqueries, void *dst, uint64_t dst_cap, void *dst_off, void *q_len, void *q_status,
+				      hipdeflate_range_summary *summary, void *stream)
+{
+	Ctx &g = cur();
+	int r = enter_call(summary, sizeof *summary);
+	if (r)
+		return r;
+	summary->bad_member = nrows;
+	if ((unit != HD_ROWS_BYTES && unit != HD_ROWS_BITS) || !stream_frame_ok(frame) || ((uintptr_t)strm & 15) || (nbytes && !strm) ||
+	    nrows >= STREAM_MAX_PARTS || nqueries > 0x7fffffffu ||
+	    (nrows && (!in_off || !in_len || !out_size || !out_off || !reach || !win_off || (win_bytes && !win))) ||
+	    (nqueries && (!q_begin || !q_end || !dst_off || !q_len || !q_status)) || (!dst && dst_cap))
+		return HD_E_ARG;
+	if (nrows == 0 || nqueries == 0)
+		return 0;
+	hipStream_t st = (hipStream_t)stream;
+	const bool bits = unit == HD_ROWS_BITS;
+	const size_t n = nrows, nq = nqueries;
+	const uint32_t wg_n = (nrows + 255) / 256, trl = stream_trl(frame);
+	std::lock_guard<std::mutex> lk(g.mu_index);
+	if (g.d_stream.reserve(hd::SeekTables::bytes(n)) || g.d_range.reserve(hd::RangeTables::bytes(n, nq)))
+		return HD_E_NOMEM;
+	const hd::SeekTables d(g.d_stream.p, n);
+	const hd::RangeTables t(g.d_range.p, n, nq);
+	// 1. the table, by the rules of its unit's decode call, and the windows' offsets
+	uint32_t hdr = 0, refused = 0;
+	if ((r = stream_open(strm, nbytes, frame, d.header, st, &hdr, &refused)))
+		return r;
+	if (refused || nbytes < (uint64_t)hdr + trl) {
+		summary->status = 1;
+		return 0;
+	}
+	if ((r = stream_words_reset(d.w, hd::CHECK_CRC32, st)))
+		return r;
+	HD_CHECK(hipMemsetAsync(d.ends, 0, 16, st));
+	if (bits)
+		hipLaunchKernelGGL(hd::k_blocks_check_rows, dim3(wg_n), dim3(256), 0, st, (const uint64_t *)in_off, (const uint32_t *)in_len,
+				   (const uint32_t *)out_size, (const uint64_t *)out_off, nrows, (uint64_t)hdr, nbytes - trl, &d.w->v.fault, d.ends);
+	else
+		hipLaunchKernelGGL(hd::k_stream_check_rows, dim3(wg_n), dim3(256), 0, st, (const uint64_t *)in_off, (const uint32_t *)in_len,
+				   (const uint32_t *)out_size, (const uint64_t *)out_off, nrows, (uint64_t)hdr, nbytes - trl, &d.w->v.fault, d.ends);
+	hipLaunchKernelGGL(hd::k_carry_check_reach, dim3(wg_n), dim3(256), 0, st, (const uint32_t *)reach, (const uint64_t *)out_off, nrows,
+			   hd::CARRY_WINDOW, &d.w->v.fault);
+	hipLaunchKernelGGL(hd::k_seek_check_win, dim3(wg_n), dim3(256), 0, st, (const uint64_t *)win_off, (const uint32_t *)reach, nrows,
+			   win_bytes, &d.w->v.fault);
+	HD_CHECK(hipGetLastError());
+	uint32_t fault = hd::IDX_NIL;
+	HD_CHECK(hipMemcpyAsync(&fault, &d.w->v.fault, 4, hipMemcpyDeviceToHost, st));
+	HD_CHECK(hipStreamSynchronize(st));
+	if (fault != hd::IDX_NIL) {
+		summary->status = 1;
+		summary->bad_member = fault;
+		return 0;
+	}
+	// 2. the queries, as hipdeflate_read_ranges_dev resolves them in bytes: lengths, first rows, coverage -> selection, ranks, layout
+	hd::RangeWords *w = t.w, h;
+	if ((r = range_plan(t, in_off, in_len, out_size, out_off, nrows, HD_RANGE_BYTES, q_begin, q_end, nqueries, dst_off, q_len, q_status, &h,
+			    summary, st)))
+		return r;
+	if (h.out_bytes > dst_cap) {
+		summary->status = 3;
+		return 0;
+	}
+	if (h.nselected == 0)                                                    // no query took a byte
+		return 0;
+	// 3. the selected rows' tables, back to back in the byte scratch
+	const uint32_t nsel = (uint32_t)h.nselected;
+	if (g.d_range_out.reserve(h.sel_bytes + 16))
+		return HD_E_NOMEM;
+	uint8_t *scratch = (uint8_t *)g.d_range_out.p;
+	const hd::SeekColumns c{ d.c_in_off, d.c_out_off, d.c_win_off, d.c_in_len, d.c_out_size, d.c_reach, d.c_row_check, d.c_row };
+	hipLaunchKernelGGL(hd::k_seek_tables, dim3(wg_n), dim3(256), 0, st, (const uint64_t *)in_off, (const uint32_t *)in_len,
+			   (const uint32_t *)out_size, (const uint32_t *)reach, (const uint64_t *)win_off, (const uint32_t *)row_check,
+			   (const uint32_t *)t.sel, (const uint64_t *)t.rank, (const uint64_t *)t.scratch_off, nrows, c);
+	// 4. and 5. group by group: the rows as symbols, then every symbol its byte -- no group needs another, so nothing is read
+	// back between them but the group's record
+	const uint64_t group_bytes = g_test_carry_group ? g_test_carry_group : HD_CARRY_GROUP_BYTES;
+	for (uint32_t r0 = 0; r0 < nsel;) {
+		uint64_t gr[4];
+		hipLaunchKernelGGL(hd::k_carry_group, dim3(1), dim3(256), 0, st, (const uint64_t *)d.c_out_off, (const uint32_t *)d.c_out_size,
+				   (const uint32_t *)d.c_reach, r0, nsel, group_bytes, d.group);
+		HD_CHECK(hipGetLastError());
+		HD_CHECK(hipMemcpyAsync(gr, d.group, 32, hipMemcpyDeviceToHost, st));
+		HD_CHECK(hipStreamSynchronize(st));
+		const uint32_t r1 = (uint32_t)gr[0], nr = r1 - r0;
+		const uint64_t begin = gr[2], gbytes = gr[3] - gr[2];
+		if (gbytes > (uint64_t)1 << 40 || g.d_stream_slots.reserve(hd::MarkerScratch::bytes(gbytes, 0)))
+			return HD_E_NOMEM;
+		const hd::MarkerScratch m(g.d_stream_slots.p, gbytes, 0);
+		const hd::CarryDecodeArgs da{ (const uint8_t *)strm, d.c_in_off, d.c_in_len, d.c_out_size, d.c_out_off, d.c_reach, r0, nr, begin,
+					      m.sym, d.out_len, d.status };
+		if (bits)
+			hipLaunchKernelGGL(hd::k_blocks_decode, dim3(nr), dim3(64), 0, st, hd::BlocksDecodeArgs{ da });
+		else
+			hipLaunchKernelGGL(hd::k_carry_decode, dim3(nr), dim3(64), 0, st, da);
+		const hd::SeekResolveArgs ra{ m.sym, begin, gr[3], d.c_out_off, d.c_out_size, d.c_reach, d.c_win_off, r0, nr, (const uint8_t *)win,
+					      scratch };
+		const uint64_t npieces = (gr[3] + hd::SEEK_PIECE - 1) / hd::SEEK_PIECE - begin / hd::SEEK_PIECE;
+		hipLaunchKernelGGL(hd::k_seek_resolve, dim3((uint32_t)npieces), dim3(64), 0, st, ra);
+		hipLaunchKernelGGL(hd::k_carry_verify, dim3((nr + 255) / 256), dim3(256), 0, st, (const int32_t *)d.status,
+				   (const uint32_t *)d.out_len, (const uint32_t *)d.c_out_size, r0, nr, &w->bad_row);
+		r0 = r1;
+	}
+	// 6. the rows' bytes against the checks the caller keeps; the first bad rank by the caller's table
+	if (row_check) {
+		hipLaunchKernelGGL(hd::k_carry_crc, dim3(nsel), dim3(64), 0, st, (const CrcTables *)g.d_ct, (const uint8_t *)scratch,
+				   (const uint64_t *)d.c_out_off, (const uint32_t *)d.c_out_size, nsel, d.crc);
+		hipLaunchKernelGGL(hd::k_seek_check_crc, dim3((nsel + 255) / 256), dim3(256), 0, st, (const uint32_t *)d.crc,
+				   (const uint32_t *)d.c_row_check, nsel, &w->bad_row);
+	}
+	hipLaunchKernelGGL(hd::k_range_verdict, dim3(1), dim3(1), 0, st, (const uint32_t *)&w->bad_row, (const uint32_t *)d.c_row, nrows,
+			   &w->bad_member);
+	// 7. every query's run of the scratch -> dst + dst_off[q]
+	const uint64_t grid_cap = (uint64_t)hd::compact_device_cus() * hd::COMPACT_WAVES_PER_CU;
+	hipLaunchKernelGGL(hd::k_range_gather, dim3((uint32_t)(h.pieces < grid_cap ? h.pieces : grid_cap)), dim3(64), 0, st,
+			   (const uint8_t *)scratch, (const uint64_t *)t.scratch_off, (const uint64_t *)out_off, (const uint32_t *)t.q_first,
+			   (const uint64_t *)t.q_from, (const uint32_t *)q_len, (const uint64_t *)dst_off, (const uint64_t *)t.piece_off,
+			   nqueries, h.pieces, (uint8_t *)dst);
+	HD_CHECK(hipGetLastError());
+	HD_CHECK(hipMemcpyAsync(&h.bad_member, &w->bad_member, 8, hipMemcpyDeviceToHost, st));
+	HD_CHECK(hipStreamSynchronize(st));
+	summary->bad_member = h.bad_member;
+	if (h.bad_member != nrows)
+		summary->status = 2;
+	return 0;
 }
 
 /* ---- host-pointer API ------------------------------------------------------ */

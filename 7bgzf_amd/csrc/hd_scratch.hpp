@@ -190,6 +190,30 @@ struct MarkerScratch : Layout<MarkerScratch> {
 	uint8_t *slack = c.take<uint8_t>(16);
 };
 
+// d_stream, hipdeflate_stream_windows_dev: the verdict words and the tiles of the scan of n reach values
+struct WindowScratch : Layout<WindowScratch> {
+	WindowScratch(void *base, size_t n_) : Layout(base), n(n_) {}
+	size_t n;
+	StreamWords *w = c.take<StreamWords>(1);
+	uint64_t *tiles = c.take<uint64_t>(scan_tiles(n));
+};
+
+// d_stream, hipdeflate_stream_read_ranges_dev (hd_seek.hpp): the check of a table of n rows, and the selected rows' compacted
+// tables with the row decoder's verdicts (at most n rows are selected; the queries' tables are a RangeTables in d_range)
+struct SeekTables : Layout<SeekTables> {
+	SeekTables(void *base, size_t n_) : Layout(base), n(n_) {}
+	size_t n;
+	StreamWords *w = c.take<StreamWords>(1);
+	uint64_t *header = c.take<uint64_t>(8);          // stream_open's eight words
+	uint64_t *ends = c.take<uint64_t>(2);            // k_stream_check_rows / k_blocks_check_rows: where the rows end
+	uint64_t *group = c.take<uint64_t>(4);           // k_carry_group's record
+	uint64_t *c_in_off = c.take<uint64_t>(n), *c_out_off = c.take<uint64_t>(n), *c_win_off = c.take<uint64_t>(n);
+	uint32_t *c_in_len = c.take<uint32_t>(n), *c_out_size = c.take<uint32_t>(n), *c_reach = c.take<uint32_t>(n);
+	uint32_t *c_row_check = c.take<uint32_t>(n), *c_row = c.take<uint32_t>(n);
+	uint32_t *out_len = c.take<uint32_t>(n), *crc = c.take<uint32_t>(n);
+	int32_t *status = c.take<int32_t>(n);
+};
+
 // the row table that stream_index makes in d_meta for the host-buffer forms, and that they read back: n rows
 struct RowTable : Layout<RowTable> {
 	RowTable(void *base, size_t n_, bool carry) : Layout(base), n(n_), nr(carry ? n_ : 0) {}

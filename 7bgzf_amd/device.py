@@ -388,6 +388,148 @@ def inflate_stream_blocks(stream, frame=_pkg.FRAME_GZIP):
     return out, x
 
 
+def stream_windows_call(out, out_size, out_off, reach, nrows, win_off, win, win_cap, row_check):
+    """one hipdeflate_stream_windows_dev: out the decoded stream, the three columns of its row table, win_off an int64
+    tensor of nrows + 1 entries, win a uint8 tensor or None (the sizing call), row_check an int32 tensor -> WindowSummary"""
+    summary = _pkg.WindowSummary()
+    rc = _pkg.lib().hipdeflate_stream_windows_dev(_ptr(out), out.numel(), _ptr(out_size), _ptr(out_off), _ptr(reach), nrows,
+                                                  _ptr(win_off), _ptr(win), win_cap, _ptr(row_check), ctypes.byref(summary), _stream())
+    _pkg._check(rc, "hipdeflate_stream_windows_dev")
+    return summary
+
+
+def stream_read_ranges_call(stream, frame, unit, in_off, in_len, out_size, out_off, reach, win_off, win, win_bytes, row_check, nrows,
+                            begins, ends, dst, dst_cap):
+    """one hipdeflate_stream_read_ranges_dev: begins / ends int64 device tensors (the bits of the u64 values), dst a uint8
+    tensor of any alignment or None, row_check an int32 tensor or None -> (dst_off, q_len, q_status, RangeSummary)"""
+    nq = begins.numel()
+    dst_off = torch.zeros(nq, dtype=torch.int64, device=stream.device)
+    q_len = torch.zeros(nq, dtype=torch.int32, device=stream.device)
+    q_status = torch.zeros(nq, dtype=torch.int32, device=stream.device)
+    summary = _pkg.RangeSummary()
+    rc = _pkg.lib().hipdeflate_stream_read_ranges_dev(
+        _ptr(stream), stream.numel(), frame, unit, _ptr(in_off), _ptr(in_len), _ptr(out_size), _ptr(out_off), _ptr(reach),
+        _ptr(win_off), _ptr(win), win_bytes, _ptr(row_check), nrows, _ptr(begins), _ptr(ends), nq, _ptr(dst), dst_cap,
+        _ptr(dst_off), _ptr(q_len), _ptr(q_status), ctypes.byref(summary), _stream())
+    _pkg._check(rc, "hipdeflate_stream_read_ranges_dev")
+    return dst_off, q_len, q_status, summary
+
+
+class SeekIndex:
+    """A seek index on ONE raw / zlib / gzip stream resident in HBM: its row table (the block index's, in bits, or the carry
+    index's, in bytes), the window in front of every row and the CRC-32 of every row's bytes.  build() pays one full decode;
+    a read then decodes only the rows it touches.  The windows hold at most 32 KiB a row: row_bytes is what they cost."""
+
+    VERSION = 1
+    COLUMNS = ("in_off", "in_len", "out_size", "out_off", "reach", "win_off", "row_check")
+    _DTYPES = {"in_off": np.int64, "in_len": np.int32, "out_size": np.int32, "out_off": np.int64, "reach": np.int32,
+               "win_off": np.int64, "row_check": np.int32}
+
+    def __init__(self, stream, frame, unit, nbytes, columns, win):
+        """stream: the uint8 tensor the index belongs to (None: an index that can be saved, not read); columns: a dict of
+        the seven COLUMNS, win: the window bytes -- tensors on the stream's device, or numpy arrays where there is no stream"""
+        self.stream, self.frame, self.unit, self.nbytes = stream, int(frame), int(unit), int(nbytes)
+        self.columns, self.win = dict(columns), win
+        self.nrows = len(self.columns["in_off"])
+        if len(self.columns["win_off"]) != self.nrows + 1 or any(len(self.columns[c]) != self.nrows for c in self.COLUMNS if c != "win_off"):
+            raise ValueError("seek index: columns of uneven length")
+
+    @classmethod
+    def build(cls, stream, frame=_pkg.FRAME_GZIP, kind="blocks", row_bytes=0):
+        """index, full decode, the sizing call, the windows call; raises on any non-zero status"""
+        if kind == "blocks":
+            in_off, in_len, out_size, out_off, reach, x = index_stream_blocks(stream, frame, row_bytes=row_bytes)
+            n, unit, decode = x.nrows, _pkg.ROWS_BITS, inflate_stream_blocks_call
+        elif kind == "carry":
+            in_off, in_len, out_size, out_off, reach, x = index_stream_carry(stream, frame)
+            n, unit, decode = x.nchunks, _pkg.ROWS_BYTES, inflate_stream_carry_call
+        else:
+            raise ValueError("kind = %r: 'blocks' or 'carry'" % (kind,))
+        if x.status:
+            raise _pkg.HipDeflateError("seek index: the %s index answers status %d (%d rows)" % (kind, x.status, n))
+        out = torch.empty(x.out_bytes, dtype=torch.uint8, device=stream.device)
+        s = decode(stream, frame, in_off, in_len, out_size, out_off, reach, n, out, x.out_bytes)
+        if s.status:
+            raise _pkg.HipDeflateError("seek index: the full decode answers status %d (bad_chunk %d of %d)" % (s.status, s.bad_chunk, n))
+        cols = [c[:n].contiguous() for c in (in_off, in_len, out_size, out_off, reach)]
+        win_off = torch.zeros(n + 1, dtype=torch.int64, device=stream.device)
+        row_check = torch.zeros(n, dtype=torch.int32, device=stream.device)
+        w = stream_windows_call(out, cols[2], cols[3], cols[4], n, win_off, None, 0, row_check)
+        if w.status not in (0, 3):
+            raise _pkg.HipDeflateError("seek index: the windows call answers status %d (row %d)" % (w.status, w.bad_row))
+        win = torch.empty(w.win_bytes, dtype=torch.uint8, device=stream.device)
+        w = stream_windows_call(out, cols[2], cols[3], cols[4], n, win_off, win, win.numel(), row_check)
+        if w.status:
+            raise _pkg.HipDeflateError("seek index: the windows call answers status %d (row %d)" % (w.status, w.bad_row))
+        return cls(stream, frame, unit, stream.numel(), dict(zip(cls.COLUMNS, cols + [win_off, row_check])), win)
+
+    @property
+    def total(self):
+        """the decoded bytes of the stream (the table's last row is on the host only behind save / load)"""
+        o, s = self.columns["out_off"], self.columns["out_size"]
+        return int(o[-1]) + (int(s[-1]) & 0xffffffff) if self.nrows else 0
+
+    def _call(self, begins, ends, dst, dst_cap):
+        c = self.columns
+        return stream_read_ranges_call(self.stream, self.frame, self.unit, c["in_off"], c["in_len"], c["out_size"], c["out_off"],
+                                       c["reach"], c["win_off"], self.win, self.win.numel(), c["row_check"], self.nrows, begins, ends,
+                                       dst, dst_cap)
+
+    def read_ranges(self, begins, ends):
+        """the bytes of the ranges [begins[q], ends[q]) of the decoded stream; only the rows they touch are decoded
+        -> (out, dst_off, q_len, q_status, RangeSummary), as DeviceInflate.read_ranges answers"""
+        if self.stream is None:
+            raise _pkg.HipDeflateError("seek index: loaded without its stream")
+        begins, ends = _u64_tensor(begins, self.stream.device), _u64_tensor(ends, self.stream.device)
+        if begins.numel() != ends.numel():
+            raise ValueError("%d begins, %d ends" % (begins.numel(), ends.numel()))
+        s = self._call(begins, ends, None, 0)[3]                                  # the sizing call
+        if s.status not in (0, 3):
+            raise _pkg.HipDeflateError("seek read: status %d, row %d" % (s.status, s.bad_member))
+        out = torch.empty(s.out_bytes, dtype=torch.uint8, device=self.stream.device)
+        dst_off, q_len, q_status, s = self._call(begins, ends, out, out.numel())
+        if s.status:
+            raise _pkg.HipDeflateError("seek read: status %d, row %d" % (s.status, s.bad_member))
+        return out, dst_off, q_len, q_status, s
+
+    def read(self, begin, end):
+        """the bytes [begin, end) of the decoded stream -> uint8 tensor"""
+        out, _, _, q_status, _ = self.read_ranges([begin], [end])
+        if int(q_status[0]):
+            raise ValueError("seek read: [%d, %d) is refused (q_status %d)" % (begin, end, int(q_status[0])))
+        return out
+
+    def save(self, path):
+        """one numpy.savez file: a version number, frame, unit, nbytes, the seven columns and the window bytes"""
+        def host(a):
+            return a.cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        arrays = {c: host(self.columns[c]).astype(self._DTYPES[c], copy=False) for c in self.COLUMNS}
+        with open(path, "wb") as f:
+            np.savez(f, version=np.int64(self.VERSION), frame=np.int64(self.frame), unit=np.int64(self.unit),
+                     nbytes=np.int64(self.nbytes), win=host(self.win).astype(np.uint8, copy=False), **arrays)
+
+    @classmethod
+    def load(cls, path, stream):
+        """the index save() wrote, for `stream` (a uint8 device tensor: the columns go to its device; or a bytes-like object,
+        for which they stay numpy arrays and nothing touches a device).  Refuses another version, and a stream of another length."""
+        with np.load(path) as z:
+            version = int(z["version"])
+            if version != cls.VERSION:
+                raise _pkg.HipDeflateError("seek index: version %d, this is version %d" % (version, cls.VERSION))
+            nbytes = int(z["nbytes"])
+            have = stream.numel() if isinstance(stream, torch.Tensor) else len(stream)
+            if nbytes != have:
+                raise _pkg.HipDeflateError("seek index: made for a stream of %d bytes, this one has %d" % (nbytes, have))
+            cols = {c: z[c].astype(cls._DTYPES[c]) for c in cls.COLUMNS}
+            win, frame, unit = z["win"].astype(np.uint8), int(z["frame"]), int(z["unit"])
+        if unit not in (_pkg.ROWS_BYTES, _pkg.ROWS_BITS):
+            raise _pkg.HipDeflateError("seek index: unit %d" % unit)
+        if isinstance(stream, torch.Tensor):
+            cols = {c: torch.from_numpy(a).to(stream.device) for c, a in cols.items()}
+            return cls(stream, frame, unit, nbytes, cols, torch.from_numpy(win).to(stream.device))
+        return cls(None, frame, unit, nbytes, cols, win)
+
+
 def check_combine(check, lens, kind=_pkg.CHECK_CRC32):
     """the CRC-32 (kind 0) / Adler-32 (kind 1) of a concatenation from the checks and lengths of its parts: int32 device
     tensors holding the bits of the u32 values -> int"""

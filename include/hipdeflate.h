@@ -359,7 +359,8 @@ typedef struct hipdeflate_range_summary {
 	uint64_t nrefused;    /* queries with q_status != 0 */
 	uint64_t bad_member;  /* status 2: lowest index, in the CALLER's table, of a decoded member whose inflate
 	                       * disagrees with its trailer; nmembers otherwise */
-	uint32_t status;      /* 0 ok | 2 a decoded member is bad | 3 dst too small */
+	uint32_t status;      /* 0 ok | 2 a decoded member is bad | 3 dst too small (| 1 the table is refused:
+	                       * hipdeflate_stream_read_ranges_dev alone) */
 } hipdeflate_range_summary;
 /* Status 3 (out_bytes > dst_cap): nothing is inflated and dst is not touched; q_len, dst_off, q_status and the summary are
  * complete, so a call with dst == NULL and dst_cap == 0 is the sizing call.  Status 2: a selected member disagrees with its
@@ -668,6 +669,82 @@ void hipdeflate_test_blocks_counts(uint64_t *out2);
  * ascending; *count HOST = its length, pos[] (u64, device) gets the first min(*count, max_pos).  (Synchronises the stream.) */
 int hipdeflate_test_block_candidates_dev(const void *strm, uint64_t nbytes, uint64_t first, void *pos, uint32_t max_pos,
 					 uint64_t *count /* HOST */, void *stream);
+/* ---- ... and a SEEK INDEX on either table: the window in front of every row, and ranged reads on it ----------------------
+ * Role: the index with windows of zran, gztool and rapidgzip.  The two decodes above decode the whole stream every time; data
+ * that is resident in HBM is read more than once, and to get one byte of it that is a full decode.  A row of the carry table
+ * or the block table names bytes in front of itself only within reach[i], and the row decoders turn every such reference
+ * into a marker that points straight into those reach[i] bytes.  Keep the reach[i] bytes in front of every row once, behind
+ * one full decode, and every row stands alone: a ranged read decodes only the rows it touches, in no order, and a read of
+ * the whole stream runs no serial pass at all.
+ *   What the windows cost: reach[i] <= 32768, so the windows hold at most 32 KiB a ROW, whatever the row's size -- row_bytes
+ * of the block index (the chunk size of a flushing writer) is the knob.  At the default 128 KiB rows they are at most a
+ * quarter of the decoded size; at 4,096-byte rows of word-shaped text they were seven times the data.
+ *
+ * hipdeflate_stream_windows_dev makes the windows.  out[0, out_bytes) is the decoded stream: what
+ * hipdeflate_stream_inflate_carry_dev or hipdeflate_stream_inflate_blocks_dev wrote with status 0 for this table.  Only the
+ * output-side columns are used -- out_size, out_off, reach, device arrays of nrows entries -- so the call serves byte rows and
+ * bit rows alike.  win_off: u64[nrows + 1], win: win_cap bytes, row_check: u32[nrows] (may be NULL: no checks are taken), all
+ * device memory.  *summary (host memory): */
+typedef struct hipdeflate_window_summary {
+	uint64_t win_bytes;   /* win_off[nrows] = sum of reach; with status 3: the need */
+	uint64_t bad_row;     /* status 1: the lowest row at fault; nrows otherwise */
+	uint32_t status;      /* 0 ok | 1 the table is refused | 3 win_cap too small */
+} hipdeflate_window_summary;
+/*   status 1  out_off is not the exclusive prefix sum of out_size from 0, or the total is not out_bytes; reach[i] > 32768 or
+ *             reach[i] > out_off[i].  bad_row = the lowest row at fault; nrows == 0 (a stream has its final row) names row 0.
+ *             Nothing is written.
+ *   otherwise win_off is the exclusive prefix sum of reach with nrows + 1 entries, always written: win == NULL with
+ *             win_cap == 0 is the sizing call.
+ *   status 3  win_cap < win_off[nrows].  Neither win nor row_check is touched.
+ *   status 0  win[win_off[i] .. win_off[i+1]) = out[out_off[i] - reach[i] .. out_off[i]); row_check[i] = the CRC-32 of row i's
+ *             out_size[i] bytes, whatever the frame (a row of size 0: 0).  No byte of win at or behind win_cap is written.
+ * out and win need no alignment.  Returns 0 whenever the call ran.  (Synchronises the stream; takes turns as the indexes do.) */
+int hipdeflate_stream_windows_dev(const void *out, uint64_t out_bytes,
+				  const void *out_size, const void *out_off, const void *reach, uint32_t nrows,
+				  void *win_off /* u64[nrows + 1] */, void *win, uint64_t win_cap,
+				  void *row_check /* u32[nrows] */, hipdeflate_window_summary *summary /* HOST */, void *stream);
+/* The ranged read: hipdeflate_read_ranges_dev for one stream.  unit says what in_off / in_len count: */
+#define HD_ROWS_BYTES 0   /* bytes: the table of hipdeflate_stream_index_carry_dev */
+#define HD_ROWS_BITS  1   /* bits:  the table of hipdeflate_stream_index_blocks_dev */
+/* The five columns are the index's, win_off / win / row_check what hipdeflate_stream_windows_dev made of them (win_bytes =
+ * the bytes of win that may be read; row_check may be NULL: the rows' bytes are not checked then).  The queries are
+ * HD_RANGE_BYTES queries of hipdeflate_read_ranges_dev, rule for rule: begin > end is refused (q_status 1), end is clipped to
+ * the total, begin at or behind the total gives length 0, 2^32 bytes or more after clipping give q_status 2; duplicate,
+ * nested and unsorted queries each get a copy of their own; a refused query disturbs nothing.  dst_off, q_len, q_status and
+ * the summary behave as in that call; bad_member names a ROW.  A row is decoded if and only if an accepted query takes at
+ * least one byte of it.  In this order:
+ *   HD_E_ARG  a NULL summary; a unit that is neither of the two; a frame other than RAW / ZLIB / GZIP; strm not 16-byte
+ *             aligned; NULL tables where there are rows; NULL query arrays where there are queries; dst == NULL with dst_cap != 0.
+ *   status 1  (a value this call alone gives the struct) the table breaks a rule of its unit's decode call -- everything
+ *             hipdeflate_stream_inflate_carry_dev / hipdeflate_stream_inflate_blocks_dev answers status 1 for on the rows, the
+ *             reach rule included -- or the stream's header is refused (bad_member = nrows); or win_off[0] != 0, or
+ *             win_off[i+1] - win_off[i] != reach[i], or row i's window ends behind win_bytes (so a table that is right but for
+ *             win_off[nrows] > win_bytes names the first row whose window does).  bad_member = the lowest row at fault.
+ *             Nothing is decoded, and the query arrays are not written.
+ *   status 3  the sum of q_len exceeds dst_cap.  Nothing is decoded; the three query arrays and the summary are complete --
+ *             dst == NULL with dst_cap == 0 is the sizing call.
+ *   status 2  bad_member = the lowest selected row, by the caller's table, that fails: it does not decode by its unit's rule
+ *             (the flush rule; the exact end bit), is not out_size[i] long, reaches further back than reach[i], or -- with
+ *             row_check -- the CRC-32 of its bytes is not row_check[i].  dst is unspecified for the queries that touch a
+ *             failed row; every other query has its bytes.
+ * The stream's trailer is NOT examined: the full decode in front of the windows call did that, and a read sees only the
+ * rows it touches.  Without row_check a wrong byte in win goes unnoticed.  nrows == 0 or nqueries == 0 returns 0 with a zero
+ * summary (bad_member = nrows).  No byte of strm at or behind nbytes, none of win at or behind win_bytes is read; no byte of
+ * dst outside [0, out_bytes) is written; what the table states is checked, never trusted.
+ *   The passes: the table check; the queries resolved as the member call does it; the selected rows' tables compacted; the
+ * selected rows decoded to 16-bit symbols in groups of HD_CARRY_GROUP_BYTES of SELECTED output (hipdeflate_test_carry_group
+ * sizes them here too) by the row decoder of the unit, as it stands; all rows of the group side by side turning every
+ * symbol into its byte or win[win_off[i] + reach[i] - distance], eight symbols to a load and eight bytes to a store; the
+ * checks; the gather of hipdeflate_read_ranges_dev.  Scratch, the library's, grow-only: 2 bytes per output byte of the
+ * largest group, and sel_bytes, the sum of the selected rows' out_size -- so a read of the whole stream holds the stream
+ * twice beside dst: this limit is stated, not lifted.  Returns 0 whenever the call ran.  (Synchronises the stream, once a
+ * group; takes turns with the indexes and the other stream calls.)  There is no host-buffer form. */
+int hipdeflate_stream_read_ranges_dev(const void *strm, uint64_t nbytes, int frame, int unit,
+				      const void *in_off, const void *in_len, const void *out_size, const void *out_off, const void *reach,
+				      const void *win_off, const void *win, uint64_t win_bytes, const void *row_check /* may be NULL */, uint32_t nrows,
+				      const void *q_begin, const void *q_end, uint32_t nqueries,
+				      void *dst, uint64_t dst_cap, void *dst_off, void *q_len, void *q_status,
+				      hipdeflate_range_summary *summary /* HOST */, void *stream);
 /* the fold on its own: check[] / len[] device arrays of n parts (u32 each, n < 2^31), kind 0 = CRC-32, 1 = Adler-32; *result HOST.
  * The check of the concatenation of the parts from the parts' own: the role of crc_append (the hosts' serial fold, after
  * zlib's crc32_combine) with one lane per part -- part i contributes check[i] moved over the S_i bytes behind it, S_i a
