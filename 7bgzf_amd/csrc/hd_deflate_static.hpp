@@ -441,6 +441,12 @@ __global__ __launch_bounds__(64) void k_deflate_static(DeflateArgs a)
 	fid.init(lane);
 	Fn8Cross fcross;                     // the cross-row stages' identity registers: read by fn8_scan_state0 alone
 	fcross.init(lane);
+	// level 1, the steps of a group: the lane number with the match token's constant part on it, K = HD_TOKEN_MATCH_TAG -
+	// (3 << 16).  pk = S + lane_k is the step's position register there: pk - c is the token word's base whole, and the one
+	// other reader of the position, the long-match events, masks its addresses into the ring (K's low 16 bits are zero).
+	// Opaque, as Fn8Cross is: the compiler cannot make it again from `lane`, an add per step
+	uint32_t lane_k = lane + (HD_TOKEN_MATCH_TAG - (3u << 16));
+	asm volatile("" : "+v"(lane_k));
 	HashConsts hk;
 	hk.init(HS);
 	CrcLanes crc;
@@ -736,12 +742,18 @@ __global__ __launch_bounds__(64) void k_deflate_static(DeflateArgs a)
 		// Conditions live as 64-bit lane masks in scalar registers (hd_device.hpp "lane masks"): each is the
 		// ballot of ONE compare, they are combined by s_and / s_andn2 and reach the lanes again through sel().
 		const uint64_t lanem = (INNER || lanes == 64) ? ~0ull : (1ull << (lanes & 63)) - 1;   // lanes inside the block
-		const uint32_t p = S + lane;
+		// GROUP (level 1's steps of a group): p is the position + K (lane_k above).  Its readers there are the token word
+		// and the long-match events' ring addresses, which are masked; the general steps and the parse kernel, which
+		// compare p with the block's end, keep the position itself
+		constexpr bool GROUP = !TOK && INNER && ROOM258;
+		const uint32_t p = S + (GROUP ? lane_k : lane);
 		const uint32_t cv0 = fc.v, cvh0 = fc.vh;
 		const uint32_t room = n - p;                  // >= 4 where a match can start
 		const uint32_t c = fc.c, cp = c - 1;
-		const uint32_t cv = __builtin_amdgcn_alignbyte(qc.c1, qc.c0, cp & 3);
-		const uint32_t cvh = __builtin_amdgcn_alignbyte(qc.c2, qc.c1, cp & 3);
+		// (v_alignbyte_b32 reads bits [1:0] of its shift operand and no others -- hipdeflate_selftest() checks that on the
+		// device -- so the candidate's position goes in whole: no v_and_b32 ..., 3 in front of the pair)
+		const uint32_t cv = __builtin_amdgcn_alignbyte(qc.c1, qc.c0, cp);
+		const uint32_t cvh = __builtin_amdgcn_alignbyte(qc.c2, qc.c1, cp);
 		const uint32_t x = cvh ^ cvh0;
 		const uint64_t xm = __ballot(cvh == cvh0);                      // all eight bytes agree
 		const uint32_t len8 = sel(xm, 8u, 4u + ((uint32_t)__builtin_ctz(x) >> 3));     // (x == 0: not selected)
@@ -774,7 +786,8 @@ __global__ __launch_bounds__(64) void k_deflate_static(DeflateArgs a)
 		const uint64_t livem = ~0ull << carry;                       // lanes the last match does not cover (carry < 64)
 		// (token words are prepared here, ahead of the scan: independent work for the wait states between its
 		// DPP stages)  match: HD_TOKEN_MATCH_TAG | (len - 3) << 16 | (dist - 1), dist - 1 = p - c
-		const uint32_t mw_base = (p + (HD_TOKEN_MATCH_TAG - (3u << 16) - 1u)) - cp;
+		// (GROUP: the constant is in p already, and the word is one v_sub_u32 here and one v_lshl_add_u32 below)
+		const uint32_t mw_base = GROUP ? p - c : (p + (HD_TOKEN_MATCH_TAG - (3u << 16) - 1u)) - cp;
 		const uint32_t lit = cv0 & 0xff;
 		// K16: length over 16 bytes (valid on the capped lanes).  (The dwords are read here, and the kernel is bound
 		// by its instruction count: it skips all of this in a step without a capped lane -- a quarter of the steps on
@@ -786,8 +799,8 @@ __global__ __launch_bounds__(64) void k_deflate_static(DeflateArgs a)
 			const uint32_t c2 = qc.c2;
 			const uint32_t p2 = wp[2], p3 = wp[3], p4 = wp[4];
 			const uint32_t c3 = wc[3], c4 = wc[4];
-			const uint32_t xa = __builtin_amdgcn_alignbyte(p3, p2, p & 3) ^ __builtin_amdgcn_alignbyte(c3, c2, cp & 3);   // bytes 8..11
-			const uint32_t xb = __builtin_amdgcn_alignbyte(p4, p3, p & 3) ^ __builtin_amdgcn_alignbyte(c4, c3, cp & 3);   // bytes 12..15
+			const uint32_t xa = __builtin_amdgcn_alignbyte(p3, p2, p & 3) ^ __builtin_amdgcn_alignbyte(c3, c2, cp);   // bytes 8..11
+			const uint32_t xb = __builtin_amdgcn_alignbyte(p4, p3, p & 3) ^ __builtin_amdgcn_alignbyte(c4, c3, cp);   // bytes 12..15
 			// (v_ffbl_b32 of 0 is -1: >> 3 and min 4 turn it into "all four agree"; ka >> 2 is 1 exactly then)
 			uint32_t fa, fb;
 			asm("v_ffbl_b32 %0, %1" : "=v"(fa) : "v"(xa));
@@ -948,6 +961,12 @@ __global__ __launch_bounds__(64) void k_deflate_static(DeflateArgs a)
 			//          an SGPR written by the SALU needs no wait states before v_readlane uses it as lane select
 			//   gone   the old starts in (m, x): one s_bfm_b64 of min(x, 64) - m - 1 ones from bit m + 1 (m == 63
 			//          makes it empty)
+			//   ring   THE RING IS THE KERNEL'S FIRST LDS OBJECT, at LDS address 0: it has the largest alignment (W), and
+			//          the objects are laid out by falling alignment.  So the ring address of an index is the index AND
+			//          W - 1 and nothing else -- v_and_b32 with a literal, VOP2 -- where the general form
+			//          (x & (W - 1)) | base is a VOP3 with a scalar source, in the dearer class, OR-ing in a zero.
+			//          Stated here and nowhere else; tests/test_l1_trim_isa.py holds the layout by the listing (the
+			//          table's accesses carry offset:W + 16).  The parse kernel's K16 loop above keeps the general form
 			uint64_t todo = capmask;
 			uint64_t cm = starts & todo;
 			if (cm) {
@@ -961,8 +980,8 @@ __global__ __launch_bounds__(64) void k_deflate_static(DeflateArgs a)
 	"Lhd_ext_%=:\n\t"                                                                    \
 	"v_add_u32 %[t0], %[x], %[p]\n\t"                                                    \
 	"v_add_u32 %[t1], %[cq], %[lane]\n\t"                                                \
-	"v_and_or_b32 %[t0], %[t0], %[msk], %[rb]\n\t"                                       \
-	"v_and_or_b32 %[t1], %[t1], %[msk], %[rb]\n\t"                                       \
+	"v_and_b32 %[t0], %[wm], %[t0]\n\t"                                                  \
+	"v_and_b32 %[t1], %[wm], %[t1]\n\t"                                                  \
 	"ds_read_u8 %[t0], %[t0]\n\t"                                                        \
 	"ds_read_u8 %[t1], %[t1] offset:2\n\t"                                               \
 	"s_waitcnt lgkmcnt(0)\n\t"                                                           \
@@ -1006,7 +1025,7 @@ __global__ __launch_bounds__(64) void k_deflate_static(DeflateArgs a)
 						asm volatile(HD_L1_EVENTS("")
 						  : [starts] "+s"(starts), [todo] "+s"(todo), [cm] "+s"(cm), [lenv] "+v"(lenv), [t0] "=&v"(t0), [t1] "=&v"(t1),
 						    [x] "=&s"(x), [cq] "=&s"(cq), [len] "=&s"(len), [k] "=&s"(k), [fresh] "=&s"(fresh)
-						  : [cp] "v"(cp), [p] "v"(p), [lane] "v"(lane), [msk] "s"(W - 1), [rb] "v"(ring_lds)
+						  : [cp] "v"(cp), [p] "v"(p), [lane] "v"(lane), [wm] "n"(W - 1)
 						  : "vcc", "scc", "memory");
 					else
 						asm volatile(HD_L1_EVENTS("s_sub_u32 %[k], %[left], m0\n\t"
@@ -1015,7 +1034,7 @@ __global__ __launch_bounds__(64) void k_deflate_static(DeflateArgs a)
 								       "s_add_u32 %[x], %[len], m0\n\t")
 						  : [starts] "+s"(starts), [todo] "+s"(todo), [cm] "+s"(cm), [lenv] "+v"(lenv), [t0] "=&v"(t0), [t1] "=&v"(t1),
 						    [x] "=&s"(x), [cq] "=&s"(cq), [len] "=&s"(len), [k] "=&s"(k), [fresh] "=&s"(fresh)
-						  : [cp] "v"(cp), [p] "v"(p), [lane] "v"(lane), [msk] "s"(W - 1), [rb] "v"(ring_lds), [left] "s"(n - S)
+						  : [cp] "v"(cp), [p] "v"(p), [lane] "v"(lane), [wm] "n"(W - 1), [left] "s"(n - S)
 						  : "vcc", "scc", "memory");
 				} while (cm);
 #undef HD_L1_EVENTS

@@ -292,16 +292,18 @@ __device__ __forceinline__ uint32_t sel(uint64_t mask, uint32_t a, uint32_t b)
 
 // ---- token queue in a register ---------------------------------------------------
 // The lanes in `tm` hold a token each; the k-th of them (in lane order) sends `tw` to lane (q + k) mod 64 -- ds_permute_b32, the
-// LDS crossbar without LDS memory: lane i's data lands in lane (address_i / 4) mod 64.  A lane without a token sends to
-// lane q - 1, which a token wants only when all 64 lanes have one -- and then no lane is without.  So no token ever shares its
-// destination; lanes nobody sends to read 0.  The address is NOT masked here: the instruction takes it modulo 64 lanes
-// (q + k <= 126, q - 1 may be -1), which hipdeflate_selftest() checks on the device together with the rest of this.
+// LDS crossbar without LDS memory: lane i's data lands in lane (address_i / 4) mod 64.  A lane without a token sends too, by
+// the same rule: its rank is the number of tokens below it, which is the rank of the first token ABOVE it, so it sends to that
+// token's destination -- and of several lanes that send to one lane the HIGHEST source lane's data arrives (gfx950; what its
+// LDS does for ds_write_b16, hd_selftest.hip k_selftest_lds_order), so the token wins every such collision and no select
+// keeps the other lanes out.  The lanes above the step's last token send to lane (q + count) mod 64, which no token of the
+// step wants (count < 64 where a lane is without) and which is no queue entry, neither before a pass nor behind one: what
+// wraps round is [0, q + count - 64).  Lanes nobody sends to read 0.  The address is NOT masked here: the instruction takes it
+// modulo 64 lanes (q + k <= 127).  hipdeflate_selftest() checks the collision order, the wrap and the rest of this on the device.
 __device__ __forceinline__ uint32_t queue_push(uint64_t tm, uint32_t q, uint32_t tw)
 {
 	const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(tm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)tm, 0));
-	uint32_t k;                                  // rank, or -1 (an inline constant: no register, no move)
-	asm("v_cndmask_b32_e64 %0, -1, %1, %2" : "=v"(k) : "v"(rank), "s"(tm));
-	return (uint32_t)__builtin_amdgcn_ds_permute((int)((k + q) << 2), (int)tw);
+	return (uint32_t)__builtin_amdgcn_ds_permute((int)((rank + q) << 2), (int)tw);
 }
 
 // ---- hash -> table slot ---------------------------------------------------------

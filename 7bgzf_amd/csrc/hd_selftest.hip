@@ -70,6 +70,28 @@ __global__ __launch_bounds__(64) void k_selftest_queue_push(const uint64_t *mask
 	out[c * 64 + lane] = hd::queue_push(tm, qn, 0x5a000000u | (c << 8) | lane);
 }
 
+// queue_push lets the lanes without a token send as well, to the destination of the first token above them, and leans on
+// what ds_permute_b32 does when several lanes send to one: the HIGHEST source lane's data arrives (as the highest lane's
+// store stays in k_selftest_lds_order).  Case c: lane l sends its word to lane dst[c * 64 + l] mod 64 (the address is not
+// masked: the instruction takes it modulo 64 lanes); out = what every lane received
+__global__ __launch_bounds__(64) void k_selftest_permute_order(const uint32_t *dst, uint32_t *out)
+{
+	const uint32_t c = blockIdx.x, lane = threadIdx.x;
+	out[c * 64 + lane] = (uint32_t)__builtin_amdgcn_ds_permute((int)(dst[c * 64 + lane] << 2), (int)(0xa5000000u | (c << 8) | lane));
+}
+
+// The step aligns a candidate's bytes with v_alignbyte_b32 and passes the candidate's POSITION as the shift operand: the
+// instruction must read bits [1:0] of it and no others.  (In assembly: the compiler must not get to reason about the
+// builtin's operand.)  in: a, b, shift per lane; out = ({a, b} >> 8 * shift)[31:0] as the device computes it
+__global__ __launch_bounds__(64) void k_selftest_alignbyte(const uint32_t *in, uint32_t *out)
+{
+	const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+	const uint32_t a = in[3 * i], b = in[3 * i + 1], s = in[3 * i + 2];
+	uint32_t r;
+	asm volatile("v_alignbyte_b32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(s));
+	out[i] = r;
+}
+
 // one wavefront per frequency vector through the encoder's Huffman construction
 __global__ __launch_bounds__(64) void k_selftest_build(const uint32_t *freq, uint32_t nsyms, uint32_t maxbits, uint8_t *lens)
 {
@@ -160,7 +182,8 @@ static int hd_probe_queue_push(void)
 			bad = 0;
 			for (uint32_t c = 0; c < nc; c++) {
 				uint32_t k = 0, wrong = 0;
-				uint64_t fed = hm[c] == ~0ull ? 0ull : 1ull << ((hq[c] - 1) & 63);   // lanes somebody sends to
+				// lanes somebody sends to.  (The lanes above the last token send to lane q + count, which is no entry: whatever arrives)
+				uint64_t fed = hm[c] >> 63 ? 0ull : 1ull << ((hq[c] + (uint32_t)__builtin_popcountll(hm[c])) & 63);
 				for (uint32_t l = 0; l < 64; l++)
 					if ((hm[c] >> l) & 1) {
 						wrong += ho[c * 64 + ((hq[c] + k) & 63)] != (0x5a000000u | (c << 8) | l);
@@ -180,6 +203,112 @@ static int hd_probe_queue_push(void)
 	free(ho);
 	(void)hipFree(dm);
 	(void)hipFree(dq);
+	(void)hipFree(dout);
+	return bad;
+}
+
+// ---- ds_permute_b32 with several senders per destination: the highest source lane's data arrives ----
+// queue_push leans on it (hd_device.hpp).  Collisions of 2..64 senders on every destination lane, the sender sets drawn at
+// random (the other lanes send elsewhere, colliding as they may), then every lane on one of 2^k destinations at random, with
+// address bits above the lane number set.  Every lane must read its highest sender's word, or 0 where nobody sent.
+// Returns the number of lanes that read something else; < 0 on an allocation or launch error.
+static int hd_probe_permute_order(void)
+{
+	const uint32_t n_fix = 63 * 64, n_rnd = 7 * 32, nc = n_fix + n_rnd;
+	uint32_t *hd = (uint32_t *)malloc(nc * 64 * 4), *ho = (uint32_t *)malloc(nc * 64 * 4), *dd = nullptr, *dout = nullptr;
+	int bad = -1;
+	if (hd && ho && hipMalloc((void **)&dd, nc * 64 * 4) == hipSuccess && hipMalloc((void **)&dout, nc * 64 * 4) == hipSuccess) {
+		uint64_t seed = 0x2545f4914f6cdd1dull;
+		auto rnd = [&]() -> uint32_t {
+			seed = seed * 6364136223846793005ull + 1442695040888963407ull;
+			return (uint32_t)(seed >> 33);
+		};
+		for (uint32_t c = 0; c < nc; c++) {
+			uint32_t *d = hd + c * 64;
+			if (c < n_fix) {
+				const uint32_t g = 2 + c / 64, to = c % 64;          // g senders on lane `to`
+				uint8_t order[64];
+				for (uint32_t l = 0; l < 64; l++)
+					order[l] = (uint8_t)l;
+				for (uint32_t l = 63; l > 0; l--) {                  // a random order of the lanes: its first g send to `to`
+					const uint32_t j = rnd() % (l + 1);
+					const uint8_t t = order[l];
+					order[l] = order[j];
+					order[j] = t;
+				}
+				for (uint32_t k = 0; k < 64; k++)
+					d[order[k]] = k < g ? to : (to + 1 + rnd() % 63) & 63;
+			} else {
+				const uint32_t span = 1u << (1 + (c - n_fix) % 7);       // 2, 4, ..., 64 destinations; then 128: all 64, bit 6 set at random
+				for (uint32_t l = 0; l < 64; l++)
+					d[l] = rnd() % span + ((c & 1) ? 64u * (rnd() & 0xffff) : 0u);
+			}
+		}
+		bool ok = hipMemcpy(dd, hd, nc * 64 * 4, hipMemcpyHostToDevice) == hipSuccess;
+		if (ok) {
+			hipLaunchKernelGGL(k_selftest_permute_order, dim3(nc), dim3(64), 0, 0, dd, dout);
+			ok = hipGetLastError() == hipSuccess && hipMemcpy(ho, dout, nc * 64 * 4, hipMemcpyDeviceToHost) == hipSuccess;
+		}
+		if (ok) {
+			bad = 0;
+			for (uint32_t c = 0; c < nc; c++)
+				for (uint32_t l = 0; l < 64; l++) {
+					uint32_t want = 0;
+					for (uint32_t k = 0; k < 64; k++)
+						if ((hd[c * 64 + k] & 63) == l)
+							want = 0xa5000000u | (c << 8) | k;       // the highest sender stays
+					if (ho[c * 64 + l] != want && bad++ < 5)
+						fprintf(stderr, "hipdeflate: ds_permute_b32 collision order: case %u lane %u read %08x, highest sender's word is %08x\n",
+							c, l, ho[c * 64 + l], want);
+				}
+		}
+	}
+	free(hd);
+	free(ho);
+	(void)hipFree(dd);
+	(void)hipFree(dout);
+	return bad;
+}
+
+// ---- v_alignbyte_b32 reads bits [1:0] of its shift operand only ----
+// Shift operands with every byte offset under: no upper bit, all of them, each upper bit alone, all but each one, and random
+// upper bits; against ({a, b} >> 8 * (shift & 3))[31:0].  Returns the number of lanes that differ; < 0 on an error.
+static int hd_probe_alignbyte(void)
+{
+	const uint32_t nb = 2 + 30 + 30 + 66, n = nb * 64;
+	uint32_t *hi = (uint32_t *)malloc(n * 12), *ho = (uint32_t *)malloc(n * 4), *din = nullptr, *dout = nullptr;
+	int bad = -1;
+	if (hi && ho && hipMalloc((void **)&din, n * 12) == hipSuccess && hipMalloc((void **)&dout, n * 4) == hipSuccess) {
+		uint64_t seed = 0x9e3779b97f4a7c15ull;
+		for (uint32_t i = 0; i < n; i++) {
+			const uint32_t blk = i / 64;
+			seed = seed * 6364136223846793005ull + 1442695040888963407ull;
+			hi[3 * i] = (uint32_t)(seed >> 32);
+			hi[3 * i + 1] = (uint32_t)seed * 2654435761u + i;
+			seed = seed * 6364136223846793005ull + 1442695040888963407ull;
+			const uint32_t up = blk == 0 ? 0u : blk == 1 ? ~3u : blk < 32 ? 4u << (blk - 2) : blk < 62 ? ~3u & ~(4u << (blk - 32))
+					  : (uint32_t)(seed >> 32) & ~3u;
+			hi[3 * i + 2] = up | (i & 3);
+		}
+		bool ok = hipMemcpy(din, hi, n * 12, hipMemcpyHostToDevice) == hipSuccess;
+		if (ok) {
+			hipLaunchKernelGGL(k_selftest_alignbyte, dim3(nb), dim3(64), 0, 0, din, dout);
+			ok = hipGetLastError() == hipSuccess && hipMemcpy(ho, dout, n * 4, hipMemcpyDeviceToHost) == hipSuccess;
+		}
+		if (ok) {
+			bad = 0;
+			for (uint32_t i = 0; i < n; i++) {
+				const uint64_t wide = ((uint64_t)hi[3 * i] << 32) | hi[3 * i + 1];
+				const uint32_t want = (uint32_t)(wide >> (8 * (hi[3 * i + 2] & 3)));
+				if (ho[i] != want && bad++ < 5)
+					fprintf(stderr, "hipdeflate: v_alignbyte_b32 {%08x, %08x} by %08x gave %08x, want %08x\n",
+						hi[3 * i], hi[3 * i + 1], hi[3 * i + 2], ho[i], want);
+			}
+		}
+	}
+	free(hi);
+	free(ho);
+	(void)hipFree(din);
 	(void)hipFree(dout);
 	return bad;
 }
@@ -259,6 +388,20 @@ extern "C" int hipdeflate_selftest(void)
 	// ---- the level-1 token queue's cross-lane push ----------------------------------
 	{
 		const int bad = hd_probe_queue_push();
+		if (bad < 0)
+			return HD_E_NOMEM;
+		fails += bad;
+	}
+	// ---- ... and the collision order of ds_permute_b32 it leans on --------------------------------
+	{
+		const int bad = hd_probe_permute_order();
+		if (bad < 0)
+			return HD_E_NOMEM;
+		fails += bad;
+	}
+	// ---- the shift operand of v_alignbyte_b32 (the level-1 and level-2 step) --------------------------
+	{
+		const int bad = hd_probe_alignbyte();
 		if (bad < 0)
 			return HD_E_NOMEM;
 		fails += bad;
