@@ -106,6 +106,7 @@ EXPORTS = [
     "hipdeflate_stream_index_dev", "hipdeflate_stream_inflate_table_dev", "hip_inflate_stream",
     "hipdeflate_stream_index_carry_dev", "hipdeflate_stream_inflate_carry_dev", "hip_inflate_stream_carry",
     "hipdeflate_test_carry_group", "hipdeflate_test_carry_times",
+    "hipdeflate_stream_deflate_carry_dev", "hip_deflate_stream_carry",
     "hipdeflate_stream_index_blocks_dev", "hipdeflate_stream_inflate_blocks_dev", "hip_inflate_stream_blocks",
     "hipdeflate_test_block_headers_dev", "hipdeflate_test_blocks_times", "hipdeflate_test_blocks_counts",
     "hipdeflate_test_block_candidates_dev",
@@ -206,6 +207,8 @@ def lib():
                                                 ctypes.c_uint64, _vp, ctypes.c_uint64, ctypes.POINTER(StreamSummary), _vp]
     L.hipdeflate_check_combine_dev.argtypes = [_vp, _vp, ctypes.c_uint32, ctypes.c_int, ctypes.POINTER(ctypes.c_uint32), _vp]
     L.hip_deflate_stream.argtypes = [_vp, sz_p, _vp, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_uint32]
+    L.hipdeflate_stream_deflate_carry_dev.argtypes = L.hipdeflate_stream_deflate_dev.argtypes
+    L.hip_deflate_stream_carry.argtypes = L.hip_deflate_stream.argtypes
     L.hipdeflate_stream_index_dev.argtypes = [_vp, ctypes.c_uint64, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp, _vp, _vp,
                                               ctypes.POINTER(StreamIndexSummary), _vp]
     L.hipdeflate_stream_inflate_table_dev.argtypes = [_vp, ctypes.c_uint64, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.c_uint32, _vp,
@@ -328,15 +331,25 @@ def hip_deflate_flush(data, level=1, cap=None):
     return r, bytes(dst[: n.value]) if r == 0 else b""
 
 
-def hip_deflate_stream(data, level=6, frame=FRAME_GZIP, chunk=1 << 16, cap=None):
-    """-> (ret, bytes): ONE raw / zlib / gzip stream of `data`, coded in independent chunks of `chunk` bytes on the
-    device (hipdeflate_stream_deflate_dev behind a host buffer); cap: the room, the bound by default"""
+def _deflate_stream_host(func, data, level, frame, chunk, cap):
     src = as_u8(data)
     cap = int(lib().hipdeflate_stream_bound(len(src), chunk, level, frame)) if cap is None else cap
     dst = np.zeros(max(cap, 1), dtype=np.uint8)
     n = ctypes.c_size_t(cap)
-    r = lib().hip_deflate_stream(_p(dst), ctypes.byref(n), _p(src), len(src), level, frame, chunk)
+    r = func(_p(dst), ctypes.byref(n), _p(src), len(src), level, frame, chunk)
     return r, bytes(dst[: n.value]) if r == 0 else b""
+
+
+def hip_deflate_stream(data, level=6, frame=FRAME_GZIP, chunk=1 << 16, cap=None):
+    """-> (ret, bytes): ONE raw / zlib / gzip stream of `data`, coded in independent chunks of `chunk` bytes on the
+    device (hipdeflate_stream_deflate_dev behind a host buffer); cap: the room, the bound by default"""
+    return _deflate_stream_host(lib().hip_deflate_stream, data, level, frame, chunk, cap)
+
+
+def hip_deflate_stream_carry(data, level=6, frame=FRAME_GZIP, chunk=1 << 16, cap=None):
+    """hip_deflate_stream with every chunk primed by the 32 KiB in front of it (hipdeflate_stream_deflate_carry_dev behind a host
+    buffer) -> (ret, bytes)"""
+    return _deflate_stream_host(lib().hip_deflate_stream_carry, data, level, frame, chunk, cap)
 
 
 def hip_inflate_stream(data, cap, frame=FRAME_GZIP):

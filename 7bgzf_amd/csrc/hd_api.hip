@@ -886,7 +886,7 @@ static hd::DeflateArgs deflate_args(const Ctx &g, const void *in, const uint64_t
 
 static int batch_deflate_dev_impl(const void *in, const void *in_off, const void *in_len, uint32_t nblocks, int level,
 				  int frame, void *out, uint64_t out_stride, uint32_t out_cap, void *out_len,
-				  void *crc32, void *status, void *stream, uint32_t max_in)
+				  void *crc32, void *status, void *stream, uint32_t max_in, uint32_t prime_max = 0)
 {
 	Ctx &g = cur();
 	int r = ensure();
@@ -900,6 +900,8 @@ static int batch_deflate_dev_impl(const void *in, const void *in_off, const void
 	hd::DeflateArgs a = deflate_args(g, in, (const uint64_t *)in_off, (const uint32_t *)in_len, nblocks, level, frame, latency, out,
 					 out_stride, out_cap, (uint32_t *)out_len, (uint32_t *)crc32, (int32_t *)status,
 					 hd::split_max_block(out_stride, out_cap), max_in);
+	// (the chunks of one stream that carry the window: the workgroup levels' throughput form alone -- DeflateArgs::prime_max)
+	a.prime_max = (level >= HD_WG_LEVEL && !a.lat) ? prime_max : 0u;
 	const uint64_t need = scratch_need(nblocks, a.split_max, level, latency);
 	if (!need) {
 		if ((r = launch_deflate(a, level, st)))
@@ -1471,8 +1473,10 @@ int hipdeflate_check_combine_dev(const void *check, const void *len, uint32_t n,
 	return 0;
 }
 
-int hipdeflate_stream_deflate_dev(const void *in, uint64_t nbytes, uint32_t chunk_bytes, int level, int frame, void *dst,
-				  uint64_t dst_cap, void *chunk_off, hipdeflate_stream_summary *summary, void *stream)
+// both forms of the stream: chunks that know nothing of each other (prime_max 0), or every chunk parsed with the
+// min(prime_max, its offset) & ~1023 bytes in front of it as its history (levels 3..9; hipdeflate_stream_deflate_carry_dev)
+static int stream_deflate_impl(const void *in, uint64_t nbytes, uint32_t chunk_bytes, int level, int frame, void *dst, uint64_t dst_cap,
+			       void *chunk_off, hipdeflate_stream_summary *summary, void *stream, uint32_t prime_max)
 {
 	Ctx &g = cur();
 	int r = enter_call(summary, sizeof *summary);
@@ -1503,8 +1507,9 @@ int hipdeflate_stream_deflate_dev(const void *in, uint64_t nbytes, uint32_t chun
 	for (uint32_t c0 = 0; c0 < nchunks; c0 += (uint32_t)W) {
 		const uint32_t w = nchunks - c0 < W ? nchunks - c0 : (uint32_t)W, wgs = (w + 255) / 256;
 		hipLaunchKernelGGL(hd::k_stream_table, dim3(wgs), dim3(256), 0, st, c0, w, chunk_bytes, nbytes, t.in_off, t.in_len);
+		// (k_stream_table's offsets are relative to `in` in every window: a window's first chunk is primed like any other)
 		if ((r = batch_deflate_dev_impl(in, t.in_off, t.in_len, w, level, HD_FRAME_RAW_FLUSH, slots, slot, (uint32_t)slot, t.out_len, t.crc,
-						t.status, stream, 0)))
+						t.status, stream, 0, prime_max)))
 			return r;
 		// every chunk's place in the stream, straight into the caller's table where there is one: the running total goes
 		// from window to window as the scan's base
@@ -1548,6 +1553,18 @@ int hipdeflate_stream_deflate_dev(const void *in, uint64_t nbytes, uint32_t chun
 	summary->check = check;
 	summary->status = bad_chunk != nchunks ? 2u : fits ? 0u : 3u;
 	return 0;
+}
+
+int hipdeflate_stream_deflate_dev(const void *in, uint64_t nbytes, uint32_t chunk_bytes, int level, int frame, void *dst,
+				  uint64_t dst_cap, void *chunk_off, hipdeflate_stream_summary *summary, void *stream)
+{
+	return stream_deflate_impl(in, nbytes, chunk_bytes, level, frame, dst, dst_cap, chunk_off, summary, stream, 0);
+}
+
+int hipdeflate_stream_deflate_carry_dev(const void *in, uint64_t nbytes, uint32_t chunk_bytes, int level, int frame, void *dst,
+					uint64_t dst_cap, void *chunk_off, hipdeflate_stream_summary *summary, void *stream)
+{
+	return stream_deflate_impl(in, nbytes, chunk_bytes, level, frame, dst, dst_cap, chunk_off, summary, stream, HD_WG_WINDOW);
 }
 
 // a row table as a decoder takes it: the caller's columns, or (the decode by chunk table) the scratch's own
@@ -3520,8 +3537,9 @@ int hip_inflate_flush(unsigned char *dest, size_t *destLen, const unsigned char 
 	return inflate_one(dest, destLen, source, sourceLen, hd::INF_FLUSHED);
 }
 
-int hip_deflate_stream(unsigned char *dest, size_t *destLen, const unsigned char *source, size_t sourceLen, int level, int frame,
-		       uint32_t chunk_bytes)
+// hip_deflate_stream and, with every chunk primed by the bytes in front of it (carry), hip_deflate_stream_carry: stage, code, fetch
+static int deflate_stream_host(unsigned char *dest, size_t *destLen, const unsigned char *source, size_t sourceLen, int level, int frame,
+			       uint32_t chunk_bytes, bool carry)
 {
 	Ctx &g = cur();
 	int r = ensure();
@@ -3539,7 +3557,8 @@ int hip_deflate_stream(unsigned char *dest, size_t *destLen, const unsigned char
 	if (sourceLen)
 		HD_CHECK(hipMemcpyAsync(g.d_in.p, source, sourceLen, hipMemcpyHostToDevice, g.stream));
 	hipdeflate_stream_summary s;
-	if ((r = hipdeflate_stream_deflate_dev(g.d_in.p, sourceLen, chunk_bytes, level, frame, g.d_packed.p, cap, nullptr, &s, g.stream)))
+	if ((r = stream_deflate_impl(g.d_in.p, sourceLen, chunk_bytes, level, frame, g.d_packed.p, cap, nullptr, &s, g.stream,
+				     carry ? HD_WG_WINDOW : 0u)))
 		return r;
 	g.stream_drained(g.stream);
 	if (s.status)
@@ -3547,6 +3566,18 @@ int hip_deflate_stream(unsigned char *dest, size_t *destLen, const unsigned char
 	HD_CHECK(hipMemcpy(dest, g.d_packed.p, s.out_bytes, hipMemcpyDeviceToHost));
 	*destLen = s.out_bytes;
 	return 0;
+}
+
+int hip_deflate_stream(unsigned char *dest, size_t *destLen, const unsigned char *source, size_t sourceLen, int level, int frame,
+		       uint32_t chunk_bytes)
+{
+	return deflate_stream_host(dest, destLen, source, sourceLen, level, frame, chunk_bytes, false);
+}
+
+int hip_deflate_stream_carry(unsigned char *dest, size_t *destLen, const unsigned char *source, size_t sourceLen, int level, int frame,
+			     uint32_t chunk_bytes)
+{
+	return deflate_stream_host(dest, destLen, source, sourceLen, level, frame, chunk_bytes, true);
 }
 
 // hip_inflate_stream and, for a stream whose flushes carry the window (carry), hip_inflate_stream_carry: stage, index,

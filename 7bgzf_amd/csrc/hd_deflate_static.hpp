@@ -113,6 +113,10 @@ struct DeflateArgs {
 	uint32_t take_sub = 0;
 	uint32_t *poison = nullptr;
 	uint32_t beside_keep = BESIDE_KEEP_MAX;      // emit wavefronts a CU keeps (tests: hipdeflate_test_beside(keep = 0): nobody stays)
+	// the workgroup levels' throughput form: the most history a block may use, 0 or HD_WG_WINDOW.  != 0: block b is parsed with the
+	// min(prime_max, in_off[b]) & ~(HD_WG_CUT - 1) bytes in front of it in the table and the window (k_primed_wg: no token for them, its
+	// CRC-32 the block's alone, distances up to 32768 into them) -- a.in + in_off[b] is then one buffer's offset, not any address
+	uint32_t prime_max = 0;
 	// host side only: a WgBeside (hd_deflate_wg.hpp) -- the second stream and the events of that scheme; nullptr = emit behind parse
 	void *beside = nullptr;
 };

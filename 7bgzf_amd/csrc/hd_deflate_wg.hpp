@@ -136,8 +136,16 @@ __device__ __forceinline__ uint64_t wg_uniform64(uint64_t v)
 // WAYS: positions per bucket = candidates verified per position (1, 2 or 4); LAZY: the lazy rule (else greedy)
 // BESIDE: the instantiation that runs with the emit kernel resident beside it (launch_wg): its LDS is passed at launch, its records go
 // through the L2, its blocks raise flags; BESIDE = 0 is the kernel of rounds 4-5 to the instruction
-template <int WAYS, int LAZY, int BESIDE = 0>
-__global__ __launch_bounds__(64 * HD_WG_WAVES) __attribute__((amdgpu_waves_per_eu(4, BESIDE ? 5 : 4))) void k_parse_wg(DeflateArgs a)
+// PRIMED: the block is parsed with the bytes in front of it as its history (a.prime_max: one gzip / zlib / raw stream whose chunks
+// carry the window, hipdeflate_stream_deflate_carry_dev).  prime = min(a.prime_max, a.in_off[b]) rounded down to whole pieces: the
+// block's first byte stays on a piece boundary and the source 16-byte aligned where a.in is.  Every position below is a position in
+// (history || block): the history's pieces pass through the ring and are REPLAYED like the pieces in front of a sharer's range, so
+// the tokens behind the boundary are those of a one-block parse of both, their distances up to 32768 into the history.  Only what
+// leaves the kernel is in the block's own coordinates: the tokens, the pieces' counts and the CRC-32, which are the block's alone --
+// the emit kernels see an ordinary block of in_len[b] bytes.  A template parameter, not a branch: the instantiations without it are
+// what they were, to the register.  (One workgroup per block: the shared parse of latency launches is not primed.)
+template <int WAYS, int LAZY, int BESIDE, int PRIMED>
+__device__ __forceinline__ void parse_wg(const DeflateArgs &a)
 {
 	static_assert(WAYS == 1 || WAYS == 2 || WAYS == 4, "a bucket is 2, 4 or 8 bytes");
 	// BESIDE: DYNAMIC shared memory, on purpose: with the 131 KB declared statically the compiler knows that one workgroup fills the CU
@@ -158,11 +166,18 @@ __global__ __launch_bounds__(64 * HD_WG_WAVES) __attribute__((amdgpu_waves_per_e
 	const uint32_t lane = threadIdx.x & 63, w = uniform(threadIdx.x >> 6);      // (the compiler must know that w is one value per wavefront)
 	// a.wg_split workgroups share a block's parse (latency launches): workgroup q of SP takes the pieces [pfirst, plast) and,
 	// to have the table the pieces in front of them leave, REPLAYS those pieces' table turns first (hashes + bucket stores,
-	// no verify, no tokens: an eighth of a piece's work)
-	const uint32_t SP = a.wg_split > 1 ? a.wg_split : 1u;
+	// no verify, no tokens: an eighth of a piece's work at one way -- a quarter at four, measured on the primed form, whose replays
+	// are the history's pieces: profiles/stream_encode_carry_timing.txt)
+	const uint32_t SP = (!PRIMED && a.wg_split > 1) ? a.wg_split : 1u;
 	const uint32_t bi = blockIdx.x / SP, q = blockIdx.x % SP, b = a.first + bi;
-	const uint8_t *src = a.stage_in ? a.stage_in + (uint64_t)bi * WG_STAGE_STRIDE : a.in + a.in_off[b];
-	const uint32_t n = a.in_len[b];
+	uint32_t prime = 0;
+	if (PRIMED) {
+		const uint64_t at = a.in_off[b];
+		prime = (uint32_t)(at < a.prime_max ? at : (uint64_t)a.prime_max) & ~(uint32_t)(HD_WG_CUT - 1);
+	}
+	const uint8_t *src = PRIMED ? a.in + (a.in_off[b] - prime) : a.stage_in ? a.stage_in + (uint64_t)bi * WG_STAGE_STRIDE : a.in + a.in_off[b];
+	const uint32_t nown = a.in_len[b];               // the block's own bytes: what is coded and what the CRC-32 covers
+	const uint32_t n = PRIMED ? nown + prime : nown; // ... and what passes through the ring: (history || block)
 	const bool aligned = (((uintptr_t)src) & 15) == 0;
 	const CrcTables *ct = a.ct;
 	const SplitLayout lay = wg_layout(a.split_max);
@@ -176,10 +191,12 @@ __global__ __launch_bounds__(64 * HD_WG_WAVES) __attribute__((amdgpu_waves_per_e
 	// host-pointer calls, pipes, latency contexts, the per-block codecs: round 5 -- a block LONGER THAN ITS ROOM is coded and
 	// goes through whenever its stream fits, as libdeflate_deflate's does, lib/zlibutil.c:179-192; rounds 4 refused it), the
 	// slot where only the device knows them (hipdeflate_batch_deflate_dev: there a block longer than its slot is refused)
-	const bool refused = n > a.split_max;
+	const bool refused = nown > a.split_max;
 	const bool beside = BESIDE != 0;                 // the emit kernel runs beside this one and reads the records as the flags go up (launch_wg)
 	const uint32_t npieces = refused ? 0u : (n + HD_WG_CUT - 1) / HD_WG_CUT;
-	const uint32_t pfirst = npieces * q / SP, plast = npieces * (q + 1) / SP;    // (SP == 1: all of them)
+	// (SP == 1: all of them; PRIMED: the history's pieces are the ones replayed)
+	const uint32_t pfirst = PRIMED ? prime / HD_WG_CUT : npieces * q / SP, plast = PRIMED ? npieces : npieces * (q + 1) / SP;
+	const uint32_t own0 = PRIMED ? pfirst : 0u;      // the block's own first piece: tokens, counts and CRC are told from there
 
 	// ---- LDS: the table zero, the words ------------------------------------------------------------------------------
 	for (uint32_t i = threadIdx.x; i < WG_TABLE_BYTES / 16; i += 64 * WG_NW)
@@ -222,13 +239,13 @@ __global__ __launch_bounds__(64 * HD_WG_WAVES) __attribute__((amdgpu_waves_per_e
 	if (w == WG_NP && !poisoned) {
 		// ================= the filler =====================================================================================
 		CrcLanes crc;
-		crc.init(lane, n);
+		crc.init(lane, nown);
 		uint4 pend = make_uint4(0, 0, 0, 0);
 		if (bulk && q) {
 			// (the block's CRC-32 is workgroup 0's)
 		} else if (bulk) {
-			for (uint32_t k = 0; k < npieces; k++)
-				crc.fold(ct, k, k * HD_PIECE + 16 * lane + 16 <= n, *(const uint4 *)((const uint8_t *)L.ring32 + k * HD_PIECE + 16 * lane));
+			for (uint32_t k = own0; k < npieces; k++)
+				crc.fold(ct, k - own0, (k - own0) * HD_PIECE + 16 * lane + 16 <= nown, *(const uint4 *)((const uint8_t *)L.ring32 + k * HD_PIECE + 16 * lane));
 		} else if (npieces) {
 			pend = load_slot(src, n, 0, lane, aligned);
 		}
@@ -269,9 +286,10 @@ __global__ __launch_bounds__(64 * HD_WG_WAVES) __attribute__((amdgpu_waves_per_e
 			if (lane == 0)
 				*vfilled = k + 1;
 			WG_BARRIER();
-			crc.fold(ct, k, k * HD_PIECE + 16 * lane + 16 <= n, v);
+			if (!PRIMED || k >= own0)
+				crc.fold(ct, k - own0, (k - own0) * HD_PIECE + 16 * lane + 16 <= nown, v);
 		}
-		crcv = crc.finish(ct, lane, n, src + (n & ~15u));
+		crcv = crc.finish(ct, lane, nown, src + prime + (nown & ~15u));
 	}
 	if ((w != WG_NP || bulk) && !poisoned) {
 		// ================= a parser (bulk: the filler too, once its CRC is folded) =====================================
@@ -366,7 +384,7 @@ __global__ __launch_bounds__(64 * HD_WG_WAVES) __attribute__((amdgpu_waves_per_e
 			// ---- the piece: verify, lazy rule, walk, tokens -- nothing here waits for another wavefront ----------------
 			uint32_t E = P0;                           // first position no token covers yet
 			uint32_t cnt = 0, c_lit = 0, c_long = 0;
-			uint32_t *const ptok = tok + P0;           // the piece's tokens
+			uint32_t *const ptok = tok + (P0 - prime); // the piece's tokens
 			for (uint32_t t = 0; t < nst; t++) {
 				const uint32_t S = P0 + 64 * t, p = S + lane;
 				const uint32_t lanes = pend - S < 64 ? pend - S : 64;
@@ -544,13 +562,13 @@ __global__ __launch_bounds__(64 * HD_WG_WAVES) __attribute__((amdgpu_waves_per_e
 			}
 			if (lane == 0) {
 				if (beside) {
-					uint32_t *rp = (uint32_t *)&rec_piece[j];
+					uint32_t *rp = (uint32_t *)&rec_piece[j - own0];
 					__hip_atomic_store(rp + 0, cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 					__hip_atomic_store(rp + 1, c_lit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 					__hip_atomic_store(rp + 2, cnt - c_lit - c_long, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 					__hip_atomic_store(rp + 3, c_long, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 				} else {
-					rec_piece[j] = make_uint4(cnt, c_lit, cnt - c_lit - c_long, c_long);
+					rec_piece[j - own0] = make_uint4(cnt, c_lit, cnt - c_lit - c_long, c_long);
 				}
 			}
 		}
@@ -580,6 +598,19 @@ __global__ __launch_bounds__(64 * HD_WG_WAVES) __attribute__((amdgpu_waves_per_e
 			__hip_atomic_exchange(&a.ready[32 * (size_t)(a.span_sub ? b : bi)], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 		}
 	}
+}
+
+template <int WAYS, int LAZY, int BESIDE = 0>
+__global__ __launch_bounds__(64 * HD_WG_WAVES) __attribute__((amdgpu_waves_per_eu(4, BESIDE ? 5 : 4))) void k_parse_wg(DeflateArgs a)
+{
+	parse_wg<WAYS, LAZY, BESIDE, 0>(a);
+}
+
+// the parse of a block that carries the window of the bytes in front of it (parse_wg's PRIMED): a kernel of its own name
+template <int WAYS, int LAZY, int BESIDE = 0>
+__global__ __launch_bounds__(64 * HD_WG_WAVES) __attribute__((amdgpu_waves_per_eu(4, BESIDE ? 5 : 4))) void k_primed_wg(DeflateArgs a)
+{
+	parse_wg<WAYS, LAZY, BESIDE, 1>(a);
 }
 
 // the gate in front of a parse that runs BESIDE its emit kernel (launch_wg): one wavefront that waits until `want` emit
@@ -656,6 +687,37 @@ constexpr uint32_t WG_BESIDE_CANDIDATES = 1536;  // ... kept from this many that
 constexpr uint32_t WG_BESIDE_MIN = 512;          // blocks in a sub-batch below which the emit kernel simply follows the parse
 constexpr uint32_t WG_BESIDE_MAX_BLOCK = 2097152; // ... and the longest block it is used for (one wavefront writes a member: 5 ms per MiB is the launch's tail)
 
+// the parse of one sub-batch at a level's rung of the ladder (HD_WG_WAYS / HD_WG_LAZY), in one of its four forms: beside its emit
+// kernel or not, primed with the bytes in front of every block (s.prime_max) or not
+template <int WAYS, int LAZY>
+inline void launch_parse_rung(const DeflateArgs &s, bool beside, hipStream_t st)
+{
+	const dim3 grid(s.count * s.wg_split), block(64 * HD_WG_WAVES);
+	if (s.prime_max) {
+		if (beside)
+			hipLaunchKernelGGL((k_primed_wg<WAYS, LAZY, 1>), grid, block, WG_LDS_DYNAMIC, st, s);
+		else
+			hipLaunchKernelGGL((k_primed_wg<WAYS, LAZY>), grid, block, 0, st, s);
+	} else {
+		if (beside)
+			hipLaunchKernelGGL((k_parse_wg<WAYS, LAZY, 1>), grid, block, WG_LDS_DYNAMIC, st, s);
+		else
+			hipLaunchKernelGGL((k_parse_wg<WAYS, LAZY>), grid, block, 0, st, s);
+	}
+}
+
+inline void launch_parse_wg(const DeflateArgs &s, int level, bool beside, hipStream_t st)
+{
+	if (HD_WG_WAYS(level) == 4)
+		launch_parse_rung<4, 1>(s, beside, st);
+	else if (HD_WG_WAYS(level) == 2)
+		launch_parse_rung<2, 1>(s, beside, st);
+	else if (HD_WG_LAZY(level))
+		launch_parse_rung<1, 1>(s, beside, st);
+	else
+		launch_parse_rung<1, 0>(s, beside, st);
+}
+
 // blocks [first, first + count) of a sub-batch: the workgroup parse, then the emit-only kernel over its records
 inline void launch_wg(const DeflateArgs &a, int level, hipStream_t st)
 {
@@ -669,6 +731,10 @@ inline void launch_wg(const DeflateArgs &a, int level, hipStream_t st)
 			(void)hipFuncSetAttribute((const void *)k_parse_wg<2, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WG_LDS_DYNAMIC);
 			(void)hipFuncSetAttribute((const void *)k_parse_wg<1, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WG_LDS_DYNAMIC);
 			(void)hipFuncSetAttribute((const void *)k_parse_wg<1, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WG_LDS_DYNAMIC);
+			(void)hipFuncSetAttribute((const void *)k_primed_wg<4, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WG_LDS_DYNAMIC);
+			(void)hipFuncSetAttribute((const void *)k_primed_wg<2, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WG_LDS_DYNAMIC);
+			(void)hipFuncSetAttribute((const void *)k_primed_wg<1, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WG_LDS_DYNAMIC);
+			(void)hipFuncSetAttribute((const void *)k_primed_wg<1, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WG_LDS_DYNAMIC);
 			asked[dev] = true;
 		}
 	}
@@ -763,35 +829,7 @@ inline void launch_wg(const DeflateArgs &a, int level, hipStream_t st)
 				hipLaunchKernelGGL(k_gate, dim3(1), dim3(64), 0, st, emitted + (k - 2), cnt, 1u << 22, s.poison);
 			}
 		}
-		const dim3 grid(s.count * s.wg_split), block(64 * HD_WG_WAVES);
-		if (HD_WG_WAYS(level) == 4)
-			{
-			if (bs)
-				hipLaunchKernelGGL((k_parse_wg<4, 1, 1>), grid, block, WG_LDS_DYNAMIC, st, s);
-			else
-				hipLaunchKernelGGL((k_parse_wg<4, 1>), grid, block, 0, st, s);
-		}
-		else if (HD_WG_WAYS(level) == 2)
-			{
-			if (bs)
-				hipLaunchKernelGGL((k_parse_wg<2, 1, 1>), grid, block, WG_LDS_DYNAMIC, st, s);
-			else
-				hipLaunchKernelGGL((k_parse_wg<2, 1>), grid, block, 0, st, s);
-		}
-		else if (HD_WG_LAZY(level))
-			{
-			if (bs)
-				hipLaunchKernelGGL((k_parse_wg<1, 1, 1>), grid, block, WG_LDS_DYNAMIC, st, s);
-			else
-				hipLaunchKernelGGL((k_parse_wg<1, 1>), grid, block, 0, st, s);
-		}
-		else
-			{
-			if (bs)
-				hipLaunchKernelGGL((k_parse_wg<1, 0, 1>), grid, block, WG_LDS_DYNAMIC, st, s);
-			else
-				hipLaunchKernelGGL((k_parse_wg<1, 0>), grid, block, 0, st, s);
-		}
+		launch_parse_wg(s, level, bs != nullptr, st);
 		if (a.lat) {
 			// the per-block boundary (HD_FRAME_LATENCY, blocks up to 64 KiB): the member written by a workgroup, the same bytes
 			launch_emit_wg(s, st);

@@ -176,10 +176,7 @@ def deflate_stream_call(data, level, frame, chunk, dst, dst_cap, chunk_off):
     return summary
 
 
-def deflate_stream(data, level=6, frame=_pkg.FRAME_GZIP, chunk=1 << 16):
-    """uint8 tensor -> (stream, chunk_off, StreamSummary): ONE raw / zlib / gzip stream of the whole tensor, coded in
-    independent chunks of `chunk` bytes side by side.  The stream is allocated at hipdeflate_stream_bound and narrowed to
-    out_bytes; chunk_off (int64, nchunks + 1 entries) is the table inflate_stream wants."""
+def _deflate_stream(call, data, level, frame, chunk):
     n = data.numel()
     nchunks = (n + chunk - 1) // chunk
     bound = int(_pkg.lib().hipdeflate_stream_bound(n, chunk, level, frame))
@@ -187,10 +184,33 @@ def deflate_stream(data, level=6, frame=_pkg.FRAME_GZIP, chunk=1 << 16):
         raise ValueError("chunk = %d: a multiple of 16 in [16, 64 MiB]" % chunk)
     dst = torch.empty(bound, dtype=torch.uint8, device=data.device)
     chunk_off = torch.zeros(nchunks + 1, dtype=torch.int64, device=data.device)
-    s = deflate_stream_call(data, level, frame, chunk, dst, bound, chunk_off)
+    s = call(data, level, frame, chunk, dst, bound, chunk_off)
     if s.status:
         raise _pkg.HipDeflateError("stream encode: status %d, chunk %d" % (s.status, s.bad_chunk))
     return dst[:s.out_bytes], chunk_off, s
+
+
+def deflate_stream(data, level=6, frame=_pkg.FRAME_GZIP, chunk=1 << 16):
+    """uint8 tensor -> (stream, chunk_off, StreamSummary): ONE raw / zlib / gzip stream of the whole tensor, coded in
+    independent chunks of `chunk` bytes side by side.  The stream is allocated at hipdeflate_stream_bound and narrowed to
+    out_bytes; chunk_off (int64, nchunks + 1 entries) is the table inflate_stream wants."""
+    return _deflate_stream(deflate_stream_call, data, level, frame, chunk)
+
+
+def deflate_stream_carry_call(data, level, frame, chunk, dst, dst_cap, chunk_off):
+    """one hipdeflate_stream_deflate_carry_dev: deflate_stream_call's arguments -> StreamSummary"""
+    summary = _pkg.StreamSummary()
+    rc = _pkg.lib().hipdeflate_stream_deflate_carry_dev(_ptr(data), data.numel(), chunk, level, frame, _ptr(dst), dst_cap,
+                                                        _ptr(chunk_off), ctypes.byref(summary), _stream())
+    _pkg._check(rc, "hipdeflate_stream_deflate_carry_dev")
+    return summary
+
+
+def deflate_stream_carry(data, level=6, frame=_pkg.FRAME_GZIP, chunk=1 << 16):
+    """deflate_stream with every chunk primed by the min(32768, its offset) & ~1023 bytes in front of it (levels 3..9): the
+    one-block ratio at any chunk size, for streams that serial inflaters read.  -> (stream, chunk_off, StreamSummary);
+    the decode on the device is inflate_stream_carry, not inflate_stream."""
+    return _deflate_stream(deflate_stream_carry_call, data, level, frame, chunk)
 
 
 def inflate_stream_call(stream, frame, chunk_off, nchunks, chunk, out_bytes, out, out_cap):

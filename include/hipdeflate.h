@@ -416,6 +416,30 @@ uint64_t hipdeflate_stream_bound(uint64_t nbytes, uint32_t chunk_bytes, int leve
 int hipdeflate_stream_deflate_dev(const void *in, uint64_t nbytes, uint32_t chunk_bytes, int level, int frame,
 				  void *dst, uint64_t dst_cap, void *chunk_off /* u64[nchunks + 1], may be NULL */,
 				  hipdeflate_stream_summary *summary /* HOST */, void *stream);
+/* The same encoder with every chunk PRIMED by the input in front of it -- what pigz writes by default, where the call above is
+ * pigz -i.  Arguments, refusals, statuses, summary, chunk_off, the sizing call, the windows of HD_STREAM_WINDOW_BYTES and the
+ * turn-taking are hipdeflate_stream_deflate_dev's, rule for rule, and so is the layout: header | chunk 0 .. n-1 | 03 00 |
+ * trailer, every chunk ending in 00 00 ff ff on a byte boundary at chunk_off[i + 1] - 4.  hipdeflate_stream_bound covers this form
+ * too (a chunk's worst case is still stored + flush).  The one difference, at levels 3..9: chunk i, which starts at input byte
+ * s = i * chunk_bytes, is parsed with
+ *     prime(i) = min(32768, s) & ~1023
+ * bytes in front of it in the table and the window.  No token is made for those bytes and the chunk's CRC-32 / Adler-32 covers
+ * the chunk alone, but its matches may name any of them: distances go up to 32768 across the seam.  The rounding down to 1024
+ * keeps the chunk's first byte on a piece boundary of the parse (no match crosses one: hipdeflate_params.h HD_WG_CUT) and
+ * in + s - prime(i) 16-byte aligned; with chunk_bytes a multiple of 1024 every chunk behind the first 32 KiB has the whole
+ * window.  A chunk's tokens are those of a one-block parse of (its history || itself) behind the seam.  Chunk 0 has no history: a
+ * stream of one chunk is byte for byte hipdeflate_stream_deflate_dev's, and so is chunk 0 of any stream.
+ * Levels 0..2 have windows of 4 KiB or none, and a fresh window per 0xff00 bytes costs them under 1 % as it is: there the call
+ * writes exactly the bytes of hipdeflate_stream_deflate_dev.
+ * What the form costs a READER: every zlib, and any serial inflate, reads it as it reads any stream.  But the decode by chunk
+ * table, hipdeflate_stream_inflate_dev, answers status 2 at the first chunk that reaches back (never wrong bytes): its chunks
+ * are no longer independent.  The decode for this form is the carry pair below (hipdeflate_stream_index_carry_dev /
+ * hipdeflate_stream_inflate_carry_dev), which takes 8..11 times the time of the full-flush decode (README).  This form is for
+ * streams that serial inflaters will read -- a .gz, a zlib buffer, a PNG IDAT: it has the one-block ratio at any chunk size --;
+ * the independent form stays the default for everything this library decodes itself. */
+int hipdeflate_stream_deflate_carry_dev(const void *in, uint64_t nbytes, uint32_t chunk_bytes, int level, int frame,
+					void *dst, uint64_t dst_cap, void *chunk_off /* u64[nchunks + 1], may be NULL */,
+					hipdeflate_stream_summary *summary /* HOST */, void *stream);
 /* The inverse -- the device-resident form of what a dictzip reader does with its RA table (applet/7dictzip.c:318-323): given
  * the table, the chunks are inflated side by side, chunk i by the flush-rule batch inflate into out + i * chunk_bytes with
  * exactly its size as room, and the result is held to the trailer.  Streams of other writers qualify if they are cut the
@@ -754,6 +778,9 @@ int hipdeflate_check_combine_dev(const void *check, const void *len, uint32_t n,
 /* host-buffer form of the encoder: stages through the device; *destLen in = room, out = bytes; 0, or 1 = does not fit */
 int hip_deflate_stream(unsigned char *dest, size_t *destLen, const unsigned char *source, size_t sourceLen,
 		       int level, int frame, uint32_t chunk_bytes);
+/* ... and of hipdeflate_stream_deflate_carry_dev: the same bytes as the device call's */
+int hip_deflate_stream_carry(unsigned char *dest, size_t *destLen, const unsigned char *source, size_t sourceLen,
+			     int level, int frame, uint32_t chunk_bytes);
 /* test entry: chunks per window of the encoder (0 restores the default) */
 void hipdeflate_test_stream_window(uint32_t chunks);
 
