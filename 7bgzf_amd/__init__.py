@@ -45,6 +45,12 @@ class MemberSummary(ctypes.Structure):
                 ("status", ctypes.c_uint32)]
 
 
+class MemberAnySummary(ctypes.Structure):
+    """hipdeflate_member_any_summary (include/hipdeflate.h)"""
+    _fields_ = [("nmembers", ctypes.c_uint64), ("out_bytes", ctypes.c_uint64), ("end_offset", ctypes.c_uint64),
+                ("ncandidates", ctypes.c_uint64), ("nsized", ctypes.c_uint64), ("status", ctypes.c_uint32)]
+
+
 class RangeSummary(ctypes.Structure):
     """hipdeflate_range_summary (include/hipdeflate.h)"""
     _fields_ = [("out_bytes", ctypes.c_uint64), ("nselected", ctypes.c_uint64), ("sel_bytes", ctypes.c_uint64),
@@ -100,7 +106,7 @@ EXPORTS = [
     "hipdeflate_unpipe_result", "hipdeflate_unpipe_close", "hipdeflate_test_build_lengths", "hipdeflate_test_beside",
     "hip_inflate_flush", "hipdeflate_batch_inflate_flush", "hipdeflate_batch_inflate_flush_dev", "hipdeflate_bound",
     "hipdeflate_compact_span_dev", "hipdeflate_index_members_dev", "hipdeflate_verify_members_dev",
-    "hipdeflate_read_ranges_dev",
+    "hipdeflate_read_ranges_dev", "hipdeflate_index_members_any_dev", "hip_inflate_members",
     "hipdeflate_stream_bound", "hipdeflate_stream_deflate_dev", "hipdeflate_stream_inflate_dev",
     "hipdeflate_check_combine_dev", "hip_deflate_stream", "hipdeflate_test_stream_window",
     "hipdeflate_stream_index_dev", "hipdeflate_stream_inflate_table_dev", "hip_inflate_stream",
@@ -230,6 +236,9 @@ def lib():
     L.hipdeflate_stream_inflate_blocks_dev.argtypes = [_vp, ctypes.c_uint64, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint32, _vp,
                                                        ctypes.c_uint64, ctypes.POINTER(StreamSummary), _vp]
     L.hip_inflate_stream_blocks.argtypes = [_vp, sz_p, _vp, ctypes.c_size_t, ctypes.c_int, sz_p]
+    L.hipdeflate_index_members_any_dev.argtypes = [_vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp, _vp,
+                                                   _vp, _vp, ctypes.POINTER(MemberAnySummary), _vp]
+    L.hip_inflate_members.argtypes = [_vp, sz_p, _vp, ctypes.c_size_t, sz_p]
     L.hipdeflate_test_block_headers_dev.argtypes = [_vp, ctypes.c_uint64, _vp, ctypes.c_uint32, _vp, _vp]
     L.hipdeflate_test_blocks_times.argtypes = [ctypes.POINTER(ctypes.c_double)]
     L.hipdeflate_test_blocks_times.restype = None
@@ -380,6 +389,16 @@ def hip_inflate_stream_blocks(data, cap, frame=FRAME_GZIP):
     dst = np.zeros(max(cap, 1), dtype=np.uint8)
     n, used = ctypes.c_size_t(cap), ctypes.c_size_t(0)
     r = lib().hip_inflate_stream_blocks(_p(dst), ctypes.byref(n), _p(src), len(src), frame, ctypes.byref(used))
+    return r, bytes(dst[: n.value]) if r == 0 else b"", n.value, used.value
+
+
+def hip_inflate_members(data, cap):
+    """a file of gzip members, with or without a length field (`cat a.gz b.gz`), behind host buffers: the member index that
+    sizes by decoding, the batch inflate and the verify -> (ret, bytes, need, in_used), as hip_inflate_stream gives them"""
+    src = as_u8(data)
+    dst = np.zeros(max(cap, 1), dtype=np.uint8)
+    n, used = ctypes.c_size_t(cap), ctypes.c_size_t(0)
+    r = lib().hip_inflate_members(_p(dst), ctypes.byref(n), _p(src), len(src), ctypes.byref(used))
     return r, bytes(dst[: n.value]) if r == 0 else b"", n.value, used.value
 
 

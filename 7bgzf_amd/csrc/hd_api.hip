@@ -1172,8 +1172,9 @@ static int enter_call(void *summary, size_t bytes)
 
 // Pass 1 and 2 over src[0, n).  lo == nullptr: the member index's (k_index_flag, k_index_write); no candidate leaves d_cand
 // alone.  Else a stream index's: the markers from *lo on (k_stream_flag, k_stream_write) behind candidate 0, *lo itself.
+// any_lo (INDEX_ANY, lo == nullptr): the member index's passes with the matcher of members that state no length, from *any_lo on.
 static int chain_candidates(Ctx &g, const uint8_t *src, uint64_t n, const uint32_t *lo, hd::IndexKind kind, uint32_t max_members,
-			    hd::IndexWords *&w, hd::IndexCand &c, uint32_t &ncand, hipStream_t st)
+			    hd::IndexWords *&w, hd::IndexCand &c, uint32_t &ncand, hipStream_t st, const uint64_t *any_lo = nullptr)
 {
 	const uint64_t nwords = (n + hd::IDX_WORD - 1) / hd::IDX_WORD, ntb64 = (nwords + hd::IDX_TILE_WORDS - 1) / hd::IDX_TILE_WORDS;
 	if (ntb64 > 0x7fffffffu)
@@ -1188,6 +1189,8 @@ static int chain_candidates(Ctx &g, const uint8_t *src, uint64_t n, const uint32
 	if (ntb) {
 		if (lo)
 			hipLaunchKernelGGL(hd::k_stream_flag, dim3(ntb), dim3(256), 0, st, src, n, (uint64_t)*lo, b.bitmap, b.tile_cnt);
+		else if (any_lo)
+			hipLaunchKernelGGL(hd::k_any_flag, dim3(ntb), dim3(256), 0, st, src, n, *any_lo, b.bitmap, b.tile_cnt);
 		else
 			hipLaunchKernelGGL(hd::k_index_flag, dim3(ntb), dim3(256), 0, st, src, n, b.bitmap, b.tile_cnt);
 		index_scan(b.tile_cnt, ntb, b.tiles, b.tile_off, &b.w->ncand, st);
@@ -1205,8 +1208,12 @@ static int chain_candidates(Ctx &g, const uint8_t *src, uint64_t n, const uint32
 		return HD_E_NOMEM;
 	c = hd::IndexCand(g.d_cand.p, ncand, max_rows, kind);
 	if (!lo) {
-		hipLaunchKernelGGL(hd::k_index_write, dim3(ntb), dim3(256), 0, st, src, n, (const uint64_t *)b.bitmap, nwords,
-				   (const uint64_t *)b.tile_off, c.pos);
+		if (any_lo)
+			hipLaunchKernelGGL(hd::k_any_write, dim3(ntb), dim3(256), 0, st, src, n, *any_lo, (const uint64_t *)b.bitmap, nwords,
+					   (const uint64_t *)b.tile_off, c.pos);
+		else
+			hipLaunchKernelGGL(hd::k_index_write, dim3(ntb), dim3(256), 0, st, src, n, (const uint64_t *)b.bitmap, nwords,
+					   (const uint64_t *)b.tile_off, c.pos);
 		return 0;
 	}
 	HD_CHECK(hipMemsetAsync(c.pos, 0, 8, st));
@@ -1283,6 +1290,80 @@ int hipdeflate_index_members_dev(const void *blob, uint64_t nbytes, uint32_t max
 	}
 	hipLaunchKernelGGL(hd::k_index_verdict, dim3(1), dim3(1), 0, st, src, nbytes, nrows, max_members, &w->rows);
 	return chain_read(w, &summary->nmembers, &summary->out_bytes, &summary->end_offset, &summary->status, st);
+}
+
+// hipdeflate_index_members_any_dev under mu_index: the chain index with a links pass in two steps around the sizing of the
+// candidates that state no length (hd_index.hpp).  The passes run over blob from the 16-byte granule of first_offset on,
+// and the candidates' positions count from there.
+static int members_any_index(Ctx &g, const uint8_t *blob, uint64_t nbytes, uint64_t first_offset, uint32_t max_members, uint32_t max_in,
+			     void *in_off, void *in_len, void *out_size, void *out_off, void *crc_want,
+			     hipdeflate_member_any_summary *summary, hipStream_t st)
+{
+	const uint64_t base = first_offset & ~(uint64_t)15, lo = first_offset - base, n = nbytes - base;
+	const uint8_t *src = blob + base;
+	hd::IndexWords *w = nullptr;
+	hd::IndexCand c;
+	uint32_t ncand = 0;
+	int r;
+	if ((r = chain_candidates(g, src, n, nullptr, hd::INDEX_ANY, max_members, w, c, ncand, st, &lo)))
+		return r;
+	const uint32_t nwg = (ncand + 255) / 256;
+	uint64_t nrows = 0, nsized = 0;
+	if (ncand) {
+		hipLaunchKernelGGL(hd::k_any_classify, dim3(nwg), dim3(256), 0, st, src, n, (const uint64_t *)c.pos, ncand, c.cls, c.hdr, c.total,
+				   c.asize, c.tosize);
+		index_scan(c.tosize, ncand, c.tiles, c.rank, &w->spare, st);
+		HD_CHECK(hipGetLastError());
+		HD_CHECK(hipMemcpyAsync(&nsized, &w->spare, 8, hipMemcpyDeviceToHost, st));
+		HD_CHECK(hipStreamSynchronize(st));
+		if (nsized) {
+			const uint32_t ns = (uint32_t)nsized;
+			hipLaunchKernelGGL(hd::k_any_compact, dim3(nwg), dim3(256), 0, st, (const uint32_t *)c.tosize, (const uint64_t *)c.rank, ncand,
+					   c.sub);
+			hipLaunchKernelGGL(hd::k_member_open, dim3(ns), dim3(64), 0, st, src, n, (const uint64_t *)c.pos, (const uint32_t *)c.sub, ns,
+					   max_in, c.hdr, c.astat);
+			hipLaunchKernelGGL(hd::k_inflate_member, dim3(ns), dim3(64), 0, st,
+					   hd::MemberArgs{ src, c.pos, c.sub, ns, max_in, n, c.hdr, c.asize, c.total, c.astat });
+		}
+		hipLaunchKernelGGL(hd::k_any_links, dim3(nwg), dim3(256), 0, st, n, lo, max_in, (const uint64_t *)c.pos, ncand,
+				   (const uint32_t *)c.tosize, (const int32_t *)c.astat, c.cls, (const uint32_t *)c.total, c.succ0, c.mark);
+		if ((r = chain_rank(c, ncand, c.total, w, &nrows, st)))
+			return r;
+		if (nrows) {
+			const uint32_t ntab = (uint32_t)(nrows < max_members ? nrows : max_members);
+			hipLaunchKernelGGL(hd::k_any_tables, dim3(nwg), dim3(256), 0, st, src, base, (const uint64_t *)c.pos, (const uint32_t *)c.hdr,
+					   (const uint32_t *)c.total, (const uint32_t *)c.asize, (const uint32_t *)c.tosize, (const uint32_t *)c.mark,
+					   (const uint64_t *)c.rank, ncand, nrows, max_members, (uint64_t *)in_off, (uint32_t *)in_len,
+					   (uint32_t *)out_size, (uint32_t *)crc_want, &w->end_offset);
+			if (ntab)
+				index_scan((const uint32_t *)out_size, ntab, c.tiles, (uint64_t *)out_off, &w->out_bytes, st);
+		}
+	}
+	hipLaunchKernelGGL(hd::k_any_verdict, dim3(1), dim3(1), 0, st, src, n, base, lo, (const uint64_t *)c.pos, (const uint32_t *)c.cls, ncand,
+			   nrows, max_members, &w->rows);
+	summary->ncandidates = ncand;
+	summary->nsized = nsized;
+	return chain_read(w, &summary->nmembers, &summary->out_bytes, &summary->end_offset, &summary->status, st);
+}
+
+int hipdeflate_index_members_any_dev(const void *blob, uint64_t nbytes, uint64_t first_offset, uint32_t max_members, uint32_t max_member_in,
+				     void *in_off, void *in_len, void *out_size, void *out_off, void *crc_want,
+				     hipdeflate_member_any_summary *summary, void *stream)
+{
+	Ctx &g = cur();
+	int r = enter_call(summary, sizeof *summary);
+	if (r)
+		return r;
+	if (((uintptr_t)blob & 15) || (nbytes && !blob) || first_offset > nbytes || max_member_in >= HD_INFLATE_MAX_IN ||
+	    (max_members && (!in_off || !in_len || !out_size || !out_off || !crc_want)))
+		return HD_E_ARG;
+	summary->end_offset = first_offset;
+	if (first_offset == nbytes)
+		return 0;
+	std::lock_guard<std::mutex> lk(g.mu_index);
+	return members_any_index(g, (const uint8_t *)blob, nbytes, first_offset, max_members,
+				 max_member_in ? max_member_in : (uint32_t)HD_INFLATE_MAX_IN - 1, in_off, in_len, out_size, out_off, crc_want, summary,
+				 (hipStream_t)stream);
 }
 
 int hipdeflate_verify_members_dev(const void *status, const void *out_len, const void *crc32, const void *out_size,
@@ -3651,6 +3732,63 @@ int hip_inflate_stream_carry(unsigned char *dest, size_t *destLen, const unsigne
 int hip_inflate_stream_blocks(unsigned char *dest, size_t *destLen, const unsigned char *source, size_t sourceLen, int frame, size_t *in_used)
 {
 	return inflate_stream_host(dest, destLen, source, sourceLen, frame, in_used, true, true);
+}
+
+// stage, index (the sizing call, then on a table of that size in d_meta), inflate into d_packed, verify
+int hip_inflate_members(unsigned char *dest, size_t *destLen, const unsigned char *source, size_t sourceLen, size_t *in_used)
+{
+	Ctx &g = cur();
+	int r = ensure();
+	if (r)
+		return r;
+	if (!destLen || (*destLen && !dest) || (sourceLen && !source))
+		return HD_E_ARG;
+	std::lock_guard<std::mutex> lk(g.mu);
+	if ((r = bind_device(g)))
+		return r;
+	if (g.d_in.reserve(up16(sourceLen) + 16))
+		return HD_E_NOMEM;
+	if (sourceLen)
+		HD_CHECK(hipMemcpyAsync(g.d_in.p, source, sourceLen, hipMemcpyHostToDevice, g.stream));
+	hipdeflate_member_any_summary ms;
+	if ((r = hipdeflate_index_members_any_dev(g.d_in.p, sourceLen, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, &ms, g.stream)))
+		return r;
+	if (ms.status == 3) {
+		if (ms.nmembers > 0x7fffffffu || g.d_meta.reserve(hd::MemberTables::bytes((size_t)ms.nmembers)))
+			return HD_E_NOMEM;
+		const hd::MemberTables t(g.d_meta.p, (size_t)ms.nmembers);
+		if ((r = hipdeflate_index_members_any_dev(g.d_in.p, sourceLen, 0, (uint32_t)ms.nmembers, 0, t.in_off, t.in_len, t.out_size, t.out_off,
+							  t.crc_want, &ms, g.stream)))
+			return r;
+	}
+	g.stream_drained(g.stream);
+	if (in_used)
+		*in_used = ms.end_offset;
+	if (ms.status)
+		return 1;
+	if (ms.out_bytes > *destLen) {
+		*destLen = ms.out_bytes;
+		return 3;
+	}
+	const uint32_t n = (uint32_t)ms.nmembers;
+	if (n) {
+		if (g.d_packed.reserve(up16(ms.out_bytes) + 16))
+			return HD_E_NOMEM;
+		const hd::MemberTables t(g.d_meta.p, n);
+		if ((r = launch_inflate({ (const uint8_t *)g.d_in.p, t.in_off, t.in_len, n, (uint8_t *)g.d_packed.p, t.out_off, t.out_size, t.out_len, t.crc,
+					  t.status, g.d_ct, 0 },
+					g.stream)))
+			return r;
+		uint64_t bad = n;
+		if ((r = hipdeflate_verify_members_dev(t.status, t.out_len, t.crc, t.out_size, t.crc_want, n, &bad, g.stream)))
+			return r;
+		if (bad != n)
+			return 1;
+		if (ms.out_bytes)
+			HD_CHECK(hipMemcpy(dest, g.d_packed.p, ms.out_bytes, hipMemcpyDeviceToHost));
+	}
+	*destLen = ms.out_bytes;
+	return 0;
 }
 
 } // extern "C"

@@ -11,9 +11,13 @@
 //   4. k_members_tables: the marked candidates, ranked by a prefix count, become the four tables of batch_inflate_dev;
 //   5. k_index_verdict names where the walk stopped and why.
 // k_members_verify is the trailer check behind the inflate (applet/7bgzf.c:340-352 on the host).
+// The second half of the file is the same walk for members that state no length (hipdeflate_index_members_any_dev): the
+// matcher without the FEXTRA requirement, and a links pass that sizes such a member by decoding it (k_inflate_member).
 // Every read of the blob is bounded by nbytes, whatever the blob says.
 #pragma once
 #include "hd_compact.hpp"
+#include "hd_frame.hpp"
+#include "hd_inflate_size.hpp"
 
 namespace hd {
 
@@ -39,17 +43,20 @@ __device__ __forceinline__ void index_load20(const uint8_t *blob, uint64_t nbyte
 	}
 }
 
-// bit k: the four bytes at o + k are 1f 8b 08 FLG with FLG & 0xe4 == 0x04
-__device__ __forceinline__ uint32_t index_match16(const uint32_t (&d)[5])
+// bit k: the four bytes at o + k, as a little-endian word w, have (w & MASK) == WANT
+template <uint32_t MASK, uint32_t WANT> __device__ __forceinline__ uint32_t index_match16_of(const uint32_t (&d)[5])
 {
 	uint32_t m = 0;
 #pragma unroll
 	for (uint32_t k = 0; k < 16; k++) {
 		const uint32_t w = (k & 3) ? __builtin_amdgcn_alignbyte(d[(k >> 2) + 1], d[k >> 2], k & 3) : d[k >> 2];
-		m |= (uint32_t)((w & 0xe4ffffffu) == 0x04088b1fu) << k;
+		m |= (uint32_t)((w & MASK) == WANT) << k;
 	}
 	return m;
 }
+
+// bit k: the four bytes at o + k are 1f 8b 08 FLG with FLG & 0xe4 == 0x04
+__device__ __forceinline__ uint32_t index_match16(const uint32_t (&d)[5]) { return index_match16_of<0xe4ffffffu, 0x04088b1fu>(d); }
 
 // The matcher of the two passes is a parameter: m(d, o) = the bits k of the granule at o whose position o + k matches, and
 // a match at position q makes the candidate q + M::SHIFT.  MatchMember is the member index's: a candidate is where the
@@ -317,6 +324,214 @@ __global__ __launch_bounds__(256) void k_members_verify(const int32_t *status, c
 		if (v != IDX_NIL)
 			atomicMin(first_bad, v);
 	}
+}
+
+/* ---- members that state no length (hipdeflate_index_members_any_dev) ----
+   The walk above over blob[lo, n): a candidate is any 1f 8b 08 FLG without a reserved bit, all four bytes in front of n.
+   A member whose extra field is one of the five known kinds is member_parse's, to the bit (rule A); every other one is
+   sized by decoding it without output inside its window of max_in bytes (rule B: k_member_open, k_inflate_member).  The
+   links pass is therefore two steps with the sizing of the compacted rule-B subset between them:
+     k_any_classify -> scan, k_any_compact -> k_member_open, k_inflate_member -> k_any_links -> k_index_jump ... as above. */
+
+constexpr uint32_t MEMBER_LONG = 4;                  // (= hipdeflate_member_any_summary.status 4)
+
+// positions o + k >= lo (lo < 16: the call starts the pass on the granule that holds it) whose four bytes end at or before n
+// -- index_load20's zeros behind n would complete a magic with FLG 0
+struct MatchAny {
+	uint64_t lo, n;
+	static constexpr uint32_t SHIFT = 0;
+	__device__ __forceinline__ uint32_t operator()(const uint32_t (&d)[5], uint64_t o) const
+	{
+		uint32_t m = index_match16_of<0xe0ffffffu, 0x00088b1fu>(d);
+		if (o < lo)
+			m &= 0xffffu << (uint32_t)(lo - o);
+		if (o + 20 > n)
+			m &= o + 4 > n ? 0u : (1u << (uint32_t)(n - o - 3)) - 1;
+		return m;
+	}
+};
+
+__global__ __launch_bounds__(256) void k_any_flag(const uint8_t *blob, uint64_t nbytes, uint64_t lo, uint64_t *bitmap, uint32_t *tile_cnt)
+{
+	index_flag_body(blob, nbytes, bitmap, tile_cnt, MatchAny{ lo, nbytes });
+}
+
+__global__ __launch_bounds__(256) void k_any_write(const uint8_t *blob, uint64_t nbytes, uint64_t lo, const uint64_t *bitmap,
+						    uint64_t nwords, const uint64_t *tile_off, uint64_t *pos)
+{
+	index_write_body(blob, nbytes, bitmap, nwords, tile_off, pos, MatchAny{ lo, nbytes });
+}
+
+// rule A applies: FEXTRA, and XLEN and the tag are those of one of the five kinds, by member_parse's tests
+__device__ __forceinline__ bool member_states_length(const uint8_t *blob, uint64_t p, uint64_t nbytes)
+{
+	const uint64_t avail = nbytes - p;
+	const uint8_t *b = blob + p;
+	if (!(b[3] & 4) || avail < 12)
+		return false;
+	const uint32_t xlen = index_rd16(b + 10);
+	if ((xlen != 4 && xlen != 6 && xlen != 8 && xlen != 20) || avail < 12 + (uint64_t)xlen)
+		return false;
+	const uint32_t tag = index_rd32(b + 12);
+	return (xlen == 6 && tag == 0x00024342u) || (xlen == 8 && (tag == 0x00045a4du || tag == 0x00044749u)) ||
+	       (xlen == 20 && tag == 0x00104749u) || (xlen == 4 && (tag >> 24) == 0x7d);
+}
+
+// step 1, one lane per candidate: rule A decides at once (cls, hdr, total); rule B marks the candidate to be sized
+__global__ __launch_bounds__(256) void k_any_classify(const uint8_t *blob, uint64_t nbytes, const uint64_t *pos, uint32_t ncand,
+						       uint32_t *cls, uint32_t *hdr, uint32_t *total, uint32_t *osize, uint32_t *tosize)
+{
+	const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+	if (i >= ncand)
+		return;
+	const uint64_t p = pos[i];
+	const bool a = member_states_length(blob, p, nbytes);
+	Member m = { MEMBER_BAD, 0, 0 };
+	if (a)
+		m = member_parse<true>(blob, p, nbytes);
+	cls[i] = m.cls;
+	hdr[i] = m.hdr;
+	total[i] = m.total;
+	osize[i] = 0;
+	tosize[i] = !a;
+}
+
+// the rule-B subset, ascending: sub[rank[i]] = i
+__global__ __launch_bounds__(256) void k_any_compact(const uint32_t *tosize, const uint64_t *rank, uint32_t ncand, uint32_t *sub)
+{
+	const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+	if (i < ncand && tosize[i])
+		sub[rank[i]] = i;
+}
+
+// One wavefront per candidate to size: its header by k_frame_open's gzip rules, read in stream order inside the window
+// [p, p + min(nbytes - p, max_in)).  status HD_OK: hdr[] bytes of header, and at least one byte of the window behind them;
+// PIECE_CUT: a header byte, or the stream's first, lies at or behind the window's end.  Nothing in a header is BAD: the
+// matcher saw the magic and FLG.  The names are scanned by all 64 lanes.
+__global__ __launch_bounds__(64) void k_member_open(const uint8_t *blob, uint64_t nbytes, const uint64_t *pos, const uint32_t *sub,
+						     uint32_t nsub, uint32_t max_in, uint32_t *hdr, int32_t *status)
+{
+	const uint32_t b = blockIdx.x, lane = threadIdx.x;
+	if (b >= nsub)
+		return;
+	const uint32_t row = sub[b];
+	const uint64_t p = pos[row], left = nbytes - p;
+	const uint32_t n = left < max_in ? (uint32_t)left : max_in;
+	const uint8_t *src = blob + p;
+	const uint32_t flg = src[3];                                             // (a candidate: p + 4 <= nbytes)
+	uint32_t at = 10;
+	bool ok = at < n;
+	if (ok && (flg & 4)) {                                                   // FEXTRA
+		ok = n >= 12;
+		if (ok) {
+			at = 12 + index_rd16(src + 10);
+			ok = at < n;
+		}
+	}
+	if (ok && (flg & 8)) {                                                   // FNAME
+		at = frame_skip_cstring(src, at, n, lane);
+		ok = at < n;
+	}
+	if (ok && (flg & 16)) {                                                  // FCOMMENT
+		at = frame_skip_cstring(src, at, n, lane);
+		ok = at < n;
+	}
+	if (ok && (flg & 2)) {                                                   // FHCRC: skipped, not verified
+		at += 2;
+		ok = at < n;
+	}
+	if (lane == 0) {
+		hdr[row] = ok ? at : 0u;
+		status[row] = ok ? HD_OK : PIECE_CUT;
+	}
+}
+
+// step 2, one lane per candidate: the sized candidates get their class -- what ran out of the window is CUT where the
+// window ends at nbytes and LONG where max_in ended it; a stream of 2^32 bytes or more is no member -- and every member's
+// end is resolved to a candidate, as k_index_links does.  The head of the chain is the candidate at lo.
+__global__ __launch_bounds__(256) void k_any_links(uint64_t nbytes, uint64_t lo, uint32_t max_in, const uint64_t *pos, uint32_t ncand,
+						    const uint32_t *tosize, const int32_t *pstat, uint32_t *cls, const uint32_t *total,
+						    uint32_t *succ, uint32_t *mark)
+{
+	const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+	if (i >= ncand)
+		return;
+	const uint64_t p = pos[i];
+	uint32_t c = cls[i];
+	if (tosize[i]) {
+		const int32_t st = pstat[i];
+		c = st == HD_OK ? MEMBER_OK : st != PIECE_CUT ? MEMBER_BAD : nbytes - p <= max_in ? MEMBER_CUT : MEMBER_LONG;
+		cls[i] = c;
+	}
+	uint32_t s = IDX_NIL;
+	if (c == MEMBER_OK) {
+		const uint64_t next = p + total[i];
+		uint32_t l = i + 1, h = ncand;
+		while (l < h) {
+			const uint32_t mid = l + ((h - l) >> 1);
+			if (pos[mid] < next)
+				l = mid + 1;
+			else
+				h = mid;
+		}
+		if (l < ncand && pos[l] == next)
+			s = l;
+	}
+	succ[i] = s;
+	mark[i] = i == 0 && p == lo && c == MEMBER_OK;
+}
+
+// k_members_tables with offsets from `base` on (pos[] counts from there) and out_size from the decode where there was one
+__global__ __launch_bounds__(256) void k_any_tables(const uint8_t *blob, uint64_t base, const uint64_t *pos, const uint32_t *hdr,
+						     const uint32_t *total, const uint32_t *osize, const uint32_t *tosize, const uint32_t *mark,
+						     const uint64_t *rank, uint32_t ncand, uint64_t nrows, uint32_t max_members, uint64_t *in_off,
+						     uint32_t *in_len, uint32_t *out_size, uint32_t *crc_want, uint64_t *end_offset)
+{
+	const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+	if (i >= ncand || !mark[i])
+		return;
+	const uint64_t r = rank[i], p = pos[i];
+	const uint32_t h = hdr[i], t = total[i];
+	if (r < max_members) {
+		in_off[r] = base + p + h;
+		in_len[r] = t - h;
+		crc_want[r] = index_rd32(blob + p + t - 8);
+		out_size[r] = tosize[i] ? osize[i] : index_rd32(blob + p + t - 4);
+	}
+	if (r + 1 == nrows)
+		*end_offset = p + t;
+}
+
+// sum[] = { nmembers, out_bytes, end_offset, status }.  The stop position's verdict is its candidate's class; a position
+// that is no candidate is BAD, or CUT where fewer than four bytes are left and the magic fits as far as they go.
+__global__ void k_any_verdict(const uint8_t *blob, uint64_t nbytes, uint64_t base, uint64_t lo, const uint64_t *pos, const uint32_t *cls,
+			      uint32_t ncand, uint64_t nrows, uint32_t max_members, uint64_t *sum)
+{
+	const uint64_t end = nrows ? sum[2] : lo;
+	uint64_t status = 0;
+	if (end < nbytes) {
+		uint32_t l = 0, h = ncand;
+		while (l < h) {
+			const uint32_t mid = l + ((h - l) >> 1);
+			if (pos[mid] < end)
+				l = mid + 1;
+			else
+				h = mid;
+		}
+		if (l < ncand && pos[l] == end) {
+			status = cls[l];
+		} else {
+			const uint64_t avail = nbytes - end;
+			const uint8_t *b = blob + end;
+			const bool fits = avail < 4 && b[0] == 0x1f && (avail < 2 || b[1] == 0x8b) && (avail < 3 || b[2] == 8);
+			status = fits ? MEMBER_CUT : MEMBER_BAD;
+		}
+	}
+	if (nrows > max_members)
+		status = 3;
+	sum[0] = nrows;
+	sum[2] = base + end;
+	sum[3] = status;
 }
 
 } // namespace hd

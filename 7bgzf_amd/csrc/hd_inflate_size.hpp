@@ -70,6 +70,24 @@ struct PieceArgs {
 	uint32_t *stop;                  // PIECE_FLUSH | PIECE_FINAL, 0 where the piece does not decode
 };
 constexpr int32_t PIECE_CUT = 4;
+// The member form (k_inflate_member, hd_index.hpp): a piece that is the DEFLATE stream of a gzip member nobody stated the
+// length of.  Candidate sub[b] of pos[] starts a member whose header k_member_open measured (hdr[], and status[] HD_OK; any
+// other status: nothing is decoded and every column stays); its window ends at nbytes or max_in bytes behind the
+// candidate, whichever comes first.  The only stop is the end of a final block -- a flush point is none -- and behind it
+// the trailer's eight bytes must lie inside the window (PIECE_CUT where they do not) and its ISIZE equal the decoded
+// length (HD_BAD_DATA).  osize[] = that length, total[] = header + stream + 8; both 0 where status[] is not HD_OK.
+struct MemberArgs {
+	const uint8_t *in;
+	const uint64_t *pos;             // every candidate of the index
+	const uint32_t *sub;             // the ncand of them to size; the five columns below are indexed by candidate
+	uint32_t ncand;
+	uint32_t max_in;                 // < HD_INFLATE_MAX_IN
+	uint64_t nbytes;                 // > pos[i] for every i
+	const uint32_t *hdr;
+	uint32_t *osize;
+	uint32_t *total;
+	int32_t *status;                 // HD_OK | HD_BAD_DATA | HD_INSUFFICIENT_SPACE | PIECE_CUT
+};
 constexpr uint32_t PIECE_FLUSH = 1, PIECE_FINAL = 2, PIECE_NEXT = 3, PIECE_PAST_HEADER = 4;
 // The carried form (k_carry_piece, hd_carry.hpp): a piece of a stream whose writer kept the window across the flush.  A
 // distance past the bytes the piece has put out is no fault then -- 32768 is DEFLATE's most, and the bytes in front of the
@@ -84,7 +102,7 @@ struct CarryPieceArgs : PieceArgs {
 // tables of a dynamic block built, LEN / NLEN of a stored one agreeing -- says so in stop[] (PIECE_PAST_HEADER: a count for
 // the bench, no link and no verdict looks at it).
 
-template <bool PIECE, class Args, bool CARRY = false, bool BITS = false> __device__ __forceinline__ void inflate_size_body(const Args &a)
+template <bool PIECE, class Args, bool CARRY = false, bool BITS = false, bool MEMBER = false> __device__ __forceinline__ void inflate_size_body(const Args &a)
 {
 	__shared__ InfSizeLds L;
 	const uint32_t lane = threadIdx.x;
@@ -92,7 +110,18 @@ template <bool PIECE, class Args, bool CARRY = false, bool BITS = false> __devic
 	uint64_t p_off;
 	uint32_t n;
 	[[maybe_unused]] uint32_t sh = 0;              // (block form) the candidate's bit in its byte
-	if constexpr (PIECE) {
+	[[maybe_unused]] uint32_t row = b;             // (member form) the candidate this wavefront sizes
+	if constexpr (MEMBER) {
+		if (b >= a.ncand)
+			return;
+		row = a.sub[b];
+		if (a.status[row] != HD_OK)                // the header did not fit the window
+			return;
+		const uint64_t p = a.pos[row], left = a.nbytes - p;
+		const uint32_t h = a.hdr[row];             // < the window: k_member_open
+		p_off = p + h;
+		n = (left < a.max_in ? (uint32_t)left : a.max_in) - h;
+	} else if constexpr (PIECE) {
 		if (b >= a.ncand)
 			return;
 		p_off = a.pos[b];
@@ -229,7 +258,7 @@ template <bool PIECE, class Args, bool CARRY = false, bool BITS = false> __devic
 			if (len > n - ip) { st = HD_BAD_DATA; cut = true; break; }
 			pos += len;
 			R.seek_byte(ip + len);
-			if constexpr (PIECE && !BITS) {
+			if constexpr (PIECE && !BITS && !MEMBER) {
 				if (!bfinal && len == 0) {
 					stop = PIECE_FLUSH;
 					break;
@@ -313,7 +342,28 @@ template <bool PIECE, class Args, bool CARRY = false, bool BITS = false> __devic
 			}
 		}
 	}
-	if constexpr (PIECE) {
+	if constexpr (MEMBER) {
+		// cut as a piece is; then the trailer behind the byte the stream ended on (used <= n)
+		if (cut || R.consumed_bits() > 8 * (int64_t)n)
+			st = PIECE_CUT;
+		uint32_t used = 0;
+		if (st == HD_OK) {
+			used = (uint32_t)((R.consumed_bits() + 7) >> 3);
+			if (n - used < 8) {
+				st = PIECE_CUT;
+			} else {
+				const uint8_t *t = src + used + 4;
+				const uint32_t isize = t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16) | ((uint32_t)t[3] << 24);
+				if (isize != (uint32_t)pos)
+					st = HD_BAD_DATA;
+			}
+		}
+		if (lane == 0) {
+			a.osize[row] = st == HD_OK ? (uint32_t)pos : 0u;
+			a.total[row] = st == HD_OK ? (uint32_t)(p_off - a.pos[row]) + used + 8u : 0u;
+			a.status[row] = st;
+		}
+	} else if constexpr (PIECE) {
 		// with the decoder's position past the input -- at a stop it reached through the zero bits, or at the failure they
 		// led to -- the piece is cut, whatever else the decoder found there
 		if (cut || R.consumed_bits() > 8 * (int64_t)n)
@@ -356,5 +406,6 @@ template <bool PIECE, class Args, bool CARRY = false, bool BITS = false> __devic
 
 __global__ __launch_bounds__(64) void k_inflate_size(SizeArgs a) { inflate_size_body<false>(a); }
 __global__ __launch_bounds__(64) void k_inflate_piece(PieceArgs a) { inflate_size_body<true>(a); }
+__global__ __launch_bounds__(64) void k_inflate_member(MemberArgs a) { inflate_size_body<true, MemberArgs, false, false, true>(a); }
 
 } // namespace hd

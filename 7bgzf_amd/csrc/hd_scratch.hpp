@@ -102,22 +102,28 @@ struct IndexBitmap : Layout<IndexBitmap> {
 };
 
 // d_cand: ncand candidates in columns of nc, and the tiles of two scans, of ncand and of max_rows elements.  The successor
-// tables are dead when the rank scan runs: rank lies over them.
-enum IndexKind { INDEX_MEMBERS, INDEX_STREAM, INDEX_CARRY, INDEX_BLOCKS };
+// tables are dead when the rank scan runs: rank lies over them.  INDEX_ANY (members that state no length) is INDEX_MEMBERS
+// with every candidate's class and the columns of its sizing subset; its subset scan runs before the successor tables are
+// written, into rank as well.
+enum IndexKind { INDEX_MEMBERS, INDEX_STREAM, INDEX_CARRY, INDEX_BLOCKS, INDEX_ANY };
 struct IndexCand : Layout<IndexCand> {
 	IndexCand(void *base = nullptr, size_t ncand = 0, size_t max_rows = 0, IndexKind kind = INDEX_MEMBERS)
-		: Layout(base), nc((ncand + 3) & ~(size_t)3), ntiles(scan_tiles(ncand) + scan_tiles(max_rows)), nm(kind == INDEX_MEMBERS ? nc : 0),
-		  ns(kind == INDEX_MEMBERS ? 0 : nc), nr(kind == INDEX_CARRY || kind == INDEX_BLOCKS ? nc : 0) {}
-	size_t nc, ntiles, nm, ns, nr;
+		: Layout(base), nc((ncand + 3) & ~(size_t)3), ntiles(scan_tiles(ncand) + scan_tiles(max_rows)),
+		  nm(kind == INDEX_MEMBERS || kind == INDEX_ANY ? nc : 0), ns(kind == INDEX_MEMBERS || kind == INDEX_ANY ? 0 : nc),
+		  nr(kind == INDEX_CARRY || kind == INDEX_BLOCKS ? nc : 0), na(kind == INDEX_ANY ? nc : 0) {}
+	size_t nc, ntiles, nm, ns, nr, na;
 	uint64_t *tiles = c.take<uint64_t>(ntiles), *pos = c.take<uint64_t>(nc);
 	size_t succ_at = c.bytes();
 	uint32_t *succ0 = c.take<uint32_t>(nc), *succ1 = c.take<uint32_t>(nc);
 	uint64_t *rank = c.over<uint64_t>(succ_at, nc);
 	uint32_t *mark = c.take<uint32_t>(nc);
-	uint32_t *hdr = c.take<uint32_t>(nm), *total = c.take<uint32_t>(nm);                                         // INDEX_MEMBERS
+	uint32_t *hdr = c.take<uint32_t>(nm), *total = c.take<uint32_t>(nm);                                         // INDEX_MEMBERS, INDEX_ANY
 	uint32_t *used = c.take<uint32_t>(ns), *osize = c.take<uint32_t>(ns), *stop = c.take<uint32_t>(ns);          // both stream indexes
 	int32_t *pstat = c.take<int32_t>(ns);
 	uint32_t *reach = c.take<uint32_t>(nr);                                                                      // INDEX_CARRY, INDEX_BLOCKS
+	uint32_t *cls = c.take<uint32_t>(na), *tosize = c.take<uint32_t>(na), *sub = c.take<uint32_t>(na);           // INDEX_ANY
+	uint32_t *asize = c.take<uint32_t>(na);
+	int32_t *astat = c.take<int32_t>(na);
 };
 
 // d_blocks, the block index's merge (hd_blocks.hpp): the np pieces of the chain in rank order, and the rows they merge into
@@ -221,6 +227,16 @@ struct RowTable : Layout<RowTable> {
 	uint64_t *in_off = c.take<uint64_t>(n), *out_off = c.take<uint64_t>(n);
 	uint32_t *in_len = c.take<uint32_t>(n), *out_size = c.take<uint32_t>(n), *reach = c.take<uint32_t>(nr);
 	uint8_t *slack = c.take<uint8_t>(64);            // room behind the rows, as the table has always had
+};
+
+// the member table that hip_inflate_members makes in d_meta, and the inflate's answers on it: n members
+struct MemberTables : Layout<MemberTables> {
+	MemberTables(void *base, size_t n_) : Layout(base), n(n_) {}
+	size_t n;
+	uint64_t *in_off = c.take<uint64_t>(n), *out_off = c.take<uint64_t>(n);
+	uint32_t *in_len = c.take<uint32_t>(n), *out_size = c.take<uint32_t>(n), *crc_want = c.take<uint32_t>(n);
+	uint32_t *out_len = c.take<uint32_t>(n), *crc = c.take<uint32_t>(n);
+	int32_t *status = c.take<int32_t>(n);
 };
 
 } // namespace hd

@@ -75,6 +75,18 @@ class DeviceInflate:
         self.nmembers = min(summary.nmembers, self.max_members)
         return summary
 
+    def index_any(self, blob, first_offset=0, max_member_in=0):
+        """index() for members that may state no length (hipdeflate_index_members_any_dev): the walk starts at first_offset, a
+        member without a known length field is sized by decoding at most max_member_in of its bytes (0: no bound below the
+        library's) -> MemberAnySummary; the same tensors are filled, so run(blob, out, summary) and read_ranges work on them"""
+        summary = _pkg.MemberAnySummary()
+        rc = _pkg.lib().hipdeflate_index_members_any_dev(
+            _ptr(blob), blob.numel(), first_offset, self.max_members, max_member_in, _ptr(self.in_off), _ptr(self.in_len),
+            _ptr(self.out_size), _ptr(self.out_off), _ptr(self.crc_want), ctypes.byref(summary), _stream())
+        _pkg._check(rc, "hipdeflate_index_members_any_dev")
+        self.nmembers = min(summary.nmembers, self.max_members)
+        return summary
+
     def verify(self, nmembers):
         """-> index of the first member whose inflate result disagrees with its trailer, nmembers if none"""
         first_bad = ctypes.c_uint64()
@@ -89,7 +101,8 @@ class DeviceInflate:
         `summary`: what index(blob) has just answered for these tables, to spare the second pass over the blob"""
         s = summary if summary is not None else self.index(blob)
         if s.status:
-            why = {1: "not a member", 2: "member cut off", 3: "more members than max_members = %d" % self.max_members}
+            why = {1: "not a member", 2: "member cut off", 3: "more members than max_members = %d" % self.max_members,
+                   4: "member longer than max_member_in"}
             raise _pkg.HipDeflateError("member index: %s at offset %d (%d members)" % (why[s.status], s.end_offset, s.nmembers))
         if out.numel() < s.out_bytes:
             raise _pkg.HipDeflateError("output of %d bytes, the members hold %d" % (out.numel(), s.out_bytes))
@@ -153,6 +166,49 @@ def inflate_container(blob):
     out = torch.empty(s.out_bytes, dtype=torch.uint8, device=blob.device)
     d.run(blob, out, s)
     return out
+
+
+def _index_any_sized(blob, first_offset, max_member_in):
+    """the sizing call, then the index on tables of that size -> (DeviceInflate, MemberAnySummary)"""
+    n = DeviceInflate(0, blob.device).index_any(blob, first_offset, max_member_in).nmembers
+    d = DeviceInflate(n, blob.device)
+    return d, d.index_any(blob, first_offset, max_member_in)
+
+
+def inflate_gzip_members(blob, max_member_in=0):
+    """uint8 tensor, 16-byte aligned, holding a file of gzip members with or without a length field (`cat a.gz b.gz`, the
+    records of a .warc.gz) -> uint8 tensor of its contents: the sizing call, the index, one allocation, the batch inflate
+    and the verify, like inflate_container.  A member longer than max_member_in (0: HD_INFLATE_MAX_IN - 1) raises."""
+    d, s = _index_any_sized(blob, 0, max_member_in)
+    out = torch.empty(s.out_bytes, dtype=torch.uint8, device=blob.device)
+    d.run(blob, out, s)
+    return out
+
+
+def inflate_gzip_file(blob, max_member_in=0):
+    """inflate_gzip_members for any .gz at all: where the index stops at a member longer than max_member_in (status 4), that
+    one member is decoded as a plain stream in parallel rows (inflate_stream_blocks, on a 16-byte aligned copy of the blob
+    from the member on) and the index resumes behind it -> uint8 tensor of the file's contents"""
+    parts, at, n = [], 0, blob.numel()
+    while at < n:
+        d, s = _index_any_sized(blob, at, max_member_in)
+        if s.status not in (0, 4):
+            why = {1: "not a member", 2: "member cut off"}
+            raise _pkg.HipDeflateError("member index: %s at offset %d (%d members)" % (why.get(s.status, "?"), s.end_offset, s.nmembers))
+        if s.nmembers:
+            out = torch.empty(s.out_bytes, dtype=torch.uint8, device=blob.device)
+            s4, s.status = s.status, 0
+            d.run(blob, out, s)
+            s.status = s4
+            parts.append(out)
+        at = s.end_offset
+        if s.status == 4:
+            tail = torch.empty(n - at + 16, dtype=torch.uint8, device=blob.device)[:n - at]       # (a fresh allocation: aligned)
+            tail.copy_(blob[at:])
+            out, x = inflate_stream_blocks(tail, _pkg.FRAME_GZIP)
+            parts.append(out)
+            at += x.end_offset
+    return torch.cat(parts) if parts else torch.empty(0, dtype=torch.uint8, device=blob.device)
 
 
 def read_ranges(blob, begins, ends, kind=_pkg.RANGE_BYTES):

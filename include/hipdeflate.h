@@ -238,7 +238,8 @@ int hipdeflate_batch_inflate_flush_dev(const void *in, const void *in_off,
  *   the stream may use at most in_len[i] - header - trailer bytes, and the trailer is read at the byte it really ended on.
  * out_len[i] = bytes produced; check[i] (may be NULL) = the CRC-32 (RAW, GZIP) or Adler-32 (ZLIB) of the output;
  * in_used[i] (may be NULL) = header + stream rounded up to a whole byte + trailer, the reference's actual_in_nbytes: added
- * to in_off[i] it is where a member behind this one starts (the walk over concatenated members stays with the caller).
+ * to in_off[i] it is where a member behind this one starts (the walk over concatenated members stays with the caller here;
+ * hipdeflate_index_members_any_dev below does it on the device).
  * All three are 0 for a member that fails.  No byte at or behind in_off[i] + in_len[i] is read, whatever a header
  * claims; no byte of out outside [out_off[i], out_off[i] + out_len[i]) is written, beyond what
  * hipdeflate_batch_inflate_dev writes: the decoded prefix of a member that fails, inside its room.  A member of
@@ -331,6 +332,66 @@ int hipdeflate_index_members_dev(const void *blob, uint64_t nbytes, uint32_t max
 int hipdeflate_verify_members_dev(const void *status, const void *out_len, const void *crc32,
 				  const void *out_size, const void *crc_want, uint32_t nmembers,
 				  uint64_t *first_bad /* HOST: index, or nmembers if none */, void *stream);
+
+/* ---- ... and members that state NO length: `cat a.gz b.gz`, the records of a .warc.gz, `gzip >> log.gz` ----------------
+ * Role: the loop a serial reader runs over such a file -- inflate one member to learn where it ends, read the trailer, start
+ * again behind it (the reader of applet/7gzip.c, called once per member) -- whose every step waits for the one before.
+ * hipdeflate_index_members_any_dev makes the same five tables, with the same meaning, as hipdeflate_index_members_dev, for a
+ * file whose members may or may not carry a length field; in_off is absolute in blob, out_off starts at 0.  Everything
+ * behind it -- hipdeflate_batch_inflate_dev, hipdeflate_verify_members_dev, hipdeflate_read_ranges_dev -- takes the table
+ * unchanged.
+ *   The walk starts at first_offset (any byte position; first_offset == nbytes: no members, status 0; beyond: HD_E_ARG).  The
+ * CANDIDATES are all positions p >= first_offset with 1f 8b 08 and FLG & 0xe0 == 0 whose four bytes lie in front of nbytes.
+ * The member at a candidate is read from its window [p, min(nbytes, p + cap)) by one of two rules:
+ *   rule A  FEXTRA is set and the extra field is one of the five kinds above, by XLEN and tag: the member is what
+ *           hipdeflate_index_members_dev makes of it -- its length is the field's, nothing is decoded, cap is unbounded, and
+ *           a field whose length is below header + trailer is BAD (it does not fall through to rule B);
+ *   rule B  everything else -- no FEXTRA, or an extra field of any other shape: the header by the rules of
+ *           hipdeflate_batch_inflate_framed_dev's HD_FRAME_GZIP (FEXTRA / FNAME / FCOMMENT / FHCRC skipped), the DEFLATE
+ *           stream decoded WITHOUT OUTPUT to the end of its final block (a flush point is no stop), the eight trailer bytes
+ *           behind the byte the stream ended on, ISIZE equal to the decoded length; cap = max_member_in (0 means
+ *           HD_INFLATE_MAX_IN - 1, which is also the most; more: HD_E_ARG).  out_size = the decoded length, crc_want = the
+ *           trailer's CRC-32, which is not examined here: hipdeflate_verify_members_dev does that, as for every member.
+ *           A member of 2^32 decoded bytes or more is no member (BAD).
+ * A candidate is read in stream order -- header fields, stream, trailer -- and the first event decides: a byte that rules a
+ * member out is BAD; a needed byte at or behind the window's end is CUT where the window ends at nbytes and TOO LONG where
+ * max_member_in ended it.  Only the chain from first_offset decides: a magic inside a stored payload or inside another
+ * member is a candidate that nothing links to.  *summary (host memory): */
+typedef struct hipdeflate_member_any_summary {
+	uint64_t nmembers;     /* members in the table (status 3: members the chain has) */
+	uint64_t out_bytes;    /* sum of out_size over the table */
+	uint64_t end_offset;   /* where the walk stopped; == nbytes when status is 0 */
+	uint64_t ncandidates;  /* positions at or behind first_offset that can start a member */
+	uint64_t nsized;       /* of those, the ones that state no known length (rule B) */
+	uint32_t status;       /* 0 | 1 not a member at end_offset | 2 member at end_offset cut off | 3 table too small
+	                          | 4 the member at end_offset is longer than max_member_in */
+} hipdeflate_member_any_summary;
+/* status is that of the position the walk stopped at: 1 for BAD and for a position that is no candidate; 2 for CUT, and for
+ * fewer than four bytes left whose magic fits as far as it goes; 4 for TOO LONG.  With status 1, 2 or 4 the members in
+ * front of end_offset are in the table and usable -- a caller may decode the long member another way (the block index) and
+ * resume behind it with first_offset.  Status 3 and the sizing call (max_members == 0, NULL tables) are those of
+ * hipdeflate_index_members_dev.  On every blob for which that call answers status 0, this one with first_offset 0 writes
+ * the same five tables and the same nmembers, out_bytes and end_offset.
+ *   `blob` must be 16-byte aligned; no byte at or behind blob + nbytes is read, nothing behind nmembers entries is written.
+ * Stated costs.  Every rule-B candidate is decoded once, one wavefront each, whether the chain reaches it or not: nsized
+ * decodes of at most max_member_in bytes.  A true member costs about the size pass of its stream (about half an inflate);
+ * a decoy -- chance makes one per 2^27 bytes, a file that embeds .gz files has theirs -- costs one bounded decode, and most
+ * end inside their first block header; a blob of adversarial magics costs nsized * max_member_in at the worst, so a caller
+ * that does not trust its input passes a bound.  A file of BGZF / MiGz members has nsized == 0 and costs the old call plus
+ * one compaction.  Scratch: 48 bytes per candidate, the library's, grow-only.  Returns 0 whenever the index ran.
+ * (Synchronises the stream; takes turns as the other indexes do.) */
+int hipdeflate_index_members_any_dev(const void *blob, uint64_t nbytes, uint64_t first_offset,
+				     uint32_t max_members, uint32_t max_member_in,
+				     void *in_off, void *in_len, void *out_size, void *out_off, void *crc_want,
+				     hipdeflate_member_any_summary *summary /* HOST */, void *stream);
+/* host-buffer form -- the `gzip -dc` of a multi-member file, and the reader of applet/7gzip.c for such files: stages source,
+ * runs the index above (twice: the sizing call, then on a table of that size), hipdeflate_batch_inflate_dev and
+ * hipdeflate_verify_members_dev.  *destLen: in = room, out = bytes; *in_used (may be NULL) = end_offset.  Returns 0; 1 for
+ * index status 1 / 2 / 4 or a member whose inflate or trailer disagrees; 3 when the room is too small, with *destLen = the
+ * need; HD_E_*.  A member of HD_INFLATE_MAX_IN bytes or more is status 4 here: such a file is hip_inflate_stream_blocks'. */
+int hip_inflate_members(unsigned char *dest, size_t *destLen,
+			const unsigned char *source, size_t sourceLen,
+			size_t *in_used);
 
 /* Ranged reads on that table -- what a BGZF index is for (`bgzip -b OFFSET -s SIZE`, the chunks of a .bai / .tbi lookup):
  * nqueries ranges [q_begin[q], q_end[q]) of the decoded file are delivered, and only the members they touch are inflated,
@@ -496,7 +557,7 @@ typedef struct hipdeflate_stream_index_summary {
  * one piece's input; 0 means HD_INFLATE_MAX_IN - 1, which is also the most (more: HD_E_ARG).
  *   status 0  the chain's last row ended in a final block, and the trailer's bytes lie behind it.  Bytes behind the trailer
  *             are allowed and are not looked at: end_offset says where a following member would start, and the walk over
- *             concatenated members is the caller's.  The trailer's contents are not examined (the decode below does that).
+ *             concatenated members is the caller's (or hipdeflate_index_members_any_dev's).  The trailer's contents are not examined (the decode below does that).
  *   status 1  the piece that starts at end_offset does not decode: bad data, a distance past the bytes the piece has put out,
  *             2^32 bytes of output, or more than max_chunk_in bytes of input with payload left behind them; or the header is
  *             refused (end_offset 0, hdr_bytes 0, ncandidates 0).
