@@ -113,6 +113,8 @@ EXPORTS = [
     "hipdeflate_stream_index_carry_dev", "hipdeflate_stream_inflate_carry_dev", "hip_inflate_stream_carry",
     "hipdeflate_test_carry_group", "hipdeflate_test_carry_times",
     "hipdeflate_stream_deflate_carry_dev", "hip_deflate_stream_carry",
+    "hipdeflate_batch_deflate_dict_dev", "hipdeflate_batch_inflate_dict_dev", "hipdeflate_batch_deflate_dict",
+    "hipdeflate_batch_inflate_dict", "hipdeflate_test_dict_replay",
     "hipdeflate_stream_index_blocks_dev", "hipdeflate_stream_inflate_blocks_dev", "hip_inflate_stream_blocks",
     "hipdeflate_test_block_headers_dev", "hipdeflate_test_blocks_times", "hipdeflate_test_blocks_counts",
     "hipdeflate_test_block_candidates_dev",
@@ -197,6 +199,17 @@ def lib():
                                                       _vp, _vp]
     L.hipdeflate_batch_inflate_size.argtypes = [_vp, _vp, _vp, ctypes.c_uint32, ctypes.c_int, _vp, _vp, _vp]
     L.hipdeflate_batch_inflate_framed.argtypes = [_vp, _vp, _vp, ctypes.c_uint32, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
+    # the preset-dictionary forms: the plain calls' arguments with (dict, dict_len) behind level / frame, and no frame on the encode side
+    L.hipdeflate_batch_deflate_dict_dev.argtypes = [_vp, _vp, _vp, ctypes.c_uint32, ctypes.c_int, _vp, ctypes.c_uint32, _vp,
+                                                    ctypes.c_uint64, ctypes.c_uint32, _vp, _vp, _vp, _vp]
+    L.hipdeflate_batch_inflate_dict_dev.argtypes = [_vp, _vp, _vp, ctypes.c_uint32, ctypes.c_int, _vp, ctypes.c_uint32, _vp, _vp, _vp,
+                                                    _vp, _vp, _vp, _vp, _vp]
+    L.hipdeflate_batch_deflate_dict.argtypes = [_vp, _vp, _vp, ctypes.c_uint32, ctypes.c_int, _vp, ctypes.c_uint32, _vp,
+                                                ctypes.c_uint64, ctypes.c_uint32, _vp, _vp, _vp]
+    L.hipdeflate_batch_inflate_dict.argtypes = [_vp, _vp, _vp, ctypes.c_uint32, ctypes.c_int, _vp, ctypes.c_uint32, _vp, _vp, _vp, _vp,
+                                                _vp, _vp, _vp]
+    L.hipdeflate_test_dict_replay.argtypes = [ctypes.c_int]
+    L.hipdeflate_test_dict_replay.restype = None
     L.hipdeflate_scan_sizes_dev.argtypes = [_vp, ctypes.c_uint32, ctypes.c_uint64, _vp, _vp, _vp]
     L.hipdeflate_compact_dev.argtypes = [_vp, ctypes.c_uint64, _vp, _vp, ctypes.c_uint32, _vp, _vp]
     L.hipdeflate_compact_span_dev.argtypes = [_vp, ctypes.c_uint64, _vp, _vp, ctypes.c_uint32, _vp, ctypes.c_uint64, _vp]
@@ -501,6 +514,27 @@ def batch_deflate(data, offs, lens, level=1, frame=FRAME_RAW, slot=None):
     return members, crc, st
 
 
+def batch_deflate_dict(data, offs, lens, dictionary, level=6, slot=None):
+    """batch_deflate with a preset dictionary shared by every block (hipdeflate_batch_deflate_dict): raw members for
+    zlib.decompressobj(-15, zdict=dictionary).  -> (members list, crc32 array, status array)."""
+    src = as_u8(data)
+    offs = _np(offs, np.uint64)
+    lens = _np(lens, np.uint32)
+    d = as_u8(dictionary)
+    nb = len(offs)
+    if slot is None:
+        mx = int(lens.max()) if nb else 0
+        slot = int(lib().hipdeflate_bound(mx, level))
+    out = np.zeros(max(nb * slot, 1), dtype=np.uint8)
+    olen = np.zeros(nb, dtype=np.uint32)
+    crc = np.zeros(nb, dtype=np.uint32)
+    st = np.zeros(nb, dtype=np.int32)
+    _check(lib().hipdeflate_batch_deflate_dict(_p(src), _p(offs), _p(lens), nb, level, _p(d) if len(d) else None, len(d), _p(out),
+                                               slot, slot, _p(olen), _p(crc), _p(st)), "hipdeflate_batch_deflate_dict")
+    members = [bytes(out[i * slot: i * slot + int(olen[i])]) for i in range(nb)]
+    return members, crc, st
+
+
 def batch_inflate(streams, caps, want_crc=True, flushed=False):
     """Inflate a list of raw-DEFLATE streams.  -> (outputs list, crc32 array, status array).
     flushed: the streams are full-flushed chunks (hipdeflate_batch_inflate_flush)."""
@@ -563,6 +597,28 @@ def batch_inflate_framed(streams, caps, frame=FRAME_ZLIB):
     st = np.zeros(nb, dtype=np.int32)
     _check(lib().hipdeflate_batch_inflate_framed(_p(src), _p(ioff), _p(ilen), nb, frame, _p(out), _p(ooff), _p(caps), _p(olen),
                                                  _p(chk), _p(used), _p(st)), "hipdeflate_batch_inflate_framed")
+    outs = [bytes(out[int(ooff[i]): int(ooff[i]) + int(olen[i])]) if st[i] == 0 else b"" for i in range(nb)]
+    return outs, chk, used, st
+
+
+def batch_inflate_dict(streams, caps, dictionary, frame=FRAME_RAW):
+    """batch_inflate_framed for raw or zlib members written with a preset dictionary (hipdeflate_batch_inflate_dict).
+    -> (outputs list, check array, in_used array, status array)."""
+    src, ioff, ilen = _pack_streams(streams)
+    d = as_u8(dictionary)
+    nb = len(streams)
+    caps = _np(caps, np.uint32)
+    ooff = np.zeros(nb, dtype=np.uint64)
+    if nb:
+        ooff[1:] = np.cumsum(caps[:-1].astype(np.uint64))
+    out = np.zeros(max(int(caps.astype(np.uint64).sum()), 1), dtype=np.uint8)
+    olen = np.zeros(nb, dtype=np.uint32)
+    chk = np.zeros(nb, dtype=np.uint32)
+    used = np.zeros(nb, dtype=np.uint32)
+    st = np.zeros(nb, dtype=np.int32)
+    _check(lib().hipdeflate_batch_inflate_dict(_p(src), _p(ioff), _p(ilen), nb, frame, _p(d) if len(d) else None, len(d), _p(out),
+                                               _p(ooff), _p(caps), _p(olen), _p(chk), _p(used), _p(st)),
+           "hipdeflate_batch_inflate_dict")
     outs = [bytes(out[int(ooff[i]): int(ooff[i]) + int(olen[i])]) if st[i] == 0 else b"" for i in range(nb)]
     return outs, chk, used, st
 

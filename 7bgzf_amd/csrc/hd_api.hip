@@ -171,12 +171,13 @@ struct Ctx {
 	uint32_t *d_stalls = nullptr;    // blocks the workgroup parse gave up on (hipdeflate_stall_count)
 	// host-pointer API pools (guarded by mu)
 	std::mutex mu;
-	Buf d_in, d_meta, d_slots, d_packed, d_scratch;
+	Buf d_in, d_meta, d_slots, d_packed, d_scratch, d_dict;
 	Buf h_in{ nullptr, 0, true }, h_meta{ nullptr, 0, true }, h_out{ nullptr, 0, true };
 	// device-pointer API scratch (token slabs for the dynamic levels), guarded by mu_dev
 	std::mutex mu_dev;
 	SharedScratch tok, tiles;        // token slabs and segment slots of a launch / the tile sums of a scan
 	SharedScratch frame;             // the payload table of a framed inflate or size pass (hd_frame.hpp)
+	SharedScratch dict;              // a dictionary call's staged history and what is made of it once per call (DictScratch below)
 	hd::WgBeside beside;             // the workgroup levels' emit kernel beside their parse (hd_deflate_wg.hpp), with tok
 	// the last encode launch and the grid of the last gather (hipdeflate_test_compact_grid), behind a mutex of their own:
 	// level 1 launches without mu_dev
@@ -189,6 +190,7 @@ struct Ctx {
 		tok.drained(st);
 		tiles.drained(st);
 		frame.drained(st);
+		dict.drained(st);
 	}
 	// member index scratch (hd_index.hpp): the bitmap and tile counts of the blob, the candidate list and its successor
 	// tables.  An index call waits for its stream before it returns, so calls take turns by holding mu_index.
@@ -709,7 +711,7 @@ void hipdeflate_shutdown(void)
 			continue;
 		(void)hipSetDevice(g.device);
 		(void)hipDeviceSynchronize();                        // launches on callers' streams may still use our scratch
-		for (Buf *b : { &g.d_in, &g.d_meta, &g.d_slots, &g.d_packed, &g.d_scratch, &g.h_in, &g.h_meta, &g.h_out, &g.d_index,
+		for (Buf *b : { &g.d_in, &g.d_meta, &g.d_slots, &g.d_packed, &g.d_scratch, &g.d_dict, &g.h_in, &g.h_meta, &g.h_out, &g.d_index,
 				&g.d_cand, &g.d_range, &g.d_range_out, &g.d_stream, &g.d_stream_slots, &g.d_blocks })
 			b->release();
 		(void)hipFree(g.d_ct);
@@ -719,6 +721,7 @@ void hipdeflate_shutdown(void)
 		g.tok.reset();
 		g.tiles.reset();
 		g.frame.reset();
+		g.dict.reset();
 		g.enc.reset();
 		g.beside.release();
 		g.d_ct = nullptr;
@@ -884,9 +887,30 @@ static hd::DeflateArgs deflate_args(const Ctx &g, const void *in, const uint64_t
 	return a;
 }
 
+// A dictionary call's library scratch (Ctx::dict): [ the history: the used tail of an encode call's dictionary from byte 0, or the
+// last bytes of a decode call's dictionary ENDING at byte HD_WG_WINDOW | the table an encode call's history leaves
+// (k_dict_table) | a decode call's words: the dictionary's Adler-32, and the one-row table the Adler kernel reads it by ]
+struct DictScratch {
+	uint8_t *p;
+	static constexpr size_t TABLE = HD_WG_WINDOW, WORDS = TABLE + hd::WG_DICT_TABLE_BYTES, BYTES = WORDS + 64;
+	uint8_t *history() const { return p; }
+	uint8_t *history_end() const { return p + HD_WG_WINDOW; }
+	uint32_t *table() const { return (uint32_t *)(p + TABLE); }
+	uint64_t *one_off() const { return (uint64_t *)(p + WORDS); }
+	uint32_t *one_len() const { return (uint32_t *)(p + WORDS + 8); }
+	uint32_t *adler() const { return (uint32_t *)(p + WORDS + 12); }
+};
+// the bytes of a dictionary an encode call uses: its last 32 KiB at most, in whole pieces of the parse
+static inline uint32_t dict_used_bytes(uint32_t dict_len)
+{
+	return (dict_len < HD_WG_WINDOW ? dict_len : (uint32_t)HD_WG_WINDOW) & ~(uint32_t)(HD_WG_CUT - 1);
+}
+static bool g_test_dict_replay = false;                       // hipdeflate_test_dict_replay
+
 static int batch_deflate_dev_impl(const void *in, const void *in_off, const void *in_len, uint32_t nblocks, int level,
 				  int frame, void *out, uint64_t out_stride, uint32_t out_cap, void *out_len,
-				  void *crc32, void *status, void *stream, uint32_t max_in, uint32_t prime_max = 0)
+				  void *crc32, void *status, void *stream, uint32_t max_in, uint32_t prime_max = 0,
+				  const void *dict = nullptr, uint32_t dict_len = 0)
 {
 	Ctx &g = cur();
 	int r = ensure();
@@ -922,9 +946,28 @@ static int batch_deflate_dev_impl(const void *in, const void *in_off, const void
 		beside_fits = false;
 	}
 	a.scratch = (uint8_t *)g.tok.buf.p;
+	// a preset dictionary (hipdeflate_batch_deflate_dict_dev): its used tail into aligned scratch and, unless a test asks for the
+	// replay everywhere, the table it leaves -- once per call, in front of the parse.  (Its scratch grows before either is entered.)
+	const uint32_t dict_used = dict_used_bytes(dict_len);
+	const bool with_dict = dict_used && level >= HD_WG_LEVEL && !a.lat;
+	if (with_dict && g.dict.buf.grow_keep_old(DictScratch::BYTES))
+		return HD_E_NOMEM;
 	if ((r = g.tok.enter(st)))
 		return r;
-	if (level >= HD_WG_LEVEL && !a.lat && beside_fits && beside_allowed() && g.beside.init() == 0) {
+	hd::WgDict wd;
+	if (with_dict) {
+		if ((r = g.dict.enter(st)))
+			return r;
+		const DictScratch ds{ (uint8_t *)g.dict.buf.p };
+		HD_CHECK(hipMemcpyAsync(ds.history(), (const uint8_t *)dict + (dict_len - dict_used), dict_used, hipMemcpyDeviceToDevice, st));
+		wd.hist = ds.history();
+		wd.used = dict_used;
+		if (!g_test_dict_replay) {
+			wd.table = ds.table();
+			hd::launch_dict_table(a, level, wd, st);
+		}
+	}
+	if (level >= HD_WG_LEVEL && !a.lat && !with_dict && beside_fits && beside_allowed() && g.beside.init() == 0) {
 		a.beside = &g.beside;
 		// (emit wavefronts a CU keeps: three -- but two beside the four-way parse of BGZF-sized blocks, where the third costs the parse
 		// more than it takes off the launch's end: encode_l6 123.8 -> 125.8 GB/s, 1 MiB members the other way, 131.1 -> 128.5;
@@ -932,8 +975,17 @@ static int batch_deflate_dev_impl(const void *in, const void *in_off, const void
 		const uint32_t keep = (HD_WG_WAYS(level) == 4 && a.split_max <= 65536) ? 2u : 3u;
 		a.beside_keep = g_test_beside_keep < keep ? g_test_beside_keep : keep;
 	}
-	if ((r = launch_deflate(a, level, st)))
+	if (with_dict) {
+		// (a workgroup level's raw members: launch_deflate's work is the workgroup launch alone)
+		if (nblocks) {
+			hd::launch_wg(a, level, st, &wd);
+			HD_CHECK(hipGetLastError());
+		}
+		if ((r = g.dict.leave(st)))
+			return r;
+	} else if ((r = launch_deflate(a, level, st))) {
 		return r;
+	}
 	note_encode(g, st, out, level, nblocks);
 	return g.tok.leave(st);
 }
@@ -945,6 +997,21 @@ int hipdeflate_batch_deflate_dev(const void *in, const void *in_off, const void 
 	return batch_deflate_dev_impl(in, in_off, in_len, nblocks, level, frame, out, out_stride, out_cap, out_len, crc32, status,
 				      stream, 0);
 }
+
+int hipdeflate_batch_deflate_dict_dev(const void *in, const void *in_off, const void *in_len, uint32_t nblocks, int level,
+				      const void *dict, uint32_t dict_len, void *out, uint64_t out_stride, uint32_t out_cap,
+				      void *out_len, void *crc32, void *status, void *stream)
+{
+	if (!dict && dict_len) {
+		const int r = ensure();
+		return r ? r : HD_E_ARG;
+	}
+	// (levels 0..2, a dictionary below one piece: batch_deflate_dev_impl leaves the dictionary alone -- the plain call's bytes)
+	return batch_deflate_dev_impl(in, in_off, in_len, nblocks, level, HD_FRAME_RAW, out, out_stride, out_cap, out_len, crc32, status,
+				      stream, 0, 0, dict, dict_len);
+}
+
+void hipdeflate_test_dict_replay(int on) { g_test_dict_replay = on != 0; }
 
 // the decode launch over a table (one layout on every side: hd_tables.hpp)
 static hd::InflateArgs inflate_args(const Ctx &g, const void *in, const hd::DecTable &t, uint32_t nblocks, void *out, bool want_crc,
@@ -1083,6 +1150,86 @@ int hipdeflate_batch_inflate_framed_dev(const void *in, const void *in_off, cons
 			   (const uint32_t *)t.chk, nblocks, frame, (uint32_t *)out_len, (uint32_t *)check, (uint32_t *)in_used,
 			   (int32_t *)status);
 	HD_CHECK(hipGetLastError());
+	return g.frame.leave(st);
+}
+
+int hipdeflate_batch_inflate_dict_dev(const void *in, const void *in_off, const void *in_len, uint32_t nblocks, int frame,
+				      const void *dict, uint32_t dict_len, void *out, const void *out_off, const void *out_cap,
+				      void *out_len, void *check, void *in_used, void *status, void *stream)
+{
+	Ctx &g = cur();
+	int r = ensure();
+	if (r)
+		return r;
+	if ((frame != HD_FRAME_RAW && frame != HD_FRAME_ZLIB) || !out_len || !status || (!dict && dict_len))
+		return HD_E_ARG;
+	if (nblocks == 0)
+		return 0;
+	// (raw members and no dictionary: the framed call's launch as it is -- no scratch, no turn to take)
+	if (frame == HD_FRAME_RAW && dict_len == 0)
+		return hipdeflate_batch_inflate_framed_dev(in, in_off, in_len, nblocks, frame, out, out_off, out_cap, out_len, check, in_used,
+							   status, stream);
+	hipStream_t st = (hipStream_t)stream;
+	std::lock_guard<std::mutex> lk(g.mu_dev);
+	// the payload table, and behind it one more column: the members that do not name the dictionary
+	const size_t table_bytes = (FrameTable::bytes(nblocks) + 15) & ~(size_t)15;
+	if (g.frame.buf.grow_keep_old(table_bytes + 4 * (size_t)nblocks) || g.dict.buf.grow_keep_old(DictScratch::BYTES))
+		return HD_E_NOMEM;
+	const FrameTable t(g.frame.buf.p, nblocks);
+	uint32_t *const plain = (uint32_t *)((uint8_t *)g.frame.buf.p + table_bytes);
+	const DictScratch ds{ (uint8_t *)g.dict.buf.p };
+	if ((r = g.frame.enter(st)) || (r = g.dict.enter(st)))
+		return r;
+	// the window a member starts with: the dictionary's last 32 KiB at most, ending where the kernel's loads are aligned
+	const uint32_t D = dict_len < HD_WG_WINDOW ? dict_len : (uint32_t)HD_WG_WINDOW;
+	if (D)
+		HD_CHECK(hipMemcpyAsync(ds.history_end() - D, (const uint8_t *)dict + (dict_len - D), D, hipMemcpyDeviceToDevice, st));
+	hd::InflateDictArgs a{};
+	a.in = (const uint8_t *)in;
+	a.in_off = (const uint64_t *)in_off;
+	a.in_len = (const uint32_t *)in_len;
+	a.nblocks = nblocks;
+	a.out = (uint8_t *)out;
+	a.out_off = (const uint64_t *)out_off;
+	a.out_cap = (const uint32_t *)out_cap;
+	a.out_len = (uint32_t *)out_len;
+	a.crc = (uint32_t *)check;
+	a.status = (int32_t *)status;
+	a.ct = g.d_ct;
+	a.used = in_used ? (uint32_t *)in_used : t.used;
+	a.dict_end = ds.history_end();
+	a.dict_len = D;
+	a.plain = nullptr;
+	if (frame == HD_FRAME_RAW) {                                  // no header, no trailer: the inflate's answer is the member's
+		hipLaunchKernelGGL(hd::k_dict_inflate, dim3(nblocks), dim3(64), 0, st, a);
+	} else {
+		// DICTID is the Adler-32 of the WHOLE dictionary as given: one more chunk for the Adler kernel, read where the caller has it
+		if (dict_len) {
+			HD_CHECK(hipMemsetAsync(ds.one_off(), 0, 8, st));
+			HD_CHECK(hipMemsetD32Async((hipDeviceptr_t)ds.one_len(), (int)dict_len, 1, st));
+			hipLaunchKernelGGL(hd::k_chunk_adler, dim3(1), dim3(64), 0, st, (const uint8_t *)dict, (const uint64_t *)ds.one_off(),
+					   (const uint32_t *)ds.one_len(), (const uint32_t *)nullptr, 1u, ds.adler());
+		}
+		hipLaunchKernelGGL(hd::k_dict_open, dim3((nblocks + 255) / 256), dim3(256), 0, st, (const uint8_t *)in, (const uint64_t *)in_off,
+				   (const uint32_t *)in_len, nblocks, (const uint32_t *)ds.adler(), dict_len ? 1u : 0u, t.p_off, t.p_len, t.verdict,
+				   plain);
+		a.in_off = t.p_off;
+		a.in_len = t.p_len;
+		a.crc = nullptr;
+		a.used = t.used;
+		a.plain = plain;
+		hipLaunchKernelGGL(hd::k_dict_inflate, dim3(nblocks), dim3(64), 0, st, a);
+		// (a member whose inflate failed has out_len 0: nothing is read)
+		hipLaunchKernelGGL(hd::k_chunk_adler, dim3(nblocks), dim3(64), 0, st, (const uint8_t *)out, (const uint64_t *)out_off,
+				   (const uint32_t *)out_len, (const uint32_t *)out_cap, nblocks, t.chk);
+		hipLaunchKernelGGL(hd::k_frame_close, dim3((nblocks + 255) / 256), dim3(256), 0, st, (const uint8_t *)in,
+				   (const uint64_t *)in_off, (const uint64_t *)t.p_off, (const int32_t *)t.verdict, (const uint32_t *)t.used,
+				   (const uint32_t *)t.chk, nblocks, frame, (uint32_t *)out_len, (uint32_t *)check, (uint32_t *)in_used,
+				   (int32_t *)status);
+	}
+	HD_CHECK(hipGetLastError());
+	if ((r = g.dict.leave(st)))
+		return r;
 	return g.frame.leave(st);
 }
 
@@ -2495,14 +2642,28 @@ int hipdeflate_stream_read_ranges_dev(const void *strm, uint64_t nbytes, int fra
 
 /* ---- host-pointer API ------------------------------------------------------ */
 
-int hipdeflate_batch_deflate(const uint8_t *in, const uint64_t *in_off, const uint32_t *in_len, uint32_t nblocks,
-			     int level, int frame, uint8_t *out, uint64_t out_stride, uint32_t out_cap,
-			     uint32_t *out_len, uint32_t *crc32, int32_t *status)
+// a host dictionary into device memory (Ctx::d_dict; the caller holds g.mu and has bound the device): what the device calls take
+static int stage_dict(Ctx &g, const uint8_t *dict, uint32_t dict_len)
+{
+	if (!dict_len)
+		return 0;
+	if (g.d_dict.reserve(dict_len))
+		return HD_E_NOMEM;
+	HD_CHECK(hipMemcpyAsync(g.d_dict.p, dict, dict_len, hipMemcpyHostToDevice, g.stream));
+	return 0;
+}
+
+// hipdeflate_batch_deflate, and with a dictionary hipdeflate_batch_deflate_dict (frame: HD_FRAME_RAW)
+static int batch_deflate_host(const uint8_t *in, const uint64_t *in_off, const uint32_t *in_len, uint32_t nblocks,
+			      int level, int frame, uint8_t *out, uint64_t out_stride, uint32_t out_cap,
+			      uint32_t *out_len, uint32_t *crc32, int32_t *status, const uint8_t *dict, uint32_t dict_len)
 {
 	Ctx &g = cur();
 	int r = ensure();
 	if (r)
 		return r;
+	if (!dict && dict_len)
+		return HD_E_ARG;
 	if (nblocks == 0)
 		return 0;
 	if (!in_off || !in_len || !out || !out_len || (frame & ~HD_FRAME_LATENCY) < HD_FRAME_RAW ||
@@ -2510,6 +2671,8 @@ int hipdeflate_batch_deflate(const uint8_t *in, const uint64_t *in_off, const ui
 		return HD_E_ARG;
 	std::lock_guard<std::mutex> lk(g.mu);
 	if ((r = bind_device(g)))
+		return r;
+	if ((r = stage_dict(g, dict, dict_len)))
 		return r;
 
 	// pack the blocks 16-byte aligned into pinned memory (one H2D, aligned fast path)
@@ -2541,7 +2704,7 @@ int hipdeflate_batch_deflate(const uint8_t *in, const uint64_t *in_off, const ui
 	HD_CHECK(table_copy(d, h, h.inputs(), hipMemcpyHostToDevice, g.stream));
 	r = batch_deflate_dev_impl(g.d_in.p, d.in_off(), d.in_len(), nblocks, level, frame, g.d_slots.p, slot,
 				   (uint32_t)(cap_user < slot ? cap_user : slot), d.out_len(), d.crc(), d.status(), g.stream,
-				   max_len ? (uint32_t)max_len : 1u);
+				   max_len ? (uint32_t)max_len : 1u, 0, dict_len ? g.d_dict.p : nullptr, dict_len);
 	if (r)
 		return r;
 	// gather on the device so that only the compressed bytes cross PCIe
@@ -2572,6 +2735,21 @@ int hipdeflate_batch_deflate(const uint8_t *in, const uint64_t *in_off, const ui
 		po += out_len[i];
 	}
 	return 0;
+}
+
+int hipdeflate_batch_deflate(const uint8_t *in, const uint64_t *in_off, const uint32_t *in_len, uint32_t nblocks,
+			     int level, int frame, uint8_t *out, uint64_t out_stride, uint32_t out_cap,
+			     uint32_t *out_len, uint32_t *crc32, int32_t *status)
+{
+	return batch_deflate_host(in, in_off, in_len, nblocks, level, frame, out, out_stride, out_cap, out_len, crc32, status, nullptr, 0);
+}
+
+int hipdeflate_batch_deflate_dict(const uint8_t *in, const uint64_t *in_off, const uint32_t *in_len, uint32_t nblocks,
+				  int level, const uint8_t *dict, uint32_t dict_len, uint8_t *out, uint64_t out_stride,
+				  uint32_t out_cap, uint32_t *out_len, uint32_t *crc32, int32_t *status)
+{
+	return batch_deflate_host(in, in_off, in_len, nblocks, level, HD_FRAME_RAW, out, out_stride, out_cap, out_len, crc32, status, dict,
+				  dict_len);
 }
 
 static int batch_inflate_host(const uint8_t *in, const uint64_t *in_off, const uint32_t *in_len, uint32_t nblocks,
@@ -2707,9 +2885,11 @@ int hipdeflate_batch_inflate_size(const uint8_t *in, const uint64_t *in_off, con
 	return 0;
 }
 
-int hipdeflate_batch_inflate_framed(const uint8_t *in, const uint64_t *in_off, const uint32_t *in_len, uint32_t nblocks, int frame,
-				    uint8_t *out, const uint64_t *out_off, const uint32_t *out_cap, uint32_t *out_len,
-				    uint32_t *check, uint32_t *in_used, int32_t *status)
+// hipdeflate_batch_inflate_framed, and with_dict hipdeflate_batch_inflate_dict
+static int batch_inflate_framed_host(const uint8_t *in, const uint64_t *in_off, const uint32_t *in_len, uint32_t nblocks, int frame,
+				     uint8_t *out, const uint64_t *out_off, const uint32_t *out_cap, uint32_t *out_len,
+				     uint32_t *check, uint32_t *in_used, int32_t *status, bool with_dict, const uint8_t *dict,
+				     uint32_t dict_len)
 {
 	Ctx &g = cur();
 	int r = ensure();
@@ -2717,12 +2897,16 @@ int hipdeflate_batch_inflate_framed(const uint8_t *in, const uint64_t *in_off, c
 		return r;
 	if (!member_frame_ok(frame) || !out_len || !status)
 		return HD_E_ARG;
+	if (with_dict && (frame == HD_FRAME_GZIP || (!dict && dict_len)))
+		return HD_E_ARG;
 	if (nblocks == 0)
 		return 0;
 	if (!in_off || !in_len || !out_off || !out_cap)
 		return HD_E_ARG;
 	std::lock_guard<std::mutex> lk(g.mu);
 	if ((r = bind_device()))
+		return r;
+	if (with_dict && (r = stage_dict(g, dict, dict_len)))
 		return r;
 	// the decode table, and in_used as one more column behind it
 	const size_t n = nblocks, meta_bytes = hd::DecTable::bytes(n) + 4 * n;
@@ -2744,8 +2928,12 @@ int hipdeflate_batch_inflate_framed(const uint8_t *in, const uint64_t *in_off, c
 		oo += up16(out_cap[i]);
 	}
 	HD_CHECK(table_copy(d, h, h.inputs(), hipMemcpyHostToDevice, g.stream));
-	if ((r = hipdeflate_batch_inflate_framed_dev(g.d_in.p, d.in_off(), d.in_len(), nblocks, frame, g.d_slots.p, d.out_off(), d.out_cap(),
-						     d.out_len(), d.crc(), d_used, d.status(), g.stream)))
+	r = with_dict ? hipdeflate_batch_inflate_dict_dev(g.d_in.p, d.in_off(), d.in_len(), nblocks, frame, dict_len ? g.d_dict.p : nullptr,
+							  dict_len, g.d_slots.p, d.out_off(), d.out_cap(), d.out_len(), d.crc(), d_used,
+							  d.status(), g.stream)
+		      : hipdeflate_batch_inflate_framed_dev(g.d_in.p, d.in_off(), d.in_len(), nblocks, frame, g.d_slots.p, d.out_off(),
+							    d.out_cap(), d.out_len(), d.crc(), d_used, d.status(), g.stream);
+	if (r)
 		return r;
 	HD_CHECK(table_copy(h, d, h.results_crc(), hipMemcpyDeviceToHost, g.stream));
 	HD_CHECK(hipMemcpyAsync(h_used, d_used, 4 * n, hipMemcpyDeviceToHost, g.stream));
@@ -2763,6 +2951,22 @@ int hipdeflate_batch_inflate_framed(const uint8_t *in, const uint64_t *in_off, c
 			memcpy(out + out_off[i], (const uint8_t *)g.h_out.p + h.out_off()[i], out_len[i]);
 	}
 	return 0;
+}
+
+int hipdeflate_batch_inflate_framed(const uint8_t *in, const uint64_t *in_off, const uint32_t *in_len, uint32_t nblocks, int frame,
+				    uint8_t *out, const uint64_t *out_off, const uint32_t *out_cap, uint32_t *out_len,
+				    uint32_t *check, uint32_t *in_used, int32_t *status)
+{
+	return batch_inflate_framed_host(in, in_off, in_len, nblocks, frame, out, out_off, out_cap, out_len, check, in_used, status, false,
+					 nullptr, 0);
+}
+
+int hipdeflate_batch_inflate_dict(const uint8_t *in, const uint64_t *in_off, const uint32_t *in_len, uint32_t nblocks, int frame,
+				  const uint8_t *dict, uint32_t dict_len, uint8_t *out, const uint64_t *out_off, const uint32_t *out_cap,
+				  uint32_t *out_len, uint32_t *check, uint32_t *in_used, int32_t *status)
+{
+	return batch_inflate_framed_host(in, in_off, in_len, nblocks, frame, out, out_off, out_cap, out_len, check, in_used, status, true,
+					 dict, dict_len);
 }
 
 /* ---- streaming encoder and decoder (SlotRing above) -------------------------------- */

@@ -1535,7 +1535,8 @@ inline void launch_level2(const DeflateArgs &a, hipStream_t st)
 	hipLaunchKernelGGL((k_deflate_dynamic<W, H, 0, HD_INTRA_DIST>), dim3(dynamic_grid(a.nblocks)), dim3(64), 0, st, f);
 }
 
-void launch_wg(const DeflateArgs &a, int level, hipStream_t st);       // hd_deflate_wg.hpp
+struct WgDict;
+void launch_wg(const DeflateArgs &a, int level, hipStream_t st, const WgDict *dict = nullptr);       // hd_deflate_wg.hpp
 
 inline int launch_deflate_dynamic(const DeflateArgs &a, int level, hipStream_t st)
 {

@@ -109,6 +109,25 @@ __device__ __forceinline__ uint32_t wg_common_bits(uint32_t x0, uint32_t x1, uin
 
 typedef uint32_t wg_u32x16 __attribute__((ext_vector_type(16)));
 
+// one step's bucket outside a piece's turn (k_dict_wg, the history's last step): parse_wg's `bucket`, rule for rule
+template <int WAYS>
+__device__ __forceinline__ void wg_bucket(WG_LDS uint8_t *tab8, uint32_t h, uint32_t p, uint32_t &ox, uint32_t &oy)
+{
+	if (WAYS == 4) {
+		const unsigned long long o64 = *(WG_LDS const volatile unsigned long long *)(tab8 + h);   // ds_read_b64
+		ox = (uint32_t)o64;
+		oy = (uint32_t)(o64 >> 32);
+		*(wg_word_p)(tab8 + h) = (ox << 16) | (p & 0xffffu);
+		*(wg_word_p)(tab8 + h + 4) = __builtin_amdgcn_alignbit(oy, ox, 16);
+	} else if (WAYS == 2) {
+		ox = *(wg_word_p)(tab8 + h);
+		*(wg_word_p)(tab8 + h) = (ox << 16) | (p & 0xffffu);
+	} else {
+		ox = *(volatile WG_LDS uint16_t *)(tab8 + h);
+		*(volatile WG_LDS uint16_t *)(tab8 + h) = (uint16_t)p;
+	}
+}
+
 // the blocks of a latency launch, from wherever the caller has them (a latency context: pinned host memory) into device
 // memory, once, for the workgroups that share their parse: one workgroup per block, four 16-byte loads per thread in flight
 constexpr uint32_t WG_STAGE_STRIDE = 65536;
@@ -144,9 +163,28 @@ __device__ __forceinline__ uint64_t wg_uniform64(uint64_t v)
 // leaves the kernel is in the block's own coordinates: the tokens, the pieces' counts and the CRC-32, which are the block's alone --
 // the emit kernels see an ordinary block of in_len[b] bytes.  A template parameter, not a branch: the instantiations without it are
 // what they were, to the register.  (One workgroup per block: the shared parse of latency launches is not primed.)
+// PRIMED == WG_HIST_DICT: the history is the launch's PRESET DICTIONARY (hipdeflate_batch_deflate_dict_dev): the dh.used bytes at
+// dh.hist -- whole pieces, aligned library scratch -- in front of EVERY block, wherever the block lies: a piece below own0 is loaded
+// from there, a piece from own0 on from the block, each source with its own alignment flag.  Everything else is the primed form.
+// Every block of such a launch would replay the same pieces into the same table; where (history || block) fits the ring whole
+// and dh.table is given, the workgroup COPIES the table k_dict_table made of the history, turns the history's last step
+// itself -- the keys of its last positions reach into the block -- and starts at piece own0.  The same table, the same tokens.
+// PRIMED == WG_HIST_TABLE: that kernel's body: one workgroup replays the history's pieces but their last step and writes the
+// table out; no block, no tokens, no records.
+constexpr int WG_HIST_FRONT = 1, WG_HIST_DICT = 2, WG_HIST_TABLE = 3;
+constexpr uint32_t WG_DICT_TABLE_WORDS = WG_TABLE_BYTES / 4 + 2;       // the table and its spare bucket; word [WG_DICT_TABLE_WORDS]: the build gave up
+constexpr uint32_t WG_DICT_TABLE_BYTES = (WG_DICT_TABLE_WORDS + 1 + 3) / 4 * 16;
+// a dictionary launch's history: an argument of the dictionary kernels alone (DeflateArgs is every encode kernel's, and stays)
+struct WgDict {
+	const uint8_t *hist = nullptr;   // `used` bytes, 16-byte aligned
+	uint32_t used = 0;               // whole pieces, at most HD_WG_WINDOW
+	uint32_t *table = nullptr;       // k_dict_table's output, k_dict_wg's input (nullptr there: every block replays the history)
+};
+
 template <int WAYS, int LAZY, int BESIDE, int PRIMED>
-__device__ __forceinline__ void parse_wg(const DeflateArgs &a)
+__device__ __forceinline__ void parse_wg(const DeflateArgs &a, const WgDict &dh = WgDict())
 {
+	constexpr bool DICT = PRIMED == WG_HIST_DICT, TABLE = PRIMED == WG_HIST_TABLE;
 	static_assert(WAYS == 1 || WAYS == 2 || WAYS == 4, "a bucket is 2, 4 or 8 bytes");
 	// BESIDE: DYNAMIC shared memory, on purpose: with the 131 KB declared statically the compiler knows that one workgroup fills the CU
 	// and pads the kernel's register count from 95 to 97 (-> 104 allocated) "so that no fifth wavefront fits a SIMD" -- which also
@@ -171,13 +209,32 @@ __device__ __forceinline__ void parse_wg(const DeflateArgs &a)
 	const uint32_t SP = (!PRIMED && a.wg_split > 1) ? a.wg_split : 1u;
 	const uint32_t bi = blockIdx.x / SP, q = blockIdx.x % SP, b = a.first + bi;
 	uint32_t prime = 0;
-	if (PRIMED) {
+	if constexpr (DICT || TABLE) {
+		prime = dh.used;
+	} else if (PRIMED) {
 		const uint64_t at = a.in_off[b];
 		prime = (uint32_t)(at < a.prime_max ? at : (uint64_t)a.prime_max) & ~(uint32_t)(HD_WG_CUT - 1);
 	}
-	const uint8_t *src = PRIMED ? a.in + (a.in_off[b] - prime) : a.stage_in ? a.stage_in + (uint64_t)bi * WG_STAGE_STRIDE : a.in + a.in_off[b];
-	const uint32_t nown = a.in_len[b];               // the block's own bytes: what is coded and what the CRC-32 covers
-	const uint32_t n = PRIMED ? nown + prime : nown; // ... and what passes through the ring: (history || block)
+	const uint8_t *src;
+	uint32_t nown_, n_;
+	if constexpr (DICT) {
+		// (src is the block's own first byte: the history lies at dh.hist)
+		src = a.in + a.in_off[b];
+		nown_ = a.in_len[b];
+		n_ = nown_ + prime;
+	} else if constexpr (TABLE) {
+		// (there is no block, and the history is keyed up to the position in front of its last step)
+		static_assert(HD_LAZY_KEY_BYTES >= 2 && HD_LAZY_KEY_BYTES <= 65, "k_dict_table: the last piece has its sixteen steps, the keys end inside the history");
+		src = dh.hist;
+		nown_ = 0;
+		n_ = prime - 65 + HD_LAZY_KEY_BYTES;
+	} else {
+		src = PRIMED ? a.in + (a.in_off[b] - prime) : a.stage_in ? a.stage_in + (uint64_t)bi * WG_STAGE_STRIDE : a.in + a.in_off[b];
+		nown_ = a.in_len[b];
+		n_ = PRIMED ? nown_ + prime : nown_;
+	}
+	const uint32_t nown = nown_;                     // the block's own bytes: what is coded and what the CRC-32 covers
+	const uint32_t n = n_;                           // ... and what passes through the ring: (history || block)
 	const bool aligned = (((uintptr_t)src) & 15) == 0;
 	const CrcTables *ct = a.ct;
 	const SplitLayout lay = wg_layout(a.split_max);
@@ -197,10 +254,33 @@ __device__ __forceinline__ void parse_wg(const DeflateArgs &a)
 	// (SP == 1: all of them; PRIMED: the history's pieces are the ones replayed)
 	const uint32_t pfirst = PRIMED ? prime / HD_WG_CUT : npieces * q / SP, plast = PRIMED ? npieces : npieces * (q + 1) / SP;
 	const uint32_t own0 = PRIMED ? pfirst : 0u;      // the block's own first piece: tokens, counts and CRC are told from there
+	// slot (k, lane) of (history || block) from where it lies
+	auto load_piece = [&](uint32_t k) -> uint4 {
+		if constexpr (DICT)
+			return k < own0 ? load_slot(dh.hist, prime, k, lane, true) : load_slot(src, nown, k - own0, lane, aligned);
+		else if constexpr (TABLE)
+			return load_slot(src, prime, k, lane, true);
+		else
+			return load_slot(src, n, k, lane, aligned);
+	};
+	// DICT: the history's table is copied, not replayed, where nothing leaves the ring
+	[[maybe_unused]] bool snap = false;
+	if constexpr (DICT)
+		snap = npieces <= HD_WG_RING / HD_PIECE && !refused && dh.table != nullptr;
 
 	// ---- LDS: the table zero, the words ------------------------------------------------------------------------------
-	for (uint32_t i = threadIdx.x; i < WG_TABLE_BYTES / 16; i += 64 * WG_NW)
-		((uint4 *)L.table)[i] = make_uint4(0, 0, 0, 0);
+	if constexpr (DICT) {
+		if (snap) {
+			for (uint32_t i = threadIdx.x; i < WG_TABLE_BYTES / 16; i += 64 * WG_NW)
+				((uint4 *)L.table)[i] = ((const uint4 *)dh.table)[i];
+		} else {
+			for (uint32_t i = threadIdx.x; i < WG_TABLE_BYTES / 16; i += 64 * WG_NW)
+				((uint4 *)L.table)[i] = make_uint4(0, 0, 0, 0);
+		}
+	} else {
+		for (uint32_t i = threadIdx.x; i < WG_TABLE_BYTES / 16; i += 64 * WG_NW)
+			((uint4 *)L.table)[i] = make_uint4(0, 0, 0, 0);
+	}
 	if (threadIdx.x < WG_NW)
 		L.cur[threadIdx.x] = 0xffffffffu;
 	// A block that fits the ring whole (every BGZF block; everything behind the per-block boundary) is brought in by ALL
@@ -214,7 +294,7 @@ __device__ __forceinline__ void parse_wg(const DeflateArgs &a)
 #pragma unroll
 		for (uint32_t i = 0; i < HD_WG_RING / HD_PIECE / WG_NW; i++)
 			if (w + WG_NW * i < npieces)
-				v[i] = load_slot(src, n, w + WG_NW * i, lane, aligned);
+				v[i] = load_piece(w + WG_NW * i);
 #pragma unroll
 		for (uint32_t i = 0; i < HD_WG_RING / HD_PIECE / WG_NW; i++)
 			if (w + WG_NW * i < npieces) {
@@ -231,8 +311,35 @@ __device__ __forceinline__ void parse_wg(const DeflateArgs &a)
 		L.fail = (BESIDE != 0 && a.poison && __hip_atomic_load(a.poison, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) ? 1u : 0u;
 		L.filled = bulk ? npieces : 0u;
 		L.table[WG_TABLE_BYTES / 4] = L.table[WG_TABLE_BYTES / 4 + 1] = 0;
+		if constexpr (DICT) {
+			if (snap) {
+				L.turn = L.next = own0;
+				L.table[WG_TABLE_BYTES / 4] = dh.table[WG_TABLE_BYTES / 4];
+				L.table[WG_TABLE_BYTES / 4 + 1] = dh.table[WG_TABLE_BYTES / 4 + 1];
+				L.fail = dh.table[WG_DICT_TABLE_WORDS];          // (a build that gave up: the block is given up too, and counted)
+			}
+		}
 	}
 	__syncthreads();
+	if constexpr (DICT) {
+		if (snap) {
+			// the history's last step, which k_dict_table left out: the keys of its last positions reach into this block
+			if (w == 0) {
+				HashConsts6 hk;
+				hk.init(WG_TABLE_BYTES / 4);
+				hk.m = 0x10000u - 2 * WAYS;
+				const uint32_t p = prime - 64 + lane;
+				const uint32_t *q4 = L.ring32 + (p >> 2);
+				const uint32_t d0 = q4[0], d1 = q4[1], d2 = q4[2];
+				const uint32_t v = __builtin_amdgcn_alignbyte(d1, d0, p), vh = __builtin_amdgcn_alignbyte(d2, d1, p);
+				const uint32_t h = hash_slot_addr6(v, vh, hk);
+				uint32_t ox = 0, oy = 0;
+				if (p + HD_LAZY_KEY_BYTES <= n)
+					wg_bucket<WAYS>((WG_LDS uint8_t *)Lp->table, h, p, ox, oy);
+			}
+			__syncthreads();
+		}
+	}
 	const bool poisoned = BESIDE != 0 && uniform(L.fail) != 0;      // (nothing is read, nothing written: the emit kernel stores the block)
 
 	uint32_t crcv = 0;
@@ -247,7 +354,7 @@ __device__ __forceinline__ void parse_wg(const DeflateArgs &a)
 			for (uint32_t k = own0; k < npieces; k++)
 				crc.fold(ct, k - own0, (k - own0) * HD_PIECE + 16 * lane + 16 <= nown, *(const uint4 *)((const uint8_t *)L.ring32 + k * HD_PIECE + 16 * lane));
 		} else if (npieces) {
-			pend = load_slot(src, n, 0, lane, aligned);
+			pend = load_piece(0);
 		}
 		for (uint32_t k = 0; !bulk && k < npieces; k++) {
 			// piece k takes the place of piece k - 64, and a parser reads up to 32 pieces behind its own: k stays within
@@ -277,7 +384,7 @@ __device__ __forceinline__ void parse_wg(const DeflateArgs &a)
 			}
 			const uint4 v = pend;
 			if (k + 1 < npieces)
-				pend = load_slot(src, n, k + 1, lane, aligned);
+				pend = load_piece(k + 1);
 			const uint32_t o = (k * HD_PIECE + 16 * lane) & (HD_WG_RING - 1);
 			*(uint4 *)((uint8_t *)L.ring32 + o) = v;
 			if (o < 32)                        // the mirror behind the ring's end
@@ -289,7 +396,10 @@ __device__ __forceinline__ void parse_wg(const DeflateArgs &a)
 			if (!PRIMED || k >= own0)
 				crc.fold(ct, k - own0, (k - own0) * HD_PIECE + 16 * lane + 16 <= nown, v);
 		}
-		crcv = crc.finish(ct, lane, nown, src + prime + (nown & ~15u));
+		if constexpr (DICT)
+			crcv = crc.finish(ct, lane, nown, src + (nown & ~15u));
+		else
+			crcv = crc.finish(ct, lane, nown, src + prime + (nown & ~15u));
 	}
 	if ((w != WG_NP || bulk) && !poisoned) {
 		// ================= a parser (bulk: the filler too, once its CRC is folded) =====================================
@@ -577,6 +687,20 @@ __device__ __forceinline__ void parse_wg(const DeflateArgs &a)
 	if (beside)
 		asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 	__syncthreads();
+	if constexpr (TABLE) {
+		// the table as the history's pieces left it, and whether every turn came
+		for (uint32_t i = threadIdx.x; i < WG_TABLE_BYTES / 16; i += 64 * WG_NW)
+			((uint4 *)dh.table)[i] = ((const uint4 *)L.table)[i];
+		if (threadIdx.x < 2)
+			dh.table[WG_TABLE_BYTES / 4 + threadIdx.x] = L.table[WG_TABLE_BYTES / 4 + threadIdx.x];
+		if (threadIdx.x == 2) {
+			const bool stalled = uniform(*vfail) != 0;
+			dh.table[WG_DICT_TABLE_WORDS] = stalled ? 1u : 0u;
+			if (stalled && a.stalls)
+				atomicAdd(a.stalls, 1u);
+		}
+		return;
+	}
 	if (w == WG_NP && lane == 0) {
 		uint32_t *m = (uint32_t *)(rec + lay.off_rec);
 		const bool stalled = uniform(*vfail) != 0;
@@ -610,7 +734,21 @@ __global__ __launch_bounds__(64 * HD_WG_WAVES) __attribute__((amdgpu_waves_per_e
 template <int WAYS, int LAZY, int BESIDE = 0>
 __global__ __launch_bounds__(64 * HD_WG_WAVES) __attribute__((amdgpu_waves_per_eu(4, BESIDE ? 5 : 4))) void k_primed_wg(DeflateArgs a)
 {
-	parse_wg<WAYS, LAZY, BESIDE, 1>(a);
+	parse_wg<WAYS, LAZY, BESIDE, WG_HIST_FRONT>(a);
+}
+
+// the parse of a block whose history is the launch's preset dictionary (parse_wg's WG_HIST_DICT)
+template <int WAYS, int LAZY>
+__global__ __launch_bounds__(64 * HD_WG_WAVES) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_dict_wg(DeflateArgs a, WgDict dh)
+{
+	parse_wg<WAYS, LAZY, 0, WG_HIST_DICT>(a, dh);
+}
+
+// ... and the table that dictionary leaves, all but its last step: one workgroup, once per call (parse_wg's WG_HIST_TABLE)
+template <int WAYS>
+__global__ __launch_bounds__(64 * HD_WG_WAVES) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_dict_table(DeflateArgs a, WgDict dh)
+{
+	parse_wg<WAYS, 0, 0, WG_HIST_TABLE>(a, dh);
 }
 
 // the gate in front of a parse that runs BESIDE its emit kernel (launch_wg): one wavefront that waits until `want` emit
@@ -690,10 +828,13 @@ constexpr uint32_t WG_BESIDE_MAX_BLOCK = 2097152; // ... and the longest block i
 // the parse of one sub-batch at a level's rung of the ladder (HD_WG_WAYS / HD_WG_LAZY), in one of its four forms: beside its emit
 // kernel or not, primed with the bytes in front of every block (s.prime_max) or not
 template <int WAYS, int LAZY>
-inline void launch_parse_rung(const DeflateArgs &s, bool beside, hipStream_t st)
+inline void launch_parse_rung(const DeflateArgs &s, bool beside, hipStream_t st, const WgDict *dict)
 {
 	const dim3 grid(s.count * s.wg_split), block(64 * HD_WG_WAVES);
-	if (s.prime_max) {
+	if (dict) {
+		// (the launch's preset dictionary: on its own schedule, the emit kernel follows the parse)
+		hipLaunchKernelGGL((k_dict_wg<WAYS, LAZY>), grid, block, 0, st, s, *dict);
+	} else if (s.prime_max) {
 		if (beside)
 			hipLaunchKernelGGL((k_primed_wg<WAYS, LAZY, 1>), grid, block, WG_LDS_DYNAMIC, st, s);
 		else
@@ -706,20 +847,36 @@ inline void launch_parse_rung(const DeflateArgs &s, bool beside, hipStream_t st)
 	}
 }
 
-inline void launch_parse_wg(const DeflateArgs &s, int level, bool beside, hipStream_t st)
+inline void launch_parse_wg(const DeflateArgs &s, int level, bool beside, hipStream_t st, const WgDict *dict)
 {
 	if (HD_WG_WAYS(level) == 4)
-		launch_parse_rung<4, 1>(s, beside, st);
+		launch_parse_rung<4, 1>(s, beside, st, dict);
 	else if (HD_WG_WAYS(level) == 2)
-		launch_parse_rung<2, 1>(s, beside, st);
+		launch_parse_rung<2, 1>(s, beside, st, dict);
 	else if (HD_WG_LAZY(level))
-		launch_parse_rung<1, 1>(s, beside, st);
+		launch_parse_rung<1, 1>(s, beside, st, dict);
 	else
-		launch_parse_rung<1, 0>(s, beside, st);
+		launch_parse_rung<1, 0>(s, beside, st, dict);
+}
+
+// the table a launch's preset dictionary leaves (dict.hist, dict.used -> dict.table), at the level's ways: one workgroup
+inline void launch_dict_table(const DeflateArgs &a, int level, const WgDict &dict, hipStream_t st)
+{
+	DeflateArgs s = a;
+	s.first = 0;
+	s.count = 1;
+	s.wg_split = 1;
+	if (HD_WG_WAYS(level) == 4)
+		hipLaunchKernelGGL((k_dict_table<4>), dim3(1), dim3(64 * HD_WG_WAVES), 0, st, s, dict);
+	else if (HD_WG_WAYS(level) == 2)
+		hipLaunchKernelGGL((k_dict_table<2>), dim3(1), dim3(64 * HD_WG_WAVES), 0, st, s, dict);
+	else
+		hipLaunchKernelGGL((k_dict_table<1>), dim3(1), dim3(64 * HD_WG_WAVES), 0, st, s, dict);
 }
 
 // blocks [first, first + count) of a sub-batch: the workgroup parse, then the emit-only kernel over its records
-inline void launch_wg(const DeflateArgs &a, int level, hipStream_t st)
+// dict: every block is parsed with the launch's preset dictionary as its history (k_dict_wg; never beside, never the latency form)
+inline void launch_wg(const DeflateArgs &a, int level, hipStream_t st, const WgDict *dict)
 {
 	{
 		// (more than 64 KB of dynamic LDS has to be asked for, once per device and kernel)
@@ -760,7 +917,7 @@ inline void launch_wg(const DeflateArgs &a, int level, hipStream_t st)
 			hipLaunchKernelGGL(k_stage_in, dim3(s.count), dim3(1024), 0, st, s, stage);
 			s.stage_in = stage;
 		}
-		WgBeside *bs = (!beside_off && !a.lat && a.nblocks >= WG_BESIDE_MIN && a.split_max <= WG_BESIDE_MAX_BLOCK) ? (WgBeside *)a.beside : nullptr;
+		WgBeside *bs = (!beside_off && !a.lat && !dict && a.nblocks >= WG_BESIDE_MIN && a.split_max <= WG_BESIDE_MAX_BLOCK) ? (WgBeside *)a.beside : nullptr;
 		s.ready = s.arrived = s.next = s.emitted = s.poison = nullptr;
 		s.span_sub = 0;
 		s.scratch_b = nullptr;
@@ -829,7 +986,7 @@ inline void launch_wg(const DeflateArgs &a, int level, hipStream_t st)
 				hipLaunchKernelGGL(k_gate, dim3(1), dim3(64), 0, st, emitted + (k - 2), cnt, 1u << 22, s.poison);
 			}
 		}
-		launch_parse_wg(s, level, bs != nullptr, st);
+		launch_parse_wg(s, level, bs != nullptr, st, dict);
 		if (a.lat) {
 			// the per-block boundary (HD_FRAME_LATENCY, blocks up to 64 KiB): the member written by a workgroup, the same bytes
 			launch_emit_wg(s, st);

@@ -87,6 +87,43 @@ __global__ __launch_bounds__(64) void k_frame_open(const uint8_t *__restrict__ i
 	}
 }
 
+// k_frame_open for HD_FRAME_ZLIB members that may name a PRESET DICTIONARY (hipdeflate_batch_inflate_dict_dev): the same rules,
+// but FDICT is allowed -- four more header bytes, DICTID big-endian, which must be *dict_adler, the Adler-32 of the call's whole
+// dictionary (with_dict == 0: none was given and FDICT is refused).  plain[b] = 1 for a member without FDICT: it is decoded
+// without the dictionary, as zlib's inflate does.  One lane's work per member, 256 members a workgroup.
+__global__ __launch_bounds__(256) void k_dict_open(const uint8_t *__restrict__ in, const uint64_t *__restrict__ in_off,
+						    const uint32_t *__restrict__ in_len, uint32_t nmembers, const uint32_t *__restrict__ dict_adler,
+						    uint32_t with_dict, uint64_t *__restrict__ p_off, uint32_t *__restrict__ p_len,
+						    int32_t *__restrict__ verdict, uint32_t *__restrict__ plain)
+{
+	const uint32_t b = blockIdx.x * 256 + threadIdx.x;
+	if (b >= nmembers)
+		return;
+	const uint64_t off = in_off[b];
+	const uint8_t *src = in + off;
+	const uint32_t n = in_len[b];
+	uint32_t pos = 0, fdict = 0;
+	bool ok = n < HD_INFLATE_MAX_IN && n >= 6;
+	if (ok) {
+		const uint32_t hdr = ((uint32_t)src[0] << 8) | src[1];
+		ok = hdr % 31 == 0 && ((hdr >> 8) & 15) == 8 && (hdr >> 12) <= 7;
+		fdict = (hdr >> 5) & 1;
+		pos = 2;
+	}
+	if (ok && fdict) {
+		ok = with_dict && n >= 10;                               // DICTID, and the trailer's four bytes behind it
+		if (ok) {
+			const uint32_t id = ((uint32_t)src[2] << 24) | ((uint32_t)src[3] << 16) | ((uint32_t)src[4] << 8) | src[5];
+			ok = id == *dict_adler;
+			pos = 6;
+		}
+	}
+	p_off[b] = ok ? off + pos : off;
+	p_len[b] = ok ? n - 4 - pos : 0u;
+	verdict[b] = ok ? HD_OK : HD_BAD_DATA;
+	plain[b] = fdict ? 0u : 1u;
+}
+
 // One lane per member, behind k_inflate_framed (and k_chunk_adler for HD_FRAME_ZLIB): status[] and out_len[] hold the
 // inflate's answer and get the member's.  A member whose header was refused or whose inflate failed keeps that status;
 // HD_INSUFFICIENT_SPACE was decided before any check, as in the reference.  A member that fails has out_len, check and

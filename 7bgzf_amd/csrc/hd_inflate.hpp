@@ -52,6 +52,16 @@ struct InflateFramedArgs : InflateArgs {
 	uint32_t *used;
 };
 
+// k_dict_inflate's: every member is decoded against one PRESET DICTIONARY (hipdeflate_batch_inflate_dict_dev; inflateSetDictionary's
+// role): the dict_len <= 32768 bytes that END at dict_end (library scratch, 16-byte aligned, HD_WG_WINDOW bytes readable in front
+// of it) are the window the member starts with.  plain: where given, a member with plain[b] != 0 is decoded without it
+struct InflateDictArgs : InflateFramedArgs {
+	const uint8_t *dict_end;
+	uint32_t dict_len;
+	const uint32_t *plain;
+};
+constexpr uint32_t INF_DICT_ORIGIN = 32768;   // k_dict_inflate: the position of a member's first output byte
+
 // InflateArgs::flags: a stream may stop after a non-final block once every input byte is used -- the chunks of
 // 7dictzip / 7razf end in a full-flush marker, not in a final block, and the reference reads them with inflaters
 // that report "out of input" as success (zlib_inflate, lib/zlibutil.c:289-291; igzip_inflate, zlibutil_igzip.c:111)
@@ -95,10 +105,20 @@ static_assert(sizeof(InfLds) == 6400, "InfLds must stay within five LDS allocati
 
 // the decoder, for an output ring of RING bytes (one wavefront; L is the workgroup's LDS)
 // Args = InflateFramedArgs: the bytes consumed leave next to out_len (the framed decode finds the trailer there: hd_frame.hpp)
+// Args = InflateDictArgs: the window starts out FULL.  Positions start at a virtual origin V = INF_DICT_ORIGIN instead of 0 and the
+// dictionary's D bytes occupy [V - D, V): `pos`, `flushed`, every match source and `cap` are such positions, `dst` is the address
+// position 0 would have, and the ring holds the dictionary's last bytes at their ring addresses before the first token.  V is a
+// multiple of the ring, of a piece and of 16, so every wrap, flush and alignment rule below is untouched; what changes is what
+// leaves (out_len, the CRC's piece index and length: minus V), the "distance reaches in front of the data" checks (the data
+// starts at V - D, not at 0) and a far source's byte, which below V comes from the dictionary, per lane -- a source may
+// straddle the seam.  V = 0 and no dictionary in every other instantiation: those compile to what they were.
 template <uint32_t RING, class Args = InflateArgs>
 __device__ __forceinline__ void inflate_stream(const Args &a, InfLdsT<RING> &L)
 {
-	constexpr bool USED = std::is_same<Args, InflateFramedArgs>::value;
+	constexpr bool DICT = std::is_same<Args, InflateDictArgs>::value;
+	constexpr bool USED = std::is_same<Args, InflateFramedArgs>::value || DICT;
+	constexpr uint32_t V = DICT ? INF_DICT_ORIGIN : 0u;
+	static_assert(V % RING == 0 && V % HD_PIECE == 0, "the origin keeps ring addresses and pieces where they were");
 	constexpr uint32_t INF_NEAR = RING - 258 - 64;       // dist <= this: source is in the ring
 	const uint32_t lane = threadIdx.x;
 	const uint32_t b = blockIdx.x;
@@ -120,7 +140,29 @@ __device__ __forceinline__ void inflate_stream(const Args &a, InfLdsT<RING> &L)
 		return;
 	}
 	uint8_t *dst = a.out + a.out_off[b];
-	const uint32_t cap = a.out_cap[b];
+	uint32_t cap = a.out_cap[b];
+	uint32_t base = 0;                                   // the lowest position a match may name
+	const uint8_t *dictv = nullptr;                      // DICT: the address of position 0 on the dictionary's side
+	if constexpr (DICT) {
+		dst -= V;                                        // (never dereferenced below position V)
+		cap = V + (cap < ~V ? cap : ~V);                 // (positions are 32-bit: a room within V of 2^32 is that much shorter)
+		base = V - ((a.plain && uniform(a.plain[b])) ? 0u : a.dict_len);
+		dictv = a.dict_end - V;
+	}
+	// a byte that left the ring long ago: from the flushed output, or from the dictionary
+	auto far_byte = [&](uint32_t at) -> uint32_t {
+		if constexpr (DICT)
+		{
+			uint32_t v = 0;
+			if (at < V)
+				v = *((const __attribute__((address_space(1))) uint8_t *)dictv + at);
+			if (at >= V)
+				v = *((const __attribute__((address_space(1))) uint8_t *)dst + at);
+			return v;
+		}
+		else
+			return (uint32_t)dst[at];
+	};
 	const CrcTables *ct = a.ct;
 	const bool want_crc = a.crc != nullptr;
 	const bool dst_aligned = (((uintptr_t)dst) & 15) == 0;
@@ -188,7 +230,12 @@ __device__ __forceinline__ void inflate_stream(const Args &a, InfLdsT<RING> &L)
 	bc -= 8 * mis;
 
 	// ---- output ring + flush ---------------------------------------------
-	uint32_t pos = 0, flushed = 0;
+	uint32_t pos = V, flushed = V;
+	if constexpr (DICT) {
+		// the ring as the dictionary leaves it: its last RING bytes (in front of a shorter one: bytes no distance may name)
+		for (uint32_t i = 16 * lane; i < RING; i += 1024)
+			*(uint4 *)&L.ring[i] = *(const uint4 *)(a.dict_end - RING + i);
+	}
 	CrcLanes crc;
 	crc.init(lane, 0xffffffffu);          // length unknown yet; lane 0 seeds, fixed in finish
 	auto flush_pieces = [&]() {
@@ -202,7 +249,7 @@ __device__ __forceinline__ void inflate_stream(const Args &a, InfLdsT<RING> &L)
 					dst[flushed + 16 * lane + k] = (uint8_t)(w[k >> 2] >> (8 * (k & 3)));
 			}
 			if (want_crc)
-				crc.fold(ct, flushed / HD_PIECE, true, v);
+				crc.fold(ct, (flushed - V) / HD_PIECE, true, v);
 			flushed += HD_PIECE;
 		}
 	};
@@ -383,8 +430,13 @@ __device__ __forceinline__ void inflate_stream(const Args &a, InfLdsT<RING> &L)
 			// (one v_cmp each: written out, or the compiler takes the carry of the subtraction above and turns it
 			// back into a mask with two more instructions)
 			uint64_t far0, far1;
-			asm("v_cmp_lt_u32 %0, %1, %2" : "=s"(far0) : "v"(opos0), "v"(s0.offset));
-			asm("v_cmp_lt_u32 %0, %1, %2" : "=s"(far1) : "v"(opos1), "v"(s1.offset));
+			if constexpr (DICT) {
+				far0 = __ballot(opos0 - base < s0.offset);
+				far1 = __ballot(opos1 - base < s1.offset);
+			} else {
+				asm("v_cmp_lt_u32 %0, %1, %2" : "=s"(far0) : "v"(opos0), "v"(s0.offset));
+				asm("v_cmp_lt_u32 %0, %1, %2" : "=s"(far1) : "v"(opos1), "v"(s1.offset));
+			}
 			if ((far0 & match0) | (far1 & match1)) {   // offset > bytes out so far: decompress_template.h:724
 				st_out = HD_BAD_DATA;
 				result = 2;
@@ -439,7 +491,7 @@ __device__ __forceinline__ void inflate_stream(const Args &a, InfLdsT<RING> &L)
 						fP[k] = readlane(opos1, m);
 						sp = readlane(srcl1, m);
 					}
-					fv[k] = lane < fml[k] ? (uint32_t)dst[sp + lane] : 0u;
+					fv[k] = lane < fml[k] ? far_byte(sp + lane) : 0u;
 				}
 			};
 			auto far_store = [&]() {
@@ -487,8 +539,12 @@ __device__ __forceinline__ void inflate_stream(const Args &a, InfLdsT<RING> &L)
 						// (said with the address spaces: left generic, the compiler turns "ring byte, or the flushed byte where the source is far"
 						// into ONE flat_load_ubyte from a selected address -- every pass then goes through the flat path, LDS and memory counters both)
 						uint32_t v = *((const __attribute__((address_space(3))) uint8_t *)&L.ring[0] + (sp & (RING - 1)));
-						if (act && !ringsrc)
-							v = *((const __attribute__((address_space(1))) uint8_t *)dst + sp);
+						if (act && !ringsrc) {
+							if constexpr (DICT)
+								v = far_byte(sp);
+							else
+								v = *((const __attribute__((address_space(1))) uint8_t *)dst + sp);
+						}
 						const uint32_t di = act ? (dp & (RING - 1)) : RING + lane;
 						if (!pend) {
 							pend = true;
@@ -557,7 +613,7 @@ __device__ __forceinline__ void inflate_stream(const Args &a, InfLdsT<RING> &L)
 					asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #pragma unroll 1
 					for (uint32_t i = lane; i < mlen; i += 64)
-						L.ring[(P + i) & (RING - 1)] = dst[srcp + i];
+						L.ring[(P + i) & (RING - 1)] = (uint8_t)far_byte(srcp + i);
 				}
 			};
 			if (scalar_far) {
@@ -788,7 +844,7 @@ __device__ __forceinline__ void inflate_stream(const Args &a, InfLdsT<RING> &L)
 				const uint32_t offset = (d >> 16) + ((uint32_t)bb & ((1u << deb) - 1));
 				bb >>= deb;
 				bc -= deb;
-				if (offset > pos) { st = HD_BAD_DATA; break; }
+				if (offset > pos - base) { st = HD_BAD_DATA; break; }
 
 				// ---- match copy, 64 bytes per step ------------------------
 				if (offset <= INF_NEAR) {
@@ -813,7 +869,7 @@ __device__ __forceinline__ void inflate_stream(const Args &a, InfLdsT<RING> &L)
 					asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #pragma unroll 1
 					for (uint32_t i = lane; i < length; i += 64)
-						L.ring[(pos + i) & (RING - 1)] = dst[pos - offset + i];
+						L.ring[(pos + i) & (RING - 1)] = (uint8_t)far_byte(pos - offset + i);
 				}
 				pos += length;
 				INF_T1(2, t_tok);
@@ -837,20 +893,20 @@ __device__ __forceinline__ void inflate_stream(const Args &a, InfLdsT<RING> &L)
 			dst[i] = L.ring[i & (RING - 1)];
 		if (want_crc) {
 			// full 16-byte slots of the tail piece, then the < 16 byte remainder
-			const uint32_t piece = flushed / HD_PIECE;
+			const uint32_t piece = (flushed - V) / HD_PIECE;
 			const uint32_t o = flushed + 16 * lane;
 			const bool full = o + 16 <= pos;
 			uint4 v = make_uint4(0, 0, 0, 0);
 			if (full)
 				v = *(const uint4 *)&L.ring[o & (RING - 1)];
-			if (pos < 16)
+			if (pos - V < 16)
 				crc.s = 0;                       // no full slot at all: finish() reseeds
 			crc.fold(ct, piece, full, v);
-			crcv = crc.finish(ct, lane, pos, &L.ring[(pos & ~15u) & (RING - 1)]);
+			crcv = crc.finish(ct, lane, pos - V, &L.ring[(pos & ~15u) & (RING - 1)]);
 		}
 	}
 	if (lane == 0) {
-		a.out_len[b] = st == HD_OK ? pos : 0;
+		a.out_len[b] = st == HD_OK ? pos - V : 0;
 		if (a.status) a.status[b] = st;
 		if (a.crc) a.crc[b] = crcv;
 		if constexpr (USED)
@@ -871,6 +927,13 @@ __global__ __launch_bounds__(64) void k_inflate(InflateArgs a)
 // framed decode alone, so that the kernel every other path launches stays what it was, instruction for instruction (it stands
 // three registers below an occupancy step)
 __global__ __launch_bounds__(64) void k_inflate_framed(InflateFramedArgs a)
+{
+	__shared__ InfLds L;
+	inflate_stream<INF_RING>(a, L);
+}
+
+// ... and with a preset dictionary as every member's window (InflateDictArgs): again a kernel of its own
+__global__ __launch_bounds__(64) void k_dict_inflate(InflateDictArgs a)
 {
 	__shared__ InfLds L;
 	inflate_stream<INF_RING>(a, L);

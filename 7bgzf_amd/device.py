@@ -660,6 +660,54 @@ def inflate_members(blob, in_off, in_len, frame=_pkg.FRAME_ZLIB):
     return out, out_off, out_len, status
 
 
+def deflate_dict_call(data, in_off, in_len, level, dictionary, out, out_stride, out_cap, out_len, crc, status):
+    """one hipdeflate_batch_deflate_dict_dev over device tensors (dictionary: a uint8 tensor, or None)"""
+    dict_len = 0 if dictionary is None else dictionary.numel()
+    rc = _pkg.lib().hipdeflate_batch_deflate_dict_dev(_ptr(data), _ptr(in_off), _ptr(in_len), in_off.numel(), level,
+                                                      _ptr(dictionary) if dict_len else None, dict_len, _ptr(out), out_stride,
+                                                      out_cap, _ptr(out_len), _ptr(crc), _ptr(status), _stream())
+    _pkg._check(rc, "hipdeflate_batch_deflate_dict_dev")
+
+
+def inflate_dict_call(blob, in_off, in_len, frame, dictionary, out, out_off, out_cap, out_len, check, in_used, status):
+    """one hipdeflate_batch_inflate_dict_dev over device tensors (dictionary, check, in_used: a tensor or None)"""
+    dict_len = 0 if dictionary is None else dictionary.numel()
+    rc = _pkg.lib().hipdeflate_batch_inflate_dict_dev(_ptr(blob), _ptr(in_off), _ptr(in_len), in_off.numel(), frame,
+                                                      _ptr(dictionary) if dict_len else None, dict_len, _ptr(out), _ptr(out_off),
+                                                      _ptr(out_cap), _ptr(out_len), _ptr(check), _ptr(in_used), _ptr(status),
+                                                      _stream())
+    _pkg._check(rc, "hipdeflate_batch_inflate_dict_dev")
+
+
+def deflate_dict(data, in_off, in_len, dictionary, level=6):
+    """Compress the blocks data[in_off[i]:in_off[i] + in_len[i]] (uint8 tensor; int64 and int32 device tensors) against one
+    preset dictionary (uint8 tensor): raw members, each for zlib.decompressobj(-15, zdict=dictionary).
+    -> (slots, slot, out_len, crc, status): member i is slots[i * slot:i * slot + out_len[i]]."""
+    n = in_off.numel()
+    dev = data.device
+    slot = int(_pkg.lib().hipdeflate_bound(int(in_len.max().item()) if n else 0, level))
+    slots = torch.empty(max(n * slot, 16), dtype=torch.uint8, device=dev)
+    out_len, crc, status = (torch.zeros(n, dtype=torch.int32, device=dev) for _ in range(3))
+    deflate_dict_call(data, in_off, in_len, level, dictionary, slots, slot, slot, out_len, crc, status)
+    return slots, slot, out_len, crc, status
+
+
+def inflate_dict(blob, in_off, in_len, dictionary, frame=_pkg.FRAME_RAW, out_cap=None):
+    """Decode the raw or zlib members blob[in_off[i]:in_off[i] + in_len[i]] that were written with the preset dictionary.
+    out_cap: an int32 tensor of rooms; None: 64 KiB each.  -> (out, out_off, out_len, status)"""
+    n = in_off.numel()
+    dev = blob.device
+    if out_cap is None:
+        out_cap = torch.full((n,), 65536, dtype=torch.int32, device=dev)
+    rooms = (out_cap.to(torch.int64) + 15) & ~15
+    out_off = torch.cumsum(rooms, 0) - rooms
+    out = torch.empty(max(int(rooms.sum().item()), 16), dtype=torch.uint8, device=dev)
+    out_len, status = (torch.zeros(n, dtype=torch.int32, device=dev) for _ in range(2))
+    if n:
+        inflate_dict_call(blob, in_off, in_len, frame, dictionary, out, out_off, out_cap, out_len, None, None, status)
+    return out, out_off, out_len, status
+
+
 def block_table(total_bytes, block_size, device="cuda"):
     nb = (total_bytes + block_size - 1) // block_size
     off = torch.arange(nb, dtype=torch.int64, device=device) * block_size

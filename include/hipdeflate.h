@@ -501,6 +501,64 @@ int hipdeflate_stream_deflate_dev(const void *in, uint64_t nbytes, uint32_t chun
 int hipdeflate_stream_deflate_carry_dev(const void *in, uint64_t nbytes, uint32_t chunk_bytes, int level, int frame,
 					void *dst, uint64_t dst_cap, void *chunk_off /* u64[nchunks + 1], may be NULL */,
 					hipdeflate_stream_summary *summary /* HOST */, void *stream);
+/* ---- preset dictionary: thousands of small blocks against one shared history --------
+ * A small block with an empty window compresses badly; zlib's remedy is the preset dictionary.  Roles: deflateSetDictionary
+ * (lib/zlib/deflate.c:550-614) in front of every block's deflate, inflateSetDictionary (lib/zlib/inflate.c:1298-1329) in front
+ * of every member's inflate, and for HD_FRAME_ZLIB the FDICT bit and the DICTID field of the header (written at
+ * lib/zlib/deflate.c:1010, read at lib/zlib/inflate.c:810-822) -- for all blocks of a launch at once, with one dictionary.
+ * `dict` is a device pointer of any alignment (the library stages what it uses into aligned scratch of its own, once per call);
+ * dict == NULL with dict_len != 0 is HD_E_ARG.  Calls take turns on that scratch as they do on the token slabs.
+ *
+ * hipdeflate_batch_deflate_dict_dev: hipdeflate_batch_deflate_dev's arguments and contract -- refusals, statuses, rooms, the
+ * refusal of a block longer than its slot at levels >= 3 -- without the frame: the output is HD_FRAME_RAW, every member ends in a
+ * final block, and there is no latency form.  At levels 3..9 block b is parsed with the LAST
+ *     used = min(32768, dict_len) & ~1023
+ * bytes of the dictionary as its history: no token is made for them, crc32[b] covers the block alone, and the block's matches
+ * may name any of them -- distances go up to 32768 into the dictionary.  The rounding down to 1024 keeps the seam on a piece
+ * boundary of the parse (hipdeflate_params.h HD_WG_CUT), exactly as prime(i) above does: a block's tokens are those of a one-block
+ * parse of (that history || block) behind the seam.  Two limits follow and are meant: a dictionary SHORTER THAN 1024 BYTES is
+ * accepted and NOT USED, and UP TO 1023 BYTES AT THE FRONT of a dictionary below 32 KiB + 1023 are not used (give a
+ * dictionary whose length is a multiple of 1024, its most useful bytes last, as for zlib).  A reader sets the dictionary it was
+ * given, whole: inflateSetDictionary keeps its last 32 KiB, which contain the used bytes.
+ * dict_len == 0, used == 0 and levels 0..2 (windows of 4 KiB or none) write exactly the bytes of hipdeflate_batch_deflate_dev(...,
+ * HD_FRAME_RAW, ...), as hipdeflate_stream_deflate_carry_dev does at those levels.  A zlib (RFC 1950) wrapper with FDICT on the
+ * encode side is not built: the caller who wants one writes 2 + 4 header bytes and the Adler-32 around the raw member.
+ * The history's hash table is the same for every block of the call: it is built once (one workgroup) and every block whose
+ * (history || block) fits the parse's 64 KiB ring copies it instead of replaying up to 32 pieces; longer blocks replay.  The
+ * bytes are the same either way.  The emit kernel follows the parse (not beside it).  hipdeflate_stall_count() stays 0.
+ *
+ * hipdeflate_batch_inflate_dict_dev: hipdeflate_batch_inflate_framed_dev's arguments, arrays, result semantics (out_len, check,
+ * in_used, status), read and write bounds and its refusal of members of HD_INFLATE_MAX_IN bytes, with frame HD_FRAME_RAW or
+ * HD_FRAME_ZLIB (anything else: HD_E_ARG).  Every member starts with a full window: only the last D = min(32768, dict_len) bytes
+ * of the dictionary can be named (no rounding here), and a distance d at output position p is valid iff d <= p + D -- otherwise
+ * status 1, as without a dictionary.  check[i] and the zlib trailer cover the output alone.
+ *   HD_FRAME_ZLIB: the rules above, except that FDICT is allowed.  With FDICT four more header bytes hold DICTID, big-endian,
+ *     which must equal the Adler-32 of the WHOLE dictionary as given, all dict_len bytes (taken on the device) -- otherwise status
+ *     1; so is a member cut inside DICTID, and FDICT with dict_len == 0 (zlib's Z_NEED_DICT).  in_used counts the six header
+ *     bytes.  A member WITHOUT FDICT is decoded without the dictionary, as zlib does.
+ *   HD_FRAME_RAW: every member is decoded with the dictionary.
+ * With dict_len == 0, RAW and FDICT-free members get the verdicts, lengths and bytes of hipdeflate_batch_inflate_framed_dev,
+ * which is unchanged and keeps refusing FDICT.  (A room within 32 KiB of 2^32 bytes counts as that much shorter.) */
+int hipdeflate_batch_deflate_dict_dev(const void *in, const void *in_off, const void *in_len, uint32_t nblocks, int level,
+				      const void *dict, uint32_t dict_len,
+				      void *out, uint64_t out_stride, uint32_t out_cap,
+				      void *out_len, void *crc32, void *status, void *stream);
+int hipdeflate_batch_inflate_dict_dev(const void *in, const void *in_off, const void *in_len, uint32_t nblocks, int frame,
+				      const void *dict, uint32_t dict_len,
+				      void *out, const void *out_off, const void *out_cap,
+				      void *out_len, void *check /* u32[n], may be NULL */, void *in_used /* may be NULL */,
+				      void *status, void *stream);
+/* host-buffer forms: hipdeflate_batch_deflate's and hipdeflate_batch_inflate_framed's arguments and staging, the dictionary a
+ * host buffer too; the same bytes and answers as the device calls' */
+int hipdeflate_batch_deflate_dict(const uint8_t *in, const uint64_t *in_off, const uint32_t *in_len, uint32_t nblocks,
+				  int level, const uint8_t *dict, uint32_t dict_len, uint8_t *out, uint64_t out_stride,
+				  uint32_t out_cap, uint32_t *out_len, uint32_t *crc32, int32_t *status);
+int hipdeflate_batch_inflate_dict(const uint8_t *in, const uint64_t *in_off, const uint32_t *in_len, uint32_t nblocks, int frame,
+				  const uint8_t *dict, uint32_t dict_len, uint8_t *out, const uint64_t *out_off,
+				  const uint32_t *out_cap, uint32_t *out_len, uint32_t *check, uint32_t *in_used, int32_t *status);
+/* test entry: on != 0 makes every block of a dictionary encode replay the history (no table snapshot); 0 restores the default */
+void hipdeflate_test_dict_replay(int on);
+
 /* The inverse -- the device-resident form of what a dictzip reader does with its RA table (applet/7dictzip.c:318-323): given
  * the table, the chunks are inflated side by side, chunk i by the flush-rule batch inflate into out + i * chunk_bytes with
  * exactly its size as room, and the result is held to the trailer.  Streams of other writers qualify if they are cut the
